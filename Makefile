@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-h265 smoke tsan asan tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -23,6 +23,9 @@ smoke: build
 
 bench: build               ## headline benchmark, 1 GPU (torchrun for N > 1)
 	$(PY) bench.py
+
+bench-full: build          ## + the latency run and the reference-equivalent CPU run (vs_baseline)
+	$(PY) bench.py --full
 
 bench-h265: build          ## BASELINE config 5 shape on one GPU: 8 x 4K30 H.265
 	$(PY) bench.py --codec h265 --width 3840 --height 2160 --cams-per-gpu 8

@@ -21,7 +21,12 @@ One *step* is ``--frames-per-step`` frame intervals of every camera (default: on
 decoding at the headline rate and every step covers whole GOPs (IDR, P and B pictures in the
 stream's own proportions) rather than a transient.
 
-Latency (headline ``p50_latency_ms`` / ``p99_latency_ms``): after the timed loop the farm switches
+A plain run does only what ``value`` needs: it sets up, warms up, times the steps, writes its
+outputs when ``--dump-outputs DIR`` is given (``dump_outputs`` below) and prints the JSON line.
+The latency run and the reference-equivalent CPU run (``reference_equivalent_cpu_fps``,
+``vs_baseline``) are behind ``--full``.
+
+Latency (``--full``: ``p50_latency_ms`` / ``p99_latency_ms``): after the timed loop the farm switches
 to real time (``--fps``), and ``--clients`` concurrent gRPC clients running in separate processes
 (started before this process touches the GPU) each issue back-to-back VideoLatestImage requests
 for their own live camera through the production gRPC server: request sent -> the camera's next
@@ -148,6 +153,14 @@ def parse_args():
                          "(vep serve's default) or the grpcio ImageService")
     ap.add_argument("--latency-seconds", type=float, default=4.0,
                     help="duration of the concurrent-client latency run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the "
+                         "concurrent-client latency run (p50_latency_ms ...) and, on a GPU, the "
+                         "reference-equivalent CPU run (--ref-cpu: reference_equivalent_cpu_fps, vs_baseline). "
+                         "A plain run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the decode pipeline hands its callers as "
+                         "DIR/<name>.npy (see dump_outputs); identical from run to run for the same arguments")
     a = ap.parse_args()
     if a.keyframe_only and a.source != "rtsp":
         ap.error("--keyframe-only needs --source rtsp (the ingest filters the access units)")
@@ -213,12 +226,12 @@ class GatherCheck:
 
 
 def start_client_pool(a):
-    """Latency clients in fresh processes, started before this process touches the GPU."""
+    """Latency clients in fresh processes, started before this process touches the GPU (--full)."""
+    if not a.full or (a.clients <= 0 and a.latency_samples <= 0):
+        return None
     from vep_bench.latency_clients import ClientPool
     from video_edge_ai_proxy_amd.utils import host_cpu_budget
 
-    if a.clients <= 0 and a.latency_samples <= 0:
-        return None
     n = max(1, a.clients)
     procs = a.client_procs or max(1, min(n, host_cpu_budget() // 2))
     return ClientPool(procs, (n + procs - 1) // procs)
@@ -332,16 +345,12 @@ class RtspFarm:
         self.srv = vep.RtspServer("127.0.0.1", 0)
         self.cams = a.cams_per_gpu
         self.stream_bytes = 0
+        self._cfg_args = (vep, a, rank, compressed)
 
         def add(i):  # (the farm pre-encodes each camera's GOPs: in parallel, GIL released)
-            c = make_cfg(vep, a, rank, compressed)
-            c.seed = c.seed + i * 7919
-            c.idr_phase = (i * a.gop) // self.cams  # unsynchronised cameras
-            self.srv.add_stream(f"/cam{i}", c, realtime=False, cached_frames=a.gop * a.cache_gops)
+            self.srv.add_stream(f"/cam{i}", self.stream_cfg(i), realtime=False, cached_frames=a.gop * a.cache_gops)
 
-        from concurrent.futures import ThreadPoolExecutor
-
-        with ThreadPoolExecutor(max(1, min(self.cams, (os.cpu_count() or 4), 16))) as ex:
+        with self._pool() as ex:
             list(ex.map(add, range(self.cams)))
         self.srv.start()
         # BASELINE config 5: RTMP pass-through of every camera to a loopback RTMP server
@@ -369,6 +378,55 @@ class RtspFarm:
         self.stop_evt = threading.Event()
         self.toucher = threading.Thread(target=self._touch_loop, daemon=True)
         self.toucher.start()
+
+    def stream_cfg(self, i):
+        """Camera i's stream: its own seed and GOP phase (unsynchronised cameras)."""
+        vep, a, rank, compressed = self._cfg_args
+        c = make_cfg(vep, a, rank, compressed)
+        c.seed = c.seed + i * 7919
+        c.idr_phase = (i * a.gop) // self.cams
+        return c
+
+    def _pool(self):
+        from concurrent.futures import ThreadPoolExecutor
+
+        return ThreadPoolExecutor(max(1, min(self.cams, (os.cpu_count() or 4), 16)))
+
+    def replay_step(self, frames):
+        """--dump-outputs: where the unthrottled farm's cameras stand when the timed region ends
+        depends on the run, so the sessions are stopped and every camera is handed the first
+        `frames` access units of its own stream again (from its IDR picture; fetched from the farm
+        by an RtspClient), through the lazy decoder's entry point the ingest calls
+        (Camera::on_access_unit -> host parse -> Worker batches -> GPU reconstruction, BGR24, ring
+        publish, letterbox). One frame interval of every camera at a time, published before the
+        next is submitted: no backlog forms, so no picture is merged into a catch-up batch or shed,
+        and when this returns each camera's ring and consumer row hold the same picture in every
+        run."""
+        vep = self._cfg_args[0]
+        for sess in self.sessions:
+            sess.stop()
+        self.sessions = []
+        self.worker.flush()
+        self.srv.set_pacing(0)  # (--full: the latency run left the farm in real time)
+        before = self.stats()
+
+        def fetch(i):  # (a new session starts at the stream's first cached access unit)
+            c = vep.RtspClient(f"rtsp://127.0.0.1:{self.srv.port}/cam{i}")
+            c.open()
+            aus, why = c.read(frames, 30.0)
+            c.close()
+            if len(aus) != frames:
+                raise RuntimeError(f"--dump-outputs: camera {i} sent {len(aus)} of {frames} access units ({why})")
+            return aus
+
+        with self._pool() as ex:
+            aus = list(ex.map(fetch, range(self.cams)))
+            for k in range(frames):  # (parse on the pool's threads, GIL released)
+                list(ex.map(lambda i: self.worker.submit_au(self.idx[i], aus[i][k]), range(self.cams)))
+                self.worker.flush()
+        after = self.stats()
+        if after["errors"] != before["errors"] or after["decoded"] <= before["decoded"]:
+            raise RuntimeError(f"--dump-outputs: replayed step did not decode cleanly ({before} -> {after})")
 
     def _touch(self):  # a client is watching every camera (the lazy decoder's last_query)
         now = int(time.time() * 1000)
@@ -434,6 +492,49 @@ class RtspFarm:
         if self.sink is not None:
             self.sink.stop()
         self.worker.stop()
+
+
+DUMP_SAMPLE = 6_000_000  # values kept of an array larger than this (float32: 24 MB; two such + sums < 64 MB)
+
+
+def dump_outputs(out_dir, worker, cam_idx, batch, letterbox, rank, world):
+    """--dump-outputs DIR: what the decode pipeline hands its callers, as DIR/<name>.npy
+    (<name>_rank<r>.npy with more than one rank):
+
+      frames_sample            float32  the cameras' newest BGR24 frames (what VideoLatestImage
+                                        serves: Worker.read_latest), (cams, H, W, 3) flattened; when
+                                        that is more than DUMP_SAMPLE values, the values at
+                                        sort(numpy.random.default_rng(0).integers(0, size, DUMP_SAMPLE))
+      frames_row_sums          float64  (cams, H): the sum of the bytes of each row of each frame, so
+                                        every pixel counts
+      frames_pts               float64  (cams,): the pts of each camera's frame
+      consumer_batch_sample, consumer_batch_row_sums
+                                        the same for the letterboxed consumer batch (cams, row bytes),
+                                        summed per --letterbox bytes
+
+    The callers make the pipeline's state the same in every run first (RtspFarm.replay_step; the
+    replay sources end on a drained tick), so two builds can be compared array for array."""
+    import numpy as np
+
+    def put(name, arr):
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), arr)
+
+    def sample(name, arr, chunk):
+        flat = arr.reshape(-1)
+        if flat.size > DUMP_SAMPLE:
+            flat = flat[np.sort(np.random.default_rng(0).integers(0, flat.size, DUMP_SAMPLE))]
+        put(name + "_sample", flat.astype(np.float32))
+        put(name + "_row_sums", arr.reshape(arr.shape[0], -1, chunk).sum(axis=2, dtype=np.float64))
+
+    os.makedirs(out_dir, exist_ok=True)
+    got = [worker.read_latest(cam, 0) for cam in cam_idx]
+    if any(g is None for g in got):
+        raise RuntimeError("--dump-outputs: a camera has published no frame")
+    frames = np.stack([g[1] for g in got])
+    sample("frames", frames, frames.shape[2] * 3)
+    put("frames_pts", np.array([g[0]["pts"] for g in got], dtype=np.float64))
+    if batch.numel():
+        sample("consumer_batch", batch.cpu().numpy(), letterbox)
 
 
 def thread_cpu() -> dict:
@@ -589,9 +690,9 @@ def run_rtsp(a, vep, torch, dist, worker, world, rank, use_gpu, dev, row, compre
                               device=dev)
             dist.all_reduce(fr, op=dist.ReduceOp.SUM)
             pictures, frames, dropped, errors, wire_bytes, aus, skipped, shed = (int(v) for v in fr.tolist())
-        # latency: every rank's cameras go live (real-time farm) with the production ingest
+        # latency (--full): every rank's cameras go live (real-time farm) with the production ingest
         # (lossy: a camera that outruns the decoder skips to its next keyframe), rank 0 measures
-        if pool is not None or world > 1:
+        if a.full and (pool is not None or world > 1):
             settled = farm.go_live(a.fps)
             ls0 = farm.stats()["skipped"]
             if world > 1:
@@ -605,6 +706,10 @@ def run_rtsp(a, vep, torch, dist, worker, world, rank, use_gpu, dev, row, compre
                 lat["live_skipped"] = farm.stats()["skipped"] - ls0
             if world > 1:
                 dist.barrier()
+        if a.dump_outputs:
+            farm.replay_step(min(a.frames_per_step, a.gop * a.cache_gops))
+            sync()
+            dump_outputs(a.dump_outputs, worker, farm.idx, live, a.letterbox, rank, world)
     finally:
         if annot is not None:
             annot.close()
@@ -674,7 +779,7 @@ def run_rtsp(a, vep, torch, dist, worker, world, rank, use_gpu, dev, row, compre
                                       "whose queued job reached a keyframe restarted from it (GOP catch-up collapse "
                                       "under load); frames_decoded counts only reconstructed pictures",
             "decode_errors": errors,
-            "concurrent_clients": a.clients,
+            "concurrent_clients": a.clients if a.full else 0,
             "rank0_gpu_kernel_ms_per_step": round(gpu_ms / a.steps, 4),
             "rank0_pictures_per_launch": round(pictures / max(1, batches), 3),
             "rank0_launches_merged": merged,
@@ -695,7 +800,7 @@ def run_rtsp(a, vep, torch, dist, worker, world, rank, use_gpu, dev, row, compre
         res.update(side)  # (rank 0's side loads)
         if n_gpus_scope(res):
             res["scope"] = n_gpus_scope(res)
-        if use_gpu and not a.cpu and a.ref_cpu == "on":
+        if a.full and use_gpu and not a.cpu and a.ref_cpu == "on":
             res.update(reference_fields(a, res, world))
         elif a.cpu and a.ref_equivalent:
             res["source_definition"] = REF_CPU_DEFINITION
@@ -729,11 +834,15 @@ def payload_path(a, compressed, worker, ip0, sg0, rg0=0, end=None):
 
 REF_CPU_DEFINITION = (
     "reference-equivalent CPU path (SURVEY.md §6 / BASELINE.md: FFmpeg, Redis and the Go server cannot run "
-    "here): the same cameras, streams, RTSP farm, steps and latency clients, decoded by this repo's CPU backend "
+    "here): the same cameras, streams, RTSP farm, steps (at most 40 of them) and latency clients, decoded by "
+    "this repo's CPU backend "
     "on rank 0's host-domain CPUs (its CPU share) - CPU CABAC parse, CPU reconstruction (the portable scalar "
     "bit-exact reference, no SIMD: libavcodec's SIMD decoder is faster, so vs_baseline is an upper bound), CPU "
     "NV12->BGR24 and the read_image.py:97/:119 tobytes + SerializeToString copy chain per published frame; "
     "whole-node value = per-share rate x ranks (each GPU has its own CPU share)")
+
+
+REF_STEPS_MAX = 40
 
 
 def reference_equivalent(a):
@@ -742,7 +851,9 @@ def reference_equivalent(a):
     import subprocess
 
     args = [a for a in sys.argv[1:]]
-    drop = {"--gpus", "--ref-cpu", "--warmup"}
+    # (--steps: the CPU path takes ~25x as long per step; its rate needs no more than REF_STEPS_MAX
+    # of them, and a --full run stays within minutes however many steps the GPU run times)
+    drop = {"--gpus", "--ref-cpu", "--warmup", "--steps", "--dump-outputs"}
     out, skip = [], False
     for x in args:
         if skip:
@@ -754,13 +865,16 @@ def reference_equivalent(a):
             continue
         out.append(x)
     cmd = [sys.executable, os.path.abspath(__file__), *out, "--cpu", "--ref-equivalent", "--ref-cpu", "off",
-           "--warmup", "1"]
+           "--warmup", "1", "--steps", str(min(a.steps, REF_STEPS_MAX))]
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                         "ROLE_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT") and not k.startswith("TORCHELASTIC")}
     env["VEP_HOST_CPUS"] = a.host_domain["cpulist"]
     t0 = time.perf_counter()
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
+    try:
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
+    except subprocess.TimeoutExpired:
+        return {"error": "reference-equivalent run did not finish in 420 s"}
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if not lines:
         return {"error": f"reference-equivalent run failed (rc {r.returncode}): {r.stderr[-400:]}"}
@@ -950,6 +1064,10 @@ def main():
         fr = torch.tensor([frames, dropped, launched], dtype=torch.float64, device=dev)
         dist.all_reduce(fr, op=dist.ReduceOp.SUM)
         frames, dropped, launched = (int(v) for v in fr.tolist())
+
+    if a.dump_outputs:  # (the last tick is drained: every camera's ring and its consumer buffer hold it)
+        last = (a.warmup + a.steps) * F - 1
+        dump_outputs(a.dump_outputs, worker, list(rb.cameras), bufs[last % NB], S, rank, world)
 
     lat = None
     if pool is not None:

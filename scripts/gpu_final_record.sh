@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"; O=gpurun_out/${TAG:-finalrec}; mkdir -p "$O"
 run() {  # name, bench args...
   local n=$1; shift
-  timeout -k 10 400 python -u bench.py "$@" > "$O/$n.json" 2> "$O/$n.err" || { echo "$n failed"; tail -20 "$O/$n.err"; exit 1; }
+  timeout -k 10 400 python -u bench.py --full "$@" > "$O/$n.json" 2> "$O/$n.err" || { echo "$n failed"; tail -20 "$O/$n.err"; exit 1; }
   python -c "import json; d=json.loads(open('$O/$n.json').read().strip().splitlines()[-1]); print('$n', d['value'], d['ms_per_step'], d.get('frames_dropped'), d.get('decode_errors'), d.get('p50_latency_ms'), d.get('p99_latency_ms'), d.get('rank0_gpu_kernel_ms_per_step'))"
 }
 run headline_3000 --steps 3000 --warmup 30

@@ -21,6 +21,6 @@ for i in 1 2 3; do
 done
 run kf_only VEP_SPIN_WAIT=0 --keyframe-only --steps 60 --warmup 8
 run h265_4k VEP_SPIN_WAIT=0 --codec h265 --width 3840 --height 2160 --cams-per-gpu 8 --steps 40 --warmup 6
-timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
+timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
   || { echo "driver bench failed"; tail -20 "$O/bench_driver.err"; exit 1; }
 python -c "import json; d=json.loads(open('$O/bench_driver.json').read().strip().splitlines()[-1]); print('driver', d['value'], d['p50_latency_ms'], d['p99_latency_ms'], d['frames_dropped'])"

@@ -17,7 +17,8 @@ import os
 import numpy as np
 import pytest
 
-CLIP = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+# imageio's sample clip realshort.mp4 (its resources/images collection), stored with the tests
+CLIP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "realshort.mp4")
 
 
 def clip_aus(native):

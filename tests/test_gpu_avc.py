@@ -160,7 +160,8 @@ def test_corrupt_slices_on_gpu_recover_at_idr(native):
                 assert np.array_equal(got, want[i]), f"trial {trial}: frame {i} differs"
 
 
-CLIP = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+# imageio's sample clip realshort.mp4 (its resources/images collection), stored with the tests
+CLIP = str(__import__("pathlib").Path(__file__).resolve().parent / "golden" / "realshort.mp4")
 
 
 @pytest.mark.skipif(not __import__("os").path.exists(CLIP), reason="imageio sample clip not in this image")

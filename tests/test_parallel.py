@@ -88,7 +88,7 @@ def test_bench_two_ranks_gloo():
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu", "--width", "96", "--height", "64",
            "--cams-per-gpu", "2", "--letterbox", "32", "--latency-samples", "3", "--threads", "1",
-           "--frames-per-step", "2"]
+           "--frames-per-step", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -227,7 +227,7 @@ def test_bench_config5_rtmp_annotation_cpu():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--codec", "h265", "--rtmp", "--annotate",
            "--annotate-rate", "20", "--steps", "40", "--warmup", "2", "--width", "128", "--height", "96",
            "--cams-per-gpu", "2", "--gop", "8", "--letterbox", "32", "--clients", "2", "--client-procs", "1",
-           "--latency-seconds", "1", "--latency-samples", "5", "--threads", "2"]
+           "--latency-seconds", "1", "--latency-samples", "5", "--threads", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -250,7 +250,7 @@ def test_bench_eight_ranks_gloo():
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "8", "--steps", "3", "--warmup", "1", "--cpu", "--width", "64", "--height", "48",
            "--cams-per-gpu", "1", "--letterbox", "16", "--latency-samples", "2", "--clients", "1",
-           "--client-procs", "1", "--latency-seconds", "1", "--threads", "1", "--gop", "6"]
+           "--client-procs", "1", "--latency-seconds", "1", "--threads", "1", "--gop", "6", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -260,3 +260,39 @@ def test_bench_eight_ranks_gloo():
     assert d["gather_verified"] is True and d["gather_check"]["mismatching_rows"] == 0
     assert d["gather_check"]["checked_gathers"] >= 8 and d["collective_backend"] == "gloo"
     assert d["frames_per_step"] == 6 and d["rccl_world"] == 0
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """A plain run (no --full) times the steps and nothing else: no latency clients, no
+    reference-equivalent run; --steps sets the timed steps and ms_per_step is reported. With
+    --dump-outputs it writes what the pipeline hands its callers, the same arrays in every run
+    (two runs, started together, compared array for array)."""
+    import numpy as np
+
+    def start(out):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--steps", "2", "--warmup", "1",
+               "--width", "96", "--height", "64", "--cams-per-gpu", "2", "--gop", "6", "--letterbox", "32",
+               "--threads", "1", "--dump-outputs", str(out)]
+        return subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT)
+
+    procs = [start(tmp_path / "a"), start(tmp_path / "b")]
+    for p in procs:
+        out, err = p.communicate(timeout=300)
+        assert p.returncode == 0, err[-2000:]
+        d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["frames_dropped"] == 0
+        assert d["frames_decoded"] >= 2 * 2 * 6  # cameras x steps x frames per step
+        assert "p50_latency_ms" not in d and "reference_equivalent_cpu_fps" not in d and d["concurrent_clients"] == 0
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["consumer_batch_row_sums.npy", "consumer_batch_sample.npy", "frames_pts.npy",
+                     "frames_row_sums.npy", "frames_sample.npy"]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.shape == y.shape and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    frames = np.load(tmp_path / "a" / "frames_sample.npy")
+    assert frames.size == 2 * 64 * 96 * 3 and frames.std() > 1  # whole frames at this size, real pictures
+    assert np.load(tmp_path / "a" / "frames_row_sums.npy").sum() == frames.sum()
+    assert np.load(tmp_path / "a" / "consumer_batch_sample.npy").size == 2 * 32 * 32 * 3 // 2
