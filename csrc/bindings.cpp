@@ -1256,7 +1256,8 @@ PYBIND11_MODULE(_vep, m) {
       .def_property_readonly("launch_seq", &Worker::launch_seq)
       .def("wait_published", &Worker::wait_published, py::arg("seq"),
            py::call_guard<py::gil_scoped_release>())
-      .def("add_camera", &Worker::add_camera, py::arg("name"), py::arg("ring_slots") = 2)
+      .def("add_camera", &Worker::add_camera, py::arg("name"), py::arg("ring_slots") = 2, py::arg("history") = 0)
+      .def("history_ring_slots", &Worker::history_ring_slots, py::arg("history"))
       .def("remove_camera", &Worker::remove_camera, py::call_guard<py::gil_scoped_release>())
       .def("find", [](Worker& w, const std::string& n) { auto c = w.find(n); return c ? c->index() : -1; })
       .def("num_cameras", &Worker::num_cameras)
@@ -1358,6 +1359,8 @@ PYBIND11_MODULE(_vep, m) {
              d["width"] = ring ? ring->width() : 0;
              d["height"] = ring ? ring->height() : 0;
              d["ring_slots"] = ring ? ring->slots() : c.ring_slots_cfg;
+             d["history"] = c.history();
+             d["history_skipped"] = c.history_skipped.load();
              py::list hist;
              for (auto& h : c.lat_hist) hist.append(h.load());
              d["latency_hist"] = hist;
@@ -1387,6 +1390,62 @@ PYBIND11_MODULE(_vep, m) {
              return py::make_tuple(meta_dict(m), out);
            },
            py::arg("idx"), py::arg("after") = 0)
+      .def("read_history",
+           // [(meta, ndarray)] of the newest `count` (0 = the camera's history depth) frames with
+           // seq > after: ascending, contiguous in seq, ending at the newest frame.
+           [](Worker& w, int i, i64 after, int count) {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             std::vector<Worker::HistoryFrame> fs;
+             {
+               py::gil_scoped_release r;
+               fs = w.read_history(i, after, count);
+             }
+             py::list out;
+             for (Worker::HistoryFrame& f : fs) {
+               u8* p = f.data.release();
+               py::capsule own(p, [](void* q) { delete[] static_cast<u8*>(q); });
+               py::array_t<uint8_t> a({py::ssize_t(f.meta.height), py::ssize_t(f.meta.width), py::ssize_t(3)}, p, own);
+               out.append(py::make_tuple(meta_dict(f.meta), a));
+             }
+             return out;
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("count") = 0)
+      .def("history_seqs",
+           // the seqs read_history would return (nothing is copied)
+           [](Worker& w, int i, i64 after, int count) {
+             std::vector<i64> seqs;
+             std::shared_ptr<FrameRing> ring = cam_of(w, i).ring();
+             if (!ring) return seqs;
+             const int depth = std::max(1, ring->history());
+             std::vector<std::pair<FrameMeta, int>> v;
+             ring->range(after, count > 0 ? std::min(count, depth) : depth, v);
+             for (const auto& e : v) seqs.push_back(e.first.seq);
+             return seqs;
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("count") = 0)
+      .def("video_frames",
+           // [(seq, bytes)]: the same frames as serialized VideoFrame protos (encode_video_frame).
+           [](Worker& w, int i, i64 after, int count, const std::string& device_id) {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             std::vector<Worker::HistoryFrame> fs;
+             {
+               py::gil_scoped_release r;
+               fs = w.read_history(i, after, count);
+             }
+             py::list out;
+             for (const Worker::HistoryFrame& f : fs) {
+               const auto [pre, suf] = encode_video_frame(f.meta, f.bytes, device_id);
+               PyObject* b = PyBytes_FromStringAndSize(nullptr, Py_ssize_t(pre.size() + f.bytes + suf.size()));
+               if (!b) throw py::error_already_set();
+               char* buf = PyBytes_AS_STRING(b);
+               std::memcpy(buf, pre.data(), pre.size());
+               std::memcpy(buf + pre.size(), f.data.get(), f.bytes);
+               std::memcpy(buf + pre.size() + f.bytes, suf.data(), suf.size());
+               out.append(py::make_tuple(f.meta.seq, py::reinterpret_steal<py::object>(b)));
+             }
+             return out;
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("count") = 0, py::arg("device_id") = "")
       .def("video_frame_bound",
            // Upper bound of the serialized VideoFrame of this camera's current ring (0: no ring).
            [](Worker& w, int i, const std::string& device_id) -> size_t {
@@ -1614,6 +1673,73 @@ PYBIND11_MODULE(_vep, m) {
           d.tile_begin = 0;
           gpu::launch_decode_convert_one(d, reinterpret_cast<hipStream_t>(stream));
         });
+  // Reconstructed surface (u8 or u16 samples, 4:2:0 or 4:2:2) -> BGR24 (gpu::SurfaceBgrDesc).
+  m.def("surface_to_bgr",
+        [](uintptr_t y, uintptr_t uv, int pitch, int coded_w, int coded_h, int bit_depth, int chroma_format,
+           int crop_left, int crop_top, int out_w, int out_h, uintptr_t out, uintptr_t stream) {
+          gpu::SurfaceBgrDesc d{};
+          d.y = reinterpret_cast<const u8*>(y);
+          d.uv = reinterpret_cast<const u8*>(uv);
+          d.bgr = reinterpret_cast<u8*>(out);
+          d.pitch = pitch;
+          d.coded_w = coded_w;
+          d.coded_h = coded_h;
+          d.bit_depth = bit_depth;
+          d.chroma_format = chroma_format;
+          d.crop_left = crop_left;
+          d.crop_top = crop_top;
+          d.out_w = out_w;
+          d.out_h = out_h;
+          gpu::check_surface_bgr(d);
+          gpu::launch_surface_to_bgr_one(d, reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("y"), py::arg("uv"), py::arg("pitch"), py::arg("coded_w"), py::arg("coded_h"), py::arg("bit_depth"),
+        py::arg("chroma_format"), py::arg("crop_left"), py::arg("crop_top"), py::arg("out_w"), py::arg("out_h"),
+        py::arg("out"), py::arg("stream"));
+  // Several pictures in ONE launch (the worker's per-round launch: descriptor table in device
+  // memory, block -> picture by the tile prefix). pics: (y, uv, pitch, coded_w, coded_h, bit_depth,
+  // chroma_format, crop_left, crop_top, out_w, out_h, out) each. Waits for the launch.
+  m.def("surface_to_bgr_many",
+        [](const std::vector<std::tuple<uintptr_t, uintptr_t, int, int, int, int, int, int, int, int, int, uintptr_t>>& pics,
+           uintptr_t stream) {
+          if (pics.empty()) return 0;
+          std::vector<gpu::SurfaceBgrDesc> descs;
+          int tiles = 0;
+          for (const auto& p : pics) {
+            gpu::SurfaceBgrDesc d{};
+            d.y = reinterpret_cast<const u8*>(std::get<0>(p));
+            d.uv = reinterpret_cast<const u8*>(std::get<1>(p));
+            d.pitch = std::get<2>(p);
+            d.coded_w = std::get<3>(p);
+            d.coded_h = std::get<4>(p);
+            d.bit_depth = std::get<5>(p);
+            d.chroma_format = std::get<6>(p);
+            d.crop_left = std::get<7>(p);
+            d.crop_top = std::get<8>(p);
+            d.out_w = std::get<9>(p);
+            d.out_h = std::get<10>(p);
+            d.bgr = reinterpret_cast<u8*>(std::get<11>(p));
+            gpu::check_surface_bgr(d);
+            d.tile_begin = tiles;
+            tiles += gpu::tiles_for(d.coded_w / 16, d.coded_h / 16);
+            descs.push_back(d);
+          }
+          const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+          void* dd = nullptr;
+          const size_t bytes = descs.size() * sizeof(gpu::SurfaceBgrDesc);
+          VEP_HIP(hipMalloc(&dd, bytes));
+          try {
+            VEP_HIP(hipMemcpyAsync(dd, descs.data(), bytes, hipMemcpyHostToDevice, s));
+            gpu::launch_surface_to_bgr(static_cast<const gpu::SurfaceBgrDesc*>(dd), int(descs.size()), tiles, s);
+            VEP_HIP(hipStreamSynchronize(s));
+          } catch (...) {
+            (void)hipFree(dd);
+            throw;
+          }
+          (void)hipFree(dd);
+          return tiles;
+        },
+        py::arg("pics"), py::arg("stream"));
   m.def("letterbox",
         [](uintptr_t y, uintptr_t uv, int pitch, int src_w, int src_h, int crop_left, int crop_top,
            int size, uintptr_t out_hwc, uintptr_t out_chw, int chw_dtype, std::vector<float> mean,

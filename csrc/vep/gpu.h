@@ -72,6 +72,31 @@ void launch_decode_convert(const DecodeDesc* d_descs, int n, int total_tiles, hi
 // Single-frame variant: descriptor passed by value (op API on caller-owned buffers).
 void launch_decode_convert_one(const DecodeDesc& d, hipStream_t s);
 
+// One picture of a batched surface_to_bgr launch (device memory): a reconstructed DPB surface of
+// any supported sample format -> packed BGR24, bit-exact with cpu_nv12_to_bgr (codec.h) including
+// narrow_surface: samples above 8 bits are rounded to 8 in registers, 4:2:2 chroma rows are
+// averaged in pairs before that. Nothing is staged: no 8-bit scratch copy, no LDS. The frame
+// history path (runtime.h) converts the outputs a multi-picture job releases with it, between
+// reconstruction rounds, while their surfaces are intact.
+struct SurfaceBgrDesc {
+  const VEP_DEV u8* y;   // luma plane: u8 samples (bit_depth 8) or u16 (9..10), 16-byte aligned
+  const VEP_DEV u8* uv;  // interleaved chroma plane: coded_h / 2 rows (4:2:0) or coded_h rows (4:2:2)
+  VEP_DEV u8* bgr;       // out_h x out_w x 3
+  i32 pitch;             // samples per plane row (multiple of 16)
+  i32 coded_w, coded_h;  // multiples of 16
+  i32 bit_depth;         // 8..10
+  i32 chroma_format;     // 1 = 4:2:0, 2 = 4:2:2
+  i32 crop_left, crop_top;
+  i32 out_w, out_h;
+  i32 tile_begin;        // exclusive prefix sum of tiles over the batch
+};
+// (tiles of 128 x 32 samples: tiles_for(coded_w / 16, coded_h / 16))
+void launch_surface_to_bgr(const SurfaceBgrDesc* d_descs, int n, int total_tiles, hipStream_t s);
+void launch_surface_to_bgr_one(const SurfaceBgrDesc& d, hipStream_t s);
+// Throws unless the descriptor's geometry keeps every access of the kernel inside the planes
+// and the output (the launches above do not check).
+void check_surface_bgr(const SurfaceBgrDesc& d);
+
 // Gather: copy byte ranges from device-accessible (pinned, mapped) host memory into device
 // memory over PCIe — one workgroup per chunk, 16-byte loads per lane. Replaces a host memcpy
 // into staging + SDMA copy when the slice bytes already live in the pinned ingest pool.

@@ -174,6 +174,129 @@ void launch_decode_convert(const DecodeDesc* d_descs, int n, int total_tiles, hi
 }
 
 // ---------------------------------------------------------------------------------------------
+// surface_to_bgr: a reconstructed surface (u8 or u16 samples, 4:2:0 or 4:2:2) -> BGR24, the
+// narrowing of narrow_surface (codec.cpp) done in registers. Same shape as decode_convert's
+// phase 2 (a 256-thread workgroup on a 128 x 32 tile, lane = one 16-sample row segment, 16-byte
+// loads, three 16-byte stores) without its PCM placement and LDS staging: a streaming kernel,
+// 1.5 B read (3 B for u16, 2 / 4 B for 4:2:2) and 3 B written per pixel.
+
+typedef u32 su4 __attribute__((ext_vector_type(4)));
+
+// 16 samples at p (16-byte aligned) as dwords: 4 (u8 samples) or 8 (u16 samples)
+template <bool WIDE>
+__device__ __forceinline__ void load16(const VEP_DEV u8* p, u32* w) {
+  const su4 a = *reinterpret_cast<const VEP_DEV su4*>(p);
+  w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w;
+  if constexpr (WIDE) {
+    const su4 b = *reinterpret_cast<const VEP_DEV su4*>(p + 16);
+    w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
+  }
+}
+template <bool WIDE>
+__device__ __forceinline__ int sample_of(const u32* w, int i) {
+  if constexpr (WIDE) return int((w[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+  return int((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
+}
+
+template <bool WIDE>
+__device__ __forceinline__ void surface_to_bgr_row(const SurfaceBgrDesc& d, const int x0, const int sy,
+                                                   const int ox, const int oy) {
+  constexpr int kB = WIDE ? 2 : 1, kW = 4 * kB;
+  const int sh = d.bit_depth - 8, rnd = (1 << sh) >> 1;
+  const size_t pitch = size_t(d.pitch);
+  u32 yw[kW], ca[kW], cb[kW];
+  load16<WIDE>(d.y + (size_t(sy) * pitch + size_t(x0)) * kB, yw);
+  const bool c422 = d.chroma_format == 2;  // (wave-uniform)
+  const size_t crow = c422 ? size_t(sy & ~1) : size_t(sy >> 1);
+  load16<WIDE>(d.uv + (crow * pitch + size_t(x0)) * kB, ca);
+  if (c422) load16<WIDE>(d.uv + ((crow + 1) * pitch + size_t(x0)) * kB, cb);
+  su4 y8 = {0, 0, 0, 0}, c8 = {0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int y = min(255, (sample_of<WIDE>(yw, i) + rnd) >> sh);
+    int c = sample_of<WIDE>(ca, i);
+    if (c422) c = (c + sample_of<WIDE>(cb, i) + 1) >> 1;  // rounded mean of the row pair, then narrowed
+    c = min(255, (c + rnd) >> sh);
+    y8[i >> 2] |= u32(y) << (8 * (i & 3));
+    c8[i >> 2] |= u32(c) << (8 * (i & 3));
+  }
+  u32 o[12];
+  convert16(make_uint4(y8.x, y8.y, y8.z, y8.w), make_uint4(c8.x, c8.y, c8.z, c8.w), o);
+  if (ox >= 0 && ox + 16 <= d.out_w) {
+    // 48 contiguous bytes; 16-B aligned whenever out_w % 16 == 0 and crop_left % 16 == 0
+    u8* dst = d.bgr + (size_t(oy) * size_t(d.out_w) + size_t(ox)) * 3;
+    const su4 a = {o[0], o[1], o[2], o[3]}, bq = {o[4], o[5], o[6], o[7]}, cq = {o[8], o[9], o[10], o[11]};
+    __builtin_memcpy(dst, &a, 16);
+    __builtin_memcpy(dst + 16, &bq, 16);
+    __builtin_memcpy(dst + 32, &cq, 16);
+  } else {  // ragged left / right crop edge
+    for (int i = 0; i < 16; ++i) {
+      const int x = ox + i;
+      if (x < 0 || x >= d.out_w) continue;
+      for (int k = 0; k < 3; ++k) {
+        const int bi = 3 * i + k;
+        d.bgr[(size_t(oy) * size_t(d.out_w) + size_t(x)) * 3 + k] = u8(o[bi >> 2] >> (8 * (bi & 3)));
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void surface_to_bgr_tile(const SurfaceBgrDesc& d, const int tile) {
+  const int tiles_x = (d.coded_w / 16 + kTileMbW - 1) / kTileMbW;
+  const int tx = tile % tiles_x, ty = tile / tiles_x;
+  const int t = threadIdx.x;
+  const int x0 = (tx * kTileMbW + (t & 7)) * 16;
+  const int sy = ty * kTileMbH * 16 + (t >> 3);
+  if (x0 >= d.coded_w || sy >= d.coded_h) return;
+  const int oy = sy - d.crop_top, ox = x0 - d.crop_left;
+  if (oy < 0 || oy >= d.out_h || ox + 16 <= 0 || ox >= d.out_w) return;  // nothing of it is shown
+  if (d.bit_depth > 8) surface_to_bgr_row<true>(d, x0, sy, ox, oy);
+  else surface_to_bgr_row<false>(d, x0, sy, ox, oy);
+}
+
+__global__ __launch_bounds__(256) void surface_to_bgr_kernel(const SurfaceBgrDesc* __restrict__ descs, int n) {
+  // block -> picture: binary search over the tile prefix (wave-uniform, scalar loads)
+  const int b = blockIdx.x;
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    int mid = (lo + hi + 1) >> 1;
+    if (descs[mid].tile_begin <= b) lo = mid; else hi = mid - 1;
+  }
+  const SurfaceBgrDesc d = descs[lo];
+  surface_to_bgr_tile(d, b - d.tile_begin);
+}
+
+__global__ __launch_bounds__(256) void surface_to_bgr_one_kernel(const SurfaceBgrDesc d) {
+  surface_to_bgr_tile(d, blockIdx.x);
+}
+
+void check_surface_bgr(const SurfaceBgrDesc& d) {
+  VEP_CHECK(d.y && d.uv && d.bgr, "surface_to_bgr: null plane");
+  VEP_CHECK((reinterpret_cast<uintptr_t>(d.y) & 15) == 0 && (reinterpret_cast<uintptr_t>(d.uv) & 15) == 0,
+            "surface_to_bgr: planes must be 16-byte aligned");
+  VEP_CHECK(d.bit_depth >= 8 && d.bit_depth <= 10, "surface_to_bgr: bit depth must be 8..10");
+  VEP_CHECK(d.chroma_format == 1 || d.chroma_format == 2, "surface_to_bgr: chroma format must be 1 (4:2:0) or 2 (4:2:2)");
+  VEP_CHECK(d.coded_w > 0 && d.coded_h > 0 && d.coded_w % 16 == 0 && d.coded_h % 16 == 0 && d.coded_w <= (1 << 15) &&
+                d.coded_h <= (1 << 15),
+            "surface_to_bgr: coded size must be a positive multiple of 16");
+  VEP_CHECK(d.pitch >= d.coded_w && d.pitch % 16 == 0, "surface_to_bgr: pitch must be a multiple of 16 covering the coded width");
+  VEP_CHECK(d.crop_left >= 0 && d.crop_top >= 0 && d.out_w > 0 && d.out_h > 0 && d.crop_left + d.out_w <= d.coded_w &&
+                d.crop_top + d.out_h <= d.coded_h,
+            "surface_to_bgr: output window outside the coded picture");
+}
+
+void launch_surface_to_bgr_one(const SurfaceBgrDesc& d, hipStream_t s) {
+  hipLaunchKernelGGL(surface_to_bgr_one_kernel, dim3(tiles_for(d.coded_w / 16, d.coded_h / 16)), dim3(256), 0, s, d);
+  VEP_HIP(hipGetLastError());
+}
+
+void launch_surface_to_bgr(const SurfaceBgrDesc* d_descs, int n, int total_tiles, hipStream_t s) {
+  if (n <= 0 || total_tiles <= 0) return;
+  hipLaunchKernelGGL(surface_to_bgr_kernel, dim3(total_tiles), dim3(256), 0, s, d_descs, n);
+  VEP_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------
 // Gather (pinned host -> device). The source is read once over PCIe: 256 lanes x 16 B per
 // iteration keeps 4 KiB in flight per workgroup; dst offsets are 16-byte aligned.
 

@@ -163,7 +163,18 @@ void Decoder::start_picture(const SliceHeader& sh, int tid, const Sps& sps, cons
     for (const FramePtr& f : dpb_) used[size_t(f->slot)] = true;
     if (last_out_slot_ >= 0 && last_out_slot_ < gpu_slots_) used[size_t(last_out_slot_)] = true;
     int slot = 0;
+    if (pin_outputs_) {  // (set_pin_outputs: the pictures this access unit has output so far)
+      std::vector<bool> pinned = used;
+      for (const FramePtr& f : out)
+        if (f->slot >= 0 && f->slot < gpu_slots_) pinned[size_t(f->slot)] = true;
+      while (slot < gpu_slots_ && pinned[size_t(slot)]) ++slot;
+      // (they left the DPB, so with the current picture they fit its max_dec_pic_buffering + 2
+      // surfaces; should a stream break that, the output whose surface is taken loses its slot)
+      if (slot >= gpu_slots_) slot = 0;
+    }
     while (slot < gpu_slots_ && used[size_t(slot)]) ++slot;
+    for (const FramePtr& f : out)
+      if (pin_outputs_ && f->slot == slot && f->slot != last_out_slot_) f->slot = -1;
     VEP_CHECK(slot < gpu_slots_, "HEVC: no free DPB surface");
     cur_->slot = slot;
   } else {

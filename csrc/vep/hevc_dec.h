@@ -116,6 +116,12 @@ class Decoder {
   // pictures parsed since the last call, in decoding order.
   void set_gpu_mode(bool on) { gpu_mode_ = on; }
   bool gpu_mode() const { return gpu_mode_; }
+  // Records mode: a picture never takes the surface slot of a picture output while it started
+  // (C.5.2.2 bumping in start_picture), so every output of decode(au) stays intact until the
+  // picture AFTER the one that released it is reconstructed. Without the pin only the last
+  // output's slot is kept (last_out_slot_). Used by cameras with a frame history, which convert
+  // each output after the reconstruction round of the picture that released it.
+  void set_pin_outputs(bool on) { pin_outputs_ = on; }
   std::vector<std::shared_ptr<struct GpuPicture>> take_gpu_pictures();
   int gpu_slots() const { return gpu_slots_; }  // surfaces a camera needs (max DPB + 2)
   FramePtr last_decoded() const { return last_; }
@@ -154,7 +160,7 @@ class Decoder {
   bool first_ = true, no_rasl_output_ = true, skip_pic_ = false;
   i64 irap_tag_ = -1;  // decode tag of the last IRAP picture (RASL pictures' association)
   u32 next_uid_ = 1;
-  bool gpu_mode_ = false;
+  bool gpu_mode_ = false, pin_outputs_ = false;
   int gpu_slots_ = 0, last_out_slot_ = -1;
   std::shared_ptr<struct GpuPicture> cur_gpu_;
   // records-mode pictures recycled per decoder (recycle.h: resident buffers, no page faults)

@@ -62,15 +62,46 @@ void Device::free_pinned(void* p) {
 
 // --------------------------------------------------------------------------------- FrameRing
 
-FrameRing::FrameRing(Device& dev, int slots, int width, int height)
-    : dev_(dev), w_(width), h_(height) {
+FrameRing::FrameRing(Device& dev, int slots, int width, int height, int history)
+    : dev_(dev), w_(width), h_(height), hist_(std::max(0, history)) {
   VEP_CHECK(slots >= 1 && slots <= 4096, "ring slots out of range");
+  VEP_CHECK(hist_ == 0 || slots > hist_, "ring too small for its history");
   base_ = static_cast<u8*>(dev_.alloc(slot_bytes() * size_t(slots)));
   for (int i = 0; i < slots; ++i) slots_.emplace_back(std::make_unique<Slot>());
 }
 FrameRing::~FrameRing() { dev_.free(base_); }
 
+// History rule: the first slot from next_ that is neither being written nor one of the hist_
+// newest committed frames (seq > published - hist_).
+int FrameRing::pick_free() const {
+  const int n = int(slots_.size());
+  const i64 keep_above = published_.load() - hist_;
+  for (int k = 0; k < n; ++k) {
+    const int c = (next_ + k) % n;
+    const Slot& sl = *slots_[size_t(c)];
+    const u64 v = sl.version.load();
+    if (v & 1) continue;
+    if (v != 0 && sl.meta.seq > 0 && sl.meta.seq > keep_above) continue;  // (v 0: never written)
+    return c;
+  }
+  return -1;
+}
+
+int FrameRing::try_write() {
+  std::lock_guard<std::mutex> g(meta_mu_);
+  const int s = pick_free();
+  if (s < 0) return -1;
+  next_ = (s + 1) % int(slots_.size());
+  slots_[size_t(s)]->version.fetch_add(1, std::memory_order_acq_rel);  // odd: being written
+  slots_[size_t(s)]->meta.seq = 0;  // (range() must not take it for its old frame if the write is aborted)
+  return s;
+}
+
 int FrameRing::begin_write() {
+  if (hist_ > 0) {  // (the ring is sized so that a slot is free: Worker::history_ring_slots)
+    const int s = try_write();
+    if (s >= 0) return s;
+  }
   std::lock_guard<std::mutex> g(meta_mu_);
   // never overwrite the newest committed frame or a slot an in-flight batch is writing
   const int n = int(slots_.size());
@@ -84,7 +115,25 @@ int FrameRing::begin_write() {
   }
   next_ = (s + 1) % n;
   slots_[s]->version.fetch_add(1, std::memory_order_acq_rel);  // odd: being written
+  if (hist_ > 0) slots_[s]->meta.seq = 0;
   return s;
+}
+
+int FrameRing::range(i64 after_seq, int max_count, std::vector<std::pair<FrameMeta, int>>& out) const {
+  out.clear();
+  if (max_count <= 0) return 0;
+  std::lock_guard<std::mutex> g(meta_mu_);
+  const i64 newest = published_.load();
+  // seq s (newest, newest - 1, ...) lives in at most one stable slot; stop at the first gap
+  for (i64 s = newest; s > std::max<i64>(after_seq, 0) && int(out.size()) < max_count; --s) {
+    int hit = -1;
+    for (size_t k = 0; k < slots_.size(); ++k)
+      if (!(slots_[k]->version.load() & 1) && slots_[k]->meta.seq == s) hit = int(k);
+    if (hit < 0) break;
+    out.emplace_back(slots_[size_t(hit)]->meta, hit);
+  }
+  std::reverse(out.begin(), out.end());
+  return int(out.size());
 }
 
 void FrameRing::commit(int slot, FrameMeta meta) {
@@ -150,8 +199,10 @@ std::string LogRing::dump(bool err, size_t last) const {
 
 // ------------------------------------------------------------------------------------ Camera
 
-Camera::Camera(Worker& w, int index, std::string name, int ring_slots)
-    : ring_slots_cfg(ring_slots), w_(w), index_(index), name_(std::move(name)), use_vcn_(w.vcn()) {
+Camera::Camera(Worker& w, int index, std::string name, int ring_slots, int history)
+    : ring_slots_cfg(ring_slots), w_(w), index_(index), name_(std::move(name)), history_(history), use_vcn_(w.vcn()) {
+  // (H.265: the outputs a picture's start releases keep their surfaces until it is reconstructed)
+  hevc_.set_pin_outputs(history_ > 0);
   // Fault injection (tests of per-camera-group containment): VEP_FAULT_CAMERA=<name>[:<n>] makes
   // this camera's n-th access unit (default 1) crash the process inside its parse, as a bug in
   // the bitstream parser hit by a hostile stream would.
@@ -271,6 +322,31 @@ bool Camera::build_job(DecodeJob& job, size_t from, size_t to, bool refresh) {
         for (auto& p : hevc_.take_gpu_pictures()) job.hevc.push_back(std::move(p));
         if (!outs.empty()) of = outs.back();
         last = gop_[i].get();
+        if (history_ > 0)  // every output, with the job picture that released it
+          for (const hevc::FramePtr& f : outs) {
+            JobOutput o;
+            o.slot = f->slot;
+            o.released_by = std::max(0, int(job.hevc.size()) - 1);
+            o.rasl_of = f->rasl_of;
+            o.pic.width = f->width;
+            o.pic.height = f->height;
+            o.pic.crop_left = f->crop_left;
+            o.pic.crop_top = f->crop_top;
+            o.pic.pict_type = f->type;
+            o.pic.idr = f->keyframe;
+            FrameMeta& m = o.meta;
+            m.width = f->width;
+            m.height = f->height;
+            m.pts = f->pts;
+            m.dts = f->dts;
+            m.timestamp = f->pts;
+            m.packet = f->tag;
+            m.keyframe = keyframes_;
+            m.is_keyframe = f->keyframe;
+            m.frame_type = f->type;
+            m.arrival_ms = last->arrival_ms;
+            job.outputs.push_back(std::move(o));
+          }
       }
       decoded_upto_ = to;
       if (job.hevc.empty()) return false;
@@ -304,13 +380,43 @@ bool Camera::build_job(DecodeJob& job, size_t from, size_t to, bool refresh) {
       m.is_corrupt = false;
       m.frame_type = of->type;
       m.arrival_ms = last->arrival_ms;
+      for (JobOutput& o : job.outputs) {
+        o.pic.coded_width = pi.coded_width;
+        o.pic.coded_height = pi.coded_height;
+      }
+      if (!job.outputs.empty()) {  // (the newest one is the picture pic / meta describe)
+        job.outputs.back().pic = job.pic;
+        job.outputs.back().meta = job.meta;
+      }
       return true;
     }
     if (full_) {
       for (size_t i = from; i < to; ++i) {
         size_t nal = 0;  // (a field pair may come as one access unit: one picture per field)
-        do job.avc.push_back(avc_.parse(*gop_[i], i64(i), &nal));
-        while (nal < gop_[i]->nals.size());
+        do {
+          job.avc.push_back(avc_.parse(*gop_[i], i64(i), &nal));
+          if (history_ > 0)  // every output, with the job picture that released it
+            for (const avc::OutFrame& f : job.avc.back()->outputs) {
+              JobOutput o;
+              o.slot = f.slot;
+              o.fields = f.fields;
+              o.released_by = int(job.avc.size()) - 1;
+              o.pic = f.info;
+              FrameMeta& m = o.meta;
+              m.width = f.info.width;
+              m.height = f.info.height;
+              m.pts = f.au.pts;
+              m.dts = f.au.dts;
+              m.timestamp = f.au.pts;
+              m.packet = f.au.tag;
+              m.keyframe = keyframes_;
+              m.is_keyframe = f.au.keyframe;
+              m.is_corrupt = f.au.corrupt;
+              m.frame_type = f.info.pict_type;
+              m.arrival_ms = gop_[i]->arrival_ms;
+              job.outputs.push_back(std::move(o));
+            }
+        } while (nal < gop_[i]->nals.size());
         last = gop_[i].get();
       }
       job.pic = job.avc.back()->info;
@@ -334,6 +440,7 @@ bool Camera::build_job(DecodeJob& job, size_t from, size_t to, bool refresh) {
         m.is_corrupt = of->au.corrupt;
         m.frame_type = of->info.pict_type;
         m.arrival_ms = last->arrival_ms;  // latency: from the packet that completed the output
+        if (!job.outputs.empty()) job.outputs.back().meta = job.meta;
         decoded_upto_ = to;
         return true;
       }
@@ -638,7 +745,21 @@ Worker::~Worker() {
   if (serve_stream_) (void)hipStreamDestroy(serve_stream_);
 }
 
-int Worker::add_camera(const std::string& name, int ring_slots) {
+// Ring slots of a camera with history depth H. A batch holds up to H slots of the camera while
+// it is in flight (H - 1 history outputs and the newest frame), F = inflight() (+ 1 with lane
+// threads: the batch being launched) batches can be in flight when the next one reserves its
+// slots, and the H newest committed frames are never written: H * (F + 2) slots, so a reservation
+// always finds a free one. At 1920x1080 BGR24 (6.2 MB a slot), H = 5 and the default 3 stages
+// that is 25 slots, 155 MB of HBM per camera (CPU backend, F = 0: 10 slots of host memory).
+int Worker::history_ring_slots(int history) const {
+  if (history <= 0) return 0;
+  const int f = dev_.gpu() ? inflight() + (threaded_ ? 1 : 0) : 0;
+  return history * (f + 2);
+}
+
+int Worker::add_camera(const std::string& name, int ring_slots, int history) {
+  VEP_CHECK(history >= 0 && history <= 64, "camera history depth out of range (0..64)");
+  ring_slots = std::max(ring_slots, history_ring_slots(history));
   std::lock_guard<std::mutex> g(cams_mu_);
   for (auto& c : cams_)
     VEP_CHECK(!c || c->name() != name, "camera already registered: " + name);
@@ -653,7 +774,7 @@ int Worker::add_camera(const std::string& name, int ring_slots) {
   // `stages` batches may be in flight on the GPU (+ the lane thread's queue and the batch it is
   // launching): keep one more slot so the newest committed frame stays readable meanwhile
   const int min_slots = dev_.gpu() ? inflight() + (threaded_ ? 2 : 1) : 1;
-  cams_[size_t(idx)] = std::make_shared<Camera>(*this, idx, name, std::max(min_slots, ring_slots));
+  cams_[size_t(idx)] = std::make_shared<Camera>(*this, idx, name, std::max(min_slots, ring_slots), history);
   return idx;
 }
 
@@ -745,14 +866,16 @@ static void fold_update(MbUpdate& into, const MbUpdate& from) {
   into.frames += from.frames;
 }
 
-// Whether one of the job's own pictures reconstructs its output slot.
-static bool reconstructs_output(const DecodeJob& j) {
+// Whether one of the job's own pictures reconstructs DPB slot `slot`.
+static bool reconstructs_slot(const DecodeJob& j, int slot) {
   for (const auto& p : j.avc)
-    if ((p->structure ? p->target / 2 : p->target) == j.out_slot) return true;
+    if ((p->structure ? p->target / 2 : p->target) == slot) return true;
   for (const auto& p : j.hevc)
-    if (p->target == j.out_slot) return true;
+    if (p->target == slot) return true;
   return false;
 }
+// Whether one of the job's own pictures reconstructs its output slot.
+static bool reconstructs_output(const DecodeJob& j) { return reconstructs_slot(j, j.out_slot); }
 
 void merge_job(DecodeJob& p, DecodeJob&& job) {
   VEP_CHECK(p.cam == job.cam, "merge_job: different cameras");
@@ -780,7 +903,16 @@ void merge_job(DecodeJob& p, DecodeJob&& job) {
       p.out_slot = -1;
       p.out_fields = false;
     }
+    // (history: the same rule for every output of the kept job)
+    p.outputs.erase(std::remove_if(p.outputs.begin(), p.outputs.end(),
+                                   [&](const JobOutput& o) { return !reconstructs_slot(p, o.slot); }),
+                    p.outputs.end());
   } else if (job.general() && p.general()) {
+    const int base = int(!p.avc.empty() ? p.avc.size() : p.hevc.size());  // job's pictures follow p's
+    for (JobOutput& o : job.outputs) {
+      o.released_by += base;
+      p.outputs.push_back(std::move(o));
+    }
     p.avc.insert(p.avc.end(), job.avc.begin(), job.avc.end());
     p.hevc.insert(p.hevc.end(), job.hevc.begin(), job.hevc.end());
     p.hevc_slots = std::max(p.hevc_slots, job.hevc_slots);
@@ -971,7 +1103,7 @@ void Worker::ensure_surface(Camera& c, const PictureInfo& pi, int slots, int bd,
     s.host.assign(size_t(s.slots), HostSurface{});
     for (auto& h : s.host) h.alloc(wmbs * 16, hmbs * 16, bd, cf);
   }
-  c.set_ring(std::make_shared<FrameRing>(dev_, c.ring_slots_cfg, pi.width, pi.height));
+  c.set_ring(std::make_shared<FrameRing>(dev_, c.ring_slots_cfg, pi.width, pi.height, c.history()));
 }
 
 static inline size_t al(size_t x, size_t a = 256) { return (x + a - 1) & ~(a - 1); }
@@ -1101,8 +1233,40 @@ void Worker::prepare(std::vector<DecodeJob>& jobs, std::vector<int>& slots) {
     bool weave = jobs[i].out_fields;
     for (const auto& p : jobs[i].avc) weave |= p->structure != 0;
     ensure_surface(c, jobs[i].pic, jobs[i].dpb_slots(), jobs[i].bit_depth(), weave, jobs[i].chroma_format());
+    if (!jobs[i].outputs.empty()) reserve_history(c, jobs[i]);
     slots[i] = jobs[i].has_output() ? c.ring_->begin_write() : -1;
   }
+}
+
+// Frame history: ring slots for the job's outputs before the newest one. The last
+// min(H, outputs) outputs of the job are kept (the newest takes its slot as ever); the others,
+// and those of a job outside the multi-output path (field pictures), count as history_skipped.
+// Slots go to the newest outputs first, so when the ring has none left the older ones are dropped.
+void Worker::reserve_history(Camera& c, DecodeJob& j) {
+  const size_t nh = j.history_outputs();
+  const Camera::Surface& sf = c.surface;
+  bool eligible = c.history() > 0 && !j.out_fields && !j.ext;
+  for (const auto& p : j.avc) eligible &= p->structure == 0;
+  for (const JobOutput& o : j.outputs) eligible &= !o.fields;
+  const size_t room = size_t(std::max(0, c.history() - (j.out_slot >= 0 ? 1 : 0)));
+  const size_t keep = eligible ? std::min(nh, room) : 0;
+  const int npics = int(!j.avc.empty() ? j.avc.size() : j.hevc.size());
+  const int dpb = j.hevc.empty() ? j.dpb_slots() : j.hevc_slots;
+  size_t taken = 0;
+  for (size_t k = nh; k-- > nh - keep;) {
+    JobOutput& o = j.outputs[k];
+    // only pictures of the surfaces' and the ring's geometry (the conversion is not bounds-checked)
+    const bool fits = o.slot >= 0 && o.slot < dpb && o.slot < sf.slots && o.released_by >= 0 && o.released_by < npics &&
+                      o.pic.coded_width == sf.wmbs * 16 && o.pic.coded_height == sf.hmbs * 16 &&
+                      o.pic.width == c.ring_->width() && o.pic.height == c.ring_->height() && o.pic.crop_left >= 0 &&
+                      o.pic.crop_top >= 0 && o.pic.crop_left + o.pic.width <= o.pic.coded_width &&
+                      o.pic.crop_top + o.pic.height <= o.pic.coded_height;
+    if (!fits) continue;
+    o.ring_slot = c.ring_->try_write();
+    if (o.ring_slot < 0) break;
+    ++taken;
+  }
+  if (nh > taken) c.history_skipped.fetch_add(nh - taken, std::memory_order_relaxed);
 }
 
 namespace {
@@ -1193,6 +1357,18 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
   };
   const size_t off_wv = off_lb + al(sizeof(gpu::LetterboxDesc) * size_t(n));  // field-pair weaves
   size_t need = off_wv + al(sizeof(gpu::WeaveDesc) * size_t(n));
+  // Frame history: the outputs with a ring slot (reserve_history), by the reconstruction round
+  // (= index of the job picture) that released them; one surface_to_bgr launch after each such
+  // round, before the next round may reuse their surfaces.
+  struct HistOut {
+    int round, job, out;
+  };
+  std::vector<HistOut> hist;
+  for (int i = 0; i < n; ++i)
+    for (size_t k = 0; k < jobs[size_t(i)].outputs.size(); ++k)
+      if (jobs[size_t(i)].outputs[k].ring_slot >= 0) hist.push_back({jobs[size_t(i)].outputs[k].released_by, i, int(k)});
+  const size_t off_hist = need;
+  need += al(sizeof(gpu::SurfaceBgrDesc) * hist.size());
   std::vector<size_t> mask_off(static_cast<size_t>(n)), pay_off(static_cast<size_t>(n));
   std::vector<std::vector<size_t>> seg_off(static_cast<size_t>(n));
   auto words_of = [&](int i) { return size_t(jobs[size_t(i)].upd.mbs() + 31) / 32; };
@@ -1575,6 +1751,51 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
       gpu::fill_letterbox_geometry(l, opt_.letterbox_size, opt_.letterbox_format == gpu::kLbNV12);
     }
   }
+  // history conversions: descriptors in round order; per round {first, count, tiles}
+  // (H.264 rounds 0 .. rounds - 1 run first, then the H.265 rounds: rounds .. rounds + hrounds - 1)
+  std::vector<std::array<int, 3>> hist_round(size_t(rounds + hrounds), std::array<int, 3>{0, 0, 0});
+  {
+    for (HistOut& h : hist) {
+      const DecodeJob& j = jobs[size_t(h.job)];
+      VEP_CHECK(h.round >= 0 && h.round < int(j.avc.empty() ? j.hevc.size() : j.avc.size()),
+                "history output released by a picture outside its job");
+      if (j.avc.empty()) h.round += rounds;
+    }
+    std::stable_sort(hist.begin(), hist.end(), [](const HistOut& a, const HistOut& b) { return a.round < b.round; });
+    auto* hs = reinterpret_cast<gpu::SurfaceBgrDesc*>(st.h + off_hist);
+    for (size_t k = 0; k < hist.size(); ++k) {
+      const DecodeJob& j = jobs[size_t(hist[k].job)];
+      const JobOutput& o = j.outputs[size_t(hist[k].out)];
+      const Camera* c = cams_[size_t(j.cam)].get();
+      const Camera::Surface& sf = c->surface;
+      std::array<int, 3>& hr = hist_round[size_t(hist[k].round)];
+      if (hr[1] == 0) hr[0] = int(k);
+      gpu::SurfaceBgrDesc& d = hs[k];
+      d = gpu::SurfaceBgrDesc{};
+      d.y = sf.y + size_t(o.slot) * sf.slot_y();
+      d.uv = sf.uv + size_t(o.slot) * sf.slot_uv();
+      d.bgr = c->ring_->slot_ptr(o.ring_slot);
+      d.pitch = d.coded_w = sf.wmbs * 16;
+      d.coded_h = sf.hmbs * 16;
+      d.bit_depth = sf.bd;
+      d.chroma_format = sf.cf;
+      d.crop_left = o.pic.crop_left;
+      d.crop_top = o.pic.crop_top;
+      d.out_w = o.pic.width;
+      d.out_h = o.pic.height;
+      d.tile_begin = hr[2];
+      gpu::check_surface_bgr(d);
+      VEP_CHECK(o.slot < sf.slots && d.out_w == c->ring_->width() && d.out_h == c->ring_->height(),
+                "history output does not match the camera's surfaces");
+      hr[1] += 1;
+      hr[2] += gpu::tiles_for(sf.wmbs, sf.hmbs);
+    }
+  }
+  auto convert_history = [&](int r) {  // the outputs released by round r's pictures
+    const std::array<int, 3>& hr = hist_round[size_t(r)];
+    if (hr[1] > 0)
+      gpu::launch_surface_to_bgr(reinterpret_cast<const gpu::SurfaceBgrDesc*>(st.d + off_hist) + hr[0], hr[1], hr[2], cs);
+  };
   // AVC descriptors (device addresses known only now)
   for (int r = 0; r < rounds; ++r) {
     auto* ad = reinterpret_cast<gpu::AvcDesc*>(st.h + off_round[size_t(r)]);
@@ -1748,6 +1969,7 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
       if (narrow) gpu::launch_avc_deblock(ad, np, max_h, cs, dbk_packed_);
     }
     if (variants) gpu::launch_avc_hbd(ad, np, intra, dbk, variants, cs);  // (High 10 / 4:2:2 pictures)
+    convert_history(r);
   }
   for (int r = 0; r < hrounds; ++r) {
     const auto* hd2 = reinterpret_cast<const gpu::HevcDesc*>(st.d + off_hround[size_t(r)]);
@@ -1780,6 +2002,7 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
       gpu::launch_hevc_deblock(hd2, np, hround_work[size_t(r)][1], 1, cs);
     }
     if (sao) gpu::launch_hevc_sao(hd2, np, hround_work[size_t(r)][1], cs);
+    convert_history(rounds + r);
   }
   // VCN pictures: the video core's surfaces -> the cameras' NV12 surfaces (device copies on the
   // lane stream, ordered before the conversion; the surfaces return to rocDecode when the batch
@@ -1865,9 +2088,19 @@ void Worker::run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, 
       for (int r = 0; r < f.height / 2; ++r)
         std::memcpy(&hs.uv[size_t(r) * size_t(hs.coded_w)], f.uv + size_t(r) * f.pitch_uv, size_t(f.width));
     } else if (jobs[i].general()) {
-      for (const auto& pic : jobs[i].avc) {
+      // frame history: the outputs picture k released are converted before picture k + 1 may
+      // reuse their surfaces (cpu_nv12_to_bgr narrows u16 / 4:2:2 surfaces itself)
+      auto convert_history = [&](size_t k) {
+        for (const JobOutput& o : jobs[i].outputs)
+          if (o.ring_slot >= 0 && size_t(o.released_by) == k)
+            cpu_nv12_to_bgr(c.surface.host[size_t(o.slot)], o.pic.crop_left, o.pic.crop_top, o.pic.width, o.pic.height,
+                            c.ring_->slot_ptr(o.ring_slot));
+      };
+      for (size_t k = 0; k < jobs[i].avc.size(); ++k) {
+        const auto& pic = jobs[i].avc[k];
         if (!pic->structure) {
           avc::cpu_reconstruct(*pic, c.surface.host);
+          convert_history(k);
           continue;
         }
         auto& F = c.surface.fields;  // field slots (half-height surfaces)
@@ -1877,7 +2110,10 @@ void Worker::run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, 
             h.alloc(pic->wmbs * 16, pic->hmbs * 16, pic->bd, pic->cf);
         avc::cpu_reconstruct(*pic, F);
       }
-      for (const auto& pic : jobs[i].hevc) hevc::cpu_execute(*pic, c.surface.host);
+      for (size_t k = 0; k < jobs[i].hevc.size(); ++k) {
+        hevc::cpu_execute(*jobs[i].hevc[k], c.surface.host);
+        convert_history(k);
+      }
     } else {
       cpu_apply_update(jobs[i].upd, c.surface.host[0]);
     }
@@ -1955,14 +2191,20 @@ bool stale_output(Camera& c, const DecodeJob& j, bool check) {
                    c.bad_cra_.end());
   if (c.stale_.size() > 64) c.stale_.erase(c.stale_.begin(), c.stale_.end() - 64);
   if (!check) return false;
+  return stale_picture(c, j.out_slot, j.meta.pts, j.out_rasl_of);
+}
+
+// Whether the output (slot, pts) is one of the camera's recorded stale pictures (erased: each is
+// output once) or a RASL picture of a poisoned CRA.
+bool stale_picture(Camera& c, int slot, i64 pts, i64 rasl_of) {
   for (auto it = c.stale_.begin(); it != c.stale_.end(); ++it)
-    if (it->slot == j.out_slot && it->pts == j.meta.pts) {
+    if (it->slot == slot && it->pts == pts) {
       c.stale_.erase(it);
       return true;
     }
-  if (j.out_rasl_of >= 0)
+  if (rasl_of >= 0)
     for (const auto& b : c.bad_cra_)
-      if (b.first == j.out_rasl_of) return true;
+      if (b.first == rasl_of) return true;
   return false;
 }
 
@@ -1986,6 +2228,40 @@ void Worker::publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, cons
       cp->pictures.fetch_add(np, std::memory_order_relaxed);
     }
     const bool stale = stale_output(*cp, jobs[i], out && jobs[i].general());
+    // Frame history: the job's earlier outputs, oldest first, each under the rules of the newest
+    // one below: none from a failed job or while the camera waits for a keyframe (a refresh job's
+    // own pictures excepted), none that is stale. The hook fires once per job (here only when the
+    // newest frame is not committed below).
+    bool hist_committed = false;
+    for (JobOutput& o : jobs[i].outputs) {
+      if (o.ring_slot < 0) continue;
+      const bool ok = !(err && err[i]) && (!cp->broken_ || (jobs[i].refresh && reconstructs_slot(jobs[i], o.slot)));
+      if (!ok) {
+        cp->ring_->abort(o.ring_slot);
+        dropped_.fetch_add(1, std::memory_order_relaxed);
+      } else if (stale_picture(*cp, o.slot, o.meta.pts, o.rasl_of)) {
+        cp->ring_->abort(o.ring_slot);
+        shed_.fetch_add(1, std::memory_order_relaxed);
+        cp->shed.fetch_add(1, std::memory_order_relaxed);
+      } else {
+        o.meta.decoded_us = t;
+        cp->ring_->commit(o.ring_slot, o.meta);
+        cp->decoded.fetch_add(1, std::memory_order_relaxed);
+        frames_.fetch_add(1, std::memory_order_relaxed);
+        hist_committed = true;
+      }
+      o.ring_slot = -1;
+    }
+    struct HookOnce {  // (the paths below that do not commit the newest frame leave through here)
+      Worker& w;
+      Camera& c;
+      int cam;
+      bool armed;
+      ~HookOnce() {
+        if (!armed) return;
+        if (auto hook = std::atomic_load(&w.publish_hook_)) (*hook)(cam, c.ring_->published());
+      }
+    } hook_once{*this, *cp, jobs[i].cam, hist_committed};
     if (!out) {  // reconstruction only (its pictures wait in the reorder buffer)
       if (err && err[i]) {
         cp->errors.fetch_add(1, std::memory_order_relaxed);
@@ -2042,6 +2318,7 @@ void Worker::publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, cons
     cp->out_surface_pts = jobs[i].meta.pts;
     cp->decoded.fetch_add(1, std::memory_order_relaxed);
     frames_.fetch_add(1, std::memory_order_relaxed);
+    hook_once.armed = false;
     if (auto hook = std::atomic_load(&publish_hook_)) (*hook)(jobs[i].cam, cp->ring_->published());
   }
   batches_.fetch_add(1);
@@ -2129,6 +2406,8 @@ void Worker::launch_on(Lane& ln, Batch&& b) {
       for (size_t i = 0; i < st.jobs.size(); ++i) {
         auto& cp = cams_[size_t(st.jobs[i].cam)];
         if (cp && cp->ring_ && st.slots[i] >= 0) cp->ring_->abort(st.slots[i]);
+        for (JobOutput& o : st.jobs[i].outputs)
+          if (cp && cp->ring_ && o.ring_slot >= 0) cp->ring_->abort(o.ring_slot);
       }
       for (const auto& j : st.jobs) dropped_.fetch_add(j.has_output() ? 1 : 0, std::memory_order_relaxed);
     }
@@ -2352,6 +2631,51 @@ bool Worker::read_latest(int cam, i64 after, FrameMeta* meta, u8* dst, size_t ca
   if (!c) return false;
   std::shared_ptr<FrameRing> r = c->ring();
   return r && read_latest(*r, after, meta, dst, cap);
+}
+
+void Worker::copy_slot(FrameRing& ring, int slot, u8* dst) {
+  const size_t n = ring.slot_bytes();
+  if (!dev_.gpu()) {
+    std::memcpy(dst, ring.slot_ptr(slot), n);
+    return;
+  }
+  dev_.bind();
+  ServeBuf* b = acquire_serve(n);  // D2H through a pinned pool buffer, as read_latest
+  try {
+    VEP_HIP(hipMemcpyAsync(b->h, ring.slot_ptr(slot), n, hipMemcpyDeviceToHost, serve_stream_));
+    VEP_HIP(hipEventRecord(b->ev[0], serve_stream_));
+    VEP_HIP(hipEventSynchronize(b->ev[0]));
+    std::memcpy(dst, b->h, n);
+  } catch (...) {
+    release_serve(b);
+    throw;
+  }
+  release_serve(b);
+}
+
+std::vector<Worker::HistoryFrame> Worker::read_history(int cam, i64 after, int max_count) {
+  std::vector<HistoryFrame> res;
+  std::shared_ptr<Camera> c = camera(cam);
+  if (!c) return res;
+  std::shared_ptr<FrameRing> r = c->ring();
+  if (!r) return res;
+  // (a ring without a history keeps only its newest frame readable)
+  const int depth = std::max(1, r->history());
+  std::vector<std::pair<FrameMeta, int>> want;
+  r->range(after, max_count > 0 ? std::min(max_count, depth) : depth, want);
+  // newest first: a frame the writer took meanwhile ends the run (it and everything older is
+  // dropped, so the result stays contiguous and ends at the newest frame read)
+  for (size_t k = want.size(); k-- > 0;) {
+    HistoryFrame f;
+    f.meta = want[k].first;
+    f.bytes = r->slot_bytes();
+    f.data.reset(new u8[f.bytes]);
+    copy_slot(*r, want[k].second, f.data.get());
+    if (!r->still_valid(want[k].second, f.meta.seq)) break;
+    res.push_back(std::move(f));
+  }
+  std::reverse(res.begin(), res.end());
+  return res;
 }
 
 Worker::ServeBuf* Worker::acquire_serve(size_t n) {

@@ -64,20 +64,28 @@ class Device {
 // Ring of N decoded BGR24 frames for one camera, seqlock-published.
 class FrameRing {
  public:
-  FrameRing(Device& dev, int slots, int width, int height);
+  // history: the H newest committed frames stay readable (range()); 0 = only the newest one
+  FrameRing(Device& dev, int slots, int width, int height, int history = 0);
   ~FrameRing();
   int slots() const { return int(slots_.size()); }
+  int history() const { return hist_; }
   int width() const { return w_; }
   int height() const { return h_; }
   size_t slot_bytes() const { return size_t(w_) * h_ * 3; }
   u8* slot_ptr(int i) const { return base_ + size_t(i) * slot_bytes(); }
   // writer side (single writer: the worker thread)
+  // With a history, begin_write never returns one of the H newest committed slots; try_write is
+  // the same for a frame that may be given up: -1 when no slot is free.
   int begin_write();
+  int try_write();
   void commit(int slot, FrameMeta meta);
   // Release a slot from begin_write() without publishing (frame dropped after a failed check).
   void abort(int slot);
   // reader side: newest committed frame with seq > after (false if none)
   bool latest(i64 after, FrameMeta* meta, int* slot) const;
+  // The newest max_count committed frames with seq > after_seq (XRANGE / XREVRANGE analog):
+  // ascending, contiguous in seq and ending at the newest frame. Returns how many.
+  int range(i64 after_seq, int max_count, std::vector<std::pair<FrameMeta, int>>& out) const;
   // true if `slot` still holds the frame with publish counter `seq`
   bool still_valid(int slot, i64 seq) const;
   i64 published() const { return published_.load(std::memory_order_acquire); }
@@ -98,6 +106,23 @@ class FrameRing {
   std::atomic<int> latest_{-1};
   std::atomic<i64> published_{0};
   int next_ = 0;
+  int hist_ = 0;
+  int pick_free() const;  // history rule (meta_mu_ held): -1 when none
+};
+
+// One picture that left the reorder buffer during a job (frame history, Camera::history): a
+// job of several pictures publishes each of them, not only the newest.
+struct JobOutput {
+  int slot = -1;          // DPB slot
+  bool fields = false;    // H.264 field pair (avc::OutFrame::fields)
+  PictureInfo pic;
+  FrameMeta meta;
+  // Index of the job's picture (DecodeJob::avc / ::hevc) whose decoding released it: its surface
+  // is intact until the NEXT picture reconstructs, so it is converted right after this one's
+  // reconstruction round.
+  int released_by = 0;
+  i64 rasl_of = -1;       // H.265: a RASL picture of the CRA with this tag
+  int ring_slot = -1;     // worker (prepare): the ring slot it is converted into, -1 = skipped
 };
 
 struct DecodeJob {
@@ -123,6 +148,12 @@ struct DecodeJob {
   // pictures before the CRA, possibly dropped ones: they are not published either.
   std::vector<i64> poisoned_cra;
   i64 out_rasl_of = -1;  // H.265: the output picture is a RASL picture of the CRA with this tag
+  // Cameras with a frame history: every output of the job in output order (the last one is the
+  // out_slot / pic / meta picture above, which keeps its end-of-batch conversion). Empty for
+  // cameras without a history, fast-path and VCN jobs.
+  std::vector<JobOutput> outputs;
+  // the outputs converted by the history path: all but the newest (which out_slot describes)
+  size_t history_outputs() const { return outputs.size() - (out_slot >= 0 && !outputs.empty() ? 1 : 0); }
   // VCN backend (vcn.h): a picture decoded by the video core; the worker copies its planes into
   // the camera's surface, then converts / letterboxes / publishes it like any other frame.
   vcn::FramePtr ext;
@@ -161,7 +192,11 @@ class LogRing {
 // Camera data-plane state (one per registered RTSP process).
 class Camera {
  public:
-  Camera(Worker& w, int index, std::string name, int ring_slots);
+  Camera(Worker& w, int index, std::string name, int ring_slots, int history = 0);
+  // Frame history depth H: the ring keeps the H newest frames readable and a job of several
+  // pictures publishes its last H outputs (0: only the newest frame, as the reference's
+  // buffer.in_memory: 1).
+  int history() const { return history_; }
   const std::string& name() const { return name_; }
   int index() const { return index_; }
   // WorkerOptions::backpressure: wait (bounded) until the worker took this camera's queued job
@@ -185,6 +220,9 @@ class Camera {
   // decoded = frames published to the ring; pictures = pictures reconstructed (general path: a
   // picture can be reconstructed in one job and output by a later one)
   std::atomic<u64> packets{0}, decoded{0}, skipped{0}, errors{0}, bytes_in{0}, pictures{0}, shed{0};
+  // outputs of multi-picture jobs the history did not take: older than its depth, no free ring
+  // slot, or a job outside the multi-output path (field pairs)
+  std::atomic<u64> history_skipped{0};
   // packet arrival -> frame published (ms) histogram, upper bounds kLatBucketsMs (+inf last)
   static constexpr int kLatBuckets = 12;
   static constexpr double kLatBucketsMs[kLatBuckets - 1] = {1, 2, 5, 10, 20, 35, 50, 100, 250, 500, 1000};
@@ -237,11 +275,13 @@ class Camera {
  private:
   friend class Worker;
   friend bool stale_output(Camera& c, const DecodeJob& j, bool check);
+  friend bool stale_picture(Camera& c, int slot, i64 pts, i64 rasl_of);
   bool build_job(DecodeJob& job, size_t from, size_t to, bool refresh);
   bool build_vcn_job(DecodeJob& job, size_t from, size_t to);
   Worker& w_;
   int index_;
   std::string name_;
+  int history_ = 0;
   std::mutex mu_;
   std::vector<AuPtr> gop_;
   size_t decoded_upto_ = 0;  // gop_[0, decoded_upto_) are reconstructed on the surface
@@ -340,7 +380,10 @@ class Worker {
   // Parse strands of the live ingest services (0 when none are running).
   int ingest_parse_threads();
 
-  int add_camera(const std::string& name, int ring_slots);
+  // history: frames kept readable for read_history (0 = only the newest, as before). The ring
+  // then gets at least history_ring_slots(history) slots.
+  int add_camera(const std::string& name, int ring_slots, int history = 0);
+  int history_ring_slots(int history) const;
   void remove_camera(int idx);
   // Shared ownership: a reader (gRPC thread) keeps the camera alive across remove_camera().
   std::shared_ptr<Camera> camera(int idx);
@@ -367,6 +410,15 @@ class Worker {
   // dst_pinned: dst is page-locked (register_host) -> one DMA straight into it, no staging.
   bool read_latest(int cam, i64 after, FrameMeta* meta, u8* dst, size_t cap);
   bool read_latest(FrameRing& ring, i64 after, FrameMeta* meta, u8* dst, size_t cap, bool dst_pinned = false);
+  // Frame history: the newest max_count (0 = the camera's depth) frames with seq > after, copied
+  // to host memory, ascending and contiguous in seq, ending at the newest frame. A frame the
+  // writer reused during the read is dropped together with everything older.
+  struct HistoryFrame {
+    FrameMeta meta;
+    std::unique_ptr<u8[]> data;
+    size_t bytes = 0;
+  };
+  std::vector<HistoryFrame> read_history(int cam, i64 after, int max_count);
   // Several rings' newest frames at once (the frame bus pump): every copy into page-locked
   // destinations is queued on the serving stream before one wait; others go one by one.
   struct ReadReq {
@@ -491,6 +543,8 @@ class Worker {
   void publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, const u32* err = nullptr);
   void complete(Lane& ln, Stage& st);
   void complete_locked();
+  void copy_slot(FrameRing& ring, int slot, u8* dst);  // one ring slot -> host memory
+  void reserve_history(Camera& c, DecodeJob& j);       // ring slots of a job's earlier outputs
   WorkerOptions opt_;
   Device dev_;
   hipStream_t stream_ = nullptr, copy_stream_ = nullptr, serve_stream_ = nullptr;

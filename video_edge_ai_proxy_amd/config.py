@@ -99,6 +99,9 @@ class ServingConfig:
     bus: bool = False           # main-process serving also reads the frame bus (shared DMA per frame)
     native: bool = True
     io_threads: int = 2         # native endpoint: epoll threads per serving process
+    resp_port: int = 0          # >0: Redis-stream-compatible (RESP2) endpoint of the frame history
+                                # (server/resp.py: XLEN / XRANGE / XREVRANGE / XREAD per camera)
+    resp_host: str = "0.0.0.0"
 
 
 @dataclass
@@ -122,6 +125,14 @@ class Config:
     @property
     def ring_slots(self) -> int:
         return self.gpu.ring_slots or max(2, int(self.buffer.in_memory))
+
+    @property
+    def history_depth(self) -> int:
+        """Frames of every camera kept readable in the past (``Hub.history``, the RESP endpoint):
+        ``buffer.in_memory`` when it is > 1, the reference's ``XADD ... MAXLEN`` meaning of the
+        key; else 0 (only the newest frame, no multi-output jobs)."""
+        n = int(self.buffer.in_memory)
+        return n if n > 1 else 0
 
 
 def _merge(dc, data: dict):

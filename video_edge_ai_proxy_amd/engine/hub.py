@@ -135,7 +135,7 @@ class Hub:
                 raise CameraExists(f"camera {name!r} already running")
             wi = place_camera(name, self._loads(), self.cfg.gpu.placement)
             w = self.workers[wi]
-            cam = w.add_camera(name, self.cfg.ring_slots)
+            cam = w.add_camera(name, self.cfg.ring_slots, self.cfg.history_depth)
             w.set_idle_cutoff_ms(cam, int(self.cfg.gpu.idle_cutoff_ms))
             h = CameraHandle(name, wi, cam, rtsp, rtmp)
             disk = self.archive_dir() if disk_path is None else disk_path
@@ -300,6 +300,31 @@ class Hub:
     def latest_frame(self, name: str, after: int = 0):
         w, cam = self.worker_of(name)
         return w.read_latest(cam, after)
+
+    def history(self, name: str, after: int = 0, count: int = 0) -> list:
+        """``[(meta, ndarray)]`` of the camera's newest ``count`` (0 = ``buffer.in_memory``) frames
+        with seq > after, ascending and contiguous in seq (the reference's Redis stream of the
+        last N decoded frames). Needs ``buffer.in_memory`` > 1 to hold more than the newest."""
+        w, cam = self.worker_of(name)
+        return w.read_history(cam, after, count)
+
+    def history_bytes(self, name: str, after: int = 0, count: int = 0) -> list:
+        """``[(seq, serialized VideoFrame)]`` of the same frames."""
+        w, cam = self.worker_of(name)
+        return w.video_frames(cam, after, count, name)
+
+    def history_seqs(self, name: str, after: int = 0, count: int = 0) -> list:
+        """The seqs ``history`` would return (no frame is copied)."""
+        w, cam = self.worker_of(name)
+        return list(w.history_seqs(cam, after, count))
+
+    def published(self, name: str) -> int:
+        w, cam = self.worker_of(name)
+        return int(w.published(cam))
+
+    def wait_frame(self, name: str, after: int, timeout_ms: int) -> bool:
+        w, cam = self.worker_of(name)
+        return bool(w.wait_frame(cam, after, int(timeout_ms)))
 
     def wait_decoded(self, name: str, n: int = 1, timeout_s: float = 10.0) -> bool:
         w, cam = self.worker_of(name)

@@ -568,6 +568,17 @@ class ProcessHub:
     def wait_decoded(self, name: str, n: int = 1, timeout_s: float = 10.0) -> bool:
         return bool(self._call(name, "wait_decoded", n, timeout_s))
 
+    # The frame history lives in the worker processes' rings; the frame bus carries only each
+    # camera's newest frame, so it is served only by the in-process hub (gpu.isolation: thread).
+    def history(self, name: str, after: int = 0, count: int = 0) -> list:
+        raise NotImplementedError("frame history is not available with gpu.isolation: process")
+
+    def history_bytes(self, name: str, after: int = 0, count: int = 0) -> list:
+        raise NotImplementedError("frame history is not available with gpu.isolation: process")
+
+    def history_seqs(self, name: str, after: int = 0, count: int = 0) -> list:
+        raise NotImplementedError("frame history is not available with gpu.isolation: process")
+
 
 def _free_port() -> int:
     s = socket.socket()

@@ -2,6 +2,9 @@
 
 * :func:`nv12_to_bgr` — BT.601 limited-range NV12 -> packed BGR24 (the kernel behind
   ``VideoFrame.data``; reference: python/read_image.py:94 ``to_ndarray(format='bgr24')``).
+* :func:`surface_to_bgr` / :func:`surface_to_bgr_batch` — a reconstructed surface at its native
+  sample format (uint8 / uint16 samples, 4:2:0 / 4:2:2) -> BGR24, narrowed in registers (the
+  frame history's conversion; one launch for several pictures).
 * :func:`pcm_decode_bgr` — fused I_PCM macroblock reconstruction + conversion.
 * :func:`letterbox` — NV12 -> letterboxed model input (HWC uint8 and/or normalised CHW).
 
@@ -50,6 +53,65 @@ def nv12_to_bgr(y: torch.Tensor, uv: torch.Tensor, width: int | None = None,
     native.nv12_to_bgr(y.data_ptr(), uv.data_ptr(), 0, 0, 0, 0, W // 16, H // 16, width,
                        height, crop_left, crop_top, out.data_ptr(), _stream_ptr(y))
     return out
+
+
+def _surface_args(y: torch.Tensor, uv: torch.Tensor, bit_depth: int, chroma_format: int,
+                  width, height, crop_left: int, crop_top: int, out):
+    if not (y.is_cuda and uv.is_cuda):
+        raise ValueError("surface planes must be device tensors")
+    want = torch.uint8 if bit_depth == 8 else torch.uint16
+    if bit_depth not in (8, 9, 10):
+        raise ValueError("bit_depth must be 8, 9 or 10")
+    if y.dtype != want or uv.dtype != want:
+        raise TypeError(f"{bit_depth}-bit surface planes must be {want}")
+    if chroma_format not in (1, 2):
+        raise ValueError("chroma_format must be 1 (4:2:0) or 2 (4:2:2)")
+    if not (y.is_contiguous() and uv.is_contiguous()):
+        raise ValueError("surface planes must be contiguous")
+    H, W = y.shape
+    if W % 16 or H % 16:
+        raise ValueError("coded surface size must be macroblock aligned (multiple of 16)")
+    ch = H if chroma_format == 2 else H // 2
+    if tuple(uv.shape) != (ch, W):
+        raise ValueError(f"uv plane must be {(ch, W)}, got {tuple(uv.shape)}")
+    width = W - crop_left if width is None else width
+    height = H - crop_top if height is None else height
+    if crop_left < 0 or crop_top < 0 or width <= 0 or height <= 0 or crop_left + width > W or crop_top + height > H:
+        raise ValueError("output window outside the coded picture")
+    if out is None:
+        out = torch.empty((height, width, 3), dtype=torch.uint8, device=y.device)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (height, width, 3)):
+        raise ValueError(f"out must be a contiguous uint8 device tensor of shape {(height, width, 3)}")
+    return (y.data_ptr(), uv.data_ptr(), W, W, H, bit_depth, chroma_format, crop_left, crop_top, width, height,
+            out.data_ptr()), out
+
+
+def surface_to_bgr(y: torch.Tensor, uv: torch.Tensor, bit_depth: int = 8, chroma_format: int = 1,
+                   width: int | None = None, height: int | None = None, crop_left: int = 0,
+                   crop_top: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Convert a reconstructed surface at its native sample format to ``[height, width, 3]``
+    BGR24: uint8 planes (``bit_depth`` 8) or uint16 planes (9..10, rounded to 8 bits), chroma
+    4:2:0 (``uv`` of H/2 rows) or 4:2:2 (H rows, row pairs averaged). Bit-exact with the CPU
+    reference (narrow_surface + nv12_to_bgr_cpu)."""
+    require_gpu()
+    args, out = _surface_args(y, uv, bit_depth, chroma_format, width, height, crop_left, crop_top, out)
+    native.surface_to_bgr(*args, _stream_ptr(y))
+    return out
+
+
+def surface_to_bgr_batch(pictures) -> list:
+    """Convert several surfaces in one kernel launch. ``pictures``: dicts of the keyword arguments
+    of :func:`surface_to_bgr` (``y`` and ``uv`` required). Returns the outputs in order."""
+    require_gpu()
+    pics, outs = [], []
+    for p in pictures:
+        args, out = _surface_args(p["y"], p["uv"], p.get("bit_depth", 8), p.get("chroma_format", 1), p.get("width"),
+                                  p.get("height"), p.get("crop_left", 0), p.get("crop_top", 0), p.get("out"))
+        pics.append(args)
+        outs.append(out)
+    if pics:
+        native.surface_to_bgr_many(pics, _stream_ptr(pictures[0]["y"]))
+    return outs
 
 
 def mb_mask_prefix(mb_slot: torch.Tensor):

@@ -49,6 +49,7 @@ class HubApp:
     public_grpc_port: int = 0
     native_server: Optional[object] = None  # native.RpcServer (serving.native, main-process serving)
     consumer_loop: Optional[object] = None  # engine.consumer.ConsumerLoop (gpu.consumer_rate_hz > 0)
+    resp_server: Optional[object] = None  # server.resp.RespServer (serving.resp_port > 0)
 
     @property
     def grpc_port(self) -> int:
@@ -60,6 +61,8 @@ class HubApp:
 
     def stop(self):
         log.info("shutting down")
+        if self.resp_server is not None:
+            self.resp_server.stop()
         if self.frontends is not None:
             self.frontends.close()
         if self.native_server is not None:
@@ -185,6 +188,10 @@ def build_app(cfg: Config, host: str = "0.0.0.0", rest_port: Optional[int] = Non
 
         happ.consumer_loop = ConsumerLoop(hub, float(cfg.gpu.consumer_rate_hz), cfg.gpu.consumer_hook).start()
         metrics.consumer = happ.consumer_loop
+    if int(cfg.serving.resp_port) > 0:  # Redis-stream-compatible view of the frame history
+        from .resp import RespServer
+
+        happ.resp_server = RespServer(hub, cfg.serving.resp_host or host, int(cfg.serving.resp_port))
     if restore:
         restored = pm.restore()
         if restored:
