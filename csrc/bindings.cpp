@@ -18,6 +18,7 @@
 #include "vep/hevc_ctu.h"
 #include "vep/hevc_dec.h"
 #include "vep/hevc_kern.h"
+#include "vep/jpeg.h"
 #include "bind_ext.h"
 #include "vep/runtime.h"
 #include "vep/synth.h"
@@ -1390,6 +1391,22 @@ PYBIND11_MODULE(_vep, m) {
              return py::make_tuple(meta_dict(m), out);
            },
            py::arg("idx"), py::arg("after") = 0)
+      .def("read_latest_jpeg",
+           // (meta, bytes) of the newest frame with seq > after as a JPEG stream, None if there
+           // is none; encoded on the GPU from the ring slot (CPU backend: on the host).
+           [](Worker& w, int i, i64 after, int quality) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             FrameMeta m;
+             std::string out;
+             bool ok;
+             {
+               py::gil_scoped_release r;
+               ok = w.read_latest_jpeg(i, after, quality, &m, out);
+             }
+             if (!ok) return py::none();
+             return py::make_tuple(meta_dict(m), py::bytes(out));
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("quality") = 85)
       .def("read_history",
            // [(meta, ndarray)] of the newest `count` (0 = the camera's history depth) frames with
            // seq > after: ascending, contiguous in seq, ending at the newest frame.
@@ -1650,7 +1667,56 @@ PYBIND11_MODULE(_vep, m) {
     return o;
   });
 
+  // Baseline JPEG (vep/jpeg.h) of a packed BGR24 picture on the host: the CPU backend's encoder
+  // and the byte-exact reference of jpeg_encode.
+  m.def("jpeg_encode_cpu",
+        [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> bgr, int quality) {
+          VEP_CHECK(bgr.ndim() == 3 && bgr.shape(2) == 3 && bgr.shape(0) >= 1 && bgr.shape(1) >= 1,
+                    "jpeg_encode_cpu: (H, W, 3) uint8 picture expected");
+          const u8* p = bgr.data();
+          const int w = int(bgr.shape(1)), h = int(bgr.shape(0));
+          VEP_CHECK(bgr.shape(1) <= 65535 && bgr.shape(0) <= 65535, "jpeg: picture size out of range");
+          std::string out;
+          {
+            py::gil_scoped_release r;
+            out = jpeg::encode_cpu(p, w, h, quality);
+          }
+          return py::bytes(out);
+        },
+        py::arg("bgr"), py::arg("quality") = 85);
+
   // ---- op API on caller-owned device buffers (torch tensors pass data_ptr / stream) ----
+  // JPEG stream of a device BGR24 picture, encoded by the gfx950 kernels on `stream` of the
+  // current device (scratch: one process-wide pool per device).
+  m.def("jpeg_encode",
+        [](uintptr_t bgr, int w, int h, int quality, uintptr_t stream) {
+          static std::mutex mu;
+          static std::map<int, gpu::JpegPool*>* pools = new std::map<int, gpu::JpegPool*>();  // (never freed)
+          std::string out;
+          {
+            py::gil_scoped_release r;
+            int dev = 0;
+            VEP_HIP(hipGetDevice(&dev));
+            gpu::JpegPool* pool;
+            {
+              std::lock_guard<std::mutex> g(mu);
+              gpu::JpegPool*& slot = (*pools)[dev];
+              if (!slot) slot = new gpu::JpegPool();
+              pool = slot;
+            }
+            const u8* p = reinterpret_cast<const u8*>(bgr);
+            if (!pool->encode(p, w, h, quality, reinterpret_cast<hipStream_t>(stream), out)) {
+              // the kernels reported an overflow of their scratch: encode on the host
+              std::unique_ptr<u8[]> host(new u8[size_t(w) * size_t(h) * 3]);
+              VEP_HIP(hipMemcpyAsync(host.get(), p, size_t(w) * size_t(h) * 3, hipMemcpyDeviceToHost,
+                                     reinterpret_cast<hipStream_t>(stream)));
+              VEP_HIP(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+              out = jpeg::encode_cpu(host.get(), w, h, quality);
+            }
+          }
+          return py::bytes(out);
+        },
+        py::arg("bgr"), py::arg("w"), py::arg("h"), py::arg("quality"), py::arg("stream"));
   m.def("nv12_to_bgr",
         [](uintptr_t y, uintptr_t uv, uintptr_t mask, uintptr_t prefix, uintptr_t offsets,
            uintptr_t payload, int wmbs, int hmbs, int out_w, int out_h, int crop_left,

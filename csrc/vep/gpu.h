@@ -11,6 +11,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <condition_variable>
+#include <memory>
+#include <mutex>
+
 #include "common.h"
 
 namespace vep::gpu {
@@ -287,6 +291,58 @@ void launch_avc_deblock(const AvcDesc* d_descs, int n, int max_hmbs, hipStream_t
 // prediction, then (dbk: after launch_avc_bs) the loop filter. gpu_avc_hbd.hip
 // variants: bit 0 High 10 4:2:0, bit 1 8-bit 4:2:2, bit 2 High 10 4:2:2 pictures present
 void launch_avc_hbd(const AvcDesc* d_descs, int n, bool intra, bool dbk, int variants, hipStream_t s);
+
+// ---- baseline JPEG encoder (gpu_jpeg.hip; stream format and arithmetic: jpeg.h) -------------
+// One BGR24 picture -> the entropy-coded part of its JPEG stream, byte-identical with
+// jpeg::encode_cpu, in four launches: transform (one workgroup per 16x16 MCU), entropy (one lane
+// per restart interval, into the interval's own segment), scan (offsets of the segments in the
+// joined stream) and gather (segments + RSTm markers -> `out`).
+struct JpegDesc {
+  const VEP_DEV u8* bgr;  // h x w x 3, packed
+  i32 w, h, quality;
+  i32 mcus_x, mcus;       // MCU columns, MCUs of the picture
+  i32 intervals;          // restart intervals: ceil(mcus / jpeg::kRestartInterval)
+  VEP_DEV i16* coefs;     // device scratch: mcus x 6 x 64 quantised zigzag coefficients
+  VEP_DEV u8* seg;        // device scratch: interval i's bytes at seg + i * jpeg::kSegmentCap (the
+                          // proven worst case; every store is bound-checked all the same)
+  VEP_DEV u32* len;       // device scratch: bytes of every interval's segment
+  VEP_DEV u32* off;       // device scratch: offset of every interval in `out`
+  VEP_DEV u8* out;        // device scratch: the joined stream (no header, no EOI)
+  u32 out_cap;
+  // pinned words: [0] != 0: a segment overflowed, [1] bytes of the joined stream, [2] != 0: the
+  // joined stream does not fit out_cap. The caller zeroes them; nothing is written outside the
+  // buffers in either case.
+  VEP_DEV u32* status;
+};
+void launch_jpeg_transform(const JpegDesc& d, hipStream_t s);
+void launch_jpeg_entropy(const JpegDesc& d, hipStream_t s);
+void launch_jpeg_scan(const JpegDesc& d, hipStream_t s);
+void launch_jpeg_gather(const JpegDesc& d, hipStream_t s);
+
+// Encoder scratch of one device: up to kScratch sets, one per encode in flight, so concurrent
+// requests never share one; a set grows to the largest picture it has seen and is then reused
+// (steady state allocates nothing). Used with the device bound to the calling thread.
+class JpegPool {
+ public:
+  JpegPool();
+  ~JpegPool();
+  JpegPool(const JpegPool&) = delete;
+  JpegPool& operator=(const JpegPool&) = delete;
+  // The JPEG stream of the device picture d_bgr (h x w x 3) at `quality` 1..100, encoded on
+  // stream `s` (waits for it). False when the kernels reported an overflow: the caller encodes
+  // with jpeg::encode_cpu instead.
+  bool encode(const u8* d_bgr, int w, int h, int quality, hipStream_t s, std::string& out);
+  static constexpr int kScratch = 4;
+
+ private:
+  struct Scratch;
+  Scratch* acquire();
+  void release(Scratch* sc);
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<std::unique_ptr<Scratch>> all_;
+  std::vector<Scratch*> free_;
+};
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "color.h"
+#include "jpeg.h"
 #include "trace.h"
 
 namespace vep {
@@ -2631,6 +2632,32 @@ bool Worker::read_latest(int cam, i64 after, FrameMeta* meta, u8* dst, size_t ca
   if (!c) return false;
   std::shared_ptr<FrameRing> r = c->ring();
   return r && read_latest(*r, after, meta, dst, cap);
+}
+
+bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out) {
+  VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  std::shared_ptr<Camera> c = camera(cam);
+  if (!c) return false;
+  std::shared_ptr<FrameRing> ring = c->ring();
+  if (!ring) return false;
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    int slot;
+    if (!ring->latest(after, meta, &slot)) return false;
+    const int w = ring->width(), h = ring->height();
+    if (dev_.gpu()) {
+      dev_.bind();
+      if (!jpeg_pool_.encode(ring->slot_ptr(slot), w, h, quality, serve_stream_, out)) {
+        // the kernels reported an overflow of their scratch: encode the frame on the host
+        std::unique_ptr<u8[]> host(new u8[ring->slot_bytes()]);
+        copy_slot(*ring, slot, host.get());
+        out = jpeg::encode_cpu(host.get(), w, h, quality);
+      }
+    } else {
+      out = jpeg::encode_cpu(ring->slot_ptr(slot), w, h, quality);
+    }
+    if (ring->still_valid(slot, meta->seq)) return true;
+  }
+  return false;
 }
 
 void Worker::copy_slot(FrameRing& ring, int slot, u8* dst) {

@@ -410,6 +410,12 @@ class Worker {
   // dst_pinned: dst is page-locked (register_host) -> one DMA straight into it, no staging.
   bool read_latest(int cam, i64 after, FrameMeta* meta, u8* dst, size_t cap);
   bool read_latest(FrameRing& ring, i64 after, FrameMeta* meta, u8* dst, size_t cap, bool dst_pinned = false);
+  // The newest frame with seq > after as a JPEG stream (jpeg.h) at `quality` 1..100. On a GPU the
+  // frame is encoded where it lies, in its HBM ring slot, on the serving stream, and only the
+  // compressed bytes are copied; the CPU backend runs jpeg::encode_cpu on the host ring. A slot
+  // the writer reused during the encode is encoded again from the newer frame, as read_latest
+  // does for its copy. False if there is no such frame.
+  bool read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out);
   // Frame history: the newest max_count (0 = the camera's depth) frames with seq > after, copied
   // to host memory, ascending and contiguous in seq, ending at the newest frame. A frame the
   // writer reused during the read is dropped together with everything older.
@@ -593,6 +599,7 @@ class Worker {
   std::condition_variable serve_cv_;
   std::vector<std::unique_ptr<ServeBuf>> serve_all_;
   std::vector<ServeBuf*> serve_free_;
+  gpu::JpegPool jpeg_pool_;  // encoder scratch of read_latest_jpeg, one set per request in flight
   u8* cons_hwc_ = nullptr;
   void* cons_chw_ = nullptr;
   // consumer snapshots: exclusive while a snapshot is enqueued, shared while a lane enqueues a

@@ -87,6 +87,20 @@ def cmd_list(a):
         print(s)
 
 
+def write_frame(path: str, img) -> None:
+    """Write a BGR24 picture: ``.jpg`` / ``.jpeg`` as a JPEG (the hub's encoder, on the host), any
+    other name as a PPM."""
+    h, w = img.shape[:2]
+    if path.lower().endswith((".jpg", ".jpeg")):
+        from ._native import native
+
+        data = native.jpeg_encode_cpu(img, 85)
+    else:
+        data = f"P6 {w} {h} 255\n".encode() + img[:, :, ::-1].tobytes()
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def cmd_frame(a):
     import numpy as np
 
@@ -99,8 +113,7 @@ def cmd_frame(a):
               "shape:", [d.size for d in vf.shape.dim], "pts:", vf.pts)
         if a.out and vf.width:
             img = np.frombuffer(vf.data, np.uint8).reshape(vf.height, vf.width, 3)
-            with open(a.out, "wb") as f:
-                f.write(f"P6 {vf.width} {vf.height} 255\n".encode() + img[:, :, ::-1].tobytes())
+            write_frame(a.out, img)
 
 
 def cmd_annotate(a):
@@ -199,7 +212,7 @@ def main(argv=None):
         if name == "frame":
             p.add_argument("--keyframe", action="store_true")
             p.add_argument("--count", type=int, default=1)
-            p.add_argument("--out", default=None, help="write the last frame as PPM")
+            p.add_argument("--out", default=None, help="write the last frame: .jpg / .jpeg as a JPEG, else PPM")
         if name == "annotate":
             p.add_argument("--type", required=True)
         if name in ("storage", "proxy"):

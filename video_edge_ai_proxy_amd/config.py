@@ -102,6 +102,7 @@ class ServingConfig:
     resp_port: int = 0          # >0: Redis-stream-compatible (RESP2) endpoint of the frame history
                                 # (server/resp.py: XLEN / XRANGE / XREVRANGE / XREAD per camera)
     resp_host: str = "0.0.0.0"
+    jpeg_quality: int = 85      # frame.jpg / stream.mjpg / Hub.latest_jpeg when a request names none (1..100)
 
 
 @dataclass
@@ -168,7 +169,14 @@ def load_config(path: str | os.PathLike | None = None, data_dir: str | None = No
             cfg.data_dir = str(data_dir)
     if os.environ.get("VEP_HOST_CPUS"):
         cfg.gpu.host_cpus = [s.strip() for s in os.environ["VEP_HOST_CPUS"].split(";")]
+    validate(cfg)
     return cfg
+
+
+def validate(cfg: Config) -> None:
+    """Reject values no part of the hub can work with (ValueError)."""
+    if not 1 <= int(cfg.serving.jpeg_quality) <= 100:
+        raise ValueError(f"serving.jpeg_quality must be 1..100, got {cfg.serving.jpeg_quality}")
 
 
 _DUR = re.compile(r"(\d+(?:\.\d+)?)(ns|us|µs|ms|s|m|h)")

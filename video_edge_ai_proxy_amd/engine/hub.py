@@ -301,6 +301,16 @@ class Hub:
         w, cam = self.worker_of(name)
         return w.read_latest(cam, after)
 
+    def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None):
+        """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
+        Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
+        ``quality`` 1..100, default ``serving.jpeg_quality``."""
+        q = int(self.cfg.serving.jpeg_quality if quality is None else quality)
+        if not 1 <= q <= 100:
+            raise ValueError("quality must be 1..100")
+        w, cam = self.worker_of(name)
+        return w.read_latest_jpeg(cam, after, q)
+
     def history(self, name: str, after: int = 0, count: int = 0) -> list:
         """``[(meta, ndarray)]`` of the camera's newest ``count`` (0 = ``buffer.in_memory``) frames
         with seq > after, ascending and contiguous in seq (the reference's Redis stream of the

@@ -565,6 +565,11 @@ class ProcessHub:
     def latest_frame(self, name: str, after: int = 0):
         return self._call(name, "latest_frame", after)
 
+    def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None):
+        """(meta, JPEG bytes) or None: the worker process encodes on its GPU, only the compressed
+        bytes cross the pipe."""
+        return self._call(name, "latest_jpeg", after, quality)
+
     def wait_decoded(self, name: str, n: int = 1, timeout_s: float = 10.0) -> bool:
         return bool(self._call(name, "wait_decoded", n, timeout_s))
 

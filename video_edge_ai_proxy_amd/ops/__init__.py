@@ -7,6 +7,8 @@
   frame history's conversion; one launch for several pictures).
 * :func:`pcm_decode_bgr` — fused I_PCM macroblock reconstruction + conversion.
 * :func:`letterbox` — NV12 -> letterboxed model input (HWC uint8 and/or normalised CHW).
+* :func:`jpeg_encode` — BGR24 picture -> baseline JPEG stream (the kernels behind ``frame.jpg``),
+  byte-identical with :func:`jpeg_encode_reference`, the CPU encoder.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -237,6 +239,38 @@ def letterbox(y: torch.Tensor, uv: torch.Tensor, size: int = 640, width: int | N
                      _CHW_DTYPES[chw_dtype], list(map(float, mean)), list(map(float, std)),
                      int(pad_value), _stream_ptr(y))
     return out_hwc, out_chw
+
+
+def _check_jpeg(bgr: torch.Tensor, quality: int) -> int:
+    if bgr.dtype != torch.uint8:
+        raise TypeError("bgr must be uint8")
+    if bgr.dim() != 3 or bgr.shape[2] != 3 or bgr.shape[0] < 1 or bgr.shape[1] < 1:
+        raise ValueError(f"bgr must be [H, W, 3], got {tuple(bgr.shape)}")
+    if bgr.shape[0] > 65535 or bgr.shape[1] > 65535:
+        raise ValueError("a JPEG picture is at most 65535 x 65535")
+    if not bgr.is_contiguous():
+        raise ValueError("bgr must be contiguous")
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("quality must be an integer 1..100")
+    return quality
+
+
+def jpeg_encode(bgr: torch.Tensor, quality: int = 85) -> bytes:
+    """Encode a ``[H, W, 3]`` BGR24 device tensor as a baseline JPEG (JFIF, 4:2:0, restart
+    intervals) on the GPU; only the compressed bytes are copied to the host."""
+    require_gpu()
+    if not bgr.is_cuda:
+        raise ValueError("bgr must be a device tensor")
+    quality = _check_jpeg(bgr, quality)
+    with torch.cuda.device(bgr.device):
+        return native.jpeg_encode(bgr.data_ptr(), int(bgr.shape[1]), int(bgr.shape[0]), quality, _stream_ptr(bgr))
+
+
+def jpeg_encode_reference(bgr: torch.Tensor, quality: int = 85) -> bytes:
+    """The CPU encoder's stream of the same picture (host or device tensor): the byte-exact
+    oracle of :func:`jpeg_encode`."""
+    quality = _check_jpeg(bgr, quality)
+    return native.jpeg_encode_cpu(bgr.detach().cpu().numpy(), quality)
 
 
 # ----------------------------------------------------------------------------- references

@@ -169,7 +169,10 @@ def build_app(cfg: Config, host: str = "0.0.0.0", rest_port: Optional[int] = Non
         import uvicorn
 
         app = create_app(pm, settings, metrics)
-        sock = socket.socket(socket.AF_INET, socket.SOCK_STREAM)
+        # (proto named: asyncio sets TCP_NODELAY only on connections whose socket says IPPROTO_TCP,
+        # and without it every response smaller than a TCP window, frame.jpg among them, waits
+        # ~40 ms for the client's delayed ACK between its header and its body)
+        sock = socket.socket(socket.AF_INET, socket.SOCK_STREAM, socket.IPPROTO_TCP)
         sock.setsockopt(socket.SOL_SOCKET, socket.SO_REUSEADDR, 1)
         sock.bind((host, rport))
         rport = sock.getsockname()[1]

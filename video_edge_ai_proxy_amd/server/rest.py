@@ -10,18 +10,20 @@ server/api/rtsp_process.go:39-106, api/settings.go:38-62, api/error.go:20-31:
   GET    /api/v1/settings         500 / 200 + Settings
   POST   /api/v1/settings         400 / 500 / 202
 Errors are ``{"code": int, "message": str}``. New: ``/metrics`` (Prometheus), ``/healthz``,
-``GET /api/v1/process/{name}/frame`` (latest frame as PPM, for the portal preview), and the
-portal itself at ``/`` (replaces the Angular build, which needs a node toolchain).
+``GET /api/v1/process/{name}/frame`` (latest frame as PPM), ``.../frame.jpg`` (the same frame
+as a JPEG, encoded on the camera's GPU) and ``.../stream.mjpg`` (live MJPEG, one part per new
+frame), and the portal itself at ``/`` (replaces the Angular build, which needs a node toolchain).
 """
 from __future__ import annotations
 
 import json
 import logging
+import time
 from pathlib import Path
 
 from fastapi import FastAPI, Request
 from fastapi.middleware.cors import CORSMiddleware
-from fastapi.responses import HTMLResponse, JSONResponse, Response
+from fastapi.responses import HTMLResponse, JSONResponse, Response, StreamingResponse
 
 from ..models import Settings, StreamProcess
 from ..services.process_manager import ProcessError, ProcessManager
@@ -29,6 +31,8 @@ from ..services.settings import SettingsManager
 
 log = logging.getLogger("vep.rest")
 PORTAL = Path(__file__).with_name("portal.html")
+MJPEG_BOUNDARY = "vepframe"
+MJPEG_IDLE_S = 10.0  # a stream whose camera publishes nothing for this long ends
 
 
 def err(code: int, message: str) -> JSONResponse:
@@ -97,6 +101,78 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         h, w = img.shape[:2]
         ppm = f"P6 {w} {h} 255\n".encode() + img[:, :, ::-1].tobytes()  # BGR -> RGB
         return Response(content=ppm, media_type="image/x-portable-pixmap")
+
+    def jpeg_quality(quality):
+        if quality is None:
+            return None
+        if not 1 <= quality <= 100:
+            raise ValueError("quality must be 1..100")
+        return quality
+
+    @app.get("/api/v1/process/{name}/frame.jpg")
+    def frame_jpg(name: str, quality: int | None = None, after: int = 0):
+        try:
+            q = jpeg_quality(quality)
+        except ValueError as e:
+            return err(400, str(e))
+        try:
+            pm.hub.touch(name)
+            r = pm.hub.latest_jpeg(name, after, q)
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        if r is None:
+            return err(404, "no frame decoded yet")
+        meta, jpg = r
+        return Response(content=jpg, media_type="image/jpeg", headers={"X-Vep-Seq": str(meta["seq"])})
+
+    @app.get("/api/v1/process/{name}/stream.mjpg")
+    def stream_mjpg(name: str, fps: float = 10.0, frames: int | None = None, quality: int | None = None):
+        try:
+            q = jpeg_quality(quality)
+            if not 0 < fps <= 1000:
+                raise ValueError("fps must be in (0, 1000]")
+            if frames is not None and frames < 1:
+                raise ValueError("frames must be >= 1")
+        except ValueError as e:
+            return err(400, str(e))
+        try:
+            pm.hub.touch(name)
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+
+        def parts():
+            # one part per NEW frame (the seq cursor), at most `fps` a second; every part touches
+            # the camera, so its lazy decoder stays awake while someone watches
+            seq, sent, last_new = 0, 0, time.monotonic()
+            due = last_new
+            while frames is None or sent < frames:
+                try:
+                    pm.hub.touch(name)
+                    wait = getattr(pm.hub, "wait_frame", None)
+                    if wait is not None:
+                        if pm.hub.published(name) < seq:
+                            seq = 0  # the camera started a new ring (restart, resolution change)
+                        wait(name, seq, 500)
+                    r = pm.hub.latest_jpeg(name, seq, q)
+                except KeyError:
+                    return  # the camera was removed
+                now = time.monotonic()
+                if r is None:
+                    if now - last_new > MJPEG_IDLE_S:
+                        return
+                    if wait is None:
+                        time.sleep(min(0.05, 1.0 / fps))
+                    continue
+                meta, jpg = r
+                seq, last_new = meta["seq"], now
+                yield (f"--{MJPEG_BOUNDARY}\r\nContent-Type: image/jpeg\r\nContent-Length: {len(jpg)}\r\n"
+                       f"X-Vep-Seq: {seq}\r\n\r\n").encode() + jpg + b"\r\n"
+                sent += 1
+                due = max(due + 1.0 / fps, now)
+                if (frames is None or sent < frames) and due > now:
+                    time.sleep(due - now)
+
+        return StreamingResponse(parts(), media_type=f"multipart/x-mixed-replace; boundary={MJPEG_BOUNDARY}")
 
     @app.get("/api/v1/processlist")
     def plist():
