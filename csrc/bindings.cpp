@@ -1820,7 +1820,6 @@ PYBIND11_MODULE(_vep, m) {
           d.crop_top = crop_top;
           d.out_hwc = reinterpret_cast<u8*>(out_hwc);
           d.out_chw = reinterpret_cast<void*>(out_chw);
-          gpu::fill_letterbox_geometry(d, size, format == gpu::kLbNV12);
           gpu::LetterboxParams p{};
           p.format = format;
           p.size = size;
@@ -1830,6 +1829,8 @@ PYBIND11_MODULE(_vep, m) {
             p.inv_std[k] = 1.f / (stdv.size() == 3 ? stdv[size_t(k)] : 1.f);
           }
           p.pad_value = u8(pad);
+          gpu::check_letterbox(d, p);
+          gpu::fill_letterbox_geometry(d, size, format == gpu::kLbNV12);
           gpu::launch_letterbox_one(d, p, reinterpret_cast<hipStream_t>(stream));
         },
         py::arg("y"), py::arg("uv"), py::arg("pitch"), py::arg("src_w"), py::arg("src_h"),

@@ -379,5 +379,10 @@ void launch_nv12_to_chw(const u8* in, void* out, int n, int size, int chw_dtype,
 void launch_letterbox(const LetterboxDesc* d_descs, int n, const LetterboxParams& p,
                       hipStream_t s);
 void launch_letterbox_one(const LetterboxDesc& d, const LetterboxParams& p, hipStream_t s);
+// Throws unless the descriptor and the parameters describe a launch the kernels can run: planes
+// and an output present, a positive window that starts inside the pitch, a known format and CHW
+// dtype, S a positive multiple of 8 (the launches above do not check; the plane heights are the
+// caller's to check, the descriptor does not carry them).
+void check_letterbox(const LetterboxDesc& d, const LetterboxParams& p);
 
 }  // namespace vep::gpu

@@ -431,6 +431,18 @@ __global__ __launch_bounds__(256) void letterbox_one_kernel(const LetterboxDesc 
 static inline u8 pad_luma(u8 pad);
 __global__ void letterbox_nv12_one_kernel(const LetterboxDesc d, int size, uint8_t pad_y);
 
+void check_letterbox(const LetterboxDesc& d, const LetterboxParams& p) {
+  VEP_CHECK(d.y && d.uv, "letterbox: null plane");
+  VEP_CHECK(p.format == kLbBGR || p.format == kLbNV12, "letterbox: unknown output format");
+  VEP_CHECK(p.chw_dtype >= kChwNone && p.chw_dtype <= kChwF32, "letterbox: unknown chw dtype");
+  VEP_CHECK(p.size > 0 && p.size % 8 == 0, "letterbox: size must be a positive multiple of 8");
+  const bool chw = p.format == kLbBGR && p.chw_dtype != kChwNone && d.out_chw;
+  VEP_CHECK(d.out_hwc || chw, "letterbox: no output");
+  VEP_CHECK(d.src_w > 0 && d.src_h > 0, "letterbox: source size must be positive");
+  VEP_CHECK(d.crop_left >= 0 && d.crop_top >= 0 && d.pitch > 0 && d.crop_left + d.src_w <= d.pitch,
+            "letterbox: source window outside the planes");
+}
+
 void launch_letterbox_one(const LetterboxDesc& d, const LetterboxParams& p, hipStream_t s) {
   VEP_CHECK(p.size % 8 == 0, "letterbox size must be a multiple of 8");
   if (p.format == kLbNV12) {

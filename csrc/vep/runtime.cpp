@@ -1157,6 +1157,39 @@ static void cpu_letterbox_nv12(const HostSurface& s, const gpu::LetterboxDesc& d
     }
 }
 
+// float -> bfloat16 bits, round to nearest even (the kernels' f32_to_bf16).
+static inline u16 cpu_f32_to_bf16(float f) {
+  u32 u;
+  std::memcpy(&u, &f, 4);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return u16(u >> 16);
+}
+
+// float -> IEEE half bits, round to nearest even (what the kernels' _Float16 cast does).
+static inline u16 cpu_f32_to_f16(float f) {
+  u32 u;
+  std::memcpy(&u, &f, 4);
+  const u32 sign = (u >> 16) & 0x8000u;
+  u &= 0x7FFFFFFFu;
+  u32 o;
+  if (u >= (143u << 23)) {  // >= 65536, infinity or NaN
+    o = u > (255u << 23) ? 0x7E00u : 0x7C00u;
+  } else if (u < (113u << 23)) {  // below 2^-14: a half subnormal; the float add rounds it
+    const u32 magic = 126u << 23;  // 0.5f: its ulp is 2^-24, the half subnormal step
+    float a, m;
+    std::memcpy(&a, &u, 4);
+    std::memcpy(&m, &magic, 4);
+    a += m;
+    std::memcpy(&o, &a, 4);
+    o -= magic;
+  } else {
+    const u32 odd = (u >> 13) & 1u;
+    u += (u32(15 - 127) << 23) + 0xFFFu + odd;  // rebias; a mantissa carry rounds up to infinity
+    o = u >> 13;
+  }
+  return u16(sign | o);
+}
+
 static void cpu_letterbox(const HostSurface& s, const gpu::LetterboxDesc& d,
                           const gpu::LetterboxParams& p) {
   const int S = p.size;
@@ -1195,11 +1228,16 @@ static void cpu_letterbox(const HostSurface& s, const gpu::LetterboxDesc& d,
       if (d.out_hwc)
         for (int k = 0; k < 3; ++k)
           d.out_hwc[pix * 3 + k] = u8(std::min(std::max(v[k] + 0.5f, 0.f), 255.f));
-      if (d.out_chw && p.chw_dtype == gpu::kChwF32) {
-        float* o = static_cast<float*>(d.out_chw);
+      if (d.out_chw && p.chw_dtype != gpu::kChwNone) {
         const size_t plane = size_t(S) * S;
-        for (int k = 0; k < 3; ++k)  // RGB planes from BGR values
-          o[k * plane + pix] = (v[2 - k] * (1.f / 255.f) - p.mean[k]) * p.inv_std[k];
+        for (int k = 0; k < 3; ++k) {  // RGB planes from BGR values
+          const float c = (v[2 - k] * (1.f / 255.f) - p.mean[k]) * p.inv_std[k];
+          if (p.chw_dtype == gpu::kChwF32)
+            static_cast<float*>(d.out_chw)[k * plane + pix] = c;
+          else
+            static_cast<u16*>(d.out_chw)[k * plane + pix] =
+                p.chw_dtype == gpu::kChwF16 ? cpu_f32_to_f16(c) : cpu_f32_to_bf16(c);
+        }
       }
     }
   }
@@ -2158,8 +2196,9 @@ void Worker::run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, 
       l.out_hwc = cons_hwc_ ? cons_hwc_ + size_t(jobs[i].cam) *
                                               gpu::letterbox_bytes(int(S), opt_.letterbox_format)
                             : nullptr;
-      l.out_chw = (cons_chw_ && opt_.chw_dtype == gpu::kChwF32)
-                      ? static_cast<u8*>(cons_chw_) + size_t(jobs[i].cam) * 3 * S * S * 4
+      const size_t es = opt_.chw_dtype == gpu::kChwF32 ? 4 : 2;
+      l.out_chw = (cons_chw_ && opt_.chw_dtype != gpu::kChwNone)
+                      ? static_cast<u8*>(cons_chw_) + size_t(jobs[i].cam) * 3 * S * S * es
                       : nullptr;
       gpu::fill_letterbox_geometry(l, opt_.letterbox_size, nv12);
       if (nv12) {

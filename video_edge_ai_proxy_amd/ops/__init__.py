@@ -166,17 +166,29 @@ def letterbox_geometry(src_w: int, src_h: int, size: int, even: bool = False):
     return tuple(native.letterbox_geometry(src_w, src_h, size, even))
 
 
+def _check_letterbox(y: torch.Tensor, uv: torch.Tensor, size: int, width, height, crop_left: int,
+                     crop_top: int):
+    """Shared argument checks of the letterbox ops: the kernels read the window
+    ``[crop_top, crop_top + height) x [crop_left, crop_left + width)`` of the planes unchecked."""
+    H, W = _check_nv12(y, uv)
+    width = W - crop_left if width is None else width
+    height = H - crop_top if height is None else height
+    if size <= 0 or size % 8:
+        raise ValueError("size must be a positive multiple of 8")
+    if width <= 0 or height <= 0:
+        raise ValueError("width and height must be positive")
+    if crop_left < 0 or crop_top < 0 or crop_left + width > W or crop_top + height > H:
+        raise ValueError("source window outside the coded picture")
+    return W, int(width), int(height)
+
+
 def letterbox_nv12(y: torch.Tensor, uv: torch.Tensor, size: int = 640, width: int | None = None,
                    height: int | None = None, crop_left: int = 0, crop_top: int = 0,
                    pad_value: int = 114) -> torch.Tensor:
     """NV12 -> letterboxed NV12 ``[S*S*3/2]`` uint8 (Y and UV planes resized independently):
     the compact consumer format that crosses xGMI in the all-gather."""
     require_gpu()
-    H, W = _check_nv12(y, uv)
-    width = W - crop_left if width is None else width
-    height = H - crop_top if height is None else height
-    if size % 8:
-        raise ValueError("size must be a multiple of 8")
+    W, width, height = _check_letterbox(y, uv, size, width, height, crop_left, crop_top)
     out = torch.empty((size * size * 3 // 2,), dtype=torch.uint8, device=y.device)
     native.letterbox(y.data_ptr(), uv.data_ptr(), W, width, height, crop_left, crop_top, size,
                      out.data_ptr(), 0, 0, [0.0] * 3, [1.0] * 3, int(pad_value), _stream_ptr(y), 1)
@@ -189,6 +201,12 @@ def nv12_to_chw(batch: torch.Tensor, size: int, dtype: torch.dtype = torch.bfloa
     require_gpu()
     if batch.dtype != torch.uint8 or not batch.is_contiguous():
         raise ValueError("batch must be contiguous uint8")
+    if size <= 0 or size % 4:
+        raise ValueError("size must be a positive multiple of 4")
+    if _CHW_DTYPES.get(dtype, 0) == 0:
+        raise TypeError("dtype must be float16, bfloat16 or float32")
+    if any(float(s) == 0.0 for s in std):
+        raise ValueError("std must not contain 0")
     n = batch.numel() // (size * size * 3 // 2)
     if n * size * size * 3 // 2 != batch.numel():
         raise ValueError("batch size is not a whole number of S x S NV12 pictures")
@@ -200,20 +218,36 @@ def nv12_to_chw(batch: torch.Tensor, size: int, dtype: torch.dtype = torch.bfloa
 
 def letterbox_nv12_reference(y: torch.Tensor, uv: torch.Tensor, size: int, width: int,
                              height: int, pad_value: int = 114) -> torch.Tensor:
-    """fp32 torch reference of :func:`letterbox_nv12` (per-plane bilinear, align_corners=False)."""
-    import torch.nn.functional as F
+    """fp32 torch reference of :func:`letterbox_nv12` (per-plane bilinear, align_corners=False).
 
+    Both planes are sampled with the luma ratios ``width / nw`` and ``height / nh``: the chroma
+    plane of a picture covers ``width / 2`` chroma samples of picture (also when ``width`` is odd
+    and the plane stores ``(width + 1) // 2``), so its scale is the luma's, not the ratio of the
+    stored plane sizes an ``F.interpolate`` call would derive."""
     nw, nh, px, py = letterbox_geometry(width, height, size, even=True)
+    rx = torch.tensor(float(width), dtype=torch.float32) / float(nw)
+    ry = torch.tensor(float(height), dtype=torch.float32) / float(nh)
+
+    def axis(n, r, src):
+        s = ((torch.arange(n, dtype=torch.float32) + 0.5) * r - 0.5).clamp(min=0.0)
+        i0 = s.floor().long().clamp(max=src - 1)
+        return i0.to(y.device), (i0 + 1).clamp(max=src - 1).to(y.device), (s - i0.float()).to(y.device)
+
+    def resize(P, oh, ow):  # P: [..., h, w] float32
+        y0, y1, ly = axis(oh, ry, P.shape[-2])
+        x0, x1, lx = axis(ow, rx, P.shape[-1])
+        ly = ly[:, None]
+        top = (1 - lx) * P[..., y0, :][..., x0] + lx * P[..., y0, :][..., x1]
+        bot = (1 - lx) * P[..., y1, :][..., x0] + lx * P[..., y1, :][..., x1]
+        return (1 - ly) * top + ly * bot
+
     ypad = round(16 + pad_value * 219 / 255)
-    Y = y[:height, :width].float()[None, None]
     yo = torch.full((size, size), float(ypad), device=y.device)
-    yo[py:py + nh, px:px + nw] = F.interpolate(Y, size=(nh, nw), mode="bilinear",
-                                               align_corners=False)[0, 0]
+    yo[py:py + nh, px:px + nw] = resize(y[:height, :width].float(), nh, nw)
     cw, chh = (width + 1) // 2, (height + 1) // 2
-    C = uv[:chh, :cw * 2].float().view(chh, cw, 2).permute(2, 0, 1)[None]
+    C = uv[:chh, :cw * 2].float().view(chh, cw, 2).permute(2, 0, 1)
     co = torch.full((2, size // 2, size // 2), 128.0, device=y.device)
-    co[:, py // 2:py // 2 + nh // 2, px // 2:px // 2 + nw // 2] = F.interpolate(
-        C, size=(nh // 2, nw // 2), mode="bilinear", align_corners=False)[0]
+    co[:, py // 2:py // 2 + nh // 2, px // 2:px // 2 + nw // 2] = resize(C, nh // 2, nw // 2)
     out_y = (yo + 0.5).clamp(0, 255).floor().to(torch.uint8).flatten()
     out_c = (co + 0.5).clamp(0, 255).floor().to(torch.uint8).permute(1, 2, 0).flatten()
     return torch.cat([out_y, out_c])
@@ -225,19 +259,23 @@ def letterbox(y: torch.Tensor, uv: torch.Tensor, size: int = 640, width: int | N
               pad_value: int = 114, hwc: bool = True):
     """NV12 -> (hwc uint8 [S,S,3] BGR or None, chw [3,S,S] RGB normalised or None)."""
     require_gpu()
-    H, W = _check_nv12(y, uv)
-    width = W - crop_left if width is None else width
-    height = H - crop_top if height is None else height
-    if size % 4:
-        raise ValueError("size must be a multiple of 4")
+    W, width, height = _check_letterbox(y, uv, size, width, height, crop_left, crop_top)
+    if chw_dtype not in _CHW_DTYPES:
+        raise TypeError("chw_dtype must be None, float16, bfloat16 or float32")
+    mean, std = list(map(float, mean)), list(map(float, std))
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std must have three values (RGB)")
+    if any(s == 0.0 for s in std):
+        raise ValueError("std must not contain 0")
+    if not hwc and chw_dtype is None:
+        raise ValueError("nothing to compute: hwc is False and chw_dtype is None")
     out_hwc = torch.empty((size, size, 3), dtype=torch.uint8, device=y.device) if hwc else None
     out_chw = (torch.empty((3, size, size), dtype=chw_dtype, device=y.device)
                if chw_dtype is not None else None)
     native.letterbox(y.data_ptr(), uv.data_ptr(), W, width, height, crop_left, crop_top, size,
                      out_hwc.data_ptr() if out_hwc is not None else 0,
                      out_chw.data_ptr() if out_chw is not None else 0,
-                     _CHW_DTYPES[chw_dtype], list(map(float, mean)), list(map(float, std)),
-                     int(pad_value), _stream_ptr(y))
+                     _CHW_DTYPES[chw_dtype], mean, std, int(pad_value), _stream_ptr(y))
     return out_hwc, out_chw
 
 
