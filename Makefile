@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -74,6 +74,17 @@ $(ASAN_DIR)/jpeg_selftest: csrc/vep/jpeg.cpp csrc/tests/jpeg_selftest.cpp csrc/v
 
 asan-jpeg: $(ASAN_DIR)/jpeg_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/jpeg_selftest
+
+# The CPU scaler and wall composition alone on their edge shapes (csrc/tests/scale_selftest.cpp),
+# likewise: a stand-alone host program, no GPU.
+$(ASAN_DIR)/scale_selftest: csrc/vep/scale.cpp csrc/tests/scale_selftest.cpp csrc/vep/scale.h csrc/vep/common.h
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc csrc/vep/scale.cpp csrc/tests/scale_selftest.cpp -o $@
+
+asan-scale: $(ASAN_DIR)/scale_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/scale_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

@@ -19,6 +19,7 @@
 #include "vep/hevc_dec.h"
 #include "vep/hevc_kern.h"
 #include "vep/jpeg.h"
+#include "vep/scale.h"
 #include "bind_ext.h"
 #include "vep/runtime.h"
 #include "vep/synth.h"
@@ -1394,19 +1395,79 @@ PYBIND11_MODULE(_vep, m) {
       .def("read_latest_jpeg",
            // (meta, bytes) of the newest frame with seq > after as a JPEG stream, None if there
            // is none; encoded on the GPU from the ring slot (CPU backend: on the host).
-           [](Worker& w, int i, i64 after, int quality) -> py::object {
+           // width / height (0 = not given): fitted into that box and downscaled first; meta then
+           // carries the scaled size.
+           [](Worker& w, int i, i64 after, int quality, int width, int height) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              FrameMeta m;
              std::string out;
              bool ok;
              {
                py::gil_scoped_release r;
-               ok = w.read_latest_jpeg(i, after, quality, &m, out);
+               ok = w.read_latest_jpeg(i, after, quality, &m, out, width, height);
              }
              if (!ok) return py::none();
              return py::make_tuple(meta_dict(m), py::bytes(out));
            },
-           py::arg("idx"), py::arg("after") = 0, py::arg("quality") = 85)
+           py::arg("idx"), py::arg("after") = 0, py::arg("quality") = 85, py::arg("width") = 0,
+           py::arg("height") = 0)
+      .def("read_latest_scaled",
+           // (meta, ndarray) of the newest frame with seq > after, fitted into width x height
+           // (0 = that side not given) and downscaled where it lies; None if there is none.
+           [](Worker& w, int i, i64 after, int width, int height) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             FrameMeta m;
+             std::vector<u8> px;
+             bool ok;
+             {
+               py::gil_scoped_release r;
+               ok = w.read_latest_scaled(i, after, width, height, &m, px);
+             }
+             if (!ok) return py::none();
+             py::array_t<uint8_t> a({py::ssize_t(m.height), py::ssize_t(m.width), py::ssize_t(3)});
+             std::memcpy(a.mutable_data(), px.data(), px.size());
+             return py::make_tuple(meta_dict(m), a);
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("width") = 0, py::arg("height") = 0)
+      .def("read_wall_jpeg",
+           // (seqs, bytes): one JPEG of the newest frames of `cams` (camera indices; -1 = an empty
+           // tile), tile t fitted into cell t of a cols-wide grid of tile_width x tile_height
+           // cells (cols 0: ceil(sqrt(n))). foreign[t], if not None, is (seq, ndarray): an already
+           // scaled tile of a camera that lives on another worker. seqs[t] is 0 for a tile drawn
+           // as background.
+           [](Worker& w, const std::vector<int>& cams, int cols, int tw, int th, int quality, py::object foreign) {
+             std::vector<Worker::ForeignTile> ft;
+             std::vector<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>> keep;
+             if (!foreign.is_none()) {
+               py::list fl = foreign.cast<py::list>();
+               VEP_CHECK(fl.size() == cams.size(), "wall: one foreign tile entry per tile expected");
+               ft.resize(cams.size());
+               for (size_t t = 0; t < cams.size(); ++t) {
+                 if (fl[t].is_none()) continue;
+                 py::tuple e = fl[t].cast<py::tuple>();
+                 VEP_CHECK(e.size() == 2, "wall: a foreign tile is (seq, ndarray)");
+                 keep.push_back(e[1].cast<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>());
+                 const auto& a = keep.back();
+                 VEP_CHECK(a.ndim() == 3 && a.shape(2) == 3 && a.shape(0) >= 1 && a.shape(1) >= 1 &&
+                               a.shape(0) <= 65535 && a.shape(1) <= 65535,
+                           "wall: a foreign tile is an (H, W, 3) uint8 picture");
+                 ft[t].data = a.data();
+                 ft[t].w = int(a.shape(1));
+                 ft[t].h = int(a.shape(0));
+                 ft[t].seq = e[0].cast<i64>();
+               }
+             }
+             std::vector<i64> seqs;
+             std::string out;
+             {
+               py::gil_scoped_release r;
+               w.read_wall_jpeg(cams, cols, tw, th, quality, ft, seqs, out);
+             }
+             return py::make_tuple(seqs, py::bytes(out));
+           },
+           py::arg("cams"), py::arg("cols") = 0, py::arg("tile_width") = 320, py::arg("tile_height") = 180,
+           py::arg("quality") = 85, py::arg("foreign") = py::none())
+      .def_property("wall_max_tiles", &Worker::wall_max_tiles, &Worker::set_wall_max_tiles)
       .def("read_history",
            // [(meta, ndarray)] of the newest `count` (0 = the camera's history depth) frames with
            // seq > after: ascending, contiguous in seq, ending at the newest frame.
@@ -1685,7 +1746,146 @@ PYBIND11_MODULE(_vep, m) {
         },
         py::arg("bgr"), py::arg("quality") = 85);
 
+  // Area-average downscale and wall composition (vep/scale.h) on the host: the CPU backend's
+  // path and the byte-exact reference of resize_area / compose_wall.
+  m.def("fit_geometry",
+        [](int sw, int sh, int bw, int bh) {
+          VEP_CHECK(sw >= 1 && sh >= 1 && sw <= 65535 && sh <= 65535, "fit_geometry: source size must be 1..65535");
+          VEP_CHECK(bw >= 0 && bh >= 0 && bw <= 65535 && bh <= 65535, "fit_geometry: box sides must be 0..65535");
+          const scale::Size f = scale::fit(sw, sh, bw, bh);
+          return py::make_tuple(f.w, f.h);
+        },
+        py::arg("src_w"), py::arg("src_h"), py::arg("box_w") = 0, py::arg("box_h") = 0);
+  m.def("wall_geometry",
+        // (cols, rows, canvas_w, canvas_h) of n tiles
+        [](int n, int cols, int tw, int th) {
+          VEP_CHECK(n >= 1 && cols >= 0 && tw >= 1 && th >= 1, "wall_geometry: n, tile sides >= 1 and cols >= 0 expected");
+          const scale::Wall g = scale::wall(n, cols, tw, th);
+          return py::make_tuple(g.cols, g.rows, g.w, g.h);
+        },
+        py::arg("n"), py::arg("cols") = 0, py::arg("tile_width") = 320, py::arg("tile_height") = 180);
+  m.def("resize_area_cpu",
+        [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> bgr, int w, int h) {
+          VEP_CHECK(bgr.ndim() == 3 && bgr.shape(2) == 3 && bgr.shape(0) >= 1 && bgr.shape(1) >= 1 &&
+                        bgr.shape(0) <= 65535 && bgr.shape(1) <= 65535,
+                    "resize_area_cpu: (H, W, 3) uint8 picture of at most 65535 x 65535 expected");
+          const int sw = int(bgr.shape(1)), sh = int(bgr.shape(0));
+          VEP_CHECK(w >= 1 && h >= 1 && w <= sw && h <= sh, "resize_area_cpu: output must be 1..source size");
+          py::array_t<uint8_t> o({h, w, 3});
+          const u8* p = bgr.data();
+          u8* q = o.mutable_data();
+          {
+            py::gil_scoped_release r;
+            scale::area_cpu(p, sw, sh, size_t(sw) * 3, q, size_t(w) * 3, w, h);
+          }
+          return o;
+        },
+        py::arg("bgr"), py::arg("width"), py::arg("height"));
+  m.def("compose_wall_cpu",
+        [](py::list frames, int cols, int tw, int th) {
+          const int n = int(frames.size());
+          VEP_CHECK(n >= 1, "compose_wall_cpu: at least one tile expected");
+          VEP_CHECK(tw >= 1 && th >= 1 && tw <= 65535 && th <= 65535 && cols >= 0 && cols <= 65535,
+                    "compose_wall_cpu: tile sides must be 1..65535, cols 0..65535");
+          std::vector<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>> keep;
+          keep.reserve(size_t(n));
+          std::vector<scale::Tile> tiles((size_t(n)));
+          for (int t = 0; t < n; ++t) {
+            if (frames[size_t(t)].is_none()) continue;
+            keep.push_back(frames[size_t(t)].cast<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>());
+            const auto& a = keep.back();
+            VEP_CHECK(a.ndim() == 3 && a.shape(2) == 3 && a.shape(0) >= 1 && a.shape(1) >= 1 && a.shape(0) <= 65535 &&
+                          a.shape(1) <= 65535,
+                      "compose_wall_cpu: every tile is None or an (H, W, 3) uint8 picture");
+            tiles[size_t(t)].src = a.data();
+            tiles[size_t(t)].sw = int(a.shape(1));
+            tiles[size_t(t)].sh = int(a.shape(0));
+            tiles[size_t(t)].pitch = size_t(a.shape(1)) * 3;
+          }
+          const scale::Wall g = scale::wall(n, cols, tw, th);
+          VEP_CHECK(i64(g.cols) * tw <= 65535 && i64(g.rows) * th <= 65535, "wall: canvas sides must be <= 65535");
+          py::array_t<uint8_t> o({g.h, g.w, 3});
+          u8* q = o.mutable_data();
+          {
+            py::gil_scoped_release r;
+            scale::compose_cpu(tiles.data(), n, g.cols, tw, th, q, size_t(g.w) * 3);
+          }
+          return o;
+        },
+        py::arg("frames"), py::arg("cols") = 0, py::arg("tile_width") = 320, py::arg("tile_height") = 180);
+
   // ---- op API on caller-owned device buffers (torch tensors pass data_ptr / stream) ----
+  // Tiles (src pointer or 0, width, height) -> a caller-owned canvas of wall_geometry(n, cols,
+  // tile_width, tile_height), one launch of the gfx950 scale kernel on `stream` of the current
+  // device (descriptors: one process-wide pool per device). cols < 0: no wall, the single tile is
+  // resampled to tile_width x tile_height exactly (resize_area).
+  m.def("compose_wall",
+        [](const std::vector<std::tuple<uintptr_t, int, int>>& tiles, int cols, int tw, int th, uintptr_t canvas,
+           uintptr_t stream) {
+          static std::mutex mu;
+          static std::map<int, gpu::ScalePool*>* pools = new std::map<int, gpu::ScalePool*>();  // (never freed)
+          const int n = int(tiles.size());
+          VEP_CHECK(n >= 1 && n <= 65535, "compose_wall: 1..65535 tiles expected");
+          VEP_CHECK(tw >= 1 && th >= 1 && tw <= 65535 && th <= 65535 && cols <= 65535,
+                    "compose_wall: tile sides must be 1..65535");
+          VEP_CHECK(cols >= 0 || n == 1, "resize_area: one picture expected");
+          py::gil_scoped_release r;
+          int dev = 0;
+          VEP_HIP(hipGetDevice(&dev));
+          gpu::ScalePool* pool;
+          {
+            std::lock_guard<std::mutex> g(mu);
+            gpu::ScalePool*& slot = (*pools)[dev];
+            if (!slot) slot = new gpu::ScalePool();
+            pool = slot;
+          }
+          const scale::Wall g = cols < 0 ? scale::Wall{1, 1, tw, th} : scale::wall(n, cols, tw, th);
+          VEP_CHECK(i64(g.cols) * tw <= 65535 && i64(g.rows) * th <= 65535, "wall: canvas sides must be <= 65535");
+          hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+          const int cells = g.cols * g.rows;  // (the cells past the last tile are background too)
+          gpu::ScalePool::Set* set = pool->acquire(0, cells, 0);
+          try {
+            for (int t = 0; t < cells; ++t) {
+              gpu::ScaleDesc d{};
+              d.dst = reinterpret_cast<u8*>(canvas);
+              d.dst_pitch = u32(g.w) * 3;
+              d.src = t < n ? reinterpret_cast<const u8*>(std::get<0>(tiles[size_t(t)])) : nullptr;
+              if (cols >= 0) {
+                d.cx = (t % g.cols) * tw;
+                d.cy = (t / g.cols) * th;
+                d.cw = tw;
+                d.ch = th;
+              }
+              if (d.src) {
+                d.sw = std::get<1>(tiles[size_t(t)]);
+                d.sh = std::get<2>(tiles[size_t(t)]);
+                VEP_CHECK(d.sw >= 1 && d.sh >= 1 && d.sw <= 65535 && d.sh <= 65535, "scale: source size out of range");
+                d.src_pitch = u32(d.sw) * 3;
+                if (cols >= 0) {
+                  const scale::Placement p = scale::place(t, g.cols, tw, th, d.sw, d.sh);
+                  d.dx = p.x;
+                  d.dy = p.y;
+                  d.ow = p.w;
+                  d.oh = p.h;
+                } else {
+                  d.ow = tw;
+                  d.oh = th;
+                }
+              }
+              gpu::check_scale(d, g.w, g.h);
+              set->h_descs[t] = d;
+            }
+            gpu::ScalePool::run(*set, cells, s);
+            VEP_HIP(hipEventRecord(set->ev, s));  // the descriptors are reused by the next call
+            VEP_HIP(hipEventSynchronize(set->ev));
+          } catch (...) {
+            pool->release(set);
+            throw;
+          }
+          pool->release(set);
+        },
+        py::arg("tiles"), py::arg("cols"), py::arg("tile_width"), py::arg("tile_height"), py::arg("canvas"),
+        py::arg("stream"));
   // JPEG stream of a device BGR24 picture, encoded by the gfx950 kernels on `stream` of the
   // current device (scratch: one process-wide pool per device).
   m.def("jpeg_encode",

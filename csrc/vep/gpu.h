@@ -344,6 +344,64 @@ class JpegPool {
   std::vector<Scratch*> free_;
 };
 
+// ---- area-average downscale and the camera wall (gpu_scale.hip; arithmetic: scale.h) ---------
+// One tile of a batched scale launch (device memory): a packed BGR24 source resampled to
+// ow x oh at (dx, dy) of a canvas, byte-identical with scale::area_cpu, and the tile's cell
+// filled with scale::kBackground wherever the picture does not cover it. Tiles of one launch may
+// have different source sizes.
+struct ScaleDesc {
+  const VEP_DEV u8* src;  // sh rows of src_pitch bytes; null: the tile draws background only
+  VEP_DEV u8* dst;        // canvas origin, rows of dst_pitch bytes
+  u32 src_pitch, dst_pitch;
+  i32 sw, sh;
+  i32 dx, dy, ow, oh;     // the picture's rectangle in the canvas
+  // The cell: filled with background outside the picture, and the bound of every store of the
+  // tile. A zero-size cell means no fill; the picture's own rectangle then bounds the stores.
+  i32 cx, cy, cw, ch;
+};
+static_assert(sizeof(ScaleDesc) == 64, "ScaleDesc layout");
+// Throws unless the kernel can run the descriptor without touching memory outside the source
+// picture and outside a canvas of canvas_w x canvas_h (the launch below does not check).
+void check_scale(const ScaleDesc& d, int canvas_w, int canvas_h);
+// One launch for the n tiles: grid = (blocks of the largest tile + rows of the tallest cell) x
+// tiles. h_descs is the host copy of d_descs (the grid is sized from it).
+void launch_scale(const ScaleDesc* d_descs, const ScaleDesc* h_descs, int n, hipStream_t s);
+
+// Scale scratch of one device: up to kScratch sets, one per request in flight. A set holds a
+// canvas, a descriptor array (device + pinned host copy) and a pinned upload buffer; each grows
+// to the largest request it has seen and is then reused (steady state allocates nothing). Used
+// with the device bound to the calling thread.
+class ScalePool {
+ public:
+  struct Set {
+    u8* canvas = nullptr;         // device
+    size_t canvas_cap = 0;
+    ScaleDesc* d_descs = nullptr; // device
+    ScaleDesc* h_descs = nullptr; // pinned
+    int desc_cap = 0;
+    u8* upload = nullptr;         // pinned: host tiles on their way into the canvas, D2H results
+    size_t upload_cap = 0;
+    hipEvent_t ev = nullptr;
+    ~Set();
+  };
+  ScalePool();
+  ~ScalePool();
+  ScalePool(const ScalePool&) = delete;
+  ScalePool& operator=(const ScalePool&) = delete;
+  // A free set with room for canvas_bytes, ndescs descriptors and upload_bytes (waits for one).
+  Set* acquire(size_t canvas_bytes, int ndescs, size_t upload_bytes);
+  void release(Set* s);
+  // Copies the set's first n host descriptors up, launches them on `s` (no wait).
+  static void run(Set& set, int n, hipStream_t s);
+  static constexpr int kScratch = 4;
+
+ private:
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<std::unique_ptr<Set>> all_;
+  std::vector<Set*> free_;
+};
+
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 
 struct LetterboxDesc {

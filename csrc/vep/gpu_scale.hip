@@ -1,0 +1,281 @@
+// gfx950 (CDNA4) area-average downscale and camera wall. See gpu.h for the contract and scale.h
+// for the arithmetic, which the CPU implementation (scale.cpp) shares: both produce the same
+// bytes.
+//
+// One launch covers every tile: blockIdx.y is the tile, blockIdx.x below `fill_base` a block of
+// its picture, at or above it a row of its cell to fill with background.
+//
+// A picture block owns one output row and a chunk of at most 256 output columns, one thread per
+// output pixel. The source is a pure streaming read (1080p -> 320x180: 36 source pixels per
+// output pixel), and packed BGR rows start at any byte address, so the block stages the source
+// rows of its footprint in LDS with 16-byte loads from 16-byte aligned addresses, the unaligned
+// head and tail of every row byte by byte, several rows per barrier when they fit. A byte keeps
+// its address modulo 16 in LDS, so the LDS stores are aligned too. Each thread then reduces its
+// pixel's footprint horizontally out of LDS (wx weights: ow for every sample but the two at the
+// ends, so the inner loop only adds; sum <= 255 * sw: 32 bits) and
+// accumulates the rows vertically in registers (wy weights), in 32 bits while 255 * sw * sh fits
+// and in 64 bits above (scale::narrow). A footprint wider than the LDS buffer is staged in
+// segments of kSegPix pixels, one row at a time.
+//
+// Every store is checked against the tile's cell (or the picture's own rectangle when the tile
+// has no cell); check_scale() proves on the host that those lie inside the canvas.
+#define VEP_KERNEL_SOURCE 1  // descriptors' pointers are global-address-space here (gpu.h)
+#include <algorithm>
+
+#include "gpu.h"
+#include "scale.h"
+
+namespace vep::gpu {
+
+namespace {
+
+constexpr u32 kThreads = 256;
+constexpr u32 kLdsBytes = 24576;
+// pixels of one staged segment: 3 bytes each + up to 15 bytes of misalignment fit the buffer
+constexpr u32 kSegPix = (kLdsBytes - 16) / 3;
+static_assert(kSegPix * 3 + 15 <= kLdsBytes, "segment fits LDS");
+
+__device__ __forceinline__ u32 chunks_of(u32 ow) { return (ow + kThreads - 1) / kThreads; }
+
+// Rows rb .. rb + nr of the source, pixels [is, ie), into LDS: row rr at rr * rowcap + (its
+// address modulo 16).
+__device__ __forceinline__ void stage_rows(const VEP_DEV u8* src, u32 src_pitch, u32 rb, u32 nr, u32 is,
+                                           u32 nbytes, u32 rowcap, u8* lds) {
+  const u32 t = threadIdx.x;
+  const u32 vpr = (nbytes >> 4) + 1;  // upper bound of a row's 16-byte vectors
+  const u32 total = nr * vpr;
+  // Every load of a pass is issued before the first LDS store, so a pass costs one memory
+  // latency: the thread's head / tail byte, then up to six vectors (1080p -> 320x180 stages its
+  // six rows of 2.9 KB in one pass).
+  auto edge = [&](u32 rr, u8& x) -> u32 {  // a byte of row rr's unaligned head or tail
+    const u32 slot = t & 31u;
+    const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
+    const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
+    const u32 head = min(nbytes, (16u - mis) & 15u);
+    const u32 body = ((nbytes - head) >> 4) << 4;
+    u32 o;
+    if (slot < 16) {
+      if (slot >= head) return ~0u;
+      o = slot;
+    } else {
+      if (slot - 16 >= nbytes - head - body) return ~0u;
+      o = head + body + (slot - 16);
+    }
+    x = g[o];
+    return rr * rowcap + mis + o;
+  };
+  auto fetch = [&](u32 item, uint4& x) -> u32 {  // -> LDS offset, ~0u: no vector
+    if (item >= total) return ~0u;
+    const u32 rr = item / vpr, v = item - rr * vpr;
+    const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
+    const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
+    const u32 head = min(nbytes, (16u - mis) & 15u);
+    if (v >= ((nbytes - head) >> 4)) return ~0u;
+    x = *reinterpret_cast<const VEP_DEV uint4*>(g + head + v * 16);
+    return rr * rowcap + mis + head + v * 16;
+  };
+  u8 e = 0;
+  const u32 e_at = (t >> 5) < nr ? edge(t >> 5, e) : ~0u;  // 32 byte slots per row, 8 rows per step
+  for (u32 base = t; base < total; base += kThreads * 6) {
+    uint4 x0 = {}, x1 = {}, x2 = {}, x3 = {}, x4 = {}, x5 = {};
+    const u32 at0 = fetch(base, x0), at1 = fetch(base + kThreads, x1), at2 = fetch(base + 2 * kThreads, x2),
+              at3 = fetch(base + 3 * kThreads, x3), at4 = fetch(base + 4 * kThreads, x4),
+              at5 = fetch(base + 5 * kThreads, x5);
+    if (at0 != ~0u) *reinterpret_cast<uint4*>(lds + at0) = x0;
+    if (at1 != ~0u) *reinterpret_cast<uint4*>(lds + at1) = x1;
+    if (at2 != ~0u) *reinterpret_cast<uint4*>(lds + at2) = x2;
+    if (at3 != ~0u) *reinterpret_cast<uint4*>(lds + at3) = x3;
+    if (at4 != ~0u) *reinterpret_cast<uint4*>(lds + at4) = x4;
+    if (at5 != ~0u) *reinterpret_cast<uint4*>(lds + at5) = x5;
+  }
+  if (e_at != ~0u) lds[e_at] = e;
+  for (u32 rr = (t >> 5) + kThreads / 32; rr < nr; rr += kThreads / 32) {
+    const u32 at = edge(rr, e);
+    if (at != ~0u) lds[at] = e;
+  }
+}
+
+template <typename Acc>
+__device__ __forceinline__ void scale_block(const ScaleDesc& d, u32 k, u32 j0, u32 j1, u8* lds) {
+  // (every field is read into a register once: the descriptor itself stays in global memory)
+  const VEP_DEV u8* src = d.src;
+  const u32 src_pitch = d.src_pitch;
+  const u32 sw = u32(d.sw), sh = u32(d.sh), ow = u32(d.ow), oh = u32(d.oh);
+  const u32 ia = scale::span_lo(j0, sw, ow), ib = scale::span_hi(j1 - 1, sw, ow);
+  const u32 r0 = scale::span_lo(k, sh, oh), r1 = scale::span_hi(k, sh, oh);
+  const u32 npix = ib - ia + 1;
+  const bool fits = npix <= kSegPix;
+  const u32 rowcap = fits ? ((npix * 3 + 15 + 15) & ~15u) : kLdsBytes;
+  const u32 rpp = fits ? kLdsBytes / rowcap : 1;  // rows staged per barrier
+  const u32 j = j0 + threadIdx.x;
+  const bool active = j < j1;
+  // Only the two ends of a footprint overlap the output pixel in part; every sample between
+  // them weighs ow, so the inner loop only adds.
+  u32 lo = 0, hi = 0, w_lo = 0, w_hi = 0;
+  if (active) {
+    lo = scale::span_lo(j, sw, ow);
+    hi = scale::span_hi(j, sw, ow);
+    w_lo = scale::weight(j, lo, sw, ow);
+    w_hi = scale::weight(j, hi, sw, ow);
+  }
+  Acc a0 = 0, a1 = 0, a2 = 0;
+  u32 h0 = 0, h1 = 0, h2 = 0;
+  for (u32 rb = r0; rb <= r1; rb += rpp) {
+    const u32 nr = min(rpp, r1 - rb + 1);
+    for (u32 is = ia; is <= ib; is += kSegPix) {
+      const u32 ie = min(is + kSegPix, ib + 1);  // exclusive
+      stage_rows(src, src_pitch, rb, nr, is, (ie - is) * 3, rowcap, lds);
+      __syncthreads();
+      if (active) {
+        const u32 a = max(lo + 1, is), b = min(hi, ie);  // whole samples [a, b) of this segment
+        const bool has_lo = lo >= is && lo < ie, has_hi = hi != lo && hi >= is && hi < ie;
+        for (u32 rr = 0; rr < nr; ++rr) {
+          const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
+          const u32 row_off = rr * rowcap + (u32(reinterpret_cast<uintptr_t>(g)) & 15u);
+          const u8* l = lds + row_off;
+          u32 s0 = 0, s1 = 0, s2 = 0;
+          u32 i = a;
+          if (a + 4 <= b) {
+            // Four whole samples at a time: their 12 bytes come out of aligned LDS dwords (a third
+            // of the byte reads, which bound the kernel), realigned to B G R B | G R B G | R B G R.
+            // The last dword may lie up to 4 bytes past the row: inside the buffer's padding.
+            const u32 off = row_off + (a - is) * 3, sh = off & 3u;
+            const u32* w = reinterpret_cast<const u32*>(lds + (off & ~3u));
+            u32 d0 = w[0];
+            for (; i + 4 <= b; i += 4, w += 3) {
+              const u32 d1 = w[1], d2 = w[2], d3 = w[3];
+              const u32 r0 = __builtin_amdgcn_alignbyte(d1, d0, sh), r1 = __builtin_amdgcn_alignbyte(d2, d1, sh),
+                        r2 = __builtin_amdgcn_alignbyte(d3, d2, sh);
+              s0 += (r0 & 255u) + (r0 >> 24) + ((r1 >> 16) & 255u) + ((r2 >> 8) & 255u);
+              s1 += ((r0 >> 8) & 255u) + (r1 & 255u) + (r1 >> 24) + ((r2 >> 16) & 255u);
+              s2 += ((r0 >> 16) & 255u) + ((r1 >> 8) & 255u) + (r2 & 255u) + (r2 >> 24);
+              d0 = d3;
+            }
+          }
+          for (; i < b; ++i) {
+            const u8* p = l + (i - is) * 3;
+            s0 += p[0];
+            s1 += p[1];
+            s2 += p[2];
+          }
+          h0 += ow * s0;
+          h1 += ow * s1;
+          h2 += ow * s2;
+          if (has_lo) {
+            const u8* p = l + (lo - is) * 3;
+            h0 += w_lo * p[0];
+            h1 += w_lo * p[1];
+            h2 += w_lo * p[2];
+          }
+          if (has_hi) {
+            const u8* p = l + (hi - is) * 3;
+            h0 += w_hi * p[0];
+            h1 += w_hi * p[1];
+            h2 += w_hi * p[2];
+          }
+          if (ie == ib + 1) {  // the row is complete
+            const Acc wy = scale::weight(k, rb + rr, sh, oh);
+            a0 += wy * h0;
+            a1 += wy * h1;
+            a2 += wy * h2;
+            h0 = h1 = h2 = 0;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (!active) return;
+  const i32 x = d.dx + i32(j), y = d.dy + i32(k);
+  if (d.cw > 0 && d.ch > 0 && (x < d.cx || x >= d.cx + d.cw || y < d.cy || y >= d.cy + d.ch)) return;
+  u32 o0, o1, o2;
+  if constexpr (sizeof(Acc) == 4) {
+    const u32 den = sw * sh;
+    o0 = scale::round_div32(a0, den);
+    o1 = scale::round_div32(a1, den);
+    o2 = scale::round_div32(a2, den);
+  } else {
+    const u64 den = u64(sw) * sh;
+    o0 = scale::round_div64(a0, den);
+    o1 = scale::round_div64(a1, den);
+    o2 = scale::round_div64(a2, den);
+  }
+  VEP_DEV u8* q = d.dst + u64(y) * d.dst_pitch + u64(x) * 3;
+  q[0] = u8(o0);
+  q[1] = u8(o1);
+  q[2] = u8(o2);
+}
+
+__global__ __launch_bounds__(kThreads) void scale_kernel(const ScaleDesc* __restrict__ descs, u32 fill_base) {
+  __shared__ __attribute__((aligned(16))) u8 lds[kLdsBytes + 16];  // (+ 16: scale_block's dword reads)
+  const ScaleDesc& d = descs[blockIdx.y];
+  const u32 bx = blockIdx.x;
+  if (bx >= fill_base) {
+    // background: one row of the cell, every byte outside the picture's rectangle
+    const u32 fy = bx - fill_base;
+    if (d.cw <= 0 || d.ch <= 0 || fy >= u32(d.ch)) return;
+    const i32 y = d.cy + i32(fy);
+    const bool pic_row = d.src && y >= d.dy && y < d.dy + d.oh;
+    VEP_DEV u8* row = d.dst + u64(y) * d.dst_pitch + u64(d.cx) * 3;
+    const u32 n = u32(d.cw) * 3;
+    const u32 pa = u32(d.dx - d.cx) * 3, pb = pa + u32(d.ow) * 3;  // (check_scale: dx >= cx)
+    for (u32 b = threadIdx.x; b < n; b += kThreads)
+      if (!(pic_row && b >= pa && b < pb)) row[b] = scale::kBackground;
+    return;
+  }
+  if (!d.src) return;
+  const u32 nch = chunks_of(u32(d.ow));
+  if (bx >= nch * u32(d.oh)) return;
+  const u32 k = bx / nch, c = bx - k * nch;
+  const u32 cwid = (u32(d.ow) + nch - 1) / nch;
+  const u32 j0 = c * cwid, j1 = min(u32(d.ow), j0 + cwid);
+  if (j0 >= j1) return;
+  if (scale::narrow(u32(d.sw), u32(d.sh)))
+    scale_block<u32>(d, k, j0, j1, lds);
+  else
+    scale_block<u64>(d, k, j0, j1, lds);
+}
+
+}  // namespace
+
+void check_scale(const ScaleDesc& d, int canvas_w, int canvas_h) {
+  VEP_CHECK(d.dst, "scale: null canvas");
+  VEP_CHECK(canvas_w >= 1 && canvas_h >= 1 && canvas_w <= scale::kMaxSide && canvas_h <= scale::kMaxSide,
+            "scale: canvas size must be 1..65535");
+  VEP_CHECK(u64(d.dst_pitch) >= u64(canvas_w) * 3, "scale: canvas pitch shorter than a row");
+  const bool cell = d.cw > 0 && d.ch > 0;
+  VEP_CHECK(d.cw >= 0 && d.ch >= 0 && (d.cw > 0) == (d.ch > 0), "scale: bad cell");
+  if (cell)
+    VEP_CHECK(d.cx >= 0 && d.cy >= 0 && d.cx <= canvas_w - d.cw && d.cy <= canvas_h - d.ch,
+              "scale: cell outside the canvas");
+  if (!d.src) return;
+  VEP_CHECK(d.sw >= 1 && d.sh >= 1 && d.sw <= scale::kMaxSide && d.sh <= scale::kMaxSide,
+            "scale: source size out of range");
+  VEP_CHECK(d.ow >= 1 && d.oh >= 1 && d.ow <= d.sw && d.oh <= d.sh,
+            "scale: output must be 1..source size (no upscaling)");
+  VEP_CHECK(u64(d.src_pitch) >= u64(d.sw) * 3, "scale: source pitch shorter than a row");
+  if (cell)
+    VEP_CHECK(d.dx >= d.cx && d.dy >= d.cy && d.dx <= d.cx + d.cw - d.ow && d.dy <= d.cy + d.ch - d.oh,
+              "scale: picture outside its cell");
+  else
+    VEP_CHECK(d.dx >= 0 && d.dy >= 0 && d.dx <= canvas_w - d.ow && d.dy <= canvas_h - d.oh,
+              "scale: picture outside the canvas");
+}
+
+void launch_scale(const ScaleDesc* d_descs, const ScaleDesc* h_descs, int n, hipStream_t s) {
+  if (n <= 0) return;
+  VEP_CHECK(n <= 65535, "scale: at most 65535 tiles per launch");
+  u64 blocks = 0;
+  u32 rows = 0;
+  for (int i = 0; i < n; ++i) {
+    const ScaleDesc& d = h_descs[i];
+    if (d.src) blocks = std::max(blocks, u64((u32(d.ow) + kThreads - 1) / kThreads) * u32(d.oh));
+    if (d.cw > 0 && d.ch > 0) rows = std::max(rows, u32(d.ch));
+  }
+  if (blocks + rows == 0) return;
+  VEP_CHECK(blocks + rows < (u64(1) << 31), "scale: launch too large");
+  hipLaunchKernelGGL(scale_kernel, dim3(u32(blocks) + rows, u32(n)), dim3(kThreads), 0, s, d_descs, u32(blocks));
+  VEP_HIP(hipGetLastError());
+}
+
+}  // namespace vep::gpu

@@ -12,6 +12,7 @@
 
 #include "color.h"
 #include "jpeg.h"
+#include "scale.h"
 #include "trace.h"
 
 namespace vep {
@@ -2673,8 +2674,297 @@ bool Worker::read_latest(int cam, i64 after, FrameMeta* meta, u8* dst, size_t ca
   return r && read_latest(*r, after, meta, dst, cap);
 }
 
-bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out) {
+void Worker::set_wall_max_tiles(int n) {
+  VEP_CHECK(n >= 1 && n <= 65535, "wall: wall_max_tiles must be 1..65535");
+  wall_max_tiles_.store(n);
+}
+
+void Worker::encode_device(const u8* d_bgr, int w, int h, int quality, std::string& out) {
+  if (jpeg_pool_.encode(d_bgr, w, h, quality, serve_stream_, out)) return;
+  // the kernels reported an overflow of their scratch: encode the picture on the host
+  const size_t n = size_t(w) * size_t(h) * 3;
+  std::unique_ptr<u8[]> host(new u8[n]);
+  VEP_HIP(hipMemcpyAsync(host.get(), d_bgr, n, hipMemcpyDeviceToHost, serve_stream_));
+  VEP_HIP(hipStreamSynchronize(serve_stream_));
+  out = jpeg::encode_cpu(host.get(), w, h, quality);
+}
+
+void Worker::scale_slot(gpu::ScalePool::Set& set, const FrameRing& ring, int slot, int ow, int oh) {
+  gpu::ScaleDesc& d = set.h_descs[0];
+  d = gpu::ScaleDesc{};
+  d.src = ring.slot_ptr(slot);
+  d.sw = ring.width();
+  d.sh = ring.height();
+  d.src_pitch = u32(ring.width()) * 3;
+  d.dst = set.canvas;
+  d.dst_pitch = u32(ow) * 3;
+  d.ow = ow;
+  d.oh = oh;
+  gpu::check_scale(d, ow, oh);
+  gpu::ScalePool::run(set, 1, serve_stream_);
+}
+
+static void check_box(int width, int height) {
+  VEP_CHECK(width >= 0 && width <= scale::kMaxSide && height >= 0 && height <= scale::kMaxSide && (width || height),
+            "scale: width and height must be 1..65535");
+}
+
+bool Worker::read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst) {
+  check_box(width, height);
+  std::shared_ptr<Camera> c = camera(cam);
+  if (!c) return false;
+  std::shared_ptr<FrameRing> ring = c->ring();
+  if (!ring) return false;
+  const scale::Size f = scale::fit(ring->width(), ring->height(), width, height);
+  const size_t n = size_t(f.w) * size_t(f.h) * 3;
+  dst.resize(n);
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    int slot;
+    if (!ring->latest(after, meta, &slot)) return false;
+    if (dev_.gpu()) {
+      dev_.bind();
+      gpu::ScalePool::Set* set = scale_pool_.acquire(n, 1, n);
+      try {
+        scale_slot(*set, *ring, slot, f.w, f.h);
+        VEP_HIP(hipMemcpyAsync(set->upload, set->canvas, n, hipMemcpyDeviceToHost, serve_stream_));
+        VEP_HIP(hipEventRecord(set->ev, serve_stream_));
+        VEP_HIP(hipEventSynchronize(set->ev));
+        std::memcpy(dst.data(), set->upload, n);
+      } catch (...) {
+        scale_pool_.release(set);
+        throw;
+      }
+      scale_pool_.release(set);
+    } else {
+      scale::area_cpu(ring->slot_ptr(slot), ring->width(), ring->height(), size_t(ring->width()) * 3, dst.data(),
+                      size_t(f.w) * 3, f.w, f.h);
+    }
+    if (ring->still_valid(slot, meta->seq)) {
+      meta->width = f.w;
+      meta->height = f.h;
+      return true;
+    }
+  }
+  return false;
+}
+
+void Worker::read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
+                            const std::vector<ForeignTile>& foreign, std::vector<i64>& seqs_out, std::string& out) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  const int n = int(cams.size());
+  VEP_CHECK(n >= 1 && n <= wall_max_tiles(), "wall: the number of tiles must be 1..serving.wall_max_tiles");
+  VEP_CHECK(tw >= 1 && tw <= scale::kMaxSide && th >= 1 && th <= scale::kMaxSide, "wall: tile size must be 1..65535");
+  VEP_CHECK(cols >= 0 && cols <= scale::kMaxSide, "wall: cols out of range");
+  VEP_CHECK(foreign.empty() || int(foreign.size()) == n, "wall: one foreign tile entry per tile expected");
+  const scale::Wall g = scale::wall(n, cols, tw, th);
+  VEP_CHECK(i64(g.cols) * tw <= scale::kMaxSide && i64(g.rows) * th <= scale::kMaxSide,
+            "wall: canvas sides must be <= 65535");
+  struct TileSrc {
+    std::shared_ptr<Camera> cam;
+    std::shared_ptr<FrameRing> ring;
+    FrameMeta meta;
+    int slot = -1;
+    bool done = false;  // consistent, foreign or given up (background)
+  };
+  std::vector<TileSrc> ts((size_t(n)));
+  seqs_out.assign(size_t(n), 0);
+  size_t up_bytes = 0;
+  for (int t = 0; t < n; ++t) {
+    TileSrc& s = ts[size_t(t)];
+    if (!foreign.empty() && foreign[size_t(t)].data) {
+      const ForeignTile& f = foreign[size_t(t)];
+      VEP_CHECK(f.w >= 1 && f.h >= 1 && f.w <= tw && f.h <= th, "wall: foreign tile larger than its cell");
+      up_bytes += size_t(f.w) * size_t(f.h) * 3;
+      seqs_out[size_t(t)] = f.seq;
+      continue;
+    }
+    s.cam = camera(cams[size_t(t)]);
+    if (s.cam) s.ring = s.cam->ring();
+  }
+  const size_t pitch = size_t(g.w) * 3, canvas_bytes = pitch * size_t(g.h);
+  // tile t's descriptor from its ring's newest frame; background only when there is none
+  auto cell = [&](int t, u8* canvas) {
+    gpu::ScaleDesc d{};
+    d.dst = canvas;
+    d.dst_pitch = u32(pitch);
+    d.cx = (t % g.cols) * tw;
+    d.cy = (t / g.cols) * th;
+    d.cw = tw;
+    d.ch = th;
+    return d;
+  };
+  auto pick = [&](int t) {  // newest frame of tile t's ring -> slot / meta; false: background
+    TileSrc& s = ts[size_t(t)];
+    s.slot = -1;
+    return s.ring && s.ring->latest(0, &s.meta, &s.slot);
+  };
+  if (!dev_.gpu()) {
+    std::vector<u8> canvas(canvas_bytes);
+    std::vector<scale::Tile> tiles((size_t(n)));
+    for (int round = 0; round < 4; ++round) {
+      bool again = false;
+      for (int t = 0; t < n; ++t) {
+        TileSrc& s = ts[size_t(t)];
+        scale::Tile& tl = tiles[size_t(t)];
+        if (s.done && round) continue;
+        tl = scale::Tile{};
+        if (!foreign.empty() && foreign[size_t(t)].data) {
+          s.done = true;
+          continue;
+        }
+        if (!pick(t)) {
+          s.done = true;
+          continue;
+        }
+        tl.src = s.ring->slot_ptr(s.slot);
+        tl.sw = s.ring->width();
+        tl.sh = s.ring->height();
+        tl.pitch = size_t(tl.sw) * 3;
+      }
+      // (the host composition is cheap to repeat whole: a round redraws every tile)
+      scale::compose_cpu(tiles.data(), n, g.cols, tw, th, canvas.data(), pitch);
+      for (int t = 0; t < n; ++t) {
+        TileSrc& s = ts[size_t(t)];
+        if (!tiles[size_t(t)].src) continue;
+        if (s.ring->still_valid(s.slot, s.meta.seq)) {
+          s.done = true;
+          seqs_out[size_t(t)] = s.meta.seq;
+        } else {
+          s.done = false;
+          seqs_out[size_t(t)] = 0;
+          again = true;
+        }
+      }
+      if (!again) break;
+      if (round == 3) {  // still inconsistent: those tiles are drawn as background
+        // (only their cells are cleared: the other tiles were checked after they were drawn)
+        for (int t = 0; t < n; ++t) {
+          if (ts[size_t(t)].done) continue;
+          u8* p = canvas.data() + size_t((t / g.cols) * th) * pitch + size_t((t % g.cols) * tw) * 3;
+          for (int y = 0; y < th; ++y) std::memset(p + size_t(y) * pitch, scale::kBackground, size_t(tw) * 3);
+        }
+      }
+    }
+    for (int t = 0; t < n && !foreign.empty(); ++t) {
+      const ForeignTile& f = foreign[size_t(t)];
+      if (!f.data) continue;
+      u8* p = canvas.data() + size_t((t / g.cols) * th + (th - f.h) / 2) * pitch +
+              size_t((t % g.cols) * tw + (tw - f.w) / 2) * 3;
+      for (int y = 0; y < f.h; ++y) std::memcpy(p + size_t(y) * pitch, f.data + size_t(y) * f.w * 3, size_t(f.w) * 3);
+    }
+    out = jpeg::encode_cpu(canvas.data(), g.w, g.h, quality);
+    return;
+  }
+  dev_.bind();
+  const int cells = g.cols * g.rows;  // (the cells past the last tile are background too)
+  gpu::ScalePool::Set* set = scale_pool_.acquire(canvas_bytes, cells, up_bytes);
+  try {
+    std::vector<int> tile_of;  // descriptor -> tile of the current round
+    for (int round = 0; round < 5; ++round) {
+      // rounds 0..3 scale the tiles that are not settled; round 4 only clears what is left
+      tile_of.clear();
+      for (int t = 0; t < n; ++t) {
+        TileSrc& s = ts[size_t(t)];
+        if (s.done) continue;
+        gpu::ScaleDesc d = cell(t, set->canvas);
+        const bool fgn = !foreign.empty() && foreign[size_t(t)].data;
+        if (!fgn && round < 4 && pick(t)) {
+          const scale::Placement p = scale::place(t, g.cols, tw, th, s.ring->width(), s.ring->height());
+          d.src = s.ring->slot_ptr(s.slot);
+          d.sw = s.ring->width();
+          d.sh = s.ring->height();
+          d.src_pitch = u32(d.sw) * 3;
+          d.dx = p.x;
+          d.dy = p.y;
+          d.ow = p.w;
+          d.oh = p.h;
+        } else {
+          s.slot = -1;
+        }
+        gpu::check_scale(d, g.w, g.h);
+        set->h_descs[tile_of.size()] = d;
+        tile_of.push_back(t);
+      }
+      if (tile_of.empty()) break;
+      int nd = int(tile_of.size());
+      for (int t = n; t < cells && round == 0; ++t) {
+        set->h_descs[nd] = cell(t, set->canvas);
+        gpu::check_scale(set->h_descs[nd++], g.w, g.h);
+      }
+      gpu::ScalePool::run(*set, nd, serve_stream_);
+      if (round == 0 && up_bytes) {  // foreign tiles: over their (background) cells, after the launch
+        size_t off = 0;
+        for (int t = 0; t < n; ++t) {
+          const ForeignTile& f = foreign[size_t(t)];
+          if (!f.data) continue;
+          const size_t row = size_t(f.w) * 3, bytes = row * size_t(f.h);
+          std::memcpy(set->upload + off, f.data, bytes);
+          u8* p = set->canvas + size_t((t / g.cols) * th + (th - f.h) / 2) * pitch +
+                  size_t((t % g.cols) * tw + (tw - f.w) / 2) * 3;
+          VEP_HIP(hipMemcpy2DAsync(p, pitch, set->upload + off, row, row, size_t(f.h), hipMemcpyHostToDevice,
+                                   serve_stream_));
+          off += bytes;
+        }
+      }
+      VEP_HIP(hipEventRecord(set->ev, serve_stream_));
+      VEP_HIP(hipEventSynchronize(set->ev));
+      for (int t : tile_of) {
+        TileSrc& s = ts[size_t(t)];
+        if (s.slot < 0) {
+          s.done = true;  // background or foreign
+        } else if (s.ring->still_valid(s.slot, s.meta.seq)) {
+          s.done = true;
+          seqs_out[size_t(t)] = s.meta.seq;
+        }
+      }
+    }
+    encode_device(set->canvas, g.w, g.h, quality, out);
+  } catch (...) {
+    scale_pool_.release(set);
+    throw;
+  }
+  scale_pool_.release(set);
+}
+
+bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width,
+                              int height) {
+  VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  if (width || height) {
+    check_box(width, height);
+    std::shared_ptr<Camera> c = camera(cam);
+    if (!c) return false;
+    std::shared_ptr<FrameRing> ring = c->ring();
+    if (!ring) return false;
+    const scale::Size f = scale::fit(ring->width(), ring->height(), width, height);
+    const size_t n = size_t(f.w) * size_t(f.h) * 3;
+    for (int attempt = 0; attempt < 4; ++attempt) {
+      int slot;
+      if (!ring->latest(after, meta, &slot)) return false;
+      if (dev_.gpu()) {
+        dev_.bind();
+        gpu::ScalePool::Set* set = scale_pool_.acquire(n, 1, 0);
+        try {
+          scale_slot(*set, *ring, slot, f.w, f.h);
+          encode_device(set->canvas, f.w, f.h, quality, out);  // (same stream: ordered after the scale)
+        } catch (...) {
+          scale_pool_.release(set);
+          throw;
+        }
+        scale_pool_.release(set);
+      } else {
+        std::vector<u8> small(n);
+        scale::area_cpu(ring->slot_ptr(slot), ring->width(), ring->height(), size_t(ring->width()) * 3, small.data(),
+                        size_t(f.w) * 3, f.w, f.h);
+        out = jpeg::encode_cpu(small.data(), f.w, f.h, quality);
+      }
+      if (ring->still_valid(slot, meta->seq)) {
+        meta->width = f.w;
+        meta->height = f.h;
+        return true;
+      }
+    }
+    return false;
+  }
   std::shared_ptr<Camera> c = camera(cam);
   if (!c) return false;
   std::shared_ptr<FrameRing> ring = c->ring();

@@ -415,7 +415,31 @@ class Worker {
   // compressed bytes are copied; the CPU backend runs jpeg::encode_cpu on the host ring. A slot
   // the writer reused during the encode is encoded again from the newer frame, as read_latest
   // does for its copy. False if there is no such frame.
-  bool read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out);
+  // width / height (0 = not given): the frame is first fitted into that box (scale::fit, never
+  // enlarged) and downscaled by area averaging (scale.h) into pooled device scratch, on the
+  // serving stream as well. With both 0 the path and the bytes are as without them.
+  bool read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width = 0,
+                        int height = 0);
+  // The same scaled picture as packed BGR24 in host memory (dst is resized to ow * oh * 3; only
+  // those bytes are copied off the GPU); meta->width / height are the scaled size.
+  bool read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst);
+  // One picture of several cameras: a wall of scale::wall(n, cols, tw, th) cells, tile t showing
+  // the newest frame of camera cams[t] fitted into its cell and centred, background elsewhere,
+  // as a JPEG stream. One scale launch fills the canvas from the ring slots; tiles whose slot the
+  // writer reused meanwhile are scaled again (up to four rounds). seqs_out[t] is the seq shown, 0
+  // for a tile drawn as background: camera index < 0 or unknown, no ring, no frame, or still
+  // inconsistent. foreign[t].data (non-null) is an already scaled host BGR24 tile (a camera of
+  // another worker, seq as given) copied into its cell instead. Only descriptors and foreign
+  // tiles go up, only compressed bytes come down.
+  struct ForeignTile {
+    const u8* data = nullptr;  // h rows of w * 3 bytes, w <= tw, h <= th
+    int w = 0, h = 0;
+    i64 seq = 0;
+  };
+  void read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
+                      const std::vector<ForeignTile>& foreign, std::vector<i64>& seqs_out, std::string& out);
+  void set_wall_max_tiles(int n);
+  int wall_max_tiles() const { return wall_max_tiles_.load(); }
   // Frame history: the newest max_count (0 = the camera's depth) frames with seq > after, copied
   // to host memory, ascending and contiguous in seq, ending at the newest frame. A frame the
   // writer reused during the read is dropped together with everything older.
@@ -600,6 +624,12 @@ class Worker {
   std::vector<std::unique_ptr<ServeBuf>> serve_all_;
   std::vector<ServeBuf*> serve_free_;
   gpu::JpegPool jpeg_pool_;  // encoder scratch of read_latest_jpeg, one set per request in flight
+  gpu::ScalePool scale_pool_;  // canvas + descriptors of the scaled / wall reads, likewise
+  std::atomic<int> wall_max_tiles_{64};  // serving.wall_max_tiles
+  // Encode a device picture on the serving stream (host encoder if the kernels report an overflow).
+  void encode_device(const u8* d_bgr, int w, int h, int quality, std::string& out);
+  // ring slot -> ow x oh at the origin of set's canvas, on the serving stream (no wait)
+  void scale_slot(gpu::ScalePool::Set& set, const FrameRing& ring, int slot, int ow, int oh);
   u8* cons_hwc_ = nullptr;
   void* cons_chw_ = nullptr;
   // consumer snapshots: exclusive while a snapshot is enqueued, shared while a lane enqueues a

@@ -113,6 +113,16 @@ def cmd_frame(a):
               "shape:", [d.size for d in vf.shape.dim], "pts:", vf.pts)
         if a.out and vf.width:
             img = np.frombuffer(vf.data, np.uint8).reshape(vf.height, vf.width, 3)
+            if a.width or a.height:
+                # fitted into the box, never enlarged; area-averaged on the host (the hub's
+                # frame.jpg?width=&height= does the same on the GPU)
+                from ._native import native
+
+                for v in (a.width, a.height):
+                    if v is not None and not 1 <= v <= 65535:
+                        raise SystemExit("--width / --height must be 1..65535")
+                ow, oh = native.fit_geometry(vf.width, vf.height, a.width or 0, a.height or 0)
+                img = native.resize_area_cpu(np.ascontiguousarray(img), ow, oh)
             write_frame(a.out, img)
 
 
@@ -213,6 +223,8 @@ def main(argv=None):
             p.add_argument("--keyframe", action="store_true")
             p.add_argument("--count", type=int, default=1)
             p.add_argument("--out", default=None, help="write the last frame: .jpg / .jpeg as a JPEG, else PPM")
+            p.add_argument("--width", type=int, default=None, help="scale the written frame down to fit this width")
+            p.add_argument("--height", type=int, default=None, help="... and / or this height (aspect kept)")
         if name == "annotate":
             p.add_argument("--type", required=True)
         if name in ("storage", "proxy"):

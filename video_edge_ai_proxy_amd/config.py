@@ -103,6 +103,8 @@ class ServingConfig:
                                 # (server/resp.py: XLEN / XRANGE / XREVRANGE / XREAD per camera)
     resp_host: str = "0.0.0.0"
     jpeg_quality: int = 85      # frame.jpg / stream.mjpg / Hub.latest_jpeg when a request names none (1..100)
+    wall_tile: str = "320x180"  # wall.jpg / wall.mjpg / Hub.wall_jpeg: cell size "WxH" when a request names none
+    wall_max_tiles: int = 64    # cameras one wall may show (1..65535)
 
 
 @dataclass
@@ -177,6 +179,23 @@ def validate(cfg: Config) -> None:
     """Reject values no part of the hub can work with (ValueError)."""
     if not 1 <= int(cfg.serving.jpeg_quality) <= 100:
         raise ValueError(f"serving.jpeg_quality must be 1..100, got {cfg.serving.jpeg_quality}")
+    try:
+        parse_tile(cfg.serving.wall_tile)
+    except ValueError as e:
+        raise ValueError(f"serving.wall_tile: {e}") from None
+    if not 1 <= int(cfg.serving.wall_max_tiles) <= 65535:
+        raise ValueError(f"serving.wall_max_tiles must be 1..65535, got {cfg.serving.wall_max_tiles}")
+
+
+def parse_tile(s) -> tuple[int, int]:
+    """``"WxH"`` -> (W, H), both 1..65535 (the wall's cell size)."""
+    m = re.fullmatch(r"\s*(\d{1,6})\s*[xX]\s*(\d{1,6})\s*", str(s))
+    if not m:
+        raise ValueError(f"tile size must be WxH, got {s!r}")
+    w, h = int(m.group(1)), int(m.group(2))
+    if not (1 <= w <= 65535 and 1 <= h <= 65535):
+        raise ValueError(f"tile sides must be 1..65535, got {s!r}")
+    return w, h
 
 
 _DUR = re.compile(r"(\d+(?:\.\d+)?)(ns|us|µs|ms|s|m|h)")

@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 from .._native import gpu_count, native
-from ..config import Config
+from ..config import Config, parse_tile
 from ..utils import now_ms
 
 log = logging.getLogger("vep.hub")
@@ -85,6 +85,7 @@ class Hub:
                               std=list(g.std), max_cameras=int(g.max_cameras_per_gpu),
                               letterbox_format=1 if g.letterbox_format == "nv12" else 0,
                               decoder=str(getattr(g, "decoder", "native")), host_domain=dom)
+            w.wall_max_tiles = int(cfg.serving.wall_max_tiles)
             w.start()
             self.workers.append(w)
         # Consumer batch: with letterbox_size > 0 every worker letterboxes each frame it publishes
@@ -301,15 +302,111 @@ class Hub:
         w, cam = self.worker_of(name)
         return w.read_latest(cam, after)
 
-    def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None):
-        """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
-        Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
-        ``quality`` 1..100, default ``serving.jpeg_quality``."""
+    def _quality(self, quality: Optional[int]) -> int:
         q = int(self.cfg.serving.jpeg_quality if quality is None else quality)
         if not 1 <= q <= 100:
             raise ValueError("quality must be 1..100")
+        return q
+
+    @staticmethod
+    def _box(width: Optional[int], height: Optional[int]) -> tuple[int, int]:
+        """A requested size as the native layer takes it (0 = that side not given)."""
+        out = []
+        for v, what in ((width, "width"), (height, "height")):
+            if v is None:
+                out.append(0)
+                continue
+            if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 65535:
+                raise ValueError(f"{what} must be an integer 1..65535")
+            out.append(v)
+        return out[0], out[1]
+
+    def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
+                    width: Optional[int] = None, height: Optional[int] = None):
+        """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
+        Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
+        ``quality`` 1..100, default ``serving.jpeg_quality``. With ``width`` and / or ``height``
+        the frame is first fitted into that box (aspect kept, never enlarged) and downscaled by
+        area averaging, on the GPU as well; ``meta`` then carries the scaled size."""
+        q = self._quality(quality)
+        bw, bh = self._box(width, height)
         w, cam = self.worker_of(name)
-        return w.read_latest_jpeg(cam, after, q)
+        if not (bw or bh):
+            return w.read_latest_jpeg(cam, after, q)
+        return w.read_latest_jpeg(cam, after, q, bw, bh)
+
+    def latest_scaled(self, name: str, after: int = 0, width: Optional[int] = None,
+                      height: Optional[int] = None):
+        """``(meta, ndarray)`` of the newest frame with seq > after, fitted into ``width x height``
+        and downscaled on the camera's GPU; only the small picture is copied to the host."""
+        bw, bh = self._box(width, height)
+        if not (bw or bh):
+            raise ValueError("width or height required")
+        w, cam = self.worker_of(name)
+        return w.read_latest_scaled(cam, after, bw, bh)
+
+    def wall_tile(self) -> tuple[int, int]:
+        tw, th = parse_tile(self.cfg.serving.wall_tile)
+        return tw, th
+
+    def wall_layout(self, names=None, cols: Optional[int] = None, tile_width: Optional[int] = None,
+                    tile_height: Optional[int] = None):
+        """``(names, cols, rows, tile_width, tile_height)`` a wall of these arguments has."""
+        with self._lock:
+            order = sorted(self.cameras) if names is None else list(names)
+            for n in order:
+                self.handle(n)
+        dw, dh = self.wall_tile()
+        tw, th = self._box(dw if tile_width is None else tile_width, dh if tile_height is None else tile_height)
+        if cols is not None and (isinstance(cols, bool) or not isinstance(cols, int) or not 1 <= cols <= 65535):
+            raise ValueError("cols must be an integer 1..65535")
+        if not order:
+            raise ValueError("no camera to show")
+        if len(order) > int(self.cfg.serving.wall_max_tiles):
+            raise ValueError(f"a wall shows at most serving.wall_max_tiles = {self.cfg.serving.wall_max_tiles} cameras")
+        gc, gr, cw, ch = native.wall_geometry(len(order), cols or 0, tw, th)
+        if cw > 65535 or ch > 65535:
+            raise ValueError(f"canvas {cw}x{ch} larger than 65535")
+        return order, gc, gr, tw, th
+
+    def wall_jpeg(self, names=None, cols: Optional[int] = None, tile_width: Optional[int] = None,
+                  tile_height: Optional[int] = None, quality: Optional[int] = None):
+        """``({name: seq}, bytes)``: one JPEG showing the newest frame of every listed camera
+        (default: the running cameras, sorted), tile ``t`` fitted into cell ``(t % cols, t // cols)``
+        of ``tile_width x tile_height`` (default ``serving.wall_tile``) and centred, ``cols``
+        defaulting to ``ceil(sqrt(n))``. A camera without a frame shows as background, seq 0.
+
+        Rendered by the worker that owns most of the listed cameras (ties: the lowest index): its
+        cameras are scaled from their ring slots in one kernel launch; cameras of other workers are
+        scaled on their own GPU and only the small tiles travel. A wall refreshes ``last_query``
+        of every camera it shows, so it keeps their lazy decoders awake."""
+        q = self._quality(quality)
+        order, gc, gr, tw, th = self.wall_layout(names, cols, tile_width, tile_height)
+        hs = []
+        for n in order:
+            h = self.cameras.get(n)
+            if h is None:
+                raise CameraNotFound(n)
+            hs.append(h)
+        now = now_ms()
+        for h in hs:
+            self.workers[h.worker_index].set_last_query(h.cam, now)
+        count = [0] * len(self.workers)
+        for h in hs:
+            count[h.worker_index] += 1
+        home = max(range(len(count)), key=lambda i: (count[i], -i))
+        cams, foreign, any_foreign = [], [], False
+        for h in hs:
+            if h.worker_index == home:
+                cams.append(h.cam)
+                foreign.append(None)
+                continue
+            cams.append(-1)
+            r = self.workers[h.worker_index].read_latest_scaled(h.cam, 0, tw, th)
+            foreign.append(None if r is None else (int(r[0]["seq"]), r[1]))
+            any_foreign = any_foreign or r is not None
+        seqs, jpg = self.workers[home].read_wall_jpeg(cams, gc, tw, th, q, foreign if any_foreign else None)
+        return {n: int(s) for n, s in zip(order, seqs)}, jpg
 
     def history(self, name: str, after: int = 0, count: int = 0) -> list:
         """``[(meta, ndarray)]`` of the camera's newest ``count`` (0 = ``buffer.in_memory``) frames

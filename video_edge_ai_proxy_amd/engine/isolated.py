@@ -565,10 +565,27 @@ class ProcessHub:
     def latest_frame(self, name: str, after: int = 0):
         return self._call(name, "latest_frame", after)
 
-    def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None):
-        """(meta, JPEG bytes) or None: the worker process encodes on its GPU, only the compressed
-        bytes cross the pipe."""
-        return self._call(name, "latest_jpeg", after, quality)
+    def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
+                    width: Optional[int] = None, height: Optional[int] = None):
+        """(meta, JPEG bytes) or None: the worker process scales (width / height given) and encodes
+        on its GPU, only the compressed bytes cross the pipe."""
+        if width is None and height is None:
+            return self._call(name, "latest_jpeg", after, quality)
+        return self._call(name, "latest_jpeg", after, quality, width, height)
+
+    def latest_scaled(self, name: str, after: int = 0, width: Optional[int] = None,
+                      height: Optional[int] = None):
+        """(meta, ndarray) or None: scaled on the worker process's GPU, the small picture crosses
+        the pipe."""
+        return self._call(name, "latest_scaled", after, width, height)
+
+    # A wall reads the ring slots of many cameras in one launch; the rings live in the worker
+    # processes, one per GPU, so it is served only by the in-process hub (gpu.isolation: thread).
+    def wall_layout(self, names=None, cols=None, tile_width=None, tile_height=None):
+        raise NotImplementedError("the camera wall is not served with gpu.isolation: process")
+
+    def wall_jpeg(self, names=None, cols=None, tile_width=None, tile_height=None, quality=None):
+        raise NotImplementedError("the camera wall is not served with gpu.isolation: process")
 
     def wait_decoded(self, name: str, n: int = 1, timeout_s: float = 10.0) -> bool:
         return bool(self._call(name, "wait_decoded", n, timeout_s))

@@ -9,6 +9,9 @@
 * :func:`letterbox` — NV12 -> letterboxed model input (HWC uint8 and/or normalised CHW).
 * :func:`jpeg_encode` — BGR24 picture -> baseline JPEG stream (the kernels behind ``frame.jpg``),
   byte-identical with :func:`jpeg_encode_reference`, the CPU encoder.
+* :func:`resize_area` / :func:`compose_wall` — antialiased area-average downscale of BGR24
+  pictures, one or many into one canvas in a single launch (the kernel behind scaled
+  ``frame.jpg`` and ``wall.jpg``), byte-identical with their ``*_reference`` CPU twins.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -309,6 +312,114 @@ def jpeg_encode_reference(bgr: torch.Tensor, quality: int = 85) -> bytes:
     oracle of :func:`jpeg_encode`."""
     quality = _check_jpeg(bgr, quality)
     return native.jpeg_encode_cpu(bgr.detach().cpu().numpy(), quality)
+
+
+def _check_bgr(bgr: torch.Tensor, what: str = "bgr") -> tuple:
+    if bgr.dtype != torch.uint8:
+        raise TypeError(f"{what} must be uint8")
+    if bgr.dim() != 3 or bgr.shape[2] != 3 or bgr.shape[0] < 1 or bgr.shape[1] < 1:
+        raise ValueError(f"{what} must be [H, W, 3], got {tuple(bgr.shape)}")
+    if bgr.shape[0] > 65535 or bgr.shape[1] > 65535:
+        raise ValueError(f"{what} is at most 65535 x 65535")
+    if not bgr.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return int(bgr.shape[1]), int(bgr.shape[0])
+
+
+def _check_side(v, what: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 65535:
+        raise ValueError(f"{what} must be an integer 1..65535")
+    return v
+
+
+def _check_resize(bgr: torch.Tensor, width: int, height: int):
+    sw, sh = _check_bgr(bgr)
+    width, height = _check_side(width, "width"), _check_side(height, "height")
+    if width > sw or height > sh:
+        raise ValueError(f"output {width}x{height} larger than the source {sw}x{sh} (no upscaling)")
+    return sw, sh, width, height
+
+
+def resize_area(bgr: torch.Tensor, width: int, height: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Downscale a ``[H, W, 3]`` BGR24 device tensor to exactly ``[height, width, 3]`` by area
+    averaging (antialiased, exact in integers), byte-identical with :func:`resize_area_reference`."""
+    require_gpu()
+    if not bgr.is_cuda:
+        raise ValueError("bgr must be a device tensor")
+    sw, sh, width, height = _check_resize(bgr, width, height)
+    if out is None:
+        out = torch.empty((height, width, 3), dtype=torch.uint8, device=bgr.device)
+    if not (out.is_cuda and out.device == bgr.device and out.dtype == torch.uint8 and out.is_contiguous()
+            and tuple(out.shape) == (height, width, 3)):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {(height, width, 3)} on the source's device")
+    with torch.cuda.device(bgr.device):
+        native.compose_wall([(bgr.data_ptr(), sw, sh)], -1, width, height, out.data_ptr(), _stream_ptr(bgr))
+    return out
+
+
+def resize_area_reference(bgr: torch.Tensor, width: int, height: int) -> torch.Tensor:
+    """The CPU implementation's result for the same picture (host or device tensor), on the host:
+    the byte-exact oracle of :func:`resize_area`."""
+    _, _, width, height = _check_resize(bgr, width, height)
+    return torch.from_numpy(native.resize_area_cpu(bgr.detach().cpu().numpy(), width, height))
+
+
+def _check_wall(frames, cols, tile_width, tile_height):
+    frames = list(frames)
+    if not frames:
+        raise ValueError("frames must hold at least one tile")
+    tile_width, tile_height = _check_side(tile_width, "tile_width"), _check_side(tile_height, "tile_height")
+    if cols is None:
+        cols = 0
+    if isinstance(cols, bool) or not isinstance(cols, int) or not 0 <= cols <= 65535:
+        raise ValueError("cols must be an integer 1..65535 (or None)")
+    for k, f in enumerate(frames):
+        if f is not None:
+            _check_bgr(f, f"frames[{k}]")
+    gc, gr, cw, ch = native.wall_geometry(len(frames), cols, tile_width, tile_height)
+    if cw > 65535 or ch > 65535:
+        raise ValueError(f"canvas {cw}x{ch} larger than 65535")
+    return frames, cols, tile_width, tile_height, (ch, cw, 3)
+
+
+def compose_wall(frames, cols: int | None, tile_width: int, tile_height: int,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """One canvas of several pictures in one kernel launch: ``frames`` is a list of ``[H, W, 3]``
+    BGR24 device tensors (any sizes) or ``None`` (an empty tile). Tile ``t`` is fitted into cell
+    ``(t % cols, t // cols)`` of ``tile_width x tile_height`` and centred; everything else is
+    BGR (16, 16, 16). ``cols`` None: ``ceil(sqrt(n))``. Byte-identical with
+    :func:`compose_wall_reference`."""
+    require_gpu()
+    frames, cols, tile_width, tile_height, shape = _check_wall(frames, cols, tile_width, tile_height)
+    device = None
+    for f in frames:
+        if f is None:
+            continue
+        if not f.is_cuda:
+            raise ValueError("frames must be device tensors")
+        if device is None:
+            device = f.device
+        elif f.device != device:
+            raise ValueError("frames must live on one device")
+    if device is None:
+        device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=device)
+    if not (out.is_cuda and out.device == device and out.dtype == torch.uint8 and out.is_contiguous()
+            and tuple(out.shape) == shape):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on the frames' device")
+    tiles = [(0, 0, 0) if f is None else (f.data_ptr(), int(f.shape[1]), int(f.shape[0])) for f in frames]
+    with torch.cuda.device(device):
+        native.compose_wall(tiles, cols, tile_width, tile_height, out.data_ptr(), _stream_ptr(out))
+    return out
+
+
+def compose_wall_reference(frames, cols: int | None, tile_width: int, tile_height: int) -> torch.Tensor:
+    """The CPU implementation's canvas of the same tiles (host or device tensors), on the host:
+    the byte-exact oracle of :func:`compose_wall`."""
+    frames, cols, tile_width, tile_height, _ = _check_wall(frames, cols, tile_width, tile_height)
+    host = [None if f is None else f.detach().cpu().numpy() for f in frames]
+    return torch.from_numpy(native.compose_wall_cpu(host, cols, tile_width, tile_height))
 
 
 # ----------------------------------------------------------------------------- references

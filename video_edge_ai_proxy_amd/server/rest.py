@@ -12,7 +12,10 @@ server/api/rtsp_process.go:39-106, api/settings.go:38-62, api/error.go:20-31:
 Errors are ``{"code": int, "message": str}``. New: ``/metrics`` (Prometheus), ``/healthz``,
 ``GET /api/v1/process/{name}/frame`` (latest frame as PPM), ``.../frame.jpg`` (the same frame
 as a JPEG, encoded on the camera's GPU) and ``.../stream.mjpg`` (live MJPEG, one part per new
-frame), and the portal itself at ``/`` (replaces the Angular build, which needs a node toolchain).
+frame), both with ``?width=&height=`` for a picture fitted into that box and downscaled on the GPU,
+``/api/v1/wall.jpg`` / ``wall.mjpg`` / ``wall`` (one picture of many cameras and its geometry,
+docs/WALL.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
+toolchain).
 """
 from __future__ import annotations
 
@@ -109,15 +112,27 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             raise ValueError("quality must be 1..100")
         return quality
 
+    def box(width, height) -> dict:
+        """The scaling arguments of latest_jpeg: none when the request names no size, so an
+        unscaled request calls the hub exactly as before."""
+        for v, what in ((width, "width"), (height, "height")):
+            if v is not None and not 1 <= v <= 65535:
+                raise ValueError(f"{what} must be 1..65535")
+        if width is None and height is None:
+            return {}
+        return {"width": width, "height": height}
+
     @app.get("/api/v1/process/{name}/frame.jpg")
-    def frame_jpg(name: str, quality: int | None = None, after: int = 0):
+    def frame_jpg(name: str, quality: int | None = None, after: int = 0, width: int | None = None,
+                  height: int | None = None):
         try:
             q = jpeg_quality(quality)
+            size = box(width, height)
         except ValueError as e:
             return err(400, str(e))
         try:
             pm.hub.touch(name)
-            r = pm.hub.latest_jpeg(name, after, q)
+            r = pm.hub.latest_jpeg(name, after, q, **size)
         except KeyError:
             return err(404, f"process {name!r} not found")
         if r is None:
@@ -126,9 +141,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         return Response(content=jpg, media_type="image/jpeg", headers={"X-Vep-Seq": str(meta["seq"])})
 
     @app.get("/api/v1/process/{name}/stream.mjpg")
-    def stream_mjpg(name: str, fps: float = 10.0, frames: int | None = None, quality: int | None = None):
+    def stream_mjpg(name: str, fps: float = 10.0, frames: int | None = None, quality: int | None = None,
+                    width: int | None = None, height: int | None = None):
         try:
             q = jpeg_quality(quality)
+            size = box(width, height)
             if not 0 < fps <= 1000:
                 raise ValueError("fps must be in (0, 1000]")
             if frames is not None and frames < 1:
@@ -153,7 +170,7 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                         if pm.hub.published(name) < seq:
                             seq = 0  # the camera started a new ring (restart, resolution change)
                         wait(name, seq, 500)
-                    r = pm.hub.latest_jpeg(name, seq, q)
+                    r = pm.hub.latest_jpeg(name, seq, q, **size)
                 except KeyError:
                     return  # the camera was removed
                 now = time.monotonic()
@@ -167,6 +184,131 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                 seq, last_new = meta["seq"], now
                 yield (f"--{MJPEG_BOUNDARY}\r\nContent-Type: image/jpeg\r\nContent-Length: {len(jpg)}\r\n"
                        f"X-Vep-Seq: {seq}\r\n\r\n").encode() + jpg + b"\r\n"
+                sent += 1
+                due = max(due + 1.0 / fps, now)
+                if (frames is None or sent < frames) and due > now:
+                    time.sleep(due - now)
+
+        return StreamingResponse(parts(), media_type=f"multipart/x-mixed-replace; boundary={MJPEG_BOUNDARY}")
+
+    # ---- camera wall: one picture of many cameras, scaled and composed on the GPU (docs/WALL.md)
+    def wall_args(names, cols, tile, quality) -> dict:
+        from ..config import parse_tile
+
+        a = {"names": None, "cols": None, "tile_width": None, "tile_height": None, "quality": jpeg_quality(quality)}
+        if names is not None:
+            a["names"] = [n for n in names.split(",") if n]
+            if not a["names"]:
+                raise ValueError("names must list at least one camera")
+        if cols is not None:
+            if not 1 <= cols <= 65535:
+                raise ValueError("cols must be 1..65535")
+            a["cols"] = cols
+        if tile is not None:
+            a["tile_width"], a["tile_height"] = parse_tile(tile)
+        return a
+
+    def wall_call(fn, *args, **kw):
+        """(result, None) or (None, error response) of a hub wall call."""
+        try:
+            return fn(*args, **kw), None
+        except NotImplementedError as e:
+            return None, err(501, str(e))
+        except KeyError as e:
+            return None, err(404, f"process {e.args[0] if e.args else ''!r} not found")
+        except ValueError as e:
+            # no camera running is "nothing to show" (404); everything else is a bad argument
+            return None, err(404 if not pm.hub.cameras else 400, str(e))
+
+    def wall_header(order, seqs) -> str:
+        return ",".join(f"{n}:{seqs.get(n, 0)}" for n in order)
+
+    @app.get("/api/v1/wall.jpg")
+    def wall_jpg(names: str | None = None, cols: int | None = None, tile: str | None = None,
+                 quality: int | None = None):
+        try:
+            a = wall_args(names, cols, tile, quality)
+        except ValueError as e:
+            return err(400, str(e))
+        lay, bad = wall_call(pm.hub.wall_layout, a["names"], a["cols"], a["tile_width"], a["tile_height"])
+        if bad is not None:
+            return bad
+        a["names"] = lay[0]
+        r, bad = wall_call(pm.hub.wall_jpeg, **a)
+        if bad is not None:
+            return bad
+        seqs, jpg = r
+        return Response(content=jpg, media_type="image/jpeg", headers={"X-Vep-Wall": wall_header(lay[0], seqs)})
+
+    @app.get("/api/v1/wall")
+    def wall_info(names: str | None = None, cols: int | None = None, tile: str | None = None):
+        try:
+            a = wall_args(names, cols, tile, None)
+        except ValueError as e:
+            return err(400, str(e))
+        lay, bad = wall_call(pm.hub.wall_layout, a["names"], a["cols"], a["tile_width"], a["tile_height"])
+        if bad is not None:
+            return bad
+        order, gc, gr, tw, th = lay
+        tiles = []
+        for t, n in enumerate(order):
+            try:
+                seq = int(pm.hub.published(n))
+            except KeyError:
+                seq = 0
+            tiles.append({"name": n, "x": (t % gc) * tw, "y": (t // gc) * th, "w": tw, "h": th, "seq": seq})
+        return {"cols": gc, "rows": gr, "tile": [tw, th], "tiles": tiles}
+
+    @app.get("/api/v1/wall.mjpg")
+    def wall_mjpg(names: str | None = None, cols: int | None = None, tile: str | None = None,
+                  quality: int | None = None, fps: float = 10.0, frames: int | None = None):
+        try:
+            a = wall_args(names, cols, tile, quality)
+            if not 0 < fps <= 1000:
+                raise ValueError("fps must be in (0, 1000]")
+            if frames is not None and frames < 1:
+                raise ValueError("frames must be >= 1")
+        except ValueError as e:
+            return err(400, str(e))
+        lay, bad = wall_call(pm.hub.wall_layout, a["names"], a["cols"], a["tile_width"], a["tile_height"])
+        if bad is not None:
+            return bad
+        a["names"] = order = lay[0]  # the cameras of the first part stay the stream's cameras
+
+        def parts():
+            # one part whenever any tile has a newer frame, at most `fps` a second; every part
+            # touches the cameras it shows (Hub.wall_jpeg), so their lazy decoders stay awake
+            shown, sent, last_new = None, 0, time.monotonic()
+            due = last_new
+            while frames is None or sent < frames:
+                now = time.monotonic()
+                try:
+                    cur = {n: int(pm.hub.published(n)) for n in order}
+                except KeyError:
+                    return  # a camera was removed
+                if shown is not None and all(cur[n] == shown.get(n, 0) or cur[n] == 0 for n in order):
+                    if now - last_new > MJPEG_IDLE_S:
+                        return
+                    try:
+                        for n in order:
+                            pm.hub.touch(n)
+                    except KeyError:
+                        return
+                    time.sleep(min(0.05, 1.0 / fps))
+                    continue
+                try:
+                    seqs, jpg = pm.hub.wall_jpeg(**a)
+                except (KeyError, ValueError, NotImplementedError):
+                    return
+                if shown is not None and seqs == shown:
+                    # (published() moved for a frame the wall does not show yet)
+                    time.sleep(min(0.05, 1.0 / fps))
+                    if now - last_new > MJPEG_IDLE_S:
+                        return
+                    continue
+                shown, last_new = seqs, now
+                yield (f"--{MJPEG_BOUNDARY}\r\nContent-Type: image/jpeg\r\nContent-Length: {len(jpg)}\r\n"
+                       f"X-Vep-Wall: {wall_header(order, seqs)}\r\n\r\n").encode() + jpg + b"\r\n"
                 sent += 1
                 due = max(due + 1.0 / fps, now)
                 if (frames is None or sent < frames) and due > now:
