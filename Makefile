@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -85,6 +85,17 @@ $(ASAN_DIR)/scale_selftest: csrc/vep/scale.cpp csrc/tests/scale_selftest.cpp csr
 
 asan-scale: $(ASAN_DIR)/scale_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/scale_selftest
+
+# The CPU motion detector alone on its edge shapes (csrc/tests/motion_selftest.cpp), likewise: a
+# stand-alone host program, no GPU.
+$(ASAN_DIR)/motion_selftest: csrc/vep/motion.cpp csrc/tests/motion_selftest.cpp csrc/vep/motion.h csrc/vep/common.h
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc csrc/vep/motion.cpp csrc/tests/motion_selftest.cpp -o $@
+
+asan-motion: $(ASAN_DIR)/motion_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/motion_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

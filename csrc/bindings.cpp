@@ -122,6 +122,34 @@ static std::shared_ptr<Camera> cam_ref(Worker& w, int idx) {
 }
 static Camera& cam_of(Worker& w, int idx) { return *cam_ref(w, idx); }
 
+static py::dict summary_dict(const motion::Summary& s) {
+  py::dict d;
+  d["changed"] = s.changed;
+  d["active"] = s.active;
+  if (s.has_box)
+    d["box"] = py::make_tuple(s.x, s.y, s.w, s.h);
+  else
+    d["box"] = py::none();
+  d["motion"] = s.motion;
+  return d;
+}
+
+static py::dict motion_dict(const MotionResult& r) {
+  py::dict d = summary_dict(r.summary);
+  d["seq"] = r.seq;
+  d["width"] = r.width;
+  d["height"] = r.height;
+  d["cell"] = r.cell;
+  d["cols"] = r.cols;
+  d["rows"] = r.rows;
+  d["threshold"] = r.threshold;
+  d["primed"] = r.primed;
+  py::array_t<uint32_t> counts({py::ssize_t(r.rows), py::ssize_t(r.cols)});
+  std::memcpy(counts.mutable_data(), r.counts.data(), r.counts.size() * sizeof(uint32_t));
+  d["counts"] = counts;
+  return d;
+}
+
 // Stateful oracle: parse + CPU reconstruct a sequence of AUs, return the final BGR picture.
 // Streams inside the I_PCM / P_Skip subset take the fast-path parser; anything else switches to
 // the general H.264 decoder (avc.h) for good, like a Camera does.
@@ -1363,6 +1391,8 @@ PYBIND11_MODULE(_vep, m) {
              d["ring_slots"] = ring ? ring->slots() : c.ring_slots_cfg;
              d["history"] = c.history();
              d["history_skipped"] = c.history_skipped.load();
+             d["motion_evaluations"] = c.motion_evaluations.load();
+             d["motion_frames"] = c.motion_frames.load();
              py::list hist;
              for (auto& h : c.lat_hist) hist.append(h.load());
              d["latency_hist"] = hist;
@@ -1468,6 +1498,68 @@ PYBIND11_MODULE(_vep, m) {
            py::arg("cams"), py::arg("cols") = 0, py::arg("tile_width") = 320, py::arg("tile_height") = 180,
            py::arg("quality") = 85, py::arg("foreign") = py::none())
       .def_property("wall_max_tiles", &Worker::wall_max_tiles, &Worker::set_wall_max_tiles)
+      .def("read_motion",
+           // dict of the newest frame with seq > after against the camera's background model
+           // (docs/MOTION.md), None if there is no such frame. A frame is evaluated once, on the
+           // GPU from its ring slot (CPU backend: on the host); later calls get the stored answer.
+           [](Worker& w, int i, i64 after) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             MotionResult r;
+             bool ok;
+             {
+               py::gil_scoped_release rel;
+               ok = w.read_motion(i, after, r);
+             }
+             if (!ok) return py::none();
+             return motion_dict(r);
+           },
+           py::arg("idx"), py::arg("after") = 0)
+      .def("read_motion_many",
+           // [dict | None] of the newest frames of `cams`, every evaluation in one launch. None: an
+           // unknown index, no ring, no frame, or a frame that stayed inconsistent.
+           [](Worker& w, const std::vector<int>& cams) {
+             std::vector<MotionResult> rs;
+             std::vector<char> ok;
+             {
+               py::gil_scoped_release rel;
+               w.read_motion_many(cams, rs, ok);
+             }
+             py::list out;
+             for (size_t k = 0; k < rs.size(); ++k) out.append(ok[k] ? py::object(motion_dict(rs[k])) : py::object(py::none()));
+             return out;
+           },
+           py::arg("cams"))
+      .def("set_motion_params",
+           [](Worker& w, int cell, int threshold, int learn_shift, int cell_percent, int min_cells) {
+             motion::Params p;
+             p.cell = cell;
+             p.threshold = threshold;
+             p.learn_shift = learn_shift;
+             p.cell_percent = cell_percent;
+             p.min_cells = min_cells;
+             py::gil_scoped_release rel;
+             w.set_motion_params(p);
+           },
+           py::arg("cell") = 16, py::arg("threshold") = 24, py::arg("learn_shift") = 4, py::arg("cell_percent") = 25,
+           py::arg("min_cells") = 1)
+      .def_property_readonly("motion_params",
+                             [](Worker& w) {
+                               const motion::Params p = w.motion_params();
+                               py::dict d;
+                               d["cell"] = p.cell;
+                               d["threshold"] = p.threshold;
+                               d["learn_shift"] = p.learn_shift;
+                               d["cell_percent"] = p.cell_percent;
+                               d["min_cells"] = p.min_cells;
+                               return d;
+                             })
+      .def("motion_reset",
+           [](Worker& w, int i) {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             py::gil_scoped_release rel;
+             w.motion_reset(i);
+           },
+           py::arg("idx"))
       .def("read_history",
            // [(meta, ndarray)] of the newest `count` (0 = the camera's history depth) frames with
            // seq > after: ascending, contiguous in seq, ending at the newest frame.
@@ -1886,6 +1978,117 @@ PYBIND11_MODULE(_vep, m) {
         },
         py::arg("tiles"), py::arg("cols"), py::arg("tile_width"), py::arg("tile_height"), py::arg("canvas"),
         py::arg("stream"));
+  // Motion detection (vep/motion.h) on the host: the CPU backend's path and the byte-exact
+  // reference of motion_update.
+  m.def("motion_grid",
+        // (cols, rows) of the cell grid
+        [](int w, int h, int cell) {
+          VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "motion_grid: picture size must be 1..65535");
+          VEP_CHECK(cell >= motion::kMinCell && cell <= motion::kMaxCell, "motion: cell must be 4..256");
+          return py::make_tuple(motion::cells(u32(w), u32(cell)), motion::cells(u32(h), u32(cell)));
+        },
+        py::arg("width"), py::arg("height"), py::arg("cell") = 16);
+  m.def("motion_pitch", [](int w) { return motion::pitch_for(u32(w)); }, py::arg("width"));
+  m.def("motion_update_cpu",
+        // (counts uint32 (rows, cols), background uint16 (H, W)); background None: prime
+        [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> bgr, py::object background, int cell,
+           int threshold, int learn_shift) {
+          VEP_CHECK(bgr.ndim() == 3 && bgr.shape(2) == 3 && bgr.shape(0) >= 1 && bgr.shape(1) >= 1 &&
+                        bgr.shape(0) <= 65535 && bgr.shape(1) <= 65535,
+                    "motion_update_cpu: (H, W, 3) uint8 picture of at most 65535 x 65535 expected");
+          motion::check_update_params(cell, threshold, learn_shift);
+          const int w = int(bgr.shape(1)), h = int(bgr.shape(0));
+          py::array_t<uint16_t, py::array::c_style | py::array::forcecast> bg;
+          const uint16_t* in = nullptr;
+          if (!background.is_none()) {
+            VEP_CHECK(py::isinstance<py::array>(background) && py::array(background).dtype().is(py::dtype::of<uint16_t>()),
+                      "motion_update_cpu: the background must be a uint16 array");
+            bg = background.cast<py::array_t<uint16_t, py::array::c_style | py::array::forcecast>>();
+            VEP_CHECK(bg.ndim() == 2 && bg.shape(0) == h && bg.shape(1) == w,
+                      "motion_update_cpu: the background must be (H, W) like the picture");
+            in = bg.data();
+          }
+          const int cols = int(motion::cells(u32(w), u32(cell))), rows = int(motion::cells(u32(h), u32(cell)));
+          py::array_t<uint32_t> counts({rows, cols});
+          py::array_t<uint16_t> out({h, w});
+          const u8* p = bgr.data();
+          uint32_t* cp = counts.mutable_data();
+          uint16_t* op = out.mutable_data();
+          {
+            py::gil_scoped_release r;
+            motion::update_cpu(p, w, h, size_t(w) * 3, in, op, size_t(w), cell, threshold, learn_shift, cp);
+          }
+          return py::make_tuple(counts, out);
+        },
+        py::arg("bgr"), py::arg("background") = py::none(), py::arg("cell") = 16, py::arg("threshold") = 24,
+        py::arg("learn_shift") = 4);
+  m.def("motion_summarize",
+        // {changed, active, box, motion} of a counts grid
+        [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> counts, int w, int h, int cell,
+           int cell_percent, int min_cells) {
+          VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "motion_summarize: picture size must be 1..65535");
+          VEP_CHECK(cell >= motion::kMinCell && cell <= motion::kMaxCell, "motion: cell must be 4..256");
+          VEP_CHECK(counts.ndim() == 2 && counts.shape(0) == py::ssize_t(motion::cells(u32(h), u32(cell))) &&
+                        counts.shape(1) == py::ssize_t(motion::cells(u32(w), u32(cell))),
+                    "motion_summarize: counts must be the (rows, cols) grid of the picture");
+          return summary_dict(motion::summarize(counts.data(), w, h, cell, cell_percent, min_cells));
+        },
+        py::arg("counts"), py::arg("width"), py::arg("height"), py::arg("cell") = 16, py::arg("cell_percent") = 25,
+        py::arg("min_cells") = 1);
+  // Pictures (src, w, h, bg_in or 0, bg_out, bg_pitch in samples, counts) on caller-owned device
+  // buffers: one launch of the gfx950 motion kernel on `stream` of the current device
+  // (descriptors: one process-wide pool per device). src is h x w x 3 packed, the planes h rows of
+  // bg_pitch u16, counts the (rows, cols) uint32 grid.
+  m.def("motion_update",
+        [](const std::vector<std::tuple<uintptr_t, int, int, uintptr_t, uintptr_t, int, uintptr_t>>& pics, int cell,
+           int threshold, int learn_shift, uintptr_t stream) {
+          static std::mutex mu;
+          static std::map<int, gpu::MotionPool*>* pools = new std::map<int, gpu::MotionPool*>();  // (never freed)
+          const int n = int(pics.size());
+          VEP_CHECK(n >= 1 && n <= 65535, "motion_update: 1..65535 pictures expected");
+          motion::check_update_params(cell, threshold, learn_shift);
+          py::gil_scoped_release r;
+          int dev = 0;
+          VEP_HIP(hipGetDevice(&dev));
+          gpu::MotionPool* pool;
+          {
+            std::lock_guard<std::mutex> g(mu);
+            gpu::MotionPool*& slot = (*pools)[dev];
+            if (!slot) slot = new gpu::MotionPool();
+            pool = slot;
+          }
+          hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+          gpu::MotionPool::Set* set = pool->acquire(n, 0);
+          try {
+            for (int k = 0; k < n; ++k) {
+              const auto& [src, w, h, bg_in, bg_out, bg_pitch, counts] = pics[size_t(k)];
+              VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "motion: picture size must be 1..65535");
+              VEP_CHECK(bg_pitch >= w && bg_pitch <= 65536, "motion: background pitch out of range");
+              gpu::MotionDesc d{};
+              d.src = reinterpret_cast<const u8*>(src);
+              d.src_pitch = u32(w) * 3;
+              d.bg_in = reinterpret_cast<const u16*>(bg_in);
+              d.bg_out = reinterpret_cast<u16*>(bg_out);
+              d.bg_pitch = u32(bg_pitch);
+              d.counts = reinterpret_cast<u32*>(counts);
+              d.w = w;
+              d.h = h;
+              d.cell = cell;
+              d.threshold = threshold;
+              d.learn_shift = learn_shift;
+              gpu::check_motion(d, size_t(w) * size_t(h) * 3, size_t(bg_pitch) * size_t(h),
+                                size_t(motion::cells(u32(w), u32(cell))) * motion::cells(u32(h), u32(cell)));
+              set->h_descs[k] = d;
+            }
+            gpu::MotionPool::run(*set, n, 0, s);
+            VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
+          } catch (...) {
+            pool->release(set);
+            throw;
+          }
+          pool->release(set);
+        },
+        py::arg("pictures"), py::arg("cell"), py::arg("threshold"), py::arg("learn_shift"), py::arg("stream"));
   // JPEG stream of a device BGR24 picture, encoded by the gfx950 kernels on `stream` of the
   // current device (scratch: one process-wide pool per device).
   m.def("jpeg_encode",

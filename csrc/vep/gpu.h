@@ -402,6 +402,66 @@ class ScalePool {
   std::vector<Set*> free_;
 };
 
+// ---- motion detection (gpu_motion.hip; arithmetic: motion.h) ----------------------------------
+// One picture of a batched motion launch (device memory): a packed BGR24 source compared with
+// the background plane bg_in and folded into bg_out, changed pixels counted per cell,
+// byte-identical with motion::update_cpu. Pictures of one launch may differ in size and
+// parameters.
+struct MotionDesc {
+  const VEP_DEV u8* src;      // h rows of src_pitch bytes
+  const VEP_DEV u16* bg_in;   // h rows of bg_pitch samples, 16-byte aligned; null: prime
+  VEP_DEV u16* bg_out;        // the same layout; padding samples are never written
+  VEP_DEV u32* counts;        // motion::cells(h) x motion::cells(w), every cell written once
+  u32 src_pitch;              // bytes
+  u32 bg_pitch;               // samples, a multiple of 8 (motion::pitch_for)
+  i32 w, h;
+  i32 cell, threshold, learn_shift;
+  u32 pad_;
+};
+static_assert(sizeof(MotionDesc) == 64, "MotionDesc layout");
+// Throws unless the kernel can run the descriptor without touching memory outside a source of
+// src_bytes, background planes of bg_samples u16 each and a counts array of count_cells u32
+// (the launch below does not check).
+void check_motion(const MotionDesc& d, size_t src_bytes, size_t bg_samples, size_t count_cells);
+// One launch for the n pictures: grid = (blocks of the largest picture) x pictures. h_descs is the
+// host copy of d_descs (the grid is sized from it).
+void launch_motion(const MotionDesc* d_descs, const MotionDesc* h_descs, int n, hipStream_t s);
+
+// Motion scratch of one device: up to kScratch sets, one per request in flight. A set holds a
+// descriptor array (device + pinned host copy) and a counts buffer (device + pinned host copy);
+// each grows to the largest request it has seen and is then reused. Used with the device bound to
+// the calling thread.
+class MotionPool {
+ public:
+  struct Set {
+    MotionDesc* d_descs = nullptr;  // device
+    MotionDesc* h_descs = nullptr;  // pinned
+    int desc_cap = 0;
+    u32* d_counts = nullptr;        // device: the grids of a request, one after another
+    u32* h_counts = nullptr;        // pinned: their copy on the host
+    size_t counts_cap = 0;          // cells
+    hipEvent_t ev = nullptr;
+    ~Set();
+  };
+  MotionPool();
+  ~MotionPool();
+  MotionPool(const MotionPool&) = delete;
+  MotionPool& operator=(const MotionPool&) = delete;
+  // A free set with room for ndescs descriptors and count_cells cells (waits for one).
+  Set* acquire(int ndescs, size_t count_cells);
+  void release(Set* s);
+  // Copies the set's first n host descriptors up, launches them on `s`, then copies the first
+  // count_cells cells down into h_counts and records the set's event (no wait).
+  static void run(Set& set, int n, size_t count_cells, hipStream_t s);
+  static constexpr int kScratch = 4;
+
+ private:
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<std::unique_ptr<Set>> all_;
+  std::vector<Set*> free_;
+};
+
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 
 struct LetterboxDesc {

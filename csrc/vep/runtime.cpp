@@ -705,6 +705,9 @@ Worker::~Worker() {
     dev_.free(c->surface.y8);
     dev_.free(c->surface.uv8);
     dev_.free(c->surface.hevc_xg);
+    dev_.free(c->motion.bg[0]);
+    dev_.free(c->motion.bg[1]);
+    c->motion.bg[0] = c->motion.bg[1] = nullptr;
     c->set_ring(nullptr);
   }
   if (owns_cons_) {
@@ -792,6 +795,11 @@ void Worker::remove_camera(int idx) {
   dev_.free(c->surface.y8);
   dev_.free(c->surface.uv8);
   dev_.free(c->surface.hevc_xg);
+  {
+    std::lock_guard<std::mutex> mg(c->motion.mu);
+    motion_free(c->motion);
+    c->motion.removed = true;  // (a reader that still holds the camera allocates nothing)
+  }
   c.reset();
 }
 
@@ -2987,6 +2995,227 @@ bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, 
     if (ring->still_valid(slot, meta->seq)) return true;
   }
   return false;
+}
+
+// ------------------------------------------------------------------------- motion detection
+
+void Worker::motion_free(MotionState& st) {
+  if (st.bg[0] || st.bg[1]) dev_.bind();
+  dev_.free(st.bg[0]);
+  dev_.free(st.bg[1]);
+  st.bg[0] = st.bg[1] = nullptr;
+  st.samples = 0;
+  st.w = st.h = 0;
+  st.cur = 0;
+  st.have_bg = false;
+  st.seq = 0;
+  st.ring.reset();
+  st.result = MotionResult{};
+}
+
+void Worker::set_motion_params(const motion::Params& p) {
+  motion::check_params(p);
+  {
+    std::lock_guard<std::mutex> g(motion_mu_);
+    motion_params_ = p;
+    ++motion_gen_;  // a model of an older generation counts as none
+  }
+  std::vector<std::shared_ptr<Camera>> cams;
+  {
+    std::lock_guard<std::mutex> g(cams_mu_);
+    cams = cams_;
+  }
+  for (auto& c : cams) {
+    if (!c) continue;
+    std::lock_guard<std::mutex> g(c->motion.mu);
+    motion_free(c->motion);
+  }
+}
+
+motion::Params Worker::motion_params() {
+  std::lock_guard<std::mutex> g(motion_mu_);
+  return motion_params_;
+}
+
+void Worker::motion_reset(int cam) {
+  std::shared_ptr<Camera> c = camera(cam);
+  VEP_CHECK(c, "no such camera");
+  std::lock_guard<std::mutex> g(c->motion.mu);
+  motion_free(c->motion);
+}
+
+// One camera of a motion request. Its state's mutex is held from pick to commit.
+struct Worker::MotionEval {
+  int cam = -1;
+  i64 after = 0;
+  std::shared_ptr<Camera> c;
+  std::shared_ptr<FrameRing> ring;
+  std::unique_lock<std::mutex> lock;
+  FrameMeta meta;
+  int slot = -1;
+  bool pending = false;  // needs (another) evaluation
+  bool primed = false;   // this evaluation has a model to compare with
+  size_t cells = 0, at = 0;  // its grid in the request's counts buffer
+  std::vector<u32> counts;
+  bool ok = false;
+  MotionResult result;
+};
+
+// evs: distinct cameras in ascending index (the order their mutexes are taken in).
+void Worker::motion_eval(std::vector<MotionEval>& evs) {
+  motion::Params prm;
+  u64 gen;
+  // (every camera is looked up before the first state mutex is taken: remove_camera takes a
+  // state's mutex with the camera table locked)
+  for (MotionEval& e : evs) {
+    e.c = camera(e.cam);
+    if (e.c) e.ring = e.c->ring();
+  }
+  for (MotionEval& e : evs) {
+    if (!e.ring) continue;
+    e.lock = std::unique_lock<std::mutex>(e.c->motion.mu);
+    e.pending = !e.c->motion.removed;
+  }
+  {
+    // (after the cameras' mutexes: set_motion_params stores the parameters before it takes them,
+    // so a model built here under older parameters is reset by it afterwards)
+    std::lock_guard<std::mutex> g(motion_mu_);
+    prm = motion_params_;
+    gen = motion_gen_;
+  }
+  const u32 cell = u32(prm.cell);
+  std::vector<MotionEval*> todo;
+  for (int round = 0; round < 4; ++round) {
+    todo.clear();
+    size_t total_cells = 0;
+    for (MotionEval& e : evs) {
+      if (!e.pending) continue;
+      MotionState& st = e.c->motion;
+      if (!e.ring->latest(e.after, &e.meta, &e.slot)) {
+        e.pending = false;
+        continue;
+      }
+      const bool same_ring = st.ring.lock() == e.ring;
+      if (st.gen != gen || !same_ring || st.w != e.ring->width() || st.h != e.ring->height()) {
+        motion_free(st);  // other parameters, a new ring or a new size: prime again
+        st.gen = gen;
+        st.ring = e.ring;
+      }
+      if (st.seq == e.meta.seq && st.seq != 0) {  // evaluated already: one evaluation per frame
+        e.result = st.result;
+        e.ok = true;
+        e.pending = false;
+        continue;
+      }
+      const int w = e.ring->width(), h = e.ring->height();
+      if (!st.bg[0]) {
+        const size_t samples = size_t(motion::pitch_for(u32(w))) * size_t(h);
+        dev_.bind();
+        st.bg[0] = static_cast<u16*>(dev_.alloc(samples * sizeof(u16)));
+        st.bg[1] = static_cast<u16*>(dev_.alloc(samples * sizeof(u16)));
+        st.samples = samples;
+        st.w = w;
+        st.h = h;
+      }
+      e.primed = st.have_bg;
+      e.cells = size_t(motion::cells(u32(w), cell)) * motion::cells(u32(h), cell);
+      e.at = total_cells;
+      total_cells += e.cells;
+      todo.push_back(&e);
+    }
+    if (todo.empty()) break;
+    if (dev_.gpu()) {
+      dev_.bind();
+      gpu::MotionPool::Set* set = motion_pool_.acquire(int(todo.size()), total_cells);
+      try {
+        for (size_t k = 0; k < todo.size(); ++k) {
+          MotionEval& e = *todo[k];
+          MotionState& st = e.c->motion;
+          gpu::MotionDesc d{};
+          d.src = e.ring->slot_ptr(e.slot);
+          d.src_pitch = u32(st.w) * 3;
+          d.bg_in = e.primed ? st.bg[st.cur] : nullptr;
+          d.bg_out = st.bg[st.cur ^ 1];
+          d.bg_pitch = motion::pitch_for(u32(st.w));
+          d.counts = set->d_counts + e.at;
+          d.w = st.w;
+          d.h = st.h;
+          d.cell = prm.cell;
+          d.threshold = prm.threshold;
+          d.learn_shift = prm.learn_shift;
+          gpu::check_motion(d, e.ring->slot_bytes(), st.samples, e.cells);
+          set->h_descs[k] = d;
+        }
+        gpu::MotionPool::run(*set, int(todo.size()), total_cells, serve_stream_);
+        VEP_HIP(hipEventSynchronize(set->ev));
+        for (MotionEval* e : todo) e->counts.assign(set->h_counts + e->at, set->h_counts + e->at + e->cells);
+      } catch (...) {
+        motion_pool_.release(set);
+        throw;
+      }
+      motion_pool_.release(set);
+    } else {
+      for (MotionEval* e : todo) {
+        MotionState& st = e->c->motion;
+        e->counts.resize(e->cells);
+        motion::update_cpu(e->ring->slot_ptr(e->slot), st.w, st.h, size_t(st.w) * 3, e->primed ? st.bg[st.cur] : nullptr,
+                           st.bg[st.cur ^ 1], motion::pitch_for(u32(st.w)), prm.cell, prm.threshold, prm.learn_shift,
+                           e->counts.data());
+      }
+    }
+    for (MotionEval* e : todo) {
+      if (!e->ring->still_valid(e->slot, e->meta.seq)) continue;  // redone from the newer frame, same model
+      MotionState& st = e->c->motion;
+      st.cur ^= 1;
+      st.have_bg = true;
+      st.seq = e->meta.seq;
+      MotionResult& r = st.result;
+      r.seq = e->meta.seq;
+      r.width = st.w;
+      r.height = st.h;
+      r.cell = prm.cell;
+      r.cols = int(motion::cells(u32(st.w), cell));
+      r.rows = int(motion::cells(u32(st.h), cell));
+      r.threshold = prm.threshold;
+      r.primed = e->primed;
+      r.counts = std::move(e->counts);
+      r.summary = motion::summarize(r.counts.data(), st.w, st.h, prm.cell, prm.cell_percent, prm.min_cells);
+      e->c->motion_evaluations.fetch_add(1);
+      if (r.summary.motion) e->c->motion_frames.fetch_add(1);
+      e->result = r;
+      e->ok = true;
+      e->pending = false;
+    }
+  }
+  for (MotionEval& e : evs)
+    if (e.lock.owns_lock()) e.lock.unlock();
+}
+
+bool Worker::read_motion(int cam, i64 after, MotionResult& out) {
+  std::vector<MotionEval> evs(1);
+  evs[0].cam = cam;
+  evs[0].after = after;
+  motion_eval(evs);
+  if (!evs[0].ok) return false;
+  out = std::move(evs[0].result);
+  return true;
+}
+
+void Worker::read_motion_many(const std::vector<int>& cams, std::vector<MotionResult>& out, std::vector<char>& ok) {
+  std::vector<int> order(cams);
+  std::sort(order.begin(), order.end());
+  order.erase(std::unique(order.begin(), order.end()), order.end());
+  std::vector<MotionEval> evs(order.size());
+  for (size_t k = 0; k < order.size(); ++k) evs[k].cam = order[k];
+  motion_eval(evs);
+  out.assign(cams.size(), MotionResult{});
+  ok.assign(cams.size(), 0);
+  for (size_t t = 0; t < cams.size(); ++t) {
+    const size_t k = size_t(std::lower_bound(order.begin(), order.end(), cams[t]) - order.begin());
+    if (!evs[k].ok) continue;
+    out[t] = evs[k].result;
+    ok[t] = 1;
+  }
 }
 
 void Worker::copy_slot(FrameRing& ring, int slot, u8* dst) {

@@ -26,6 +26,7 @@
 #include "hostplan.h"
 #include "ioloop.h"
 #include "gpu.h"
+#include "motion.h"
 #include "pool.h"
 #include "vcn.h"
 
@@ -108,6 +109,32 @@ class FrameRing {
   int next_ = 0;
   int hist_ = 0;
   int pick_free() const;  // history rule (meta_mu_ held): -1 when none
+};
+
+// What read_motion answers about one frame (motion.h has the arithmetic).
+struct MotionResult {
+  i64 seq = 0;                 // the frame evaluated
+  int width = 0, height = 0;
+  int cell = 0, cols = 0, rows = 0, threshold = 0;
+  bool primed = false;         // false: the frame only initialised the background
+  motion::Summary summary;
+  std::vector<u32> counts;     // rows x cols
+};
+
+// A camera's motion state: the background model (two planes, ping-pong) and the last answer.
+// Allocated on the first evaluation, freed with the camera and by Worker::motion_reset.
+struct MotionState {
+  std::mutex mu;               // one evaluation of the camera at a time
+  u16* bg[2] = {nullptr, nullptr};  // device (CPU backend: host) planes of `samples` u16 each
+  size_t samples = 0;
+  int w = 0, h = 0;            // the picture size the planes hold
+  int cur = 0;                 // bg[cur] is the model
+  bool have_bg = false;
+  bool removed = false;        // the camera left its worker: nothing is allocated any more
+  u64 gen = 0;                 // Worker::set_motion_params generation the model was built under
+  std::weak_ptr<FrameRing> ring;  // the ring `seq` counts in (a resolution change starts a new one)
+  i64 seq = 0;                 // the frame last evaluated, 0: none
+  MotionResult result;         // its answer
 };
 
 // One picture that left the reorder buffer during a job (frame history, Camera::history): a
@@ -311,6 +338,12 @@ class Camera {
   bool use_vcn_ = false;
   std::unique_ptr<vcn::Session> vcn_;
   u64 fault_after_ = 0;  // VEP_FAULT_CAMERA: crash on this access unit (0 = never)
+
+ public:
+  // motion detection (Worker::read_motion): frames evaluated, and those of them with motion.
+  // (Last in the class: the members the ingest and publish paths touch keep their places.)
+  std::atomic<u64> motion_evaluations{0}, motion_frames{0};
+  MotionState motion;
 };
 
 struct WorkerOptions {
@@ -438,6 +471,23 @@ class Worker {
   };
   void read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
                       const std::vector<ForeignTile>& foreign, std::vector<i64>& seqs_out, std::string& out);
+  // Motion detection (motion.h, docs/MOTION.md): did the newest frame with seq > after differ from
+  // the camera's background model? The frame is evaluated where it lies, in its ring slot, on the
+  // serving stream (CPU backend: motion::update_cpu on the host ring), from the model plane into
+  // the other one; only the counts grid comes down. The planes are swapped once the slot proved
+  // unchanged (still_valid), so a torn frame never reaches the model; a reused slot is evaluated
+  // again from the newer frame, up to four times. A frame is evaluated once: later calls at the
+  // same seq get the stored answer. False if there is no such frame.
+  bool read_motion(int cam, i64 after, MotionResult& out);
+  // The newest frame of several cameras, every camera that needs an evaluation in ONE launch.
+  // ok[k] is false for an unknown index, a camera without a ring or a frame, or one still
+  // inconsistent after the fourth round.
+  void read_motion_many(const std::vector<int>& cams, std::vector<MotionResult>& out, std::vector<char>& ok);
+  // Parameters are per worker (the models depend on them): validates and resets every model.
+  void set_motion_params(const motion::Params& p);
+  motion::Params motion_params();
+  // Frees the camera's model: its next evaluation primes again.
+  void motion_reset(int cam);
   void set_wall_max_tiles(int n);
   int wall_max_tiles() const { return wall_max_tiles_.load(); }
   // Frame history: the newest max_count (0 = the camera's depth) frames with seq > after, copied
@@ -685,6 +735,14 @@ class Worker {
 
  private:
   bool vcn_ = false;
+  // motion detection (last in the class, as in Camera)
+  gpu::MotionPool motion_pool_;  // descriptors + counts of the motion reads, one set per request in flight
+  std::mutex motion_mu_;         // motion_params_ / motion_gen_
+  motion::Params motion_params_;
+  u64 motion_gen_ = 1;
+  struct MotionEval;
+  void motion_eval(std::vector<MotionEval>& evs);
+  void motion_free(MotionState& st);  // (st.mu held)
 };
 
 // Protobuf wire encoding of chrys.cloud.videostreaming.v1beta1.VideoFrame

@@ -5,6 +5,7 @@
             --memory_buffer --disk_path)
   farm      synthetic RTSP camera farm (H.264 I_PCM/P_Skip streams) for tests and benchmarks
   list | frame | annotate | storage | proxy   gRPC clients (examples/*.py analogs)
+  motion    REST client of the motion detector (--device NAME --rest host:port [--watch])
 """
 from __future__ import annotations
 
@@ -157,6 +158,43 @@ def cmd_proxy(a):
     print(ImageClient(_addr(a)).Proxy(pb.ProxyRequest(device_id=a.device, passthrough=_bool(a.on))))
 
 
+def format_motion(m: dict) -> str:
+    """One line per evaluated frame of ``vep motion``."""
+    box = "-" if m.get("box") is None else "{},{} {}x{}".format(*m["box"])
+    flag = "MOTION" if m.get("motion") else ("still" if m.get("primed", True) else "primed")
+    return (f"seq {m['seq']} {flag} changed {m.get('changed', 0)} ({100.0 * m.get('score', 0.0):.2f} %) "
+            f"active {m.get('active', 0)} box {box}")
+
+
+def cmd_motion(a):
+    """REST client of ``/api/v1/process/{name}/motion``: one line per new evaluated frame."""
+    import json
+    import urllib.error
+    import urllib.parse
+    import urllib.request
+
+    base = f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/motion"
+    seq, idle = 0, 0
+    while True:
+        try:
+            with urllib.request.urlopen(f"{base}?after={seq}", timeout=10) as r:
+                m = json.loads(r.read())
+        except urllib.error.HTTPError as e:
+            if e.code != 404 or b"not found" in e.read():
+                raise SystemExit(f"motion: HTTP {e.code} for {a.device!r}")
+            m = None  # no newer frame yet
+        if m is not None:
+            seq, idle = int(m["seq"]), 0
+            print(format_motion(m), flush=True)
+            if not a.watch:
+                return
+        else:
+            idle += 1
+            if not a.watch and idle * a.interval > 10.0:
+                raise SystemExit(f"motion: no frame of {a.device!r} within 10 s")
+        time.sleep(a.interval)
+
+
 def cmd_bench(a, rest):
     """``vep bench ...`` = the repo's bench.py (headline benchmark) with the same flags."""
     import subprocess
@@ -167,7 +205,7 @@ def cmd_bench(a, rest):
     raise SystemExit(subprocess.call([sys.executable, bench, *rest]))
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="vep", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -231,9 +269,20 @@ def main(argv=None):
             p.add_argument("--on", required=True)
         p.set_defaults(fn=fn)
 
+    m = sub.add_parser("motion", help="did anything change: the hub's motion detection of one camera (REST)")
+    m.add_argument("--device", required=True)
+    m.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API")
+    m.add_argument("--watch", action="store_true", help="keep printing, one line per new evaluated frame")
+    m.add_argument("--interval", type=float, default=0.1, help="seconds between polls")
+    m.set_defaults(fn=cmd_motion)
+
     b = sub.add_parser("bench", help="run bench.py (flags passed through, e.g. --codec h265)")
     b.set_defaults(fn=None)
+    return ap
 
+
+def main(argv=None):
+    ap = build_parser()
     a, rest = ap.parse_known_args(argv)
     if a.cmd == "bench":
         cmd_bench(a, rest)

@@ -108,6 +108,21 @@ class ServingConfig:
 
 
 @dataclass
+class MotionConfig:
+    """Motion detection (docs/MOTION.md; ``Hub.motion``, ``/api/v1/motion``). The parameters hold
+    for every camera of the hub: the background models depend on them."""
+    cell: int = 16           # grid cells of cell x cell pixels (4..256)
+    threshold: int = 24      # a pixel changed when |luma - background| > threshold (0..255)
+    learn_shift: int = 4     # the background moves 1 / 2^learn_shift of the way per evaluated frame (0..8)
+    cell_percent: int = 25   # a cell is active when this share of its pixels changed (1..100)
+    min_cells: int = 1       # active cells that make a frame "motion" (>= 1)
+
+
+MOTION_RANGES = {"cell": (4, 256), "threshold": (0, 255), "learn_shift": (0, 8), "cell_percent": (1, 100),
+                 "min_cells": (1, 2 ** 31 - 1)}
+
+
+@dataclass
 class Config:
     version: str = "0.1.0"
     title: str = "vep MI355X video edge hub"
@@ -122,6 +137,7 @@ class Config:
     buffer: BufferConfig = field(default_factory=BufferConfig)
     gpu: GpuConfig = field(default_factory=GpuConfig)
     serving: ServingConfig = field(default_factory=ServingConfig)
+    motion: MotionConfig = field(default_factory=MotionConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
     bus_tag: str = ""
 
@@ -185,6 +201,10 @@ def validate(cfg: Config) -> None:
         raise ValueError(f"serving.wall_tile: {e}") from None
     if not 1 <= int(cfg.serving.wall_max_tiles) <= 65535:
         raise ValueError(f"serving.wall_max_tiles must be 1..65535, got {cfg.serving.wall_max_tiles}")
+    for key, (lo, hi) in MOTION_RANGES.items():
+        v = getattr(cfg.motion, key)
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"motion.{key} must be an integer {lo}..{hi}, got {v!r}")
 
 
 def parse_tile(s) -> tuple[int, int]:

@@ -86,6 +86,9 @@ class Hub:
                               letterbox_format=1 if g.letterbox_format == "nv12" else 0,
                               decoder=str(getattr(g, "decoder", "native")), host_domain=dom)
             w.wall_max_tiles = int(cfg.serving.wall_max_tiles)
+            m = cfg.motion
+            w.set_motion_params(int(m.cell), int(m.threshold), int(m.learn_shift), int(m.cell_percent),
+                                int(m.min_cells))
             w.start()
             self.workers.append(w)
         # Consumer batch: with letterbox_size > 0 every worker letterboxes each frame it publishes
@@ -407,6 +410,57 @@ class Hub:
             any_foreign = any_foreign or r is not None
         seqs, jpg = self.workers[home].read_wall_jpeg(cams, gc, tw, th, q, foreign if any_foreign else None)
         return {n: int(s) for n, s in zip(order, seqs)}, jpg
+
+    # ------------------------------------------------------------------ motion
+    @staticmethod
+    def _motion_dict(r, grid: bool) -> Optional[dict]:
+        """A worker's motion answer as the hub serves it."""
+        if r is None:
+            return None
+        box = r["box"]
+        out = {"seq": int(r["seq"]), "width": int(r["width"]), "height": int(r["height"]), "cell": int(r["cell"]),
+               "cols": int(r["cols"]), "rows": int(r["rows"]), "threshold": int(r["threshold"]),
+               "primed": bool(r["primed"]), "changed": int(r["changed"]), "active": int(r["active"]),
+               "score": int(r["changed"]) / float(int(r["width"]) * int(r["height"])),
+               "box": None if box is None else [int(v) for v in box], "motion": bool(r["motion"])}
+        if grid:
+            out["counts"] = [[int(v) for v in row] for row in r["counts"]]
+        return out
+
+    def motion(self, name: str, after: int = 0, grid: bool = False) -> Optional[dict]:
+        """Did the camera's newest frame with seq > after differ from its background model?
+        ``None`` when there is no such frame, else a dict of ``seq, width, height, cell, cols,
+        rows, threshold, primed, changed, active, score, box, motion`` (docs/MOTION.md), with
+        ``grid`` also ``counts``, the changed pixels of every cell. The frame is evaluated on the
+        camera's GPU, in its ring slot, once however many clients ask. Refreshes ``last_query``,
+        so asking keeps the camera's lazy decoder awake."""
+        w, cam = self.worker_of(name)
+        w.set_last_query(cam, now_ms())
+        return self._motion_dict(w.read_motion(cam, int(after)), grid)
+
+    def motion_many(self, names=None, grid: bool = False) -> dict:
+        """``{name: dict | None}`` for the newest frame of every listed camera (default: the
+        running cameras, sorted): one kernel launch per worker covers all of its cameras that
+        need an evaluation. ``None``: the camera has no frame yet."""
+        with self._lock:
+            order = sorted(self.cameras) if names is None else list(names)
+            hs = [self.handle(n) for n in order]
+        now = now_ms()
+        for h in hs:
+            self.workers[h.worker_index].set_last_query(h.cam, now)
+        out = {}
+        for wi, w in enumerate(self.workers):
+            mine = [h for h in hs if h.worker_index == wi]
+            if not mine:
+                continue
+            for h, r in zip(mine, w.read_motion_many([h.cam for h in mine])):
+                out[h.name] = self._motion_dict(r, grid)
+        return {n: out[n] for n in order}
+
+    def motion_reset(self, name: str) -> None:
+        """Forget the camera's background model: its next evaluation primes again."""
+        w, cam = self.worker_of(name)
+        w.motion_reset(cam)
 
     def history(self, name: str, after: int = 0, count: int = 0) -> list:
         """``[(meta, ndarray)]`` of the camera's newest ``count`` (0 = ``buffer.in_memory``) frames

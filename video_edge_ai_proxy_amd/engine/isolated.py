@@ -579,6 +579,20 @@ class ProcessHub:
         the pipe."""
         return self._call(name, "latest_scaled", after, width, height)
 
+    def motion(self, name: str, after: int = 0, grid: bool = False):
+        """dict or None: evaluated on the worker process's GPU, only the answer crosses the pipe."""
+        return self._call(name, "motion", after, grid)
+
+    def motion_many(self, names=None, grid: bool = False) -> dict:
+        """{name: dict | None}: forwarded per name (the rings live in the worker processes)."""
+        order = sorted(self.cameras) if names is None else list(names)
+        for n in order:
+            self.handle(n)
+        return {n: self._call(n, "motion", 0, grid) for n in order}
+
+    def motion_reset(self, name: str) -> None:
+        self._call(name, "motion_reset")
+
     # A wall reads the ring slots of many cameras in one launch; the rings live in the worker
     # processes, one per GPU, so it is served only by the in-process hub (gpu.isolation: thread).
     def wall_layout(self, names=None, cols=None, tile_width=None, tile_height=None):

@@ -12,6 +12,10 @@
 * :func:`resize_area` / :func:`compose_wall` — antialiased area-average downscale of BGR24
   pictures, one or many into one canvas in a single launch (the kernel behind scaled
   ``frame.jpg`` and ``wall.jpg``), byte-identical with their ``*_reference`` CPU twins.
+* :func:`motion_update` / :func:`motion_update_batch` — a BGR24 picture against a running
+  background model: changed pixels per cell and the updated model, one or many pictures in a
+  single launch (the kernel behind ``/motion``), byte-identical with
+  :func:`motion_update_reference`.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -420,6 +424,114 @@ def compose_wall_reference(frames, cols: int | None, tile_width: int, tile_heigh
     frames, cols, tile_width, tile_height, _ = _check_wall(frames, cols, tile_width, tile_height)
     host = [None if f is None else f.detach().cpu().numpy() for f in frames]
     return torch.from_numpy(native.compose_wall_cpu(host, cols, tile_width, tile_height))
+
+
+def _check_motion_params(cell, threshold, learn_shift):
+    for v, what, lo, hi in ((cell, "cell", 4, 256), (threshold, "threshold", 0, 255), (learn_shift, "learn_shift", 0, 8)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{what} must be an integer {lo}..{hi}")
+    return cell, threshold, learn_shift
+
+
+def _check_background(bg: torch.Tensor, w: int, h: int, what: str = "background"):
+    if bg.dtype != torch.uint16:
+        raise TypeError(f"{what} must be uint16")
+    if bg.dim() != 2 or tuple(bg.shape) != (h, w):
+        raise ValueError(f"{what} must be [H, W] = {(h, w)}, got {tuple(bg.shape)}")
+
+
+def _plane_in_place(bg: torch.Tensor) -> bool:
+    """The kernel can use the tensor's memory as it lies: samples contiguous in a row, rows a
+    multiple of 8 samples apart and 16-byte aligned."""
+    h, w = bg.shape
+    pitch = bg.stride(0) if h > 1 else native.motion_pitch(w)
+    if not ((bg.stride(1) == 1 or w == 1) and pitch % 8 == 0 and pitch >= w and bg.data_ptr() % 16 == 0):
+        return False
+    # the last group of a row is loaded whole: the last row's padding must be memory of the tensor
+    last = bg.storage_offset() + (h - 1) * pitch + native.motion_pitch(w)
+    return bg.untyped_storage().nbytes() >= last * 2
+
+
+def _padded_plane(w: int, h: int, device) -> torch.Tensor:
+    return torch.empty((h, native.motion_pitch(w)), dtype=torch.uint16, device=device)
+
+
+def motion_update_batch(pictures, cell: int = 16, threshold: int = 24, learn_shift: int = 4):
+    """One kernel launch for a list of pictures of any sizes on one device. Each entry is ``bgr``,
+    ``(bgr, background)`` or ``(bgr, background, out)`` as in :func:`motion_update`; returns the
+    list of ``(counts, background)``."""
+    require_gpu()
+    cell, threshold, learn_shift = _check_motion_params(cell, threshold, learn_shift)
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("pictures must hold at least one picture")
+    device, work, results, copies = None, [], [], []
+    keep = []  # padded copies of the inputs stay alive until the launch is done
+    for k, p in enumerate(pictures):
+        bgr, bg, out = (tuple(p) + (None, None))[:3] if isinstance(p, (tuple, list)) else (p, None, None)
+        w, h = _check_bgr(bgr, f"pictures[{k}]")
+        if not bgr.is_cuda:
+            raise ValueError("bgr must be a device tensor")
+        if device is None:
+            device = bgr.device
+        for t, what in ((bgr, "bgr"), (bg, "background"), (out, "out")):
+            if t is not None and (not t.is_cuda or t.device != device):
+                raise ValueError(f"{what} must live on the pictures' device")
+        if bg is not None:
+            _check_background(bg, w, h)
+        if out is not None:
+            _check_background(out, w, h, "out")
+            if bg is not None and out.data_ptr() == bg.data_ptr():
+                raise ValueError("out must not be the background itself (the update is out of place)")
+        dst = out if out is not None and _plane_in_place(out) else _padded_plane(w, h, device)[:, :w]
+        if out is not None and dst is not out:
+            copies.append((out, dst))
+        # one pitch for both planes: the output's
+        pitch = int(dst.stride(0)) if h > 1 else native.motion_pitch(w)
+        src = 0
+        if bg is not None:
+            if not (_plane_in_place(bg) and (h == 1 or bg.stride(0) == pitch)):
+                pad = torch.empty((h, pitch), dtype=torch.uint16, device=device)
+                pad[:, :w].copy_(bg)
+                bg = pad[:, :w]
+                keep.append(pad)
+            src = bg.data_ptr()
+        cols, rows = native.motion_grid(w, h, cell)
+        counts = torch.empty((rows, cols), dtype=torch.int32, device=device)
+        work.append((bgr.data_ptr(), w, h, src, dst.data_ptr(), pitch, counts.data_ptr()))
+        keep.append(dst)
+        results.append((counts, out if out is not None else dst))
+    with torch.cuda.device(device):
+        native.motion_update(work, cell, threshold, learn_shift, int(torch.cuda.current_stream(device).cuda_stream))
+    for out, dst in copies:
+        out.copy_(dst)
+    return results
+
+
+def motion_update(bgr: torch.Tensor, background: torch.Tensor | None = None, cell: int = 16, threshold: int = 24,
+                  learn_shift: int = 4, out: torch.Tensor | None = None):
+    """One motion evaluation of a ``[H, W, 3]`` BGR24 device tensor against ``background``, a
+    ``[H, W]`` ``torch.uint16`` plane in 8.8 fixed point (``None``: prime): ``(counts, background')``
+    with ``counts`` the ``[rows, cols]`` int32 grid of changed pixels per ``cell x cell`` cell and
+    ``background'`` the updated plane (``out`` if given, else a new tensor whose rows are padded to a
+    multiple of 8 samples). A plane whose row stride is a multiple of 8 samples and whose memory is
+    16-byte aligned is used where it lies; any other is copied to and from such a plane. Exact in
+    integers, byte-identical with :func:`motion_update_reference`. No CPU fallback."""
+    return motion_update_batch([(bgr, background, out)], cell, threshold, learn_shift)[0]
+
+
+def motion_update_reference(bgr: torch.Tensor, background: torch.Tensor | None = None, cell: int = 16,
+                            threshold: int = 24, learn_shift: int = 4):
+    """The CPU implementation's result for the same picture (host or device tensors), on the host:
+    the byte-exact oracle of :func:`motion_update`."""
+    cell, threshold, learn_shift = _check_motion_params(cell, threshold, learn_shift)
+    w, h = _check_bgr(bgr)
+    bg = None
+    if background is not None:
+        _check_background(background, w, h)
+        bg = background.detach().cpu().contiguous().numpy()
+    counts, new = native.motion_update_cpu(bgr.detach().cpu().numpy(), bg, cell, threshold, learn_shift)
+    return torch.from_numpy(counts.astype("int32")), torch.from_numpy(new)
 
 
 # ----------------------------------------------------------------------------- references

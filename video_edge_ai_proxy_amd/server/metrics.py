@@ -29,6 +29,9 @@ class HubCollector:
         rst = CounterMetricFamily("vep_camera_restarts", "ingest reconnects", labels=labels)
         lat = HistogramMetricFamily("vep_decode_latency_seconds",
                                     "packet arrival -> decoded frame published", labels=labels)
+        mev = CounterMetricFamily("vep_motion_evaluations", "frames evaluated by the motion detector", labels=labels)
+        mfr = CounterMetricFamily("vep_motion_frames_with_motion", "evaluated frames that showed motion",
+                                  labels=labels)
         for name in list(self.hub.cameras):
             try:
                 st = self.hub.state(name)
@@ -41,6 +44,8 @@ class HubCollector:
             byt.add_metric(lv, st.get("bytes_in", 0))
             run.add_metric(lv, 1.0 if st.get("running") else 0.0)
             rst.add_metric(lv, st.get("restart_count", 0))
+            mev.add_metric(lv, st.get("motion_evaluations", 0))
+            mfr.add_metric(lv, st.get("motion_frames", 0))
             hist, bounds = st.get("latency_hist"), st.get("latency_bounds_ms")
             if hist and bounds:
                 acc, buckets = 0, []
@@ -48,7 +53,7 @@ class HubCollector:
                     acc += c
                     buckets.append((str(b / 1000.0) if b != float("inf") else "+Inf", acc))
                 lat.add_metric(lv, buckets, st.get("latency_sum_ms", 0) / 1000.0)
-        yield from (pk, dec, errs, byt, run, rst, lat)
+        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr)
         wb = CounterMetricFamily("vep_worker_batches", "batched decode launches", labels=["device"])
         wf = CounterMetricFamily("vep_worker_frames", "frames decoded by the worker", labels=["device"])
         wg = CounterMetricFamily("vep_worker_gpu_ms", "GPU time of decode batches (ms)", labels=["device"])

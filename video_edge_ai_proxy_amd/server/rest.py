@@ -14,7 +14,8 @@ Errors are ``{"code": int, "message": str}``. New: ``/metrics`` (Prometheus), ``
 as a JPEG, encoded on the camera's GPU) and ``.../stream.mjpg`` (live MJPEG, one part per new
 frame), both with ``?width=&height=`` for a picture fitted into that box and downscaled on the GPU,
 ``/api/v1/wall.jpg`` / ``wall.mjpg`` / ``wall`` (one picture of many cameras and its geometry,
-docs/WALL.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
+docs/WALL.md), ``/api/v1/process/{name}/motion`` and ``/api/v1/motion`` (did anything change:
+motion detection on the GPU, docs/MOTION.md; ``DELETE .../motion`` resets the background), and the portal itself at ``/`` (replaces the Angular build, which needs a node
 toolchain).
 """
 from __future__ import annotations
@@ -315,6 +316,47 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                     time.sleep(due - now)
 
         return StreamingResponse(parts(), media_type=f"multipart/x-mixed-replace; boundary={MJPEG_BOUNDARY}")
+
+    # ---- motion detection: evaluated on the GPU where the frames lie (docs/MOTION.md)
+    @app.get("/api/v1/process/{name}/motion")
+    def motion(name: str, after: int = 0, grid: int = 0):
+        if after < 0 or grid not in (0, 1):
+            return err(400, "after must be >= 0 and grid 0 or 1")
+        try:
+            r = pm.hub.motion(name, after, bool(grid))
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        if r is None:
+            return err(404, "no newer frame decoded yet")
+        return JSONResponse(content=r, headers={"X-Vep-Seq": str(r["seq"])})
+
+    @app.delete("/api/v1/process/{name}/motion")
+    def motion_reset(name: str):
+        try:
+            pm.hub.motion_reset(name)
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        return Response(status_code=204)
+
+    @app.get("/api/v1/motion")
+    def motion_many(names: str | None = None, grid: int = 0):
+        if grid not in (0, 1):
+            return err(400, "grid must be 0 or 1")
+        order = None
+        if names is not None:
+            order = [n for n in names.split(",") if n]
+            if not order:
+                return err(400, "names must list at least one camera")
+        elif not pm.hub.cameras:
+            return err(404, "no camera running")
+        try:
+            res = pm.hub.motion_many(order, bool(grid))
+        except KeyError as e:
+            return err(404, f"process {e.args[0] if e.args else ''!r} not found")
+        cams = []
+        for n, r in res.items():
+            cams.append({"name": n, **(r if r is not None else {"seq": 0, "motion": False})})
+        return {"cameras": cams}
 
     @app.get("/api/v1/processlist")
     def plist():
