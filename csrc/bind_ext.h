@@ -7,3 +7,4 @@ void bind_mux(pybind11::module_& m);
 void bind_hevc(pybind11::module_& m);
 void bind_bus(pybind11::module_& m);
 void bind_rpc(pybind11::module_& m);
+void bind_dbk(pybind11::module_& m);  // loop filter on given records (tests)

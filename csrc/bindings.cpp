@@ -2264,4 +2264,5 @@ PYBIND11_MODULE(_vep, m) {
   bind_hevc(m);
   bind_bus(m);
   bind_rpc(m);
+  bind_dbk(m);
 }

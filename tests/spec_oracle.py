@@ -488,3 +488,207 @@ def mb_qp(prev_qpy, mb_qp_delta, bd=8):
     (52 + QpBdOffsetY)) - QpBdOffsetY."""
     off = 6 * (bd - 8)
     return ((prev_qpy + mb_qp_delta + 52 + 2 * off) % (52 + off)) - off
+
+
+# ------------------------------------------------------------------ 8.7 picture-level loop filter
+# The deblocking process of a whole picture, from the clause text: which edges exist, in which
+# order, with which bS, thresholds and samples. Frame pictures and field pictures of
+# non-MBAFF streams (MbaffFrameFlag = 0, so mixedModeEdgeFlag = 0 and fieldModeInFrameFilteringFlag
+# = 0 throughout), ChromaArrayType 1 (4:2:0). 4:2:2 is not covered: the rule that gives
+# its additional horizontal chroma edges (an 8x16 chroma block has four) their bS is not restated
+# here with its clause, so 4:2:2 stays a GPU-against-CPU comparison.
+#
+# A macroblock is described by a dict (nothing here knows the decoder's record layout):
+#   intra   bool    coded in an intra macroblock prediction mode (I_PCM included)
+#   qp      int     QPY (0 for I_PCM, 8.7.2.2: "qPp is set equal to 0"; negative above 8 bits)
+#   qpc     (int, int)  QPC of Cb and Cr for that QPY (8.7.2.2 derives them per component)
+#   idc     int     disable_deblocking_filter_idc of the MB's slice (0, 1, 2)
+#   off_a, off_b    FilterOffsetA / FilterOffsetB of the MB's slice
+#   slice   int     the slice the MB belongs to
+#   t8      bool    transform_size_8x8_flag
+#   coded   int     bit b set: the 4x4 luma block at raster position b (4 * (y // 4) + x // 4)
+#                   contains non-zero transform coefficients
+#   motion  list of 16 (non-intra only), raster 4x4: [(picture, (mvx, mvy)), ...] with one or two
+#           entries, `picture` naming the reference PICTURE (not a list index; 8.7.2.1 NOTE 1)
+
+
+def _block(mb, blk):
+    """What 8.7.2.1 asks of the 4x4 luma block `blk` (raster) of `mb`."""
+    if mb["t8"]:
+        # "the 8x8 luma block containing the sample ... associated with transform_size_8x8_flag
+        # equal to 1 ... contains non-zero transform coefficients"
+        by, bx = blk >> 2, blk & 3
+        quad = [4 * (2 * (by >> 1) + j) + 2 * (bx >> 1) + i for j in (0, 1) for i in (0, 1)]
+        coded = any((mb["coded"] >> b) & 1 for b in quad)
+    else:
+        coded = bool((mb["coded"] >> blk) & 1)
+    return {"intra": mb["intra"], "coded": coded, "motion": None if mb["intra"] else mb["motion"][blk]}
+
+
+def boundary_strength(p, q, mb_edge, vertical, field=False):
+    """8.7.2.1, luma bS of one line: p / q = {'intra', 'coded', 'motion'} of the 4x4 blocks holding
+    p0 / q0. field: field_pic_flag = 1 (every macroblock a field macroblock)."""
+    intra = p["intra"] or q["intra"]
+    # bS = 4: the edge is a macroblock edge and ...
+    #  - p0 and q0 both in frame macroblocks, either in an intra MB; or
+    #  - field_pic_flag = 1, verticalEdgeFlag = 1, p0 or q0 in an intra MB
+    if mb_edge and intra and (not field or vertical):
+        return 4
+    # bS = 3: mixedModeEdgeFlag = 0 and p0 or q0 in an intra MB (this leaves the horizontal
+    # macroblock edges of field pictures, and every internal edge)
+    if intra:
+        return 3
+    # bS = 2: the 4x4 (or, with transform_size_8x8_flag, the 8x8) luma block containing p0 or q0
+    # contains non-zero transform coefficients
+    if p["coded"] or q["coded"]:
+        return 2
+    # bS = 1 (mixedModeEdgeFlag = 0):
+    mp, mq = p["motion"], q["motion"]
+    # "different reference pictures or a different number of motion vectors are used"; NOTE 1: by
+    # the pictures referenced, without regard to list or index
+    if len(mp) != len(mq) or sorted(r for r, _ in mp) != sorted(r for r, _ in mq):
+        return 1
+    # "greater than or equal to 4 in units of quarter luma frame samples"; NOTE: a vertical
+    # difference of 4 quarter frame samples is 2 in quarter field samples
+    ylim = 2 if field else 4
+
+    def far(a, b):
+        return abs(a[0] - b[0]) >= 4 or abs(a[1] - b[1]) >= ylim
+
+    if len(mp) == 1:  # one motion vector each
+        return 1 if far(mp[0][1], mq[0][1]) else 0
+    (rp0, vp0), (rp1, vp1) = mp
+    (rq0, vq0), (rq1, vq1) = mq
+    if rp0 != rp1:
+        # two motion vectors and two different reference pictures: the vectors "for the same
+        # reference picture" are compared
+        if rp0 == rq0:
+            return 1 if far(vp0, vq0) or far(vp1, vq1) else 0
+        return 1 if far(vp0, vq1) or far(vp1, vq0) else 0
+    # two motion vectors for the same reference picture on both sides: bS 1 only when both
+    # pairings differ
+    straight = far(vp0, vq0) or far(vp1, vq1)
+    crossed = far(vp0, vq1) or far(vp1, vq0)
+    return 1 if straight and crossed else 0
+
+
+def new_deblock_stats():
+    return {"bs": [0] * 5, "pass": 0, "fail": 0, "bs4_strong": 0, "bs4_weak": 0, "ap_lt": 0, "ap_ge": 0,
+            "chroma": [0, 0]}
+
+
+def deblock_picture(y, cb, cr, mbs, wmbs, hmbs, field=False, bd=8, stats=None, writer=None):
+    """8.7 on a whole picture. y / cb / cr: 2-D integer arrays (16 hmbs x 16 wmbs, 8 hmbs x 8 wmbs),
+    filtered in place and returned. mbs: macroblock dicts in raster order (see above).
+
+    stats (new_deblock_stats()): counted per filtered line as the oracle goes, so that a test can
+    tell from the oracle alone which branches its input reaches. writer: three integer arrays
+    (shapes of y / cb / cr) and a list; every sample a filter may write (p0..p2 / q0..q2, chroma
+    p0 / q0) is labelled with the index of (mb, plane, direction, edge, line) in the list."""
+    planes = (y, cb, cr)
+    for addr in range(wmbs * hmbs):  # "on a macroblock basis, in order of increasing addresses"
+        mb = mbs[addr]
+        mx, my = addr % wmbs, addr // wmbs
+        idc = mb["idc"]
+        if idc == 1:  # every filter*EdgeFlag is 0
+            continue
+        # filterLeftMbEdgeFlag / filterTopMbEdgeFlag: 0 at the picture edge, and with idc 2 where
+        # the neighbour is not available, i.e. belongs to another slice
+        left = mx > 0 and not (idc == 2 and mbs[addr - 1]["slice"] != mb["slice"])
+        top = my > 0 and not (idc == 2 and mbs[addr - wmbs]["slice"] != mb["slice"])
+        # luma bS of all 2 x 4 edges x 16 lines first (bS depends on no sample)
+        bs = {}
+        for vertical in (True, False):
+            for e in range(4):
+                if e == 0 and not (left if vertical else top):
+                    continue
+                pmb = mb if e > 0 else mbs[addr - 1 if vertical else addr - wmbs]
+                for k in range(16):
+                    qx, qy = (4 * e, k) if vertical else (k, 4 * e)
+                    px, py = ((qx - 1) % 16, qy) if vertical else (qx, (qy - 1) % 16)
+                    bs[vertical, e, k] = boundary_strength(_block(pmb, 4 * (py >> 2) + (px >> 2)),
+                                                           _block(mb, 4 * (qy >> 2) + (qx >> 2)),
+                                                           e == 0, vertical, field)
+        for c in range(3):  # luma, then Cb, then Cr
+            plane = planes[c]
+            chroma = c > 0
+            size = 8 if chroma else 16
+            for vertical in (True, False):  # vertical edges left to right, then horizontal ones
+                for e in range(4):
+                    if e == 0 and not (left if vertical else top):
+                        continue
+                    # internal luma edges: transform_size_8x8_flag leaves only the 8x8 one; chroma
+                    # (4x4 transforms, 8 samples wide and tall): MB edge and the one at 4 = luma 8
+                    if chroma and e not in (0, 2):
+                        continue
+                    if not chroma and mb["t8"] and e in (1, 3):
+                        continue
+                    pmb = mb if e > 0 else mbs[addr - 1 if vertical else addr - wmbs]
+                    # 8.7.2.2: qPp / qPq = QPY, or for chroma the QPC of the component, of the MBs
+                    # holding p0 / q0; the filter offsets are those of the slice holding q0
+                    qp_p = pmb["qpc"][c - 1] if chroma else pmb["qp"]
+                    qp_q = mb["qpc"][c - 1] if chroma else mb["qp"]
+                    alpha, beta, tc0 = edge_thresholds(qp_p, qp_q, mb["off_a"], mb["off_b"], bd)
+                    pos = (2 if chroma else 4) * e  # the edge's offset in the component's MB
+                    for k in range(size):
+                        # chroma: "the bS of the corresponding edge of the luma" at the luma
+                        # sample (SubWidthC x, SubHeightC y)
+                        b = bs[vertical, e, 2 * k if chroma else k]
+                        if stats is not None and not chroma:
+                            stats["bs"][b] += 1
+                        if b == 0:
+                            continue
+                        if vertical:
+                            yy, x0 = my * size + k, mx * size + pos
+                            n = 2 if chroma else 4
+                            p = [int(plane[yy][x0 - 1 - i]) for i in range(n)]
+                            q = [int(plane[yy][x0 + i]) for i in range(n)]
+                        else:
+                            xx, y0 = mx * size + k, my * size + pos
+                            n = 2 if chroma else 4
+                            p = [int(plane[y0 - 1 - i][xx]) for i in range(n)]
+                            q = [int(plane[y0 + i][xx]) for i in range(n)]
+                        if chroma:
+                            p += [0, 0]
+                            q += [0, 0]
+                        if stats is not None:
+                            _count_line(stats, p, q, b, alpha, beta, c)
+                        np_, nq = filter_line(p, q, b, alpha, beta, tc0[b - 1] if b < 4 else 0, chroma, bd)
+                        m = 1 if chroma else 3
+                        if writer is not None:
+                            writer[3].append((addr, c, 0 if vertical else 1, e, k))
+                        for i in range(m):
+                            if vertical:
+                                plane[yy][x0 - 1 - i] = np_[i]
+                                plane[yy][x0 + i] = nq[i]
+                                if writer is not None:
+                                    writer[c][yy][x0 - 1 - i] = writer[c][yy][x0 + i] = len(writer[3]) - 1
+                            else:
+                                plane[y0 - 1 - i][xx] = np_[i]
+                                plane[y0 + i][xx] = nq[i]
+                                if writer is not None:
+                                    writer[c][y0 - 1 - i][xx] = writer[c][y0 + i][xx] = len(writer[3]) - 1
+    return y, cb, cr
+
+
+def _count_line(stats, p, q, b, alpha, beta, c):
+    """Which branch of 8.7.2.3 / 8.7.2.4 a line with bS b > 0 takes (from the conditions of the
+    text, for the tests' own honesty checks)."""
+    if not (abs(p[0] - q[0]) < alpha and abs(p[1] - p[0]) < beta and abs(q[1] - q[0]) < beta):
+        stats["fail"] += 1  # filterSamplesFlag = 0
+        return
+    stats["pass"] += 1
+    if c > 0:
+        stats["chroma"][c - 1] += 1
+        return
+    for s, o in ((p, q), (q, p)):
+        a = abs(s[2] - s[0])  # ap / aq
+        if b == 4:
+            if a < beta and abs(p[0] - q[0]) < ((alpha >> 2) + 2):
+                stats["bs4_strong"] += 1
+            else:
+                stats["bs4_weak"] += 1
+        elif a < beta:
+            stats["ap_lt"] += 1
+        else:
+            stats["ap_ge"] += 1
