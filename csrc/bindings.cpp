@@ -2265,4 +2265,5 @@ PYBIND11_MODULE(_vep, m) {
   bind_bus(m);
   bind_rpc(m);
   bind_dbk(m);
+  bind_hevc_lf(m);
 }

@@ -367,14 +367,15 @@ def deblock_luma(lines, bs, qpl, beta_offset, tc_offset, nfp=False, nfq=False):
     return out
 
 
-def deblock_chroma(lines, qpp, qpq, c_qp_pic_offset, tc_offset):
-    """§8.7.2.5.5 (bS 2 edges); lines[k] = [p1, p0, q0, q1]."""
+def deblock_chroma(lines, qpp, qpq, c_qp_pic_offset, tc_offset, nfp=False, nfq=False):
+    """§8.7.2.5.5 (bS 2 edges); lines[k] = [p1, p0, q0, q1]. nfp / nfq: nDp / nDq are 0 (pcm
+    with pcm_loop_filter_disabled, or cu_transquant_bypass)."""
     qpi = ((qpq + qpp + 1) >> 1) + c_qp_pic_offset
     tc = TC_PRIME[clip3(0, 53, qpc_420(qpi) + 2 + tc_offset)] * (1 << (BIT_DEPTH - 8))
     out = []
     for p1, p0, q0, q1 in lines:
         delta = clip3(-tc, tc, ((((q0 - p0) << 2) + p1 - q1 + 4) >> 3))
-        out.append([p1, clip1(p0 + delta), clip1(q0 - delta), q1])
+        out.append([p1, p0 if nfp else clip1(p0 + delta), q0 if nfq else clip1(q0 - delta), q1])
     return out
 
 
@@ -397,3 +398,229 @@ def sao_sample(nb, sao_type, band_position, eo_class, offset_val):
     if edge_idx in (0, 1, 2):
         edge_idx = 0 if edge_idx == 2 else edge_idx + 1
     return clip1(v + val[edge_idx])
+
+
+# ----------------------------------------------------------------------------- picture-level loop filters
+# Written from §8.7.2 (deblocking) and §8.7.3 (SAO) for 4:2:0 pictures whose decisions are given
+# per 4x4 luma block and per CTB. Maps are flat, row-major lists: w4 = width / 4 blocks per row,
+# ctbs per row = ceil(width / CtbSizeY). Planes are numpy arrays [row][pitch] (pitch >= width);
+# the UV plane interleaves Cb and Cr as NV12 does.
+
+def _ctb_of(pic, x, y):
+    """CTB raster address of the luma sample (x, y)."""
+    s = pic["log2ctb"]
+    return (y >> s) * ((pic["width"] + (1 << s) - 1) >> s) + (x >> s)
+
+
+def _ref_pics(pic, b, x, y):
+    """The reference pictures (ids) the block's motion vectors point to, with their mvs: the lists
+    are those of the slice that holds the block (§8.7.2.4: 'the determination of whether the
+    reference pictures are the same or different is based only on which pictures are referenced')."""
+    flags, idx, mv = pic["mf"][b]
+    sl = pic["slices"][pic["ctb_slice"][_ctb_of(pic, x, y)]]
+    return [(sl["ref_lists"][l][idx[l]], tuple(mv[l])) for l in range(2) if flags >> l & 1]
+
+
+def _mv_far(a, b):
+    return abs(a[0] - b[0]) >= 4 or abs(a[1] - b[1]) >= 4
+
+
+def _bs_pred(p, q):
+    """The motion clauses of §8.7.2.4 for p / q = [(picture, mv), ...]."""
+    if len(p) != len(q) or sorted(r for r, _ in p) != sorted(r for r, _ in q):
+        return 1
+    if len(p) == 1:
+        return int(_mv_far(p[0][1], q[0][1]))
+    (pa, pm0), (pb, pm1) = p
+    (qa, qm0), (qb, qm1) = q
+    if pa != pb:  # two different pictures: compare the vectors that refer to the same picture
+        if pa == qa:
+            return int(_mv_far(pm0, qm0) or _mv_far(pm1, qm1))
+        return int(_mv_far(pm0, qm1) or _mv_far(pm1, qm0))
+    straight = _mv_far(pm0, qm0) or _mv_far(pm1, qm1)
+    crossed = _mv_far(pm0, qm1) or _mv_far(pm1, qm0)
+    return int(straight and crossed)
+
+
+def boundary_strengths(pic):
+    """§8.7.2.2 - 8.7.2.4 -> (bs_v, bs_h): per 4x4 block, bS of its left / top edge.
+
+    pic: width, height, log2ctb; per 4x4 block intra, cbf (luma), tu_v / tu_h / pu_v / pu_h (the
+    block's left / top edge is a transform / prediction block edge), mf = (pred flags bit 0 / 1,
+    (ref_idx_l0, ref_idx_l1), ((mvx, mvy), (mvx, mvy))); per CTB ctb_slice (index into slices),
+    ctb_sord (ordinal of the slice, shared by its dependent segments) and ctb_tile; per slice
+    deblocking_disabled, across_slices and ref_lists = ([picture ids], [picture ids]);
+    across_tiles for the picture."""
+    w4, h4 = pic["width"] // 4, pic["height"] // 4
+    bs_v, bs_h = [0] * (w4 * h4), [0] * (w4 * h4)
+    for d, out in ((0, bs_v), (1, bs_h)):
+        for y4 in range(h4):
+            for x4 in range(w4):
+                x, y = x4 * 4, y4 * 4
+                pos = x if d == 0 else y
+                if pos == 0 or pos & 7:  # picture border; edges lie on the 8x8 luma grid (§8.7.2.3)
+                    continue
+                b = y4 * w4 + x4
+                tu = pic["tu_v" if d == 0 else "tu_h"][b]
+                pu = pic["pu_v" if d == 0 else "pu_h"][b]
+                if not (tu or pu):
+                    continue
+                xp, yp = (x - 1, y) if d == 0 else (x, y - 1)
+                bp = (yp // 4) * w4 + xp // 4
+                cq, cp = _ctb_of(pic, x, y), _ctb_of(pic, xp, yp)
+                sl = pic["slices"][pic["ctb_slice"][cq]]  # the current coding block holds q0
+                if sl["deblocking_disabled"]:
+                    continue
+                if pic["ctb_sord"][cq] != pic["ctb_sord"][cp] and not sl["across_slices"]:
+                    continue
+                if pic["ctb_tile"][cq] != pic["ctb_tile"][cp] and not pic["across_tiles"]:
+                    continue
+                if pic["intra"][b] or pic["intra"][bp]:
+                    out[b] = 2
+                elif tu and (pic["cbf"][b] or pic["cbf"][bp]):
+                    out[b] = 1
+                else:
+                    out[b] = _bs_pred(_ref_pics(pic, bp, xp, yp), _ref_pics(pic, b, x, y))
+    return bs_v, bs_h
+
+
+def _exempt(rec, b):
+    return bool(rec["pcm_nofilter"] and rec["pcm_map"][b])
+
+
+def deblock_picture(planes, rec, trace=None):
+    """§8.7.2.5: all vertical edges of the picture, then all horizontal edges on the result.
+
+    rec: width, height, log2ctb, cb_qp_offset, cr_qp_offset; per 4x4 block bs_v, bs_h, qp (QpY)
+    and pcm_map (pcm with pcm_loop_filter_disabled, or cu_transquant_bypass; honoured when
+    pcm_nofilter is set); per CTB ctb_slice; per slice beta_offset / tc_offset
+    (slice_*_offset_div2 * 2). Returns new (Y, UV) planes. trace, when given,
+    collects what each edge did (the case generator's coverage bookkeeping)."""
+    import numpy as np
+
+    y_pl, uv_pl = np.array(planes[0], copy=True), np.array(planes[1], copy=True)
+    w4, h4 = rec["width"] // 4, rec["height"] // 4
+    for d in (0, 1):
+        bs_map = rec["bs_v" if d == 0 else "bs_h"]
+        for y4 in range(h4):
+            for x4 in range(w4):
+                b = y4 * w4 + x4
+                bs = int(bs_map[b])
+                if not bs:
+                    continue
+                x, y = x4 * 4, y4 * 4
+                bp = b - 1 if d == 0 else b - w4
+                sl = rec["slices"][rec["ctb_slice"][_ctb_of(rec, x, y)]]  # the slice that holds q0,0
+                beta_off, tc_off = sl["beta_offset"], sl["tc_offset"]
+                qpq, qpp = int(rec["qp"][b]), int(rec["qp"][bp])
+                nfp, nfq = _exempt(rec, bp), _exempt(rec, b)
+                # luma: 4 lines across the edge, 4 samples each side
+                if d == 0:
+                    lines = [[int(v) for v in y_pl[y + k, x - 4:x + 4]] for k in range(4)]
+                else:
+                    lines = [[int(v) for v in y_pl[y - 4:y + 4, x + k]] for k in range(4)]
+                out = deblock_luma(lines, bs, (qpq + qpp + 1) >> 1, beta_off, tc_off, nfp, nfq)
+                if trace is not None:
+                    trace.append(("luma", d, x, y, bs, lines, out, qpp, qpq, nfp, nfq, beta_off, tc_off))
+                for k in range(4):
+                    if d == 0:
+                        y_pl[y + k, x - 4:x + 4] = out[k]
+                    else:
+                        y_pl[y - 4:y + 4, x + k] = out[k]
+                # chroma: bS 2 edges on the 8-sample chroma grid; a section is 4 chroma lines and
+                # takes bS and QpY at its first line (§8.7.2.5.1: bS[xDk * SubWidthC][yDm * SubHeightC])
+                pos, along = (x, y) if d == 0 else (y, x)
+                if trace is not None and not (bs == 2 and pos % 16 == 0):
+                    trace.append(("chroma_skip", d, x, y, bs))
+                if bs != 2 or pos % 16 or along % 8:
+                    continue
+                xc, yc = x // 2, y // 2
+                for c, off in ((0, rec["cb_qp_offset"]), (1, rec["cr_qp_offset"])):
+                    if d == 0:
+                        lines = [[int(uv_pl[yc + k, 2 * (xc + i) + c]) for i in range(-2, 2)] for k in range(4)]
+                    else:
+                        lines = [[int(uv_pl[yc + i, 2 * (xc + k) + c]) for i in range(-2, 2)] for k in range(4)]
+                    out = deblock_chroma(lines, qpp, qpq, off, tc_off, nfp, nfq)
+                    if trace is not None:
+                        trace.append(("chroma", d, x, y, c, lines, out, nfp, nfq))
+                    for k in range(4):
+                        for i in range(-2, 2):
+                            if d == 0:
+                                uv_pl[yc + k, 2 * (xc + i) + c] = out[k][i + 2]
+                            else:
+                                uv_pl[yc + i, 2 * (xc + k) + c] = out[k][i + 2]
+    return y_pl, uv_pl
+
+
+def sao_picture(planes, rec, trace=None):
+    """§8.7.3 on the deblocked planes; every sample reads the input, never the output.
+
+    rec adds: per CTB ctb_tile and sao_params = dict(type, band, eo, off), each a 3-list over
+    (Y, Cb, Cr) with off[c] = SaoOffsetVal[1..4]; per slice sao_luma, sao_chroma and across
+    (slice_loop_filter_across_slices_enabled_flag); ctb_slice doubles as the slices' decoding
+    order; tiles_block_sao: loop_filter_across_tiles_enabled_flag is 0."""
+    import numpy as np
+
+    src = (np.asarray(planes[0]), np.asarray(planes[1]))
+    dst = (np.array(planes[0], copy=True), np.array(planes[1], copy=True))
+    w, h, w4 = rec["width"], rec["height"], rec["width"] // 4
+    for c in range(3):
+        sub = 0 if c == 0 else 1
+        cw, ch = w >> sub, h >> sub
+        pl_in, pl_out = src[min(c, 1)], dst[min(c, 1)]
+
+        def at(x, y):
+            return int(pl_in[y, x] if c == 0 else pl_in[y, 2 * x + c - 1])
+
+        for y in range(ch):
+            for x in range(cw):
+                lx, ly = x << sub, y << sub
+                ctb = _ctb_of(rec, lx, ly)
+                si = rec["ctb_slice"][ctb]
+                sl, p = rec["slices"][si], rec["sao_params"][ctb]
+                if not (sl["sao_luma"] if c == 0 else sl["sao_chroma"]) or not p["type"][c]:
+                    continue
+                if _exempt(rec, (ly // 4) * w4 + lx // 4):
+                    if trace is not None:
+                        trace.append(("exempt", c, x, y))
+                    continue
+                nb = [[0] * 3 for _ in range(3)]
+                nb[1][1] = at(x, y)
+                refused, exempt_nb, allowed = None, False, []
+                if p["type"][c] == 2:
+                    for dx, dy in SAO_EO_OFFSETS[p["eo"][c]]:
+                        nx, ny = x + dx, y + dy
+                        if nx < 0 or ny < 0 or nx >= cw or ny >= ch:
+                            refused = refused or ("border", dx, dy)
+                            continue
+                        nctb = _ctb_of(rec, nx << sub, ny << sub)
+                        nsi = rec["ctb_slice"][nctb]
+                        if nsi != si:  # the slice of the later sample in decoding order decides
+                            later = rec["slices"][max(si, nsi)]
+                            if not later["across"]:
+                                refused = refused or ("earlier" if nsi < si else "later", dx, dy)
+                            else:
+                                allowed.append(("allowed", c, "earlier" if nsi < si else "later"))
+                        if rec["ctb_tile"][nctb] != rec["ctb_tile"][ctb]:
+                            if rec["tiles_block_sao"]:
+                                refused = refused or ("tile", dx, dy)
+                            else:
+                                allowed.append(("allowed", c, "tile"))
+                        nb[1 + dy][1 + dx] = at(nx, ny)
+                        if _exempt(rec, ((ny << sub) // 4) * w4 + (nx << sub) // 4):
+                            exempt_nb = True  # (still read: only modification is barred)
+                if refused:
+                    if trace is not None:
+                        trace.append(("refused", c) + refused)
+                    continue
+                v = sao_sample(nb, p["type"][c], p["band"][c], p["eo"][c], p["off"][c])
+                if trace is not None:
+                    trace.extend(allowed)  # (crossings of a sample that was filtered)
+                    if exempt_nb:
+                        trace.append(("exempt_nb", c, x, y))
+                    trace.append(("sao", c, x, y, p["type"][c], p["band"][c], p["eo"][c], nb, v, tuple(p["off"][c])))
+                if c == 0:
+                    pl_out[y, x] = v
+                else:
+                    pl_out[y, 2 * x + c - 1] = v
+    return dst
