@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -96,6 +96,17 @@ $(ASAN_DIR)/motion_selftest: csrc/vep/motion.cpp csrc/tests/motion_selftest.cpp 
 
 asan-motion: $(ASAN_DIR)/motion_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/motion_selftest
+
+# The CPU tamper detector alone on its edge shapes and closed forms (csrc/tests/tamper_selftest.cpp),
+# likewise: a stand-alone host program, no GPU.
+$(ASAN_DIR)/tamper_selftest: csrc/vep/tamper.cpp csrc/tests/tamper_selftest.cpp csrc/vep/tamper.h csrc/vep/motion.h csrc/vep/common.h
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc csrc/vep/tamper.cpp csrc/tests/tamper_selftest.cpp -o $@
+
+asan-tamper: $(ASAN_DIR)/tamper_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/tamper_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

@@ -134,6 +134,80 @@ static py::dict summary_dict(const motion::Summary& s) {
   return d;
 }
 
+static py::dict tamper_summary_dict(const tamper::Summary& s) {
+  py::dict d;
+  d["mean"] = s.n ? double(s.mean_sum) / double(s.n) : 0.0;
+  d["mean_sum"] = s.mean_sum;
+  d["p5"] = s.p5;
+  d["p95"] = s.p95;
+  d["energy_total"] = s.energy_total;
+  d["pairs_total"] = s.pairs_total;
+  d["sharpness"] = s.pairs_total ? double(s.energy_total) / double(s.pairs_total) : 0.0;
+  d["has_reference"] = s.has_reference;
+  d["cells"] = s.cells;
+  d["shifted"] = s.shifted;
+  d["dark"] = s.dark;
+  d["bright"] = s.bright;
+  d["flat"] = s.flat;
+  d["defocused"] = s.defocused;
+  d["moved"] = s.moved;
+  d["tampered"] = s.tampered;
+  py::list causes;
+  if (s.dark) causes.append("dark");
+  if (s.bright) causes.append("bright");
+  if (s.flat) causes.append("flat");
+  if (s.defocused) causes.append("defocused");
+  if (s.moved) causes.append("moved");
+  d["causes"] = causes;
+  return d;
+}
+
+static py::array_t<uint32_t> u32_array(const std::vector<u32>& v, py::ssize_t rows, py::ssize_t cols) {
+  py::array_t<uint32_t> a = rows < 0 ? py::array_t<uint32_t>(py::ssize_t(v.size())) : py::array_t<uint32_t>({rows, cols});
+  std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(uint32_t));
+  return a;
+}
+
+static py::dict tamper_dict(const TamperResult& r) {
+  py::dict d = tamper_summary_dict(r.summary);
+  d["seq"] = r.seq;
+  d["width"] = r.width;
+  d["height"] = r.height;
+  d["cell"] = r.cell;
+  d["cols"] = r.cols;
+  d["rows"] = r.rows;
+  d["hist"] = u32_array(r.hist, -1, 0);
+  d["sum_y"] = u32_array(r.sum_y, r.rows, r.cols);
+  d["energy"] = u32_array(r.energy, r.rows, r.cols);
+  return d;
+}
+
+static tamper::Params tamper_params_of(int cell, int dark_level, int bright_level, int spread_min, int focus_percent,
+                                       int shift_level, int shift_percent) {
+  tamper::Params p;
+  p.cell = cell;
+  p.dark_level = dark_level;
+  p.bright_level = bright_level;
+  p.spread_min = spread_min;
+  p.focus_percent = focus_percent;
+  p.shift_level = shift_level;
+  p.shift_percent = shift_percent;
+  tamper::check_params(p);
+  return p;
+}
+
+static py::dict tamper_params_dict(const tamper::Params& p) {
+  py::dict d;
+  d["cell"] = p.cell;
+  d["dark_level"] = p.dark_level;
+  d["bright_level"] = p.bright_level;
+  d["spread_min"] = p.spread_min;
+  d["focus_percent"] = p.focus_percent;
+  d["shift_level"] = p.shift_level;
+  d["shift_percent"] = p.shift_percent;
+  return d;
+}
+
 static py::dict motion_dict(const MotionResult& r) {
   py::dict d = summary_dict(r.summary);
   d["seq"] = r.seq;
@@ -1393,6 +1467,8 @@ PYBIND11_MODULE(_vep, m) {
              d["history_skipped"] = c.history_skipped.load();
              d["motion_evaluations"] = c.motion_evaluations.load();
              d["motion_frames"] = c.motion_frames.load();
+             d["tamper_evaluations"] = c.tamper_evaluations.load();
+             d["tamper_frames_tampered"] = c.tamper_frames.load();
              py::list hist;
              for (auto& h : c.lat_hist) hist.append(h.load());
              d["latency_hist"] = hist;
@@ -1558,6 +1634,64 @@ PYBIND11_MODULE(_vep, m) {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              py::gil_scoped_release rel;
              w.motion_reset(i);
+           },
+           py::arg("idx"))
+      .def("read_tamper",
+           // dict of the newest frame with seq > after: luma histogram, per-cell sums and energies
+           // and the flags derived from them (docs/TAMPER.md), None if there is no such frame. A
+           // frame is evaluated once, on the GPU from its ring slot (CPU backend: on the host);
+           // later calls get the stored answer.
+           [](Worker& w, int i, i64 after) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             TamperResult r;
+             bool ok;
+             {
+               py::gil_scoped_release rel;
+               ok = w.read_tamper(i, after, r);
+             }
+             if (!ok) return py::none();
+             return tamper_dict(r);
+           },
+           py::arg("idx"), py::arg("after") = 0)
+      .def("read_tamper_many",
+           // [dict | None] of the newest frames of `cams`, every evaluation in one launch. None: an
+           // unknown index, no ring, no frame, or a frame that stayed inconsistent.
+           [](Worker& w, const std::vector<int>& cams) {
+             std::vector<TamperResult> rs;
+             std::vector<char> ok;
+             {
+               py::gil_scoped_release rel;
+               w.read_tamper_many(cams, rs, ok);
+             }
+             py::list out;
+             for (size_t k = 0; k < rs.size(); ++k) out.append(ok[k] ? py::object(tamper_dict(rs[k])) : py::object(py::none()));
+             return out;
+           },
+           py::arg("cams"))
+      .def("set_tamper_params",
+           [](Worker& w, int cell, int dark_level, int bright_level, int spread_min, int focus_percent, int shift_level,
+              int shift_percent) {
+             const tamper::Params p =
+                 tamper_params_of(cell, dark_level, bright_level, spread_min, focus_percent, shift_level, shift_percent);
+             py::gil_scoped_release rel;
+             w.set_tamper_params(p);
+           },
+           py::arg("cell") = 32, py::arg("dark_level") = 32, py::arg("bright_level") = 224, py::arg("spread_min") = 24,
+           py::arg("focus_percent") = 50, py::arg("shift_level") = 24, py::arg("shift_percent") = 50)
+      .def_property_readonly("tamper_params", [](Worker& w) { return tamper_params_dict(w.tamper_params()); })
+      .def("tamper_set_reference",
+           // the camera's newest frame becomes its reference; False when it has no frame
+           [](Worker& w, int i) {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             py::gil_scoped_release rel;
+             return w.tamper_set_reference(i);
+           },
+           py::arg("idx"))
+      .def("tamper_reset",
+           [](Worker& w, int i) {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             py::gil_scoped_release rel;
+             w.tamper_reset(i);
            },
            py::arg("idx"))
       .def("read_history",
@@ -2089,6 +2223,136 @@ PYBIND11_MODULE(_vep, m) {
           pool->release(set);
         },
         py::arg("pictures"), py::arg("cell"), py::arg("threshold"), py::arg("learn_shift"), py::arg("stream"));
+  // Tamper detection (vep/tamper.h) on the host: the CPU backend's path and the byte-exact
+  // reference of tamper_stats.
+  m.def("tamper_grid",
+        // (cols, rows) of the cell grid
+        [](int w, int h, int cell) {
+          VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "tamper_grid: picture size must be 1..65535");
+          tamper::check_cell(cell);
+          return py::make_tuple(tamper::cells(u32(w), u32(cell)), tamper::cells(u32(h), u32(cell)));
+        },
+        py::arg("width"), py::arg("height"), py::arg("cell") = 32);
+  m.def("tamper_stats_cpu",
+        // (hist uint32 (256,), sum_y uint32 (rows, cols), energy uint32 (rows, cols))
+        [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> bgr, int cell) {
+          VEP_CHECK(bgr.ndim() == 3 && bgr.shape(2) == 3 && bgr.shape(0) >= 1 && bgr.shape(1) >= 1 &&
+                        bgr.shape(0) <= 65535 && bgr.shape(1) <= 65535,
+                    "tamper_stats_cpu: (H, W, 3) uint8 picture of at most 65535 x 65535 expected");
+          tamper::check_cell(cell);
+          const int w = int(bgr.shape(1)), h = int(bgr.shape(0));
+          const int cols = int(tamper::cells(u32(w), u32(cell))), rows = int(tamper::cells(u32(h), u32(cell)));
+          py::array_t<uint32_t> hist = py::array_t<uint32_t>(py::ssize_t(tamper::kBins));
+          py::array_t<uint32_t> sum_y({rows, cols}), energy({rows, cols});
+          const u8* p = bgr.data();
+          uint32_t* hp = hist.mutable_data();
+          uint32_t* sp = sum_y.mutable_data();
+          uint32_t* ep = energy.mutable_data();
+          {
+            py::gil_scoped_release r;
+            tamper::stats_cpu(p, w, h, size_t(w) * 3, cell, hp, sp, ep);
+          }
+          return py::make_tuple(hist, sum_y, energy);
+        },
+        py::arg("bgr"), py::arg("cell") = 32);
+  m.def("tamper_summarize",
+        // the flags of one evaluation. params: a dict with any of tamper::Params' fields;
+        // reference: None or (width, height, cell, sum_y, energy) of the frame declared normal.
+        [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> hist,
+           py::array_t<uint32_t, py::array::c_style | py::array::forcecast> sum_y,
+           py::array_t<uint32_t, py::array::c_style | py::array::forcecast> energy, int w, int h, py::dict params,
+           py::object reference) {
+          VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "tamper_summarize: picture size must be 1..65535");
+          const tamper::Params def;
+          auto get = [&](const char* key, int dflt) { return params.contains(key) ? params[key].cast<int>() : dflt; };
+          for (auto item : params) {
+            const std::string k = py::str(item.first);
+            VEP_CHECK(k == "cell" || k == "dark_level" || k == "bright_level" || k == "spread_min" ||
+                          k == "focus_percent" || k == "shift_level" || k == "shift_percent",
+                      "tamper_summarize: unknown parameter");
+          }
+          const tamper::Params p = tamper_params_of(
+              get("cell", def.cell), get("dark_level", def.dark_level), get("bright_level", def.bright_level),
+              get("spread_min", def.spread_min), get("focus_percent", def.focus_percent),
+              get("shift_level", def.shift_level), get("shift_percent", def.shift_percent));
+          const py::ssize_t cols = py::ssize_t(tamper::cells(u32(w), u32(p.cell))),
+                            rows = py::ssize_t(tamper::cells(u32(h), u32(p.cell)));
+          VEP_CHECK(hist.ndim() == 1 && hist.shape(0) == tamper::kBins, "tamper_summarize: hist must have 256 bins");
+          VEP_CHECK(sum_y.ndim() == 2 && sum_y.shape(0) == rows && sum_y.shape(1) == cols && energy.ndim() == 2 &&
+                        energy.shape(0) == rows && energy.shape(1) == cols,
+                    "tamper_summarize: sum_y and energy must be the (rows, cols) grid of the picture");
+          tamper::Reference ref;
+          bool have_ref = false;
+          if (!reference.is_none()) {
+            py::tuple t = reference.cast<py::tuple>();
+            VEP_CHECK(t.size() == 5, "tamper_summarize: reference must be (width, height, cell, sum_y, energy)");
+            ref.w = t[0].cast<int>();
+            ref.h = t[1].cast<int>();
+            ref.cell = t[2].cast<int>();
+            auto rs = t[3].cast<py::array_t<uint32_t, py::array::c_style | py::array::forcecast>>();
+            auto re = t[4].cast<py::array_t<uint32_t, py::array::c_style | py::array::forcecast>>();
+            VEP_CHECK(rs.size() == re.size(), "tamper_summarize: the reference's planes differ in size");
+            ref.sum_y.assign(rs.data(), rs.data() + rs.size());
+            for (py::ssize_t i = 0; i < re.size(); ++i) ref.energy_total += re.data()[i];
+            have_ref = true;
+          }
+          return tamper_summary_dict(
+              tamper::summarize(hist.data(), sum_y.data(), energy.data(), w, h, p, have_ref ? &ref : nullptr));
+        },
+        py::arg("hist"), py::arg("sum_y"), py::arg("energy"), py::arg("width"), py::arg("height"),
+        py::arg("params") = py::dict(), py::arg("reference") = py::none());
+  // Pictures (src, w, h, hist, sum_y, energy) on caller-owned device buffers: one launch of the
+  // gfx950 tamper kernel on `stream` of the current device (descriptors: one process-wide pool
+  // per device). src is h x w x 3 packed, hist 256 u32 (zeroed here, on the stream), the planes
+  // the (rows, cols) u32 grids.
+  m.def("tamper_stats",
+        [](const std::vector<std::tuple<uintptr_t, int, int, uintptr_t, uintptr_t, uintptr_t>>& pics, int cell,
+           uintptr_t stream) {
+          static std::mutex mu;
+          static std::map<int, gpu::TamperPool*>* pools = new std::map<int, gpu::TamperPool*>();  // (never freed)
+          const int n = int(pics.size());
+          VEP_CHECK(n >= 1 && n <= 65535, "tamper_stats: 1..65535 pictures expected");
+          tamper::check_cell(cell);
+          py::gil_scoped_release r;
+          int dev = 0;
+          VEP_HIP(hipGetDevice(&dev));
+          gpu::TamperPool* pool;
+          {
+            std::lock_guard<std::mutex> g(mu);
+            gpu::TamperPool*& slot = (*pools)[dev];
+            if (!slot) slot = new gpu::TamperPool();
+            pool = slot;
+          }
+          hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+          gpu::TamperPool::Set* set = pool->acquire(n, 0);
+          try {
+            for (int k = 0; k < n; ++k) {
+              const auto& [src, w, h, hist, sum_y, energy] = pics[size_t(k)];
+              VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "tamper: picture size must be 1..65535");
+              gpu::TamperDesc d{};
+              d.src = reinterpret_cast<const u8*>(src);
+              d.src_pitch = u32(w) * 3;
+              d.hist = reinterpret_cast<u32*>(hist);
+              d.sum_y = reinterpret_cast<u32*>(sum_y);
+              d.energy = reinterpret_cast<u32*>(energy);
+              d.w = w;
+              d.h = h;
+              d.cell = cell;
+              gpu::check_tamper(d, size_t(w) * size_t(h) * 3,
+                                size_t(tamper::cells(u32(w), u32(cell))) * tamper::cells(u32(h), u32(cell)));
+              set->h_descs[k] = d;
+            }
+            for (int k = 0; k < n; ++k)
+              VEP_HIP(hipMemsetAsync(set->h_descs[k].hist, 0, size_t(tamper::kBins) * sizeof(u32), s));
+            gpu::TamperPool::run(*set, n, 0, 0, s);
+            VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
+          } catch (...) {
+            pool->release(set);
+            throw;
+          }
+          pool->release(set);
+        },
+        py::arg("pictures"), py::arg("cell"), py::arg("stream"));
   // JPEG stream of a device BGR24 picture, encoded by the gfx950 kernels on `stream` of the
   // current device (scratch: one process-wide pool per device).
   m.def("jpeg_encode",

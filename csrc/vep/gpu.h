@@ -462,6 +462,67 @@ class MotionPool {
   std::vector<Set*> free_;
 };
 
+// ---- tamper detection (gpu_tamper.hip; arithmetic: tamper.h) -----------------------------------
+// One picture of a batched tamper launch (device memory): the luma histogram, the per-cell luma
+// sums and the per-cell squared-gradient energy of a packed BGR24 source, byte-identical with
+// tamper::stats_cpu. Pictures of one launch may differ in size and cell.
+struct TamperDesc {
+  const VEP_DEV u8* src;   // h rows of src_pitch bytes
+  VEP_DEV u32* hist;       // 256 bins, ZERO before the launch: blocks add their partial histograms
+  VEP_DEV u32* sum_y;      // tamper::cells(h) x tamper::cells(w), every cell written once
+  VEP_DEV u32* energy;     // the same layout
+  u32 src_pitch;           // bytes
+  i32 w, h;
+  i32 cell;
+  u32 pad_[4];
+};
+static_assert(sizeof(TamperDesc) == 64, "TamperDesc layout");
+// Throws unless the kernel can run the descriptor without touching memory outside a source of
+// src_bytes, two grid planes of grid_cells u32 each and a histogram of 256 u32, all three 4-byte
+// aligned and apart from each other (the launch below does not check).
+void check_tamper(const TamperDesc& d, size_t src_bytes, size_t grid_cells);
+// One launch for the n pictures: grid = (blocks of the largest picture) x pictures. h_descs is the
+// host copy of d_descs (the grid is sized from it). The histograms are zeroed by the caller, on `s`.
+void launch_tamper(const TamperDesc* d_descs, const TamperDesc* h_descs, int n, hipStream_t s);
+
+// Tamper scratch of one device: up to kScratch sets, one per request in flight. A set holds a
+// descriptor array and a results buffer (each on the device and in pinned host memory); each grows
+// to the largest request it has seen and is then reused. A request's results are the histograms
+// of all its pictures first (zeroed by one memset), then each picture's two planes. Used with the
+// device bound to the calling thread.
+class TamperPool {
+ public:
+  struct Set {
+    TamperDesc* d_descs = nullptr;  // device
+    TamperDesc* h_descs = nullptr;  // pinned
+    int desc_cap = 0;
+    u32* d_res = nullptr;           // device
+    u32* h_res = nullptr;           // pinned: its copy on the host
+    size_t res_cap = 0;             // u32 words
+    hipEvent_t ev = nullptr;
+    ~Set();
+  };
+  TamperPool();
+  ~TamperPool();
+  TamperPool(const TamperPool&) = delete;
+  TamperPool& operator=(const TamperPool&) = delete;
+  // A free set with room for ndescs descriptors and res_words result words (waits for one).
+  Set* acquire(int ndescs, size_t res_words);
+  void release(Set* s);
+  // Copies the set's first n host descriptors up, zeroes the first hist_words words of d_res,
+  // launches on `s`, then copies the first res_words words down into h_res and records the set's
+  // event (no wait). hist_words = res_words = 0: the results are the caller's own buffers, with
+  // the histograms zeroed on `s` already.
+  static void run(Set& set, int n, size_t hist_words, size_t res_words, hipStream_t s);
+  static constexpr int kScratch = 4;
+
+ private:
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<std::unique_ptr<Set>> all_;
+  std::vector<Set*> free_;
+};
+
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 
 struct LetterboxDesc {

@@ -3218,6 +3218,242 @@ void Worker::read_motion_many(const std::vector<int>& cams, std::vector<MotionRe
   }
 }
 
+// ------------------------------------------------------------------------- tamper detection
+
+void Worker::set_tamper_params(const tamper::Params& p) {
+  tamper::check_params(p);
+  {
+    std::lock_guard<std::mutex> g(tamper_mu_);
+    tamper_params_ = p;
+    ++tamper_gen_;  // an answer of an older generation counts as none
+  }
+  std::vector<std::shared_ptr<Camera>> cams;
+  {
+    std::lock_guard<std::mutex> g(cams_mu_);
+    cams = cams_;
+  }
+  for (auto& c : cams) {
+    if (!c) continue;
+    TamperState& st = c->tamper;
+    std::lock_guard<std::mutex> g(st.mu);
+    st.seq = 0;
+    st.result = TamperResult{};
+    if (st.have_ref && st.ref.cell != p.cell) {
+      st.have_ref = false;
+      st.ref = tamper::Reference{};
+    }
+  }
+}
+
+tamper::Params Worker::tamper_params() {
+  std::lock_guard<std::mutex> g(tamper_mu_);
+  return tamper_params_;
+}
+
+void Worker::tamper_reset(int cam) {
+  std::shared_ptr<Camera> c = camera(cam);
+  VEP_CHECK(c, "no such camera");
+  TamperState& st = c->tamper;
+  std::lock_guard<std::mutex> g(st.mu);
+  st.seq = 0;
+  st.result = TamperResult{};
+  st.have_ref = false;
+  st.ref = tamper::Reference{};
+}
+
+// One camera of a tamper request. Its state's mutex is held from pick to commit.
+struct Worker::TamperEval {
+  int cam = -1;
+  i64 after = 0;
+  std::shared_ptr<Camera> c;
+  std::shared_ptr<FrameRing> ring;
+  std::unique_lock<std::mutex> lock;
+  FrameMeta meta;
+  int slot = -1;
+  bool pending = false;  // needs (another) evaluation
+  int w = 0, h = 0;
+  size_t cells = 0;      // of its grid
+  size_t hist_at = 0, grid_at = 0;  // its histogram and its two planes in the request's results
+  std::vector<u32> hist, sum_y, energy;
+  bool ok = false;
+  TamperResult result;
+};
+
+// evs: distinct cameras in ascending index (the order their mutexes are taken in).
+void Worker::tamper_eval(std::vector<TamperEval>& evs, bool set_reference) {
+  tamper::Params prm;
+  u64 gen;
+  // (every camera is looked up before the first state mutex is taken, as in motion_eval)
+  for (TamperEval& e : evs) {
+    e.c = camera(e.cam);
+    if (e.c) e.ring = e.c->ring();
+  }
+  for (TamperEval& e : evs) {
+    if (!e.ring) continue;
+    e.lock = std::unique_lock<std::mutex>(e.c->tamper.mu);
+    e.pending = true;
+  }
+  {
+    // (after the cameras' mutexes: set_tamper_params stores the parameters before it takes them,
+    // so an answer built here under older parameters is reset by it afterwards)
+    std::lock_guard<std::mutex> g(tamper_mu_);
+    prm = tamper_params_;
+    gen = tamper_gen_;
+  }
+  const u32 cell = u32(prm.cell);
+  // The stored answer as the camera's reference, and summarised again against it.
+  auto make_reference = [&](TamperState& st) {
+    const TamperResult& r = st.result;
+    st.ref.w = r.width;
+    st.ref.h = r.height;
+    st.ref.cell = r.cell;
+    st.ref.sum_y = r.sum_y;
+    st.ref.energy_total = r.summary.energy_total;
+    st.have_ref = true;
+    st.result.summary = tamper::summarize(r.hist.data(), r.sum_y.data(), r.energy.data(), r.width, r.height, prm, &st.ref);
+  };
+  std::vector<TamperEval*> todo;
+  for (int round = 0; round < 4; ++round) {
+    todo.clear();
+    size_t grid_words = 0;
+    for (TamperEval& e : evs) {
+      if (!e.pending) continue;
+      TamperState& st = e.c->tamper;
+      if (!e.ring->latest(e.after, &e.meta, &e.slot)) {
+        e.pending = false;
+        continue;
+      }
+      if (st.gen != gen || st.ring.lock() != e.ring) {  // other parameters or a new ring: no stored answer
+        st.seq = 0;
+        st.result = TamperResult{};
+        if (st.have_ref && st.ref.cell != prm.cell) {
+          st.have_ref = false;
+          st.ref = tamper::Reference{};
+        }
+        st.gen = gen;
+        st.ring = e.ring;
+      }
+      if (st.seq == e.meta.seq && st.seq != 0) {  // evaluated already: one evaluation per frame
+        if (set_reference) make_reference(st);
+        e.result = st.result;
+        e.ok = true;
+        e.pending = false;
+        continue;
+      }
+      e.w = e.ring->width();
+      e.h = e.ring->height();
+      e.cells = size_t(tamper::cells(u32(e.w), cell)) * tamper::cells(u32(e.h), cell);
+      e.hist_at = todo.size() * size_t(tamper::kBins);
+      e.grid_at = grid_words;
+      grid_words += 2 * e.cells;
+      todo.push_back(&e);
+    }
+    if (todo.empty()) break;
+    const size_t hist_words = todo.size() * size_t(tamper::kBins), res_words = hist_words + grid_words;
+    for (TamperEval* e : todo) e->grid_at += hist_words;  // the planes follow the histograms
+    if (dev_.gpu()) {
+      dev_.bind();
+      gpu::TamperPool::Set* set = tamper_pool_.acquire(int(todo.size()), res_words);
+      try {
+        for (size_t k = 0; k < todo.size(); ++k) {
+          TamperEval& e = *todo[k];
+          gpu::TamperDesc d{};
+          d.src = e.ring->slot_ptr(e.slot);
+          d.src_pitch = u32(e.w) * 3;
+          d.hist = set->d_res + e.hist_at;
+          d.sum_y = set->d_res + e.grid_at;
+          d.energy = set->d_res + e.grid_at + e.cells;
+          d.w = e.w;
+          d.h = e.h;
+          d.cell = prm.cell;
+          gpu::check_tamper(d, e.ring->slot_bytes(), e.cells);
+          set->h_descs[k] = d;
+        }
+        gpu::TamperPool::run(*set, int(todo.size()), hist_words, res_words, serve_stream_);
+        VEP_HIP(hipEventSynchronize(set->ev));
+        for (TamperEval* e : todo) {
+          const u32* r = set->h_res;
+          e->hist.assign(r + e->hist_at, r + e->hist_at + tamper::kBins);
+          e->sum_y.assign(r + e->grid_at, r + e->grid_at + e->cells);
+          e->energy.assign(r + e->grid_at + e->cells, r + e->grid_at + 2 * e->cells);
+        }
+      } catch (...) {
+        tamper_pool_.release(set);
+        throw;
+      }
+      tamper_pool_.release(set);
+    } else {
+      for (TamperEval* e : todo) {
+        e->hist.resize(size_t(tamper::kBins));
+        e->sum_y.resize(e->cells);
+        e->energy.resize(e->cells);
+        tamper::stats_cpu(e->ring->slot_ptr(e->slot), e->w, e->h, size_t(e->w) * 3, prm.cell, e->hist.data(),
+                          e->sum_y.data(), e->energy.data());
+      }
+    }
+    for (TamperEval* e : todo) {
+      if (!e->ring->still_valid(e->slot, e->meta.seq)) continue;  // redone from the newer frame
+      TamperState& st = e->c->tamper;
+      st.seq = e->meta.seq;
+      TamperResult& r = st.result;
+      r.seq = e->meta.seq;
+      r.width = e->w;
+      r.height = e->h;
+      r.cell = prm.cell;
+      r.cols = int(tamper::cells(u32(e->w), cell));
+      r.rows = int(tamper::cells(u32(e->h), cell));
+      r.hist = std::move(e->hist);
+      r.sum_y = std::move(e->sum_y);
+      r.energy = std::move(e->energy);
+      r.summary = tamper::summarize(r.hist.data(), r.sum_y.data(), r.energy.data(), e->w, e->h, prm,
+                                    st.have_ref ? &st.ref : nullptr);
+      e->c->tamper_evaluations.fetch_add(1);
+      if (r.summary.tampered) e->c->tamper_frames.fetch_add(1);
+      if (set_reference) make_reference(st);
+      e->result = r;
+      e->ok = true;
+      e->pending = false;
+    }
+  }
+  for (TamperEval& e : evs)
+    if (e.lock.owns_lock()) e.lock.unlock();
+}
+
+bool Worker::read_tamper(int cam, i64 after, TamperResult& out) {
+  std::vector<TamperEval> evs(1);
+  evs[0].cam = cam;
+  evs[0].after = after;
+  tamper_eval(evs, false);
+  if (!evs[0].ok) return false;
+  out = std::move(evs[0].result);
+  return true;
+}
+
+void Worker::read_tamper_many(const std::vector<int>& cams, std::vector<TamperResult>& out, std::vector<char>& ok) {
+  std::vector<int> order(cams);
+  std::sort(order.begin(), order.end());
+  order.erase(std::unique(order.begin(), order.end()), order.end());
+  std::vector<TamperEval> evs(order.size());
+  for (size_t k = 0; k < order.size(); ++k) evs[k].cam = order[k];
+  tamper_eval(evs, false);
+  out.assign(cams.size(), TamperResult{});
+  ok.assign(cams.size(), 0);
+  for (size_t t = 0; t < cams.size(); ++t) {
+    const size_t k = size_t(std::lower_bound(order.begin(), order.end(), cams[t]) - order.begin());
+    if (!evs[k].ok) continue;
+    out[t] = evs[k].result;
+    ok[t] = 1;
+  }
+}
+
+bool Worker::tamper_set_reference(int cam) {
+  VEP_CHECK(camera(cam), "no such camera");
+  std::vector<TamperEval> evs(1);
+  evs[0].cam = cam;
+  tamper_eval(evs, true);
+  return evs[0].ok;
+}
+
 void Worker::copy_slot(FrameRing& ring, int slot, u8* dst) {
   const size_t n = ring.slot_bytes();
   if (!dev_.gpu()) {

@@ -27,6 +27,7 @@
 #include "ioloop.h"
 #include "gpu.h"
 #include "motion.h"
+#include "tamper.h"
 #include "pool.h"
 #include "vcn.h"
 
@@ -135,6 +136,28 @@ struct MotionState {
   std::weak_ptr<FrameRing> ring;  // the ring `seq` counts in (a resolution change starts a new one)
   i64 seq = 0;                 // the frame last evaluated, 0: none
   MotionResult result;         // its answer
+};
+
+// What read_tamper answers about one frame (tamper.h has the arithmetic).
+struct TamperResult {
+  i64 seq = 0;                 // the frame evaluated
+  int width = 0, height = 0;
+  int cell = 0, cols = 0, rows = 0;
+  tamper::Summary summary;
+  std::vector<u32> hist;       // 256
+  std::vector<u32> sum_y, energy;  // rows x cols each
+};
+
+// A camera's tamper state: the last answer and the optional reference grid (host memory, not
+// persisted). Nothing lives on the device.
+struct TamperState {
+  std::mutex mu;               // one evaluation of the camera at a time
+  u64 gen = 0;                 // Worker::set_tamper_params generation the answer was built under
+  std::weak_ptr<FrameRing> ring;  // the ring `seq` counts in (a resolution change starts a new one)
+  i64 seq = 0;                 // the frame last evaluated, 0: none
+  TamperResult result;         // its answer
+  bool have_ref = false;
+  tamper::Reference ref;       // the grid of the frame an operator declared normal
 };
 
 // One picture that left the reorder buffer during a job (frame history, Camera::history): a
@@ -344,6 +367,10 @@ class Camera {
   // (Last in the class: the members the ingest and publish paths touch keep their places.)
   std::atomic<u64> motion_evaluations{0}, motion_frames{0};
   MotionState motion;
+  // tamper detection (Worker::read_tamper): frames evaluated, and those of them flagged. (Last,
+  // after motion's members, for the same reason.)
+  std::atomic<u64> tamper_evaluations{0}, tamper_frames{0};
+  TamperState tamper;
 };
 
 struct WorkerOptions {
@@ -488,6 +515,27 @@ class Worker {
   motion::Params motion_params();
   // Frees the camera's model: its next evaluation primes again.
   void motion_reset(int cam);
+  // Tamper detection (tamper.h, docs/TAMPER.md): is the newest frame with seq > after dark, bright,
+  // flat, or, against the camera's reference, defocused or moved? The frame is evaluated where it
+  // lies, in its ring slot, on the serving stream (CPU backend: tamper::stats_cpu on the host
+  // ring); the histogram and the two grid planes come down and tamper::summarize runs on the host.
+  // An answer is stored once the slot proved unchanged (still_valid); a reused slot is evaluated
+  // again from the newer frame, up to four times. A frame is evaluated once: later calls at the
+  // same seq get the stored answer. False if there is no such frame.
+  bool read_tamper(int cam, i64 after, TamperResult& out);
+  // The newest frame of several cameras, every camera that needs an evaluation in ONE launch.
+  // ok[k] is false for an unknown index, a camera without a ring or a frame, or one still
+  // inconsistent after the fourth round.
+  void read_tamper_many(const std::vector<int>& cams, std::vector<TamperResult>& out, std::vector<char>& ok);
+  // Parameters are per worker: validates, resets every stored answer and drops the references
+  // whose cell changed.
+  void set_tamper_params(const tamper::Params& p);
+  tamper::Params tamper_params();
+  // Declares the camera's newest frame normal: evaluates it if needed and stores its grid as the
+  // reference (the stored answer is summarised again against it). False when there is no frame.
+  bool tamper_set_reference(int cam);
+  // Drops the camera's reference and its stored answer.
+  void tamper_reset(int cam);
   void set_wall_max_tiles(int n);
   int wall_max_tiles() const { return wall_max_tiles_.load(); }
   // Frame history: the newest max_count (0 = the camera's depth) frames with seq > after, copied
@@ -743,6 +791,13 @@ class Worker {
   struct MotionEval;
   void motion_eval(std::vector<MotionEval>& evs);
   void motion_free(MotionState& st);  // (st.mu held)
+  // tamper detection (after motion's members)
+  gpu::TamperPool tamper_pool_;  // descriptors + results of the tamper reads, one set per request in flight
+  std::mutex tamper_mu_;         // tamper_params_ / tamper_gen_
+  tamper::Params tamper_params_;
+  u64 tamper_gen_ = 1;
+  struct TamperEval;
+  void tamper_eval(std::vector<TamperEval>& evs, bool set_reference);
 };
 
 // Protobuf wire encoding of chrys.cloud.videostreaming.v1beta1.VideoFrame

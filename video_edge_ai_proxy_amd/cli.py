@@ -6,6 +6,7 @@
   farm      synthetic RTSP camera farm (H.264 I_PCM/P_Skip streams) for tests and benchmarks
   list | frame | annotate | storage | proxy   gRPC clients (examples/*.py analogs)
   motion    REST client of the motion detector (--device NAME --rest host:port [--watch])
+  tamper    REST client of the tamper detector (--device NAME --rest host:port [--watch] [--set-reference])
 """
 from __future__ import annotations
 
@@ -195,6 +196,49 @@ def cmd_motion(a):
         time.sleep(a.interval)
 
 
+def format_tamper(m: dict) -> str:
+    """One line per evaluated frame of ``vep tamper``."""
+    flag = "TAMPERED " + ",".join(m.get("causes") or []) if m.get("tampered") else "ok"
+    ref = f"shifted {m.get('shifted', 0)}" if m.get("has_reference") else "no reference"
+    return (f"seq {m['seq']} {flag} mean {m.get('mean', 0.0):.1f} p5 {m.get('p5', 0)} p95 {m.get('p95', 0)} "
+            f"sharpness {m.get('sharpness', 0.0):.1f} {ref}")
+
+
+def cmd_tamper(a):
+    """REST client of ``/api/v1/process/{name}/tamper``: one line per new evaluated frame;
+    ``--set-reference`` first declares the camera's newest frame normal."""
+    import json
+    import urllib.error
+    import urllib.parse
+    import urllib.request
+
+    base = f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/tamper"
+    seq, idle, ref_set = 0, 0, not a.set_reference
+    while True:
+        try:
+            if not ref_set:
+                req = urllib.request.Request(f"{base}/reference", method="PUT")
+                with urllib.request.urlopen(req, timeout=10):
+                    ref_set = True
+                    print("reference set", flush=True)
+            with urllib.request.urlopen(f"{base}?after={seq}", timeout=10) as r:
+                m = json.loads(r.read())
+        except urllib.error.HTTPError as e:
+            if e.code != 404 or b"not found" in e.read():
+                raise SystemExit(f"tamper: HTTP {e.code} for {a.device!r}")
+            m = None  # no (newer) frame yet
+        if m is not None:
+            seq, idle = int(m["seq"]), 0
+            print(format_tamper(m), flush=True)
+            if not a.watch:
+                return
+        else:
+            idle += 1
+            if not a.watch and idle * a.interval > 10.0:
+                raise SystemExit(f"tamper: no frame of {a.device!r} within 10 s")
+        time.sleep(a.interval)
+
+
 def cmd_bench(a, rest):
     """``vep bench ...`` = the repo's bench.py (headline benchmark) with the same flags."""
     import subprocess
@@ -275,6 +319,14 @@ def build_parser():
     m.add_argument("--watch", action="store_true", help="keep printing, one line per new evaluated frame")
     m.add_argument("--interval", type=float, default=0.1, help="seconds between polls")
     m.set_defaults(fn=cmd_motion)
+
+    t = sub.add_parser("tamper", help="does the camera still show what it should: the hub's tamper detection (REST)")
+    t.add_argument("--device", required=True)
+    t.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API")
+    t.add_argument("--watch", action="store_true", help="keep printing, one line per new evaluated frame")
+    t.add_argument("--set-reference", action="store_true", help="first declare the camera's newest frame normal")
+    t.add_argument("--interval", type=float, default=0.1, help="seconds between polls")
+    t.set_defaults(fn=cmd_tamper)
 
     b = sub.add_parser("bench", help="run bench.py (flags passed through, e.g. --codec h265)")
     b.set_defaults(fn=None)

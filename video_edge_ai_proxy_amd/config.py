@@ -123,6 +123,23 @@ MOTION_RANGES = {"cell": (4, 256), "threshold": (0, 255), "learn_shift": (0, 8),
 
 
 @dataclass
+class TamperConfig:
+    """Tamper detection (docs/TAMPER.md; ``Hub.tamper``, ``/api/v1/tamper``). The parameters hold
+    for every camera of the hub. The defaults are design choices, not measured thresholds."""
+    cell: int = 32            # grid cells of cell x cell pixels (8..128)
+    dark_level: int = 32      # dark when the mean luma is <= this (0..255)
+    bright_level: int = 224   # bright when the mean luma is >= this (0..255)
+    spread_min: int = 24      # flat when p95 - p5 of the luma histogram is < this (0..255)
+    focus_percent: int = 50   # defocused when the energy is < this share of the reference's (0..100, 0 = off)
+    shift_level: int = 24     # a cell is shifted when its mean luma moved by more than this (0..255)
+    shift_percent: int = 50   # moved when this share of the cells is shifted (1..100)
+
+
+TAMPER_RANGES = {"cell": (8, 128), "dark_level": (0, 255), "bright_level": (0, 255), "spread_min": (0, 255),
+                 "focus_percent": (0, 100), "shift_level": (0, 255), "shift_percent": (1, 100)}
+
+
+@dataclass
 class Config:
     version: str = "0.1.0"
     title: str = "vep MI355X video edge hub"
@@ -138,6 +155,7 @@ class Config:
     gpu: GpuConfig = field(default_factory=GpuConfig)
     serving: ServingConfig = field(default_factory=ServingConfig)
     motion: MotionConfig = field(default_factory=MotionConfig)
+    tamper: TamperConfig = field(default_factory=TamperConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
     bus_tag: str = ""
 
@@ -205,6 +223,10 @@ def validate(cfg: Config) -> None:
         v = getattr(cfg.motion, key)
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
             raise ValueError(f"motion.{key} must be an integer {lo}..{hi}, got {v!r}")
+    for key, (lo, hi) in TAMPER_RANGES.items():
+        v = getattr(cfg.tamper, key)
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"tamper.{key} must be an integer {lo}..{hi}, got {v!r}")
 
 
 def parse_tile(s) -> tuple[int, int]:

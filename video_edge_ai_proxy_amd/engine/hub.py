@@ -89,6 +89,9 @@ class Hub:
             m = cfg.motion
             w.set_motion_params(int(m.cell), int(m.threshold), int(m.learn_shift), int(m.cell_percent),
                                 int(m.min_cells))
+            t = cfg.tamper
+            w.set_tamper_params(int(t.cell), int(t.dark_level), int(t.bright_level), int(t.spread_min),
+                                int(t.focus_percent), int(t.shift_level), int(t.shift_percent))
             w.start()
             self.workers.append(w)
         # Consumer batch: with letterbox_size > 0 every worker letterboxes each frame it publishes
@@ -461,6 +464,69 @@ class Hub:
         """Forget the camera's background model: its next evaluation primes again."""
         w, cam = self.worker_of(name)
         w.motion_reset(cam)
+
+    # ------------------------------------------------------------------ tamper
+    @staticmethod
+    def _tamper_dict(r, grid: bool) -> Optional[dict]:
+        """A worker's tamper answer as the hub serves it."""
+        if r is None:
+            return None
+        out = {k: int(r[k]) for k in ("seq", "width", "height", "cell", "cols", "rows", "p5", "p95", "shifted")}
+        out.update({k: float(r[k]) for k in ("mean", "sharpness")})
+        out.update({k: bool(r[k]) for k in ("has_reference", "dark", "bright", "flat", "defocused", "moved",
+                                            "tampered")})
+        out["causes"] = [str(c) for c in r["causes"]]
+        if grid:
+            out["hist"] = [int(v) for v in r["hist"]]
+            out["sum_y"] = [[int(v) for v in row] for row in r["sum_y"]]
+            out["energy"] = [[int(v) for v in row] for row in r["energy"]]
+        return out
+
+    def tamper(self, name: str, after: int = 0, grid: bool = False, wake: bool = True) -> Optional[dict]:
+        """Does the camera's newest frame with seq > after still show what it should? ``None``
+        when there is no such frame, else a dict of ``seq, width, height, cell, cols, rows, mean,
+        p5, p95, sharpness, has_reference, shifted, dark, bright, flat, defocused, moved, tampered,
+        causes`` (docs/TAMPER.md), with ``grid`` also ``hist``, ``sum_y`` and ``energy``. The frame
+        is evaluated on the camera's GPU, in its ring slot, once however many clients ask.
+        ``wake`` refreshes ``last_query``, so asking keeps the camera's lazy decoder awake;
+        ``wake=False`` evaluates whatever the ring holds and leaves ``last_query`` alone (an idle
+        camera's frame is then as old as its last query)."""
+        w, cam = self.worker_of(name)
+        if wake:
+            w.set_last_query(cam, now_ms())
+        return self._tamper_dict(w.read_tamper(cam, int(after)), grid)
+
+    def tamper_many(self, names=None, grid: bool = False, wake: bool = True) -> dict:
+        """``{name: dict | None}`` for the newest frame of every listed camera (default: the
+        running cameras, sorted): one kernel launch per worker covers all of its cameras that
+        need an evaluation. ``None``: the camera has no frame yet. ``wake`` as in :meth:`tamper`."""
+        with self._lock:
+            order = sorted(self.cameras) if names is None else list(names)
+            hs = [self.handle(n) for n in order]
+        if wake:
+            now = now_ms()
+            for h in hs:
+                self.workers[h.worker_index].set_last_query(h.cam, now)
+        out = {}
+        for wi, w in enumerate(self.workers):
+            mine = [h for h in hs if h.worker_index == wi]
+            if not mine:
+                continue
+            for h, r in zip(mine, w.read_tamper_many([h.cam for h in mine])):
+                out[h.name] = self._tamper_dict(r, grid)
+        return {n: out[n] for n in order}
+
+    def tamper_reference(self, name: str) -> bool:
+        """Declare the camera's newest frame normal: its grid becomes the reference that
+        ``defocused`` and ``moved`` compare with (host memory, not kept across restarts). False
+        when the camera has no frame."""
+        w, cam = self.worker_of(name)
+        return bool(w.tamper_set_reference(cam))
+
+    def tamper_reset(self, name: str) -> None:
+        """Drop the camera's reference and its stored answer."""
+        w, cam = self.worker_of(name)
+        w.tamper_reset(cam)
 
     def history(self, name: str, after: int = 0, count: int = 0) -> list:
         """``[(meta, ndarray)]`` of the camera's newest ``count`` (0 = ``buffer.in_memory``) frames

@@ -593,6 +593,23 @@ class ProcessHub:
     def motion_reset(self, name: str) -> None:
         self._call(name, "motion_reset")
 
+    def tamper(self, name: str, after: int = 0, grid: bool = False, wake: bool = True):
+        """dict or None: evaluated on the worker process's GPU, only the answer crosses the pipe."""
+        return self._call(name, "tamper", after, grid, wake)
+
+    def tamper_many(self, names=None, grid: bool = False, wake: bool = True) -> dict:
+        """{name: dict | None}: forwarded per name (the rings live in the worker processes)."""
+        order = sorted(self.cameras) if names is None else list(names)
+        for n in order:
+            self.handle(n)
+        return {n: self._call(n, "tamper", 0, grid, wake) for n in order}
+
+    def tamper_reference(self, name: str) -> bool:
+        return bool(self._call(name, "tamper_reference"))
+
+    def tamper_reset(self, name: str) -> None:
+        self._call(name, "tamper_reset")
+
     # A wall reads the ring slots of many cameras in one launch; the rings live in the worker
     # processes, one per GPU, so it is served only by the in-process hub (gpu.isolation: thread).
     def wall_layout(self, names=None, cols=None, tile_width=None, tile_height=None):

@@ -16,6 +16,9 @@
   background model: changed pixels per cell and the updated model, one or many pictures in a
   single launch (the kernel behind ``/motion``), byte-identical with
   :func:`motion_update_reference`.
+* :func:`tamper_stats` / :func:`tamper_stats_batch` — the luma histogram, per-cell luma sums and
+  per-cell focus energy of BGR24 pictures, one or many in a single launch (the kernel behind
+  ``/tamper``), byte-identical with :func:`tamper_stats_reference`.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -532,6 +535,82 @@ def motion_update_reference(bgr: torch.Tensor, background: torch.Tensor | None =
         bg = background.detach().cpu().contiguous().numpy()
     counts, new = native.motion_update_cpu(bgr.detach().cpu().numpy(), bg, cell, threshold, learn_shift)
     return torch.from_numpy(counts.astype("int32")), torch.from_numpy(new)
+
+
+def _check_tamper_cell(cell):
+    if isinstance(cell, bool) or not isinstance(cell, int) or not 8 <= cell <= 128:
+        raise ValueError("cell must be an integer 8..128")
+    return cell
+
+
+def _u32(t: torch.Tensor) -> torch.Tensor:
+    """An int32 tensor of u32 bit patterns as int64 values."""
+    return t.to(torch.int64) & 0xFFFFFFFF
+
+
+def tamper_stats_batch(pictures, cell: int = 32, out=None):
+    """One kernel launch for a list of ``[H, W, 3]`` BGR24 device tensors of any sizes on one
+    device: the list of ``(hist, sum_y, energy)`` of :func:`tamper_stats`. ``out``: ``None`` or one
+    ``(hist, sum_y, energy)`` triple of contiguous int32 device tensors per picture, ``[256]``,
+    ``[rows, cols]`` and ``[rows, cols]``, which the kernel writes where they lie (as u32 bit
+    patterns; the histograms are zeroed on the stream first)."""
+    require_gpu()
+    cell = _check_tamper_cell(cell)
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("pictures must hold at least one picture")
+    if out is not None:
+        out = list(out)
+        if len(out) != len(pictures):
+            raise ValueError("out must hold one (hist, sum_y, energy) per picture")
+    device, work, raw = None, [], []
+    for k, bgr in enumerate(pictures):
+        w, h = _check_bgr(bgr, f"pictures[{k}]")
+        if not bgr.is_cuda:
+            raise ValueError("bgr must be a device tensor")
+        if device is None:
+            device = bgr.device
+        if bgr.device != device:
+            raise ValueError("the pictures must live on one device")
+        cols, rows = native.tamper_grid(w, h, cell)
+        if out is None:
+            bufs = (torch.empty(256, dtype=torch.int32, device=device),
+                    torch.empty((rows, cols), dtype=torch.int32, device=device),
+                    torch.empty((rows, cols), dtype=torch.int32, device=device))
+        else:
+            bufs = tuple(out[k])
+            if len(bufs) != 3:
+                raise ValueError("out must hold one (hist, sum_y, energy) per picture")
+            for t, shape, what in zip(bufs, ((256,), (rows, cols), (rows, cols)), ("hist", "sum_y", "energy")):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                    raise TypeError(f"out[{k}] {what} must be an int32 tensor")
+                if tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"out[{k}] {what} must be contiguous {shape}, got {tuple(t.shape)}")
+                if not t.is_cuda or t.device != device:
+                    raise ValueError(f"out[{k}] {what} must live on the pictures' device")
+        work.append((bgr.data_ptr(), w, h, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr()))
+        raw.append(bufs)
+    with torch.cuda.device(device):
+        native.tamper_stats(work, cell, int(torch.cuda.current_stream(device).cuda_stream))
+    return [tuple(_u32(t) for t in bufs) for bufs in raw]
+
+
+def tamper_stats(bgr: torch.Tensor, cell: int = 32, out=None):
+    """The tamper statistics of a ``[H, W, 3]`` BGR24 device tensor (csrc/vep/tamper.h):
+    ``(hist, sum_y, energy)`` with ``hist`` the ``[256]`` luma histogram, ``sum_y`` the
+    ``[rows, cols]`` luma sums of the ``cell x cell`` cells and ``energy`` their squared-gradient
+    focus measure. All three are ``torch.int64``: the kernel's values are u32 (a bin holds up to
+    65535² pixels, above int32), and int64 holds that range without a sign. Exact in integers,
+    byte-identical with :func:`tamper_stats_reference`. No CPU fallback."""
+    return tamper_stats_batch([bgr], cell, None if out is None else [out])[0]
+
+
+def tamper_stats_reference(bgr: torch.Tensor, cell: int = 32):
+    """The CPU implementation's result for the same picture (host or device tensor), on the host:
+    the byte-exact oracle of :func:`tamper_stats`, int64 like it."""
+    cell = _check_tamper_cell(cell)
+    _check_bgr(bgr)
+    return tuple(torch.from_numpy(a.astype("int64")) for a in native.tamper_stats_cpu(bgr.detach().cpu().numpy(), cell))
 
 
 # ----------------------------------------------------------------------------- references

@@ -32,6 +32,9 @@ class HubCollector:
         mev = CounterMetricFamily("vep_motion_evaluations", "frames evaluated by the motion detector", labels=labels)
         mfr = CounterMetricFamily("vep_motion_frames_with_motion", "evaluated frames that showed motion",
                                   labels=labels)
+        tev = CounterMetricFamily("vep_tamper_evaluations", "frames evaluated by the tamper detector", labels=labels)
+        tfr = CounterMetricFamily("vep_tamper_frames_tampered", "evaluated frames flagged as tampered",
+                                  labels=labels)
         for name in list(self.hub.cameras):
             try:
                 st = self.hub.state(name)
@@ -46,6 +49,8 @@ class HubCollector:
             rst.add_metric(lv, st.get("restart_count", 0))
             mev.add_metric(lv, st.get("motion_evaluations", 0))
             mfr.add_metric(lv, st.get("motion_frames", 0))
+            tev.add_metric(lv, st.get("tamper_evaluations", 0))
+            tfr.add_metric(lv, st.get("tamper_frames_tampered", 0))
             hist, bounds = st.get("latency_hist"), st.get("latency_bounds_ms")
             if hist and bounds:
                 acc, buckets = 0, []
@@ -53,7 +58,7 @@ class HubCollector:
                     acc += c
                     buckets.append((str(b / 1000.0) if b != float("inf") else "+Inf", acc))
                 lat.add_metric(lv, buckets, st.get("latency_sum_ms", 0) / 1000.0)
-        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr)
+        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr, tev, tfr)
         wb = CounterMetricFamily("vep_worker_batches", "batched decode launches", labels=["device"])
         wf = CounterMetricFamily("vep_worker_frames", "frames decoded by the worker", labels=["device"])
         wg = CounterMetricFamily("vep_worker_gpu_ms", "GPU time of decode batches (ms)", labels=["device"])

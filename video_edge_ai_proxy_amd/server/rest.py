@@ -15,7 +15,10 @@ as a JPEG, encoded on the camera's GPU) and ``.../stream.mjpg`` (live MJPEG, one
 frame), both with ``?width=&height=`` for a picture fitted into that box and downscaled on the GPU,
 ``/api/v1/wall.jpg`` / ``wall.mjpg`` / ``wall`` (one picture of many cameras and its geometry,
 docs/WALL.md), ``/api/v1/process/{name}/motion`` and ``/api/v1/motion`` (did anything change:
-motion detection on the GPU, docs/MOTION.md; ``DELETE .../motion`` resets the background), and the portal itself at ``/`` (replaces the Angular build, which needs a node
+motion detection on the GPU, docs/MOTION.md; ``DELETE .../motion`` resets the background),
+``/api/v1/process/{name}/tamper`` and ``/api/v1/tamper`` (does the camera still show what it should:
+tamper detection on the GPU, docs/TAMPER.md; ``PUT .../tamper/reference`` declares the newest frame
+normal, ``DELETE .../tamper`` forgets it), and the portal itself at ``/`` (replaces the Angular build, which needs a node
 toolchain).
 """
 from __future__ import annotations
@@ -356,6 +359,57 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         cams = []
         for n, r in res.items():
             cams.append({"name": n, **(r if r is not None else {"seq": 0, "motion": False})})
+        return {"cameras": cams}
+
+    # ---- tamper detection: dark, bright, flat, defocused, moved, from the ring slots (docs/TAMPER.md)
+    @app.get("/api/v1/process/{name}/tamper")
+    def tamper(name: str, after: int = 0, grid: int = 0, wake: int = 1):
+        if after < 0 or grid not in (0, 1) or wake not in (0, 1):
+            return err(400, "after must be >= 0, grid and wake 0 or 1")
+        try:
+            r = pm.hub.tamper(name, after, bool(grid), bool(wake))
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        if r is None:
+            return err(404, "no newer frame decoded yet")
+        return JSONResponse(content=r, headers={"X-Vep-Seq": str(r["seq"])})
+
+    @app.put("/api/v1/process/{name}/tamper/reference")
+    def tamper_reference(name: str):
+        try:
+            ok = pm.hub.tamper_reference(name)
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        if not ok:
+            return err(404, "no frame decoded yet")
+        return Response(status_code=204)
+
+    @app.delete("/api/v1/process/{name}/tamper")
+    def tamper_reset(name: str):
+        try:
+            pm.hub.tamper_reset(name)
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        return Response(status_code=204)
+
+    @app.get("/api/v1/tamper")
+    def tamper_many(names: str | None = None, grid: int = 0, wake: int = 1):
+        if grid not in (0, 1) or wake not in (0, 1):
+            return err(400, "grid and wake must be 0 or 1")
+        order = None
+        if names is not None:
+            order = [n for n in names.split(",") if n]
+            if not order:
+                return err(400, "names must list at least one camera")
+        elif not pm.hub.cameras:
+            return err(404, "no camera running")
+        try:
+            res = pm.hub.tamper_many(order, bool(grid), bool(wake))
+        except KeyError as e:
+            return err(404, f"process {e.args[0] if e.args else ''!r} not found")
+        cams = []
+        for n, r in res.items():
+            cams.append({"name": n, **(r if r is not None else {"seq": 0, "tampered": False, "causes": []})})
         return {"cameras": cams}
 
     @app.get("/api/v1/processlist")
