@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -107,6 +107,17 @@ $(ASAN_DIR)/tamper_selftest: csrc/vep/tamper.cpp csrc/tests/tamper_selftest.cpp 
 
 asan-tamper: $(ASAN_DIR)/tamper_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/tamper_selftest
+
+# The CPU privacy masks alone on their edge shapes and closed forms (csrc/tests/mask_selftest.cpp),
+# likewise: a stand-alone host program, no GPU.
+$(ASAN_DIR)/mask_selftest: csrc/vep/mask.cpp csrc/tests/mask_selftest.cpp csrc/vep/mask.h csrc/vep/common.h
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc csrc/vep/mask.cpp csrc/tests/mask_selftest.cpp -o $@
+
+asan-mask: $(ASAN_DIR)/mask_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/mask_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

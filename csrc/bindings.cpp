@@ -182,6 +182,30 @@ static py::dict tamper_dict(const TamperResult& r) {
   return d;
 }
 
+// Privacy masks cross the boundary as tuples (x0, y0, x1, y1, mode, block, b, g, r) of ints; an
+// invalid list is a ValueError.
+using MaskTuple = std::tuple<int, int, int, int, int, int, int, int, int>;
+static std::vector<mask::Mask> masks_of(const std::vector<MaskTuple>& v) {
+  std::vector<mask::Mask> out;
+  for (const MaskTuple& t : v) {
+    mask::Mask m;
+    std::tie(m.x0, m.y0, m.x1, m.y1, m.mode, m.block, m.b, m.g, m.r) = t;
+    out.push_back(m);
+  }
+  try {
+    VEP_CHECK(out.size() <= size_t(mask::kMaxMasks), "mask: at most 8 masks per camera");
+    mask::check_list(out.data(), int(out.size()));
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return out;
+}
+static std::vector<MaskTuple> mask_tuples(const std::vector<mask::Mask>& v) {
+  std::vector<MaskTuple> out;
+  for (const mask::Mask& m : v) out.emplace_back(m.x0, m.y0, m.x1, m.y1, m.mode, m.block, m.b, m.g, m.r);
+  return out;
+}
+
 static tamper::Params tamper_params_of(int cell, int dark_level, int bright_level, int spread_min, int focus_percent,
                                        int shift_level, int shift_percent) {
   tamper::Params p;
@@ -1469,6 +1493,8 @@ PYBIND11_MODULE(_vep, m) {
              d["motion_frames"] = c.motion_frames.load();
              d["tamper_evaluations"] = c.tamper_evaluations.load();
              d["tamper_frames_tampered"] = c.tamper_frames.load();
+             d["masked_frames"] = c.masked_frames.load();
+             d["mask_dropped"] = c.mask_dropped.load();
              py::list hist;
              for (auto& h : c.lat_hist) hist.append(h.load());
              d["latency_hist"] = hist;
@@ -1692,6 +1718,20 @@ PYBIND11_MODULE(_vep, m) {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              py::gil_scoped_release rel;
              w.tamper_reset(i);
+           },
+           py::arg("idx"))
+      .def("set_privacy_masks",
+           [](Worker& w, int i, const std::vector<MaskTuple>& masks) {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const std::vector<mask::Mask> ms = masks_of(masks);
+             py::gil_scoped_release rel;
+             w.set_privacy_masks(i, ms);
+           },
+           py::arg("idx"), py::arg("masks"))
+      .def("privacy_masks",
+           [](Worker& w, int i) {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             return mask_tuples(w.privacy_masks(i));
            },
            py::arg("idx"))
       .def("read_history",
@@ -2301,6 +2341,90 @@ PYBIND11_MODULE(_vep, m) {
         },
         py::arg("hist"), py::arg("sum_y"), py::arg("energy"), py::arg("width"), py::arg("height"),
         py::arg("params") = py::dict(), py::arg("reference") = py::none());
+  // Privacy masks (vep/mask.h) on the host: the CPU backend's path and the byte-exact reference
+  // of privacy_mask.
+  m.def("mask_pixels",
+        // (x0, y0, x1, y1) in pixels of a mask of a w x h picture, rounded outward
+        [](int w, int h, const MaskTuple& mk) {
+          if (w < 1 || h < 1 || w > mask::kMaxSide || h > mask::kMaxSide)
+            throw py::value_error("mask_pixels: picture size must be 1..65535");
+          const std::vector<mask::Mask> ms = masks_of({mk});
+          const mask::Rect r = mask::to_pixels(w, h, ms[0]);
+          return py::make_tuple(r.x0, r.y0, r.x1, r.y1);
+        },
+        py::arg("width"), py::arg("height"), py::arg("mask"));
+  m.def("mask_levels",
+        [](int w, int h, const std::vector<MaskTuple>& mks) {
+          if (w < 1 || h < 1 || w > mask::kMaxSide || h > mask::kMaxSide)
+            throw py::value_error("mask_levels: picture size must be 1..65535");
+          const std::vector<mask::Mask> ms = masks_of(mks);
+          std::vector<int> lv(ms.size());
+          mask::levels(w, h, ms.data(), int(ms.size()), lv.data());
+          return lv;
+        },
+        py::arg("width"), py::arg("height"), py::arg("masks"));
+  m.def("mask_apply_cpu",
+        // the list applied in order, in place, to a writable C-contiguous (H, W, 3) uint8 array
+        [](py::array_t<uint8_t, py::array::c_style> bgr, const std::vector<MaskTuple>& mks) {
+          if (bgr.ndim() != 3 || bgr.shape(2) != 3 || bgr.shape(0) < 1 || bgr.shape(1) < 1 ||
+              bgr.shape(0) > mask::kMaxSide || bgr.shape(1) > mask::kMaxSide || !bgr.writeable())
+            throw py::value_error("mask_apply_cpu: writable (H, W, 3) uint8 picture of at most 65535 x 65535 expected");
+          const std::vector<mask::Mask> ms = masks_of(mks);
+          const int h = int(bgr.shape(0)), w = int(bgr.shape(1));
+          u8* p = bgr.mutable_data();
+          py::gil_scoped_release r;
+          mask::apply_cpu(p, size_t(w) * 3, w, h, ms.data(), int(ms.size()));
+        },
+        py::arg("bgr").noconvert(), py::arg("masks"));
+  // Pictures (dst, w, h, masks) on caller-owned device buffers, masked in place: one launch of the
+  // gfx950 mask kernel per level, over all pictures, on `stream` of the current device
+  // (descriptors: one process-wide pool per device). dst is h x w x 3 packed.
+  m.def("mask_apply",
+        [](const std::vector<std::tuple<uintptr_t, int, int, std::vector<MaskTuple>>>& pics, uintptr_t stream) {
+          static std::mutex mu;
+          static std::map<int, gpu::MaskPool*>* pools = new std::map<int, gpu::MaskPool*>();  // (never freed)
+          std::vector<std::vector<mask::Mask>> lists;
+          size_t nd = 0;
+          for (const auto& pc : pics) {
+            lists.push_back(masks_of(std::get<3>(pc)));
+            nd += lists.back().size();
+          }
+          if (nd == 0) return;
+          VEP_CHECK(nd <= 65535, "mask_apply: at most 65535 masks per call");
+          py::gil_scoped_release r;
+          int dev = 0;
+          VEP_HIP(hipGetDevice(&dev));
+          gpu::MaskPool* pool;
+          {
+            std::lock_guard<std::mutex> g(mu);
+            gpu::MaskPool*& slot = (*pools)[dev];
+            if (!slot) slot = new gpu::MaskPool();
+            pool = slot;
+          }
+          hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+          gpu::MaskPool::Set* set = pool->acquire(int(nd));
+          try {
+            int k = 0;
+            for (size_t i = 0; i < pics.size(); ++i) {
+              const uintptr_t dst = std::get<0>(pics[i]);
+              const int w = std::get<1>(pics[i]), h = std::get<2>(pics[i]);
+              const std::vector<mask::Mask>& ms = lists[i];
+              if (ms.empty()) continue;
+              VEP_CHECK(w >= 1 && h >= 1 && w <= mask::kMaxSide && h <= mask::kMaxSide,
+                        "mask: picture size must be 1..65535");
+              gpu::fill_mask_descs(set->h_descs + k, reinterpret_cast<u8*>(dst), size_t(w) * size_t(h) * 3, w, h, ms.data(),
+                                   int(ms.size()));
+              k += int(ms.size());
+            }
+            gpu::MaskPool::run(*set, k, s);
+            VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
+          } catch (...) {
+            pool->release(set);
+            throw;
+          }
+          pool->release(set);
+        },
+        py::arg("pictures"), py::arg("stream"));
   // Pictures (src, w, h, hist, sum_y, energy) on caller-owned device buffers: one launch of the
   // gfx950 tamper kernel on `stream` of the current device (descriptors: one process-wide pool
   // per device). src is h x w x 3 packed, hist 256 u32 (zeroed here, on the stream), the planes

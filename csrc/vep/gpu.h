@@ -16,6 +16,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "mask.h"
 
 namespace vep::gpu {
 
@@ -514,6 +515,65 @@ class TamperPool {
   // event (no wait). hist_words = res_words = 0: the results are the caller's own buffers, with
   // the histograms zeroed on `s` already.
   static void run(Set& set, int n, size_t hist_words, size_t res_words, hipStream_t s);
+  static constexpr int kScratch = 4;
+
+ private:
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<std::unique_ptr<Set>> all_;
+  std::vector<Set*> free_;
+};
+
+// ---- privacy masks (gpu_mask.hip; arithmetic: mask.h) ------------------------------------------
+// One mask of one picture of a batched mask launch (device memory): the pixel rect x0..x1 x y0..y1
+// of a packed BGR24 picture is filled or pixelated IN PLACE, byte-identical with mask::apply_cpu.
+// A launch runs the descriptors of one level (mask::levels); pictures may differ in size.
+struct MaskDesc {
+  VEP_DEV u8* dst;    // h rows of pitch bytes (any alignment)
+  u32 pitch;          // bytes
+  i32 w, h;
+  i32 x0, y0, x1, y1; // mask::to_pixels: 0 <= x0 < x1 <= w, 0 <= y0 < y1 <= h
+  i32 mode;           // mask::Mode
+  i32 block;          // pixelate: 4..128
+  u32 bgr;            // fill: b | g << 8 | r << 16
+  i32 level;          // 0 .. mask::kMaxMasks - 1
+  u32 pad_[3];
+};
+static_assert(sizeof(MaskDesc) == 64, "MaskDesc layout");
+// Throws unless the kernel can run the descriptor without touching memory outside a picture of
+// dst_bytes (the launch below does not check).
+void check_mask(const MaskDesc& d, size_t dst_bytes);
+// One launch for the descriptors of `level` among the n: grid = (workgroups of the largest such
+// mask) x n; the others' workgroups exit. h_descs is the host copy of d_descs (the grid is sized
+// from it). Nothing is launched when no descriptor has the level. Levels are ordered by calling
+// this in ascending level on one stream.
+void launch_mask(const MaskDesc* d_descs, const MaskDesc* h_descs, int n, int level, hipStream_t s);
+// The descriptors of one picture's list: out[k] for mask k of m[0..n) (n <= mask::kMaxMasks) on
+// the packed w x h picture at dst, dst_bytes long; pixel rects and levels from mask.h, each
+// descriptor checked. Returns the number of levels.
+int fill_mask_descs(MaskDesc* out, u8* dst, size_t dst_bytes, int w, int h, const mask::Mask* m, int n);
+
+// Mask descriptors of one device: up to kScratch sets, one per request in flight, each held in
+// pinned host memory and on the device; a set grows to the largest request it has seen and is
+// then reused. Used with the device bound to the calling thread.
+class MaskPool {
+ public:
+  struct Set {
+    MaskDesc* d_descs = nullptr;  // device
+    MaskDesc* h_descs = nullptr;  // pinned
+    int desc_cap = 0;
+    hipEvent_t ev = nullptr;
+    ~Set();
+  };
+  MaskPool();
+  ~MaskPool();
+  MaskPool(const MaskPool&) = delete;
+  MaskPool& operator=(const MaskPool&) = delete;
+  Set* acquire(int ndescs);  // a free set with room for ndescs descriptors (waits for one)
+  void release(Set* s);
+  // Copies the set's first n host descriptors up, launches their levels in ascending order on `s`
+  // and records the set's event (no wait).
+  static void run(Set& set, int n, hipStream_t s);
   static constexpr int kScratch = 4;
 
  private:

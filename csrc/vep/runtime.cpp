@@ -155,6 +155,13 @@ void FrameRing::abort(int slot) {
   if (slots_[slot]->version.load() & 1) slots_[slot]->version.fetch_add(1, std::memory_order_acq_rel);
 }
 
+void FrameRing::invalidate() {
+  std::lock_guard<std::mutex> g(meta_mu_);
+  latest_.store(-1, std::memory_order_release);
+  for (auto& sl : slots_)
+    if (!(sl->version.load() & 1)) sl->meta.seq = 0;  // (0: no frame; pick_free takes such a slot as free)
+}
+
 bool FrameRing::wait_newer(i64 after, int timeout_ms) const {
   std::unique_lock<std::mutex> g(meta_mu_);
   return cv_.wait_for(g, std::chrono::milliseconds(timeout_ms),
@@ -727,6 +734,8 @@ Worker::~Worker() {
     Lane& ln = *lp;
     for (Stage& st : ln.stage) {
       dev_.free_pinned(st.err);
+      if (st.mask_h) dev_.free_pinned(st.mask_h);
+      if (st.mask_d) dev_.free(st.mask_d);
       if (st.h) hostmem::unregister_range(st.h);
       dev_.free(st.d);
       dev_.free_pinned(st.h);
@@ -1382,6 +1391,7 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
   const hipStream_t cs = ln.stream;
   std::vector<DecodeJob>& jobs = st.jobs;
   const int n = int(jobs.size());
+  st.mask_snap.clear();  // (taken after the conversions are enqueued, below)
   // Slice bytes stay in host memory: pinned AU blocks as received (hostmem.h), or this stage's
   // pinned staging buffer for pageable AUs (one host memcpy). Two ways to the GPU:
   //  * direct (default): decode_convert reads each block straight over PCIe from its host
@@ -2091,12 +2101,95 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
     gpu::launch_letterbox(reinterpret_cast<const gpu::LetterboxDesc*>(st.d + off_lb), nout, p,
                           cs);
   }
+  // Privacy masks: every ring slot this batch converted into (the newest frame's and the earlier
+  // outputs') is masked in place, behind the conversions on the lane's stream, under the lists
+  // the cameras have now; publish() commits a slot only if its camera's list is still that one.
+  if (snapshot_masks(jobs, st.mask_snap)) {
+    size_t nd = 0;
+    for (int i = 0; i < n; ++i) {
+      size_t slots_of = jobs[size_t(i)].has_output() ? 1 : 0;
+      for (const JobOutput& o : jobs[size_t(i)].outputs) slots_of += o.ring_slot >= 0 ? 1 : 0;
+      nd += slots_of * size_t(st.mask_snap[size_t(i)].n);
+    }
+    if (nd > 0) {
+      if (st.mask_cap < nd) {  // (the stage's previous batch is complete: nothing reads the old buffers)
+        if (st.mask_h) dev_.free_pinned(st.mask_h);
+        st.mask_h = nullptr;
+        if (st.mask_d) dev_.free(st.mask_d);
+        st.mask_d = nullptr;
+        st.mask_cap = 0;
+        const size_t cap = std::max<size_t>(nd, 256);
+        st.mask_h = static_cast<gpu::MaskDesc*>(dev_.alloc_pinned(cap * sizeof(gpu::MaskDesc)));
+        st.mask_d = static_cast<gpu::MaskDesc*>(dev_.alloc(cap * sizeof(gpu::MaskDesc)));
+        st.mask_cap = cap;
+      }
+      size_t k = 0;
+      int top = 0;
+      auto add = [&](const Camera& c, const MaskSnap& ms, int slot, int w, int h) {
+        VEP_CHECK(w == c.ring_->width() && h == c.ring_->height(), "masked output does not match the camera's ring");
+        top = std::max(top, gpu::fill_mask_descs(st.mask_h + k, c.ring_->slot_ptr(slot), c.ring_->slot_bytes(), w, h,
+                                                 ms.m, ms.n));
+        k += size_t(ms.n);
+      };
+      for (int i = 0; i < n; ++i) {
+        const DecodeJob& j = jobs[size_t(i)];
+        const MaskSnap& ms = st.mask_snap[size_t(i)];
+        if (ms.n == 0) continue;
+        const Camera& c = *cams_[size_t(j.cam)];
+        for (const JobOutput& o : j.outputs)
+          if (o.ring_slot >= 0) add(c, ms, o.ring_slot, o.pic.width, o.pic.height);
+        if (j.has_output()) add(c, ms, st.slots[size_t(i)], j.pic.width, j.pic.height);
+      }
+      VEP_CHECK(k == nd && nd <= 65535, "mask descriptors miscounted");
+      VEP_HIP(hipMemcpyAsync(st.mask_d, st.mask_h, nd * sizeof(gpu::MaskDesc), hipMemcpyHostToDevice, cs));
+      for (int level = 0; level < top; ++level) gpu::launch_mask(st.mask_d, st.mask_h, int(nd), level, cs);
+    }
+  }
   VEP_HIP(hipEventRecord(st.e1, cs));
   add_time(&Timers::enqueue, double(mono_us() - t_enq0));
 }
 
+bool Worker::snapshot_masks(const std::vector<DecodeJob>& jobs, std::vector<MaskSnap>& out) {
+  out.resize(jobs.size());
+  bool any = false;
+  std::lock_guard<std::mutex> g(cams_mu_);
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    MaskSnap& ms = out[i];
+    const auto& cp = cams_[size_t(jobs[i].cam)];
+    ms.gen = cp ? cp->mask_gen : 0;
+    ms.n = cp ? int(std::min(cp->masks.size(), size_t(mask::kMaxMasks))) : 0;
+    for (int k = 0; k < ms.n; ++k) ms.m[k] = cp->masks[size_t(k)];
+    any = any || ms.n > 0;
+  }
+  return any;
+}
+
+void Worker::set_privacy_masks(int cam, const std::vector<mask::Mask>& masks) {
+  VEP_CHECK(masks.size() <= size_t(mask::kMaxMasks), "mask: at most 8 masks per camera");
+  mask::check_list(masks.data(), int(masks.size()));
+  {
+    std::lock_guard<std::mutex> g(cams_mu_);
+    VEP_CHECK(cam >= 0 && size_t(cam) < cams_.size() && cams_[size_t(cam)], "no such camera");
+    Camera& c = *cams_[size_t(cam)];
+    c.masks = masks;
+    ++c.mask_gen;
+    // Fail closed: what was published under the old list is no longer readable, and publish()
+    // gives up what is in flight (it compares generations under this lock).
+    if (c.ring_) c.ring_->invalidate();
+  }
+  // the detectors' state was learned on other pixels
+  motion_reset(cam);
+  tamper_reset(cam);
+}
+
+std::vector<mask::Mask> Worker::privacy_masks(int cam) {
+  std::lock_guard<std::mutex> g(cams_mu_);
+  VEP_CHECK(cam >= 0 && size_t(cam) < cams_.size() && cams_[size_t(cam)], "no such camera");
+  return cams_[size_t(cam)]->masks;
+}
+
 void Worker::run_cpu(std::vector<DecodeJob>& jobs, std::vector<int>& slots,
-                     std::vector<u32>& err) {
+                     std::vector<u32>& err, const MaskSnap* snaps) {
   err.assign(jobs.size(), 0);
   // one task per camera (a camera's jobs stay in order: they share its surfaces)
   std::vector<std::vector<size_t>> groups;
@@ -2111,16 +2204,20 @@ void Worker::run_cpu(std::vector<DecodeJob>& jobs, std::vector<int>& slots,
     }
   }
   auto run = [&](int g) {
-    for (size_t i : groups[size_t(g)]) run_cpu_job(jobs, slots, err, i);
+    for (size_t i : groups[size_t(g)]) run_cpu_job(jobs, slots, err, i, snaps ? snaps + i : nullptr);
   };
   if (cpu_pool_ && groups.size() > 1) cpu_pool_->parallel_for(int(groups.size()), run);
   else
     for (int g = 0; g < int(groups.size()); ++g) run(g);
 }
 
-void Worker::run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, std::vector<u32>& err, size_t i) {
+void Worker::run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, std::vector<u32>& err, size_t i,
+                         const MaskSnap* snap) {
   {
     Camera& c = *cams_[size_t(jobs[i].cam)];
+    auto apply_masks = [&](u8* bgr, int w, int h) {  // the slot just converted, before anyone reads it
+      if (snap && snap->n > 0) mask::apply_cpu(bgr, size_t(w) * 3, w, h, snap->m, snap->n);
+    };
     const PictureInfo& pi = jobs[i].pic;
     for (int sl = pi.spec_lo; sl < pi.spec_hi && !err[i]; ++sl) {  // speculative headers
       const u8* b = jobs[i].upd.block(sl);
@@ -2140,9 +2237,11 @@ void Worker::run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, 
       // reuse their surfaces (cpu_nv12_to_bgr narrows u16 / 4:2:2 surfaces itself)
       auto convert_history = [&](size_t k) {
         for (const JobOutput& o : jobs[i].outputs)
-          if (o.ring_slot >= 0 && size_t(o.released_by) == k)
+          if (o.ring_slot >= 0 && size_t(o.released_by) == k) {
             cpu_nv12_to_bgr(c.surface.host[size_t(o.slot)], o.pic.crop_left, o.pic.crop_top, o.pic.width, o.pic.height,
                             c.ring_->slot_ptr(o.ring_slot));
+            apply_masks(c.ring_->slot_ptr(o.ring_slot), o.pic.width, o.pic.height);
+          }
       };
       for (size_t k = 0; k < jobs[i].avc.size(); ++k) {
         const auto& pic = jobs[i].avc[k];
@@ -2179,6 +2278,7 @@ void Worker::run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, 
     const HostSurface& src = conv ? narrow : out;
     cpu_nv12_to_bgr(src, jobs[i].pic.crop_left, jobs[i].pic.crop_top,
                     jobs[i].pic.width, jobs[i].pic.height, c.ring_->slot_ptr(slots[i]));
+    apply_masks(c.ring_->slot_ptr(slots[i]), jobs[i].pic.width, jobs[i].pic.height);
     if (opt_.ref_copies) {  // read_image.py:97 tobytes() + :119 SerializeToString()
       const size_t n = size_t(jobs[i].pic.width) * size_t(jobs[i].pic.height) * 3;
       std::vector<u8> bytes(c.ring_->slot_ptr(slots[i]), c.ring_->slot_ptr(slots[i]) + n);
@@ -2257,7 +2357,7 @@ bool stale_picture(Camera& c, int slot, i64 pts, i64 rasl_of) {
   return false;
 }
 
-void Worker::publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, const u32* err) {
+void Worker::publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, const u32* err, const MaskSnap* snaps) {
   trace::Range tr("vep.publish");
   const i64 t = mono_us();
   const i64 wall = now_ms();
@@ -2277,6 +2377,15 @@ void Worker::publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, cons
       cp->pictures.fetch_add(np, std::memory_order_relaxed);
     }
     const bool stale = stale_output(*cp, jobs[i], out && jobs[i].general());
+    // Privacy masks, fail closed: a frame converted under another list than the camera's current
+    // one is not committed (set_privacy_masks bumps mask_gen under this lock).
+    const bool mask_stale = snaps && snaps[i].gen != cp->mask_gen;
+    const bool masked = snaps && snaps[i].n > 0;
+    auto mask_drop = [&](int slot) {
+      cp->ring_->abort(slot);
+      cp->mask_dropped.fetch_add(1, std::memory_order_relaxed);
+      dropped_.fetch_add(1, std::memory_order_relaxed);
+    };
     // Frame history: the job's earlier outputs, oldest first, each under the rules of the newest
     // one below: none from a failed job or while the camera waits for a keyframe (a refresh job's
     // own pictures excepted), none that is stale. The hook fires once per job (here only when the
@@ -2292,9 +2401,12 @@ void Worker::publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, cons
         cp->ring_->abort(o.ring_slot);
         shed_.fetch_add(1, std::memory_order_relaxed);
         cp->shed.fetch_add(1, std::memory_order_relaxed);
+      } else if (mask_stale) {
+        mask_drop(o.ring_slot);
       } else {
         o.meta.decoded_us = t;
         cp->ring_->commit(o.ring_slot, o.meta);
+        if (masked) cp->masked_frames.fetch_add(1, std::memory_order_relaxed);
         cp->decoded.fetch_add(1, std::memory_order_relaxed);
         frames_.fetch_add(1, std::memory_order_relaxed);
         hist_committed = true;
@@ -2354,6 +2466,10 @@ void Worker::publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, cons
       cp->shed.fetch_add(1, std::memory_order_relaxed);
       continue;
     }
+    if (mask_stale) {
+      mask_drop(slots[i]);
+      continue;
+    }
     jobs[i].meta.decoded_us = t;
     if (jobs[i].meta.arrival_ms > 0) {
       const i64 lat = std::max<i64>(0, wall - jobs[i].meta.arrival_ms);
@@ -2363,6 +2479,7 @@ void Worker::publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, cons
       cp->lat_sum_ms.fetch_add(u64(lat), std::memory_order_relaxed);
     }
     cp->ring_->commit(slots[i], jobs[i].meta);
+    if (masked) cp->masked_frames.fetch_add(1, std::memory_order_relaxed);
     cp->out_surface_slot = jobs[i].general() && !jobs[i].out_fields ? jobs[i].target() : -1;
     cp->out_surface_pts = jobs[i].meta.pts;
     cp->decoded.fetch_add(1, std::memory_order_relaxed);
@@ -2418,7 +2535,7 @@ void Worker::complete(Lane& ln, Stage& st) {
   add_time(&Timers::wait, double(mono_us() - t0));
   float ms = 0;
   if (hipEventElapsedTime(&ms, st.e0, st.e1) == hipSuccess) ln.gpu_ms.store(ln.gpu_ms.load() + ms);
-  publish(st.jobs, st.slots, st.err);
+  publish(st.jobs, st.slots, st.err, st.mask_snap.size() == st.jobs.size() ? st.mask_snap.data() : nullptr);
   st.jobs.clear();
   st.slots.clear();
   {
@@ -2619,8 +2736,10 @@ void Worker::launch_async(std::vector<DecodeJob>& jobs) {
   if (jobs.empty()) return;
   if (!dev_.gpu()) {
     std::vector<u32> err;
-    run_cpu(jobs, slots, err);
-    publish(jobs, slots, err.data());
+    std::vector<MaskSnap> snaps;
+    snapshot_masks(jobs, snaps);
+    run_cpu(jobs, slots, err, snaps.data());
+    publish(jobs, slots, err.data(), snaps.data());
     jobs.clear();
     return;
   }

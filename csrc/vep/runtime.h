@@ -27,6 +27,7 @@
 #include "ioloop.h"
 #include "gpu.h"
 #include "motion.h"
+#include "mask.h"
 #include "tamper.h"
 #include "pool.h"
 #include "vcn.h"
@@ -83,6 +84,10 @@ class FrameRing {
   void commit(int slot, FrameMeta meta);
   // Release a slot from begin_write() without publishing (frame dropped after a failed check).
   void abort(int slot);
+  // Every committed frame stops being readable (the camera's privacy masks changed): latest, range
+  // and still_valid fail for them, so a reader in the middle of a copy retries or gets nothing.
+  // published() keeps counting; slots being written are left to their writer.
+  void invalidate();
   // reader side: newest committed frame with seq > after (false if none)
   bool latest(i64 after, FrameMeta* meta, int* slot) const;
   // The newest max_count committed frames with seq > after_seq (XRANGE / XREVRANGE analog):
@@ -371,6 +376,13 @@ class Camera {
   // after motion's members, for the same reason.)
   std::atomic<u64> tamper_evaluations{0}, tamper_frames{0};
   TamperState tamper;
+  // privacy masks (Worker::set_privacy_masks; last again). The list and its generation change
+  // under the worker's camera lock only; a frame converted under an older generation is never
+  // committed (Worker::publish).
+  std::vector<mask::Mask> masks;
+  u64 mask_gen = 0;
+  std::atomic<u64> masked_frames{0};  // committed frames that had at least one mask
+  std::atomic<u64> mask_dropped{0};   // frames given up because the list changed while they were in flight
 };
 
 struct WorkerOptions {
@@ -536,6 +548,13 @@ class Worker {
   bool tamper_set_reference(int cam);
   // Drops the camera's reference and its stored answer.
   void tamper_reset(int cam);
+  // Privacy masks (mask.h, docs/PRIVACY.md): the camera's list, applied in its ring slot after the
+  // BGR24 conversion and before the commit, so no consumer of the ring sees an unmasked pixel of a
+  // masked region. set_privacy_masks throws on an invalid list; an empty list clears. A change
+  // makes the camera's committed frames unreadable (FrameRing::invalidate), gives up the frames in
+  // flight when they complete, and resets the camera's motion model and tamper state.
+  void set_privacy_masks(int cam, const std::vector<mask::Mask>& masks);
+  std::vector<mask::Mask> privacy_masks(int cam);
   void set_wall_max_tiles(int n);
   int wall_max_tiles() const { return wall_max_tiles_.load(); }
   // Frame history: the newest max_count (0 = the camera's depth) frames with seq > after, copied
@@ -616,6 +635,11 @@ class Worker {
   std::vector<u64> avc_profile();
 
  private:
+  struct MaskSnap {  // a camera's privacy masks as a batch saw them
+    u64 gen = 0;
+    int n = 0;
+    mask::Mask m[mask::kMaxMasks];
+  };
   struct Stage {  // one pinned + device staging pair and the batch that uses it
     u8* h = nullptr;
     u8* d = nullptr;
@@ -632,6 +656,12 @@ class Worker {
     u32* err = nullptr;        // pinned per-job check flags (written by the kernel)
     const u32* err_dev = nullptr;
     size_t err_cap = 0;
+    // privacy masks: per job the camera's list and generation at launch; the batch's descriptors
+    // (pinned + device, grown to the largest batch seen)
+    std::vector<MaskSnap> mask_snap;
+    gpu::MaskDesc* mask_h = nullptr;
+    gpu::MaskDesc* mask_d = nullptr;
+    size_t mask_cap = 0;
   };
   void loop();
   void ensure_surface(Camera& c, const PictureInfo& pi, int slots, int bd = 8, bool weave = false, int cf = 1);
@@ -665,10 +695,16 @@ class Worker {
   void merge_queued(Lane& ln, Batch& b);
   void launch_on(Lane& ln, Batch&& b);  // reuse the lane's oldest stage for batch b
   void drain_lanes();
-  void run_cpu(std::vector<DecodeJob>& jobs, std::vector<int>& slots, std::vector<u32>& err);
+  void run_cpu(std::vector<DecodeJob>& jobs, std::vector<int>& slots, std::vector<u32>& err,
+               const MaskSnap* snaps = nullptr);
   // err[i] != 0: job i failed its speculative-header check (dropped, camera waits for the
   // next keyframe)
-  void publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, const u32* err = nullptr);
+  // snaps (one per job, or null): the masks the batch was converted under; a job whose camera's
+  // list has changed since is not committed
+  void publish(std::vector<DecodeJob>& jobs, std::vector<int>& slots, const u32* err = nullptr,
+               const MaskSnap* snaps = nullptr);
+  // The jobs' cameras' masks now (takes the camera lock). False: no camera of the batch has any.
+  bool snapshot_masks(const std::vector<DecodeJob>& jobs, std::vector<MaskSnap>& out);
   void complete(Lane& ln, Stage& st);
   void complete_locked();
   void copy_slot(FrameRing& ring, int slot, u8* dst);  // one ring slot -> host memory
@@ -692,7 +728,8 @@ class Worker {
   // CPU backend: reconstruction + conversion of a batch's cameras in parallel (the reference runs
   // one decoder per camera container); the host domain's CPU share threads
   std::unique_ptr<ThreadPool> cpu_pool_;
-  void run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, std::vector<u32>& err, size_t i);
+  void run_cpu_job(std::vector<DecodeJob>& jobs, std::vector<int>& slots, std::vector<u32>& err, size_t i,
+                   const MaskSnap* snap = nullptr);
 
  public:
   // host-side launch path timers (µs, cumulative): where a batch's CPU time goes (summed over

@@ -7,6 +7,7 @@
   list | frame | annotate | storage | proxy   gRPC clients (examples/*.py analogs)
   motion    REST client of the motion detector (--device NAME --rest host:port [--watch])
   tamper    REST client of the tamper detector (--device NAME --rest host:port [--watch] [--set-reference])
+  privacy   REST client of a camera's privacy masks (--device NAME --rest host:port [--set JSON | --clear])
 """
 from __future__ import annotations
 
@@ -239,6 +240,52 @@ def cmd_tamper(a):
         time.sleep(a.interval)
 
 
+def format_privacy(r: dict) -> str:
+    """What ``vep privacy`` prints: one line per mask, then the outputs the masks do not cover."""
+    lines = []
+    for k, m in enumerate(r.get("masks") or []):
+        how = f"pixelate block {m['block']}" if m["mode"] == "pixelate" else f"fill bgr ({m['b']},{m['g']},{m['r']})"
+        lines.append(f"mask {k}: x {m['x0']}..{m['x1']} y {m['y0']}..{m['y1']} (1/10000) {how}")
+    if not lines:
+        lines.append("no masks")
+    un = r.get("unmasked_outputs") or []
+    lines.append("unmasked outputs: " + (", ".join(un) if un else "none"))
+    return "\n".join(lines)
+
+
+def cmd_privacy(a):
+    """REST client of ``/api/v1/process/{name}/privacy``: ``--set`` replaces the camera's list with
+    a JSON list of masks, ``--clear`` removes it; the list in force is printed afterwards."""
+    import json
+    import urllib.error
+    import urllib.parse
+    import urllib.request
+
+    if a.set is not None and a.clear:
+        raise SystemExit("privacy: --set and --clear exclude each other")
+    url = f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/privacy"
+    try:
+        if a.set is not None:
+            try:
+                masks = json.loads(a.set)
+            except ValueError as e:
+                raise SystemExit(f"privacy: --set is not JSON: {e}")
+            req = urllib.request.Request(url, data=json.dumps(masks).encode(), method="PUT",
+                                         headers={"Content-Type": "application/json"})
+            urllib.request.urlopen(req, timeout=10).close()
+        elif a.clear:
+            urllib.request.urlopen(urllib.request.Request(url, method="DELETE"), timeout=10).close()
+        with urllib.request.urlopen(url, timeout=10) as r:
+            print(format_privacy(json.loads(r.read())), flush=True)
+    except urllib.error.HTTPError as e:
+        detail = ""
+        try:
+            detail = ": " + json.loads(e.read()).get("message", "")
+        except ValueError:
+            pass
+        raise SystemExit(f"privacy: HTTP {e.code} for {a.device!r}{detail}")
+
+
 def cmd_bench(a, rest):
     """``vep bench ...`` = the repo's bench.py (headline benchmark) with the same flags."""
     import subprocess
@@ -327,6 +374,14 @@ def build_parser():
     t.add_argument("--set-reference", action="store_true", help="first declare the camera's newest frame normal")
     t.add_argument("--interval", type=float, default=0.1, help="seconds between polls")
     t.set_defaults(fn=cmd_tamper)
+
+    pv = sub.add_parser("privacy", help="show, set or clear a camera's privacy masks (REST)")
+    pv.add_argument("--device", required=True)
+    pv.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API")
+    pv.add_argument("--set", default=None, metavar="JSON",
+                    help='a JSON list of masks, e.g. \'[{"x0":0,"y0":0,"x1":2500,"y1":10000,"mode":"pixelate","block":16}]\'')
+    pv.add_argument("--clear", action="store_true", help="remove the camera's masks")
+    pv.set_defaults(fn=cmd_privacy)
 
     b = sub.add_parser("bench", help="run bench.py (flags passed through, e.g. --codec h265)")
     b.set_defaults(fn=None)

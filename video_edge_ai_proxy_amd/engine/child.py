@@ -41,7 +41,8 @@ log = logging.getLogger("vep.child")
 # methods of Hub a parent may call
 EXPORTED = {"start_camera", "stop_camera", "state", "logs", "touch", "set_proxy", "proxy", "host_plane",
             "latest_frame_bytes", "latest_frame", "latest_jpeg", "latest_scaled", "wait_decoded", "has",
-            "motion", "motion_reset", "tamper", "tamper_reference", "tamper_reset"}
+            "motion", "motion_reset", "tamper", "tamper_reference", "tamper_reset",
+            "set_privacy_masks", "privacy_masks"}
 
 
 class RankGroup:

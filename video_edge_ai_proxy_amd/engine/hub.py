@@ -17,6 +17,7 @@ import time
 from dataclasses import dataclass, field
 from typing import Optional
 
+from .. import privacy
 from .._native import gpu_count, native
 from ..config import Config, parse_tile
 from ..utils import now_ms
@@ -136,7 +137,10 @@ class Hub:
         return self.cfg.buffer.on_disk_folder or os.path.join(self.cfg.data_dir, "archive")
 
     def start_camera(self, name: str, rtsp: str, rtmp: str = "", disk_path: Optional[str] = None,
-                     timeout_ms: int = 5000, reconnect_delay_ms: int = 1000) -> CameraHandle:
+                     timeout_ms: int = 5000, reconnect_delay_ms: int = 1000, masks=None) -> CameraHandle:
+        """``masks``: the camera's privacy masks (:mod:`..privacy`), in force before the session
+        starts, so the first frame is already masked."""
+        native_masks = privacy.to_native(masks)  # (ValueError before anything is created)
         with self._lock:
             if name in self.cameras:
                 raise CameraExists(f"camera {name!r} already running")
@@ -144,6 +148,8 @@ class Hub:
             w = self.workers[wi]
             cam = w.add_camera(name, self.cfg.ring_slots, self.cfg.history_depth)
             w.set_idle_cutoff_ms(cam, int(self.cfg.gpu.idle_cutoff_ms))
+            if native_masks:
+                w.set_privacy_masks(cam, native_masks)
             h = CameraHandle(name, wi, cam, rtsp, rtmp)
             disk = self.archive_dir() if disk_path is None else disk_path
             h.session = native.IngestSession(w, cam, name, rtsp, rtmp or "", disk or "",
@@ -527,6 +533,30 @@ class Hub:
         """Drop the camera's reference and its stored answer."""
         w, cam = self.worker_of(name)
         w.tamper_reset(cam)
+
+    # ------------------------------------------------------------------ privacy masks
+    def set_privacy_masks(self, name: str, masks) -> None:
+        """Replace the camera's privacy masks (:mod:`..privacy`; ``None`` or ``[]`` clears them;
+        ``ValueError`` on a bad list). They are written into the ring slot on the GPU before a frame
+        is published, so every consumer of the ring sees them. Fail closed: the frames published
+        under the old list stop being readable at once, frames in flight are given up, and with a
+        frame bus the camera's entry is taken off the bus before the change and put back after it
+        (a new entry generation with empty slots), so the serving processes drop their copies."""
+        native_masks = privacy.to_native(masks)
+        with self._lock:
+            h = self.handle(name)
+            w = self.workers[h.worker_index]
+            if self.bus:
+                self.bus[h.worker_index].remove(h.cam)
+            try:
+                w.set_privacy_masks(h.cam, native_masks)
+            finally:
+                if self.bus:
+                    self.bus[h.worker_index].add(h.cam, name)
+
+    def privacy_masks(self, name: str) -> list:
+        w, cam = self.worker_of(name)
+        return privacy.from_native(w.privacy_masks(cam))
 
     def history(self, name: str, after: int = 0, count: int = 0) -> list:
         """``[(meta, ndarray)]`` of the camera's newest ``count`` (0 = ``buffer.in_memory``) frames

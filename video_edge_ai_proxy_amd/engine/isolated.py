@@ -47,6 +47,7 @@ from multiprocessing.connection import Client
 from typing import Optional
 
 from ..config import Config
+from .. import privacy
 from .hub import CameraExists, CameraHandle, CameraNotFound, new_bus_tag, place_camera
 from .shm import ShmReader, remove_segments
 
@@ -314,7 +315,7 @@ class ProcessHub:
                 mine = [n for n, h in self.cameras.items() if h.worker_index == i]
                 for n in mine:  # re-add before the fresh child takes calls (until then: restarting)
                     spec = self._specs[n]
-                    res = child.call("start_camera", *spec["args"])
+                    res = child.call("start_camera", *spec["args"], masks=spec.get("masks") or None)
                     self.cameras[n].cam = res["cam"]
                     if self._proxy.get(n):
                         child.call("set_proxy", n, True)
@@ -340,17 +341,18 @@ class ProcessHub:
         return self.cfg.buffer.on_disk_folder or os.path.join(self.cfg.data_dir, "archive")
 
     def start_camera(self, name: str, rtsp: str, rtmp: str = "", disk_path: Optional[str] = None,
-                     timeout_ms: int = 5000, reconnect_delay_ms: int = 1000) -> CameraHandle:
+                     timeout_ms: int = 5000, reconnect_delay_ms: int = 1000, masks=None) -> CameraHandle:
+        masks = privacy.normalize_list(masks)  # (kept with the spec: a fresh child starts the camera masked)
         with self._lock:
             if name in self.cameras:
                 raise CameraExists(f"camera {name!r} already running")
             wi = place_camera(name, self._loads(), self.cfg.gpu.placement)
             args = (name, rtsp, rtmp or "", self.archive_dir() if disk_path is None else disk_path, timeout_ms,
                     reconnect_delay_ms)
-            res = self._children[wi].call("start_camera", *args)
+            res = self._children[wi].call("start_camera", *args, masks=masks or None)
             h = CameraHandle(name, wi, res["cam"], rtsp, rtmp)
             self.cameras[name] = h
-            self._specs[name] = {"args": args}
+            self._specs[name] = {"args": args, "masks": masks}
             return h
 
     def stop_camera(self, name: str) -> None:
@@ -609,6 +611,17 @@ class ProcessHub:
 
     def tamper_reset(self, name: str) -> None:
         self._call(name, "tamper_reset")
+
+    def set_privacy_masks(self, name: str, masks) -> None:
+        masks = privacy.normalize_list(masks)
+        with self._lock:
+            self.handle(name)
+            # the spec first: a child that dies during the call comes back with the new list
+            self._specs[name]["masks"] = masks
+            self._call(name, "set_privacy_masks", masks)
+
+    def privacy_masks(self, name: str) -> list:
+        return self._call(name, "privacy_masks")
 
     # A wall reads the ring slots of many cameras in one launch; the rings live in the worker
     # processes, one per GPU, so it is served only by the in-process hub (gpu.isolation: thread).

@@ -19,6 +19,9 @@
 * :func:`tamper_stats` / :func:`tamper_stats_batch` — the luma histogram, per-cell luma sums and
   per-cell focus energy of BGR24 pictures, one or many in a single launch (the kernel behind
   ``/tamper``), byte-identical with :func:`tamper_stats_reference`.
+* :func:`privacy_mask` / :func:`privacy_mask_batch` — fill or pixelate rectangles of BGR24
+  pictures in place, one launch per level of overlap for all pictures (the kernel that masks a
+  camera's ring slot before it is published), byte-identical with :func:`privacy_mask_reference`.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -611,6 +614,66 @@ def tamper_stats_reference(bgr: torch.Tensor, cell: int = 32):
     cell = _check_tamper_cell(cell)
     _check_bgr(bgr)
     return tuple(torch.from_numpy(a.astype("int64")) for a in native.tamper_stats_cpu(bgr.detach().cpu().numpy(), cell))
+
+
+def _check_mask_picture(bgr, what: str = "bgr") -> tuple:
+    if not isinstance(bgr, torch.Tensor) or bgr.dtype != torch.uint8:
+        raise ValueError(f"{what} must be a uint8 tensor")
+    if bgr.dim() != 3 or bgr.shape[2] != 3 or bgr.shape[0] < 1 or bgr.shape[1] < 1:
+        raise ValueError(f"{what} must be [H, W, 3], got {tuple(bgr.shape)}")
+    if bgr.shape[0] > 65535 or bgr.shape[1] > 65535:
+        raise ValueError(f"{what} is at most 65535 x 65535")
+    if not bgr.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return int(bgr.shape[1]), int(bgr.shape[0])
+
+
+def privacy_mask_batch(tensors, masks_per_tensor):
+    """Privacy masks (csrc/vep/mask.h; the dicts of :mod:`..privacy`) applied IN PLACE to a list of
+    contiguous ``[H, W, 3]`` BGR24 device tensors of any sizes on one device, each with its own
+    list (an empty list leaves its picture alone): one kernel launch per level for all pictures,
+    so one launch when no two masks of a picture overlap. Returns the tensors. Byte-identical with
+    :func:`privacy_mask_reference`. No CPU fallback."""
+    from .. import privacy
+
+    tensors = list(tensors)
+    masks_per_tensor = list(masks_per_tensor)
+    if len(tensors) != len(masks_per_tensor):
+        raise ValueError("masks_per_tensor must hold one list per tensor")
+    device, work = None, []
+    for k, (bgr, masks) in enumerate(zip(tensors, masks_per_tensor)):
+        w, h = _check_mask_picture(bgr, f"tensors[{k}]")
+        if not bgr.is_cuda:
+            raise ValueError("bgr must be a device tensor")
+        if device is None:
+            device = bgr.device
+        if bgr.device != device:
+            raise ValueError("the pictures must live on one device")
+        work.append((bgr.data_ptr(), w, h, privacy.to_native(masks)))
+    require_gpu()
+    if work and any(wk[3] for wk in work):
+        with torch.cuda.device(device):
+            native.mask_apply(work, int(torch.cuda.current_stream(device).cuda_stream))
+    return tensors
+
+
+def privacy_mask(bgr: torch.Tensor, masks):
+    """The privacy masks of ``masks`` applied in list order, IN PLACE, to a contiguous ``[H, W, 3]``
+    BGR24 device tensor, which is returned. ``fill`` sets a rect to a colour; ``pixelate`` replaces
+    every ``block x block`` block of the rect (anchored at its corner, edge blocks partial) by its
+    rounded mean, in integers. Bytes outside the rects are not written."""
+    return privacy_mask_batch([bgr], [masks])[0]
+
+
+def privacy_mask_reference(bgr: torch.Tensor, masks) -> torch.Tensor:
+    """The CPU implementation's result for the same picture (host or device tensor): a new host
+    tensor, the byte-exact oracle of :func:`privacy_mask`."""
+    from .. import privacy
+
+    _check_mask_picture(bgr)
+    out = bgr.detach().cpu().clone().numpy()
+    native.mask_apply_cpu(out, privacy.to_native(masks))
+    return torch.from_numpy(out)
 
 
 # ----------------------------------------------------------------------------- references

@@ -35,6 +35,11 @@ class HubCollector:
         tev = CounterMetricFamily("vep_tamper_evaluations", "frames evaluated by the tamper detector", labels=labels)
         tfr = CounterMetricFamily("vep_tamper_frames_tampered", "evaluated frames flagged as tampered",
                                   labels=labels)
+        pmf = CounterMetricFamily("vep_privacy_masked_frames", "published frames that had at least one privacy mask",
+                                  labels=labels)
+        pdr = CounterMetricFamily("vep_privacy_dropped_frames",
+                                  "frames given up because the privacy masks changed while they were in flight",
+                                  labels=labels)
         for name in list(self.hub.cameras):
             try:
                 st = self.hub.state(name)
@@ -51,6 +56,8 @@ class HubCollector:
             mfr.add_metric(lv, st.get("motion_frames", 0))
             tev.add_metric(lv, st.get("tamper_evaluations", 0))
             tfr.add_metric(lv, st.get("tamper_frames_tampered", 0))
+            pmf.add_metric(lv, st.get("masked_frames", 0))
+            pdr.add_metric(lv, st.get("mask_dropped", 0))
             hist, bounds = st.get("latency_hist"), st.get("latency_bounds_ms")
             if hist and bounds:
                 acc, buckets = 0, []
@@ -58,7 +65,7 @@ class HubCollector:
                     acc += c
                     buckets.append((str(b / 1000.0) if b != float("inf") else "+Inf", acc))
                 lat.add_metric(lv, buckets, st.get("latency_sum_ms", 0) / 1000.0)
-        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr, tev, tfr)
+        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr, tev, tfr, pmf, pdr)
         wb = CounterMetricFamily("vep_worker_batches", "batched decode launches", labels=["device"])
         wf = CounterMetricFamily("vep_worker_frames", "frames decoded by the worker", labels=["device"])
         wg = CounterMetricFamily("vep_worker_gpu_ms", "GPU time of decode batches (ms)", labels=["device"])

@@ -392,6 +392,35 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return err(404, f"process {name!r} not found")
         return Response(status_code=204)
 
+    # ---- privacy masks: written into the ring slot before a frame is published (docs/PRIVACY.md)
+    @app.get("/api/v1/process/{name}/privacy")
+    def privacy_get(name: str):
+        try:
+            return {"masks": pm.privacy_masks(name), "unmasked_outputs": pm.unmasked_outputs(name)}
+        except (KeyError, ProcessError):
+            return err(404, f"process {name!r} not found")
+
+    @app.put("/api/v1/process/{name}/privacy")
+    async def privacy_put(name: str, request: Request):
+        try:
+            masks = json.loads(await request.body() or b"null")
+            if not isinstance(masks, list):
+                raise ValueError("a JSON list of masks expected")
+            pm.set_privacy_masks(name, masks)
+        except ValueError as e:  # (invalid JSON included)
+            return err(422, str(e))
+        except (KeyError, ProcessError):
+            return err(404, f"process {name!r} not found")
+        return Response(status_code=204)
+
+    @app.delete("/api/v1/process/{name}/privacy")
+    def privacy_delete(name: str):
+        try:
+            pm.set_privacy_masks(name, [])
+        except (KeyError, ProcessError):
+            return err(404, f"process {name!r} not found")
+        return Response(status_code=204)
+
     @app.get("/api/v1/tamper")
     def tamper_many(names: str | None = None, grid: int = 0, wake: int = 1):
         if grid not in (0, 1) or wake not in (0, 1):

@@ -10,6 +10,9 @@ Reference parity: server/services/rtsp_process_manager.go —
   * ``List`` (:236-280): Info for every record; self-heals records whose session vanished.
   * ``ListStream`` (:191-233): like List, skipping missing sessions, honouring cancellation.
   * ``UpdateProcessInfo`` (:338-356).
+New: a camera's privacy masks (``privacy.py``) are stored under ``/privacymasks/<name>``, a prefix
+of their own (the reference-shaped process record stays as it is): :meth:`start` and :meth:`restore`
+start the camera under the stored list, :meth:`stop` deletes it.
 New: :meth:`restore` re-spawns every stored camera at boot (the reference relied on Docker's
 ``restart: always`` for that — SURVEY.md §5 checkpoint/resume row).
 """
@@ -25,12 +28,14 @@ from typing import Callable, Optional
 from ..engine.hub import CameraExists, CameraNotFound, Hub
 from ..models import (DEFAULT_IMAGE_TAG, PREFIX_RTSP_PROCESS, ContainerState, DockerLogs,
                       RTMPStreamStatus, StreamProcess)
+from .. import privacy
 from ..utils import now_ms
 from .storage import KeyNotFound, Storage
 
 log = logging.getLogger("vep.process")
 
 _NAME = re.compile(r"^[A-Za-z0-9_.\-]+$")
+PREFIX_PRIVACY_MASKS = "/privacymasks/"
 
 
 class ProcessError(RuntimeError):
@@ -72,6 +77,52 @@ class ProcessManager:
                 log.error("corrupt process record skipped: %s", e)
         return out
 
+    def stored_masks(self, name: str) -> list:
+        """The privacy masks stored for ``name`` ([] when none; a corrupt entry counts as none and
+        is logged: the operator has to set the list again)."""
+        try:
+            return privacy.normalize_list(json.loads(self.storage.get(PREFIX_PRIVACY_MASKS, name)))
+        except KeyNotFound:
+            return []
+        except (ValueError, TypeError) as e:
+            log.error("corrupt privacy mask list of %s ignored: %s", name, e)
+            return []
+
+    def set_privacy_masks(self, name: str, masks) -> list:
+        """Replace a running camera's masks (``ValueError`` on a bad list) and store them."""
+        masks = privacy.normalize_list(masks)
+        with self._lock:
+            if not self.hub.has(name):
+                raise ProcessNotFound(f"process {name!r} not found")
+            # stored first: a crash between the two steps restarts the camera masked
+            if masks:
+                self.storage.put(PREFIX_PRIVACY_MASKS, name, json.dumps(masks).encode())
+            self.hub.set_privacy_masks(name, masks)
+            if not masks:
+                self.storage.delete(PREFIX_PRIVACY_MASKS, name)
+        return masks
+
+    def privacy_masks(self, name: str) -> list:
+        if not self.hub.has(name):
+            raise ProcessNotFound(f"process {name!r} not found")
+        return self.hub.privacy_masks(name)
+
+    def unmasked_outputs(self, name: str) -> list:
+        """The active outputs of this camera that the masks do NOT cover: ``rtmp`` (the compressed
+        stream passed through), ``archive`` (the per-GOP MP4 of the compressed stream) and
+        ``consumer_batch`` (the letterbox, which reads the decoder surface)."""
+        out = []
+        try:
+            if self.hub.handle(name).rtmp and self.hub.proxy(name):
+                out.append("rtmp")
+        except KeyError:
+            raise ProcessNotFound(f"process {name!r} not found")
+        if self.hub.archive_dir():
+            out.append("archive")
+        if int(self.hub.cfg.gpu.letterbox_size) > 0:
+            out.append("consumer_batch")
+        return out
+
     # ------------------------------------------------------------------ API
     def start(self, sp: StreamProcess) -> StreamProcess:
         if not sp.rtsp_endpoint:
@@ -86,7 +137,8 @@ class ProcessManager:
                 raise ProcessError(f"process {sp.name!r} already exists")
             sp.image_tag = sp.image_tag or DEFAULT_IMAGE_TAG
             try:
-                h = self.hub.start_camera(sp.name, sp.rtsp_endpoint, sp.rtmp_endpoint or "")
+                h = self.hub.start_camera(sp.name, sp.rtsp_endpoint, sp.rtmp_endpoint or "",
+                                          masks=self.stored_masks(sp.name) or None)
             except (CameraExists, RuntimeError, ValueError) as e:
                 raise ProcessError(str(e))
             if sp.rtmp_endpoint:
@@ -114,6 +166,7 @@ class ProcessManager:
                 except ProcessNotFoundDatastore:
                     raise ProcessNotFound(f"process {name!r} not found")
             self.storage.delete(PREFIX_RTSP_PROCESS, name)
+            self.storage.delete(PREFIX_PRIVACY_MASKS, name)
 
     def info(self, name: str, persist: bool = True) -> StreamProcess:
         if not self.hub.has(name):
@@ -164,7 +217,8 @@ class ProcessManager:
             if self.hub.has(rec.name):
                 continue
             try:
-                self.hub.start_camera(rec.name, rec.rtsp_endpoint, rec.rtmp_endpoint or "")
+                self.hub.start_camera(rec.name, rec.rtsp_endpoint, rec.rtmp_endpoint or "",
+                                      masks=self.stored_masks(rec.name) or None)
                 if rec.rtmp_stream_status and rec.rtmp_stream_status.streaming and rec.rtmp_endpoint:
                     self.hub.set_proxy(rec.name, True)
                 started.append(rec.name)
