@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask tsan-scratch asan-scratch scratch-selftest tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -118,6 +118,35 @@ $(ASAN_DIR)/mask_selftest: csrc/vep/mask.cpp csrc/tests/mask_selftest.cpp csrc/v
 
 asan-mask: $(ASAN_DIR)/mask_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/mask_selftest
+
+# The scratch pool's locking alone (csrc/tests/scratch_selftest.cpp on vep/scratch.h, which
+# includes no HIP header): a stand-alone host program, no GPU. Under ThreadSanitizer, under
+# AddressSanitizer + UndefinedBehaviorSanitizer, and un-instrumented (default CPU suite).
+SCRATCH_TEST = csrc/tests/scratch_selftest.cpp csrc/vep/scratch.h
+
+$(TSAN_DIR)/scratch_selftest: $(SCRATCH_TEST)
+	mkdir -p $(TSAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=thread \
+	  -Icsrc csrc/tests/scratch_selftest.cpp -o $@ -lpthread
+
+$(ASAN_DIR)/scratch_selftest: $(SCRATCH_TEST)
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc csrc/tests/scratch_selftest.cpp -o $@ -lpthread
+
+build/selftest/scratch_selftest: $(SCRATCH_TEST)
+	mkdir -p build/selftest
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Icsrc csrc/tests/scratch_selftest.cpp -o $@ -lpthread
+
+tsan-scratch: $(TSAN_DIR)/scratch_selftest
+	cd /tmp && TSAN_OPTIONS="halt_on_error=1" $(CURDIR)/$(TSAN_DIR)/scratch_selftest
+
+asan-scratch: $(ASAN_DIR)/scratch_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/scratch_selftest
+
+scratch-selftest: build/selftest/scratch_selftest
+	cd /tmp && $(CURDIR)/build/selftest/scratch_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

@@ -27,6 +27,20 @@
 namespace py = pybind11;
 using namespace vep;
 
+// Scratch of the ops on caller-owned device buffers: one process-wide pool per device and op,
+// created under a lock on first use, never freed, then used without the lock.
+template <class Pool>
+static Pool& pool_of_current_device() {
+  static std::mutex mu;
+  static std::map<int, Pool*>* pools = new std::map<int, Pool*>();  // (never freed)
+  int dev = 0;
+  VEP_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> g(mu);
+  Pool*& slot = (*pools)[dev];
+  if (!slot) slot = new Pool();
+  return *slot;
+}
+
 static py::bytes to_bytes(const u8* p, size_t n) {
   return py::bytes(reinterpret_cast<const char*>(p), n);
 }
@@ -2088,67 +2102,51 @@ PYBIND11_MODULE(_vep, m) {
   m.def("compose_wall",
         [](const std::vector<std::tuple<uintptr_t, int, int>>& tiles, int cols, int tw, int th, uintptr_t canvas,
            uintptr_t stream) {
-          static std::mutex mu;
-          static std::map<int, gpu::ScalePool*>* pools = new std::map<int, gpu::ScalePool*>();  // (never freed)
           const int n = int(tiles.size());
           VEP_CHECK(n >= 1 && n <= 65535, "compose_wall: 1..65535 tiles expected");
           VEP_CHECK(tw >= 1 && th >= 1 && tw <= 65535 && th <= 65535 && cols <= 65535,
                     "compose_wall: tile sides must be 1..65535");
           VEP_CHECK(cols >= 0 || n == 1, "resize_area: one picture expected");
           py::gil_scoped_release r;
-          int dev = 0;
-          VEP_HIP(hipGetDevice(&dev));
-          gpu::ScalePool* pool;
-          {
-            std::lock_guard<std::mutex> g(mu);
-            gpu::ScalePool*& slot = (*pools)[dev];
-            if (!slot) slot = new gpu::ScalePool();
-            pool = slot;
-          }
+          gpu::ScalePool& pool = pool_of_current_device<gpu::ScalePool>();
           const scale::Wall g = cols < 0 ? scale::Wall{1, 1, tw, th} : scale::wall(n, cols, tw, th);
           VEP_CHECK(i64(g.cols) * tw <= 65535 && i64(g.rows) * th <= 65535, "wall: canvas sides must be <= 65535");
           hipStream_t s = reinterpret_cast<hipStream_t>(stream);
           const int cells = g.cols * g.rows;  // (the cells past the last tile are background too)
-          gpu::ScalePool::Set* set = pool->acquire(0, cells, 0);
-          try {
-            for (int t = 0; t < cells; ++t) {
-              gpu::ScaleDesc d{};
-              d.dst = reinterpret_cast<u8*>(canvas);
-              d.dst_pitch = u32(g.w) * 3;
-              d.src = t < n ? reinterpret_cast<const u8*>(std::get<0>(tiles[size_t(t)])) : nullptr;
-              if (cols >= 0) {
-                d.cx = (t % g.cols) * tw;
-                d.cy = (t / g.cols) * th;
-                d.cw = tw;
-                d.ch = th;
-              }
-              if (d.src) {
-                d.sw = std::get<1>(tiles[size_t(t)]);
-                d.sh = std::get<2>(tiles[size_t(t)]);
-                VEP_CHECK(d.sw >= 1 && d.sh >= 1 && d.sw <= 65535 && d.sh <= 65535, "scale: source size out of range");
-                d.src_pitch = u32(d.sw) * 3;
-                if (cols >= 0) {
-                  const scale::Placement p = scale::place(t, g.cols, tw, th, d.sw, d.sh);
-                  d.dx = p.x;
-                  d.dy = p.y;
-                  d.ow = p.w;
-                  d.oh = p.h;
-                } else {
-                  d.ow = tw;
-                  d.oh = th;
-                }
-              }
-              gpu::check_scale(d, g.w, g.h);
-              set->h_descs[t] = d;
+          gpu::ScalePool::Lease set = pool.acquire();
+          set->reserve(0, cells, 0);
+          for (int t = 0; t < cells; ++t) {
+            gpu::ScaleDesc d{};
+            d.dst = reinterpret_cast<u8*>(canvas);
+            d.dst_pitch = u32(g.w) * 3;
+            d.src = t < n ? reinterpret_cast<const u8*>(std::get<0>(tiles[size_t(t)])) : nullptr;
+            if (cols >= 0) {
+              d.cx = (t % g.cols) * tw;
+              d.cy = (t / g.cols) * th;
+              d.cw = tw;
+              d.ch = th;
             }
-            gpu::ScalePool::run(*set, cells, s);
-            VEP_HIP(hipEventRecord(set->ev, s));  // the descriptors are reused by the next call
-            VEP_HIP(hipEventSynchronize(set->ev));
-          } catch (...) {
-            pool->release(set);
-            throw;
+            if (d.src) {
+              d.sw = std::get<1>(tiles[size_t(t)]);
+              d.sh = std::get<2>(tiles[size_t(t)]);
+              VEP_CHECK(d.sw >= 1 && d.sh >= 1 && d.sw <= 65535 && d.sh <= 65535, "scale: source size out of range");
+              d.src_pitch = u32(d.sw) * 3;
+              if (cols >= 0) {
+                const scale::Placement p = scale::place(t, g.cols, tw, th, d.sw, d.sh);
+                d.dx = p.x;
+                d.dy = p.y;
+                d.ow = p.w;
+                d.oh = p.h;
+              } else {
+                d.ow = tw;
+                d.oh = th;
+              }
+            }
+            gpu::check_scale(d, g.w, g.h);
+            set->h_descs.p[t] = d;
           }
-          pool->release(set);
+          set->run(cells, s);
+          VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
         },
         py::arg("tiles"), py::arg("cols"), py::arg("tile_width"), py::arg("tile_height"), py::arg("canvas"),
         py::arg("stream"));
@@ -2216,51 +2214,35 @@ PYBIND11_MODULE(_vep, m) {
   m.def("motion_update",
         [](const std::vector<std::tuple<uintptr_t, int, int, uintptr_t, uintptr_t, int, uintptr_t>>& pics, int cell,
            int threshold, int learn_shift, uintptr_t stream) {
-          static std::mutex mu;
-          static std::map<int, gpu::MotionPool*>* pools = new std::map<int, gpu::MotionPool*>();  // (never freed)
           const int n = int(pics.size());
           VEP_CHECK(n >= 1 && n <= 65535, "motion_update: 1..65535 pictures expected");
           motion::check_update_params(cell, threshold, learn_shift);
           py::gil_scoped_release r;
-          int dev = 0;
-          VEP_HIP(hipGetDevice(&dev));
-          gpu::MotionPool* pool;
-          {
-            std::lock_guard<std::mutex> g(mu);
-            gpu::MotionPool*& slot = (*pools)[dev];
-            if (!slot) slot = new gpu::MotionPool();
-            pool = slot;
-          }
           hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-          gpu::MotionPool::Set* set = pool->acquire(n, 0);
-          try {
-            for (int k = 0; k < n; ++k) {
-              const auto& [src, w, h, bg_in, bg_out, bg_pitch, counts] = pics[size_t(k)];
-              VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "motion: picture size must be 1..65535");
-              VEP_CHECK(bg_pitch >= w && bg_pitch <= 65536, "motion: background pitch out of range");
-              gpu::MotionDesc d{};
-              d.src = reinterpret_cast<const u8*>(src);
-              d.src_pitch = u32(w) * 3;
-              d.bg_in = reinterpret_cast<const u16*>(bg_in);
-              d.bg_out = reinterpret_cast<u16*>(bg_out);
-              d.bg_pitch = u32(bg_pitch);
-              d.counts = reinterpret_cast<u32*>(counts);
-              d.w = w;
-              d.h = h;
-              d.cell = cell;
-              d.threshold = threshold;
-              d.learn_shift = learn_shift;
-              gpu::check_motion(d, size_t(w) * size_t(h) * 3, size_t(bg_pitch) * size_t(h),
-                                size_t(motion::cells(u32(w), u32(cell))) * motion::cells(u32(h), u32(cell)));
-              set->h_descs[k] = d;
-            }
-            gpu::MotionPool::run(*set, n, 0, s);
-            VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
-          } catch (...) {
-            pool->release(set);
-            throw;
+          gpu::MotionPool::Lease set = pool_of_current_device<gpu::MotionPool>().acquire();
+          set->reserve(n, 0);
+          for (int k = 0; k < n; ++k) {
+            const auto& [src, w, h, bg_in, bg_out, bg_pitch, counts] = pics[size_t(k)];
+            VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "motion: picture size must be 1..65535");
+            VEP_CHECK(bg_pitch >= w && bg_pitch <= 65536, "motion: background pitch out of range");
+            gpu::MotionDesc d{};
+            d.src = reinterpret_cast<const u8*>(src);
+            d.src_pitch = u32(w) * 3;
+            d.bg_in = reinterpret_cast<const u16*>(bg_in);
+            d.bg_out = reinterpret_cast<u16*>(bg_out);
+            d.bg_pitch = u32(bg_pitch);
+            d.counts = reinterpret_cast<u32*>(counts);
+            d.w = w;
+            d.h = h;
+            d.cell = cell;
+            d.threshold = threshold;
+            d.learn_shift = learn_shift;
+            gpu::check_motion(d, size_t(w) * size_t(h) * 3, size_t(bg_pitch) * size_t(h),
+                              size_t(motion::cells(u32(w), u32(cell))) * motion::cells(u32(h), u32(cell)));
+            set->h_descs.p[k] = d;
           }
-          pool->release(set);
+          set->run(n, 0, s);
+          VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
         },
         py::arg("pictures"), py::arg("cell"), py::arg("threshold"), py::arg("learn_shift"), py::arg("stream"));
   // Tamper detection (vep/tamper.h) on the host: the CPU backend's path and the byte-exact
@@ -2381,8 +2363,6 @@ PYBIND11_MODULE(_vep, m) {
   // (descriptors: one process-wide pool per device). dst is h x w x 3 packed.
   m.def("mask_apply",
         [](const std::vector<std::tuple<uintptr_t, int, int, std::vector<MaskTuple>>>& pics, uintptr_t stream) {
-          static std::mutex mu;
-          static std::map<int, gpu::MaskPool*>* pools = new std::map<int, gpu::MaskPool*>();  // (never freed)
           std::vector<std::vector<mask::Mask>> lists;
           size_t nd = 0;
           for (const auto& pc : pics) {
@@ -2392,37 +2372,23 @@ PYBIND11_MODULE(_vep, m) {
           if (nd == 0) return;
           VEP_CHECK(nd <= 65535, "mask_apply: at most 65535 masks per call");
           py::gil_scoped_release r;
-          int dev = 0;
-          VEP_HIP(hipGetDevice(&dev));
-          gpu::MaskPool* pool;
-          {
-            std::lock_guard<std::mutex> g(mu);
-            gpu::MaskPool*& slot = (*pools)[dev];
-            if (!slot) slot = new gpu::MaskPool();
-            pool = slot;
-          }
           hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-          gpu::MaskPool::Set* set = pool->acquire(int(nd));
-          try {
-            int k = 0;
-            for (size_t i = 0; i < pics.size(); ++i) {
-              const uintptr_t dst = std::get<0>(pics[i]);
-              const int w = std::get<1>(pics[i]), h = std::get<2>(pics[i]);
-              const std::vector<mask::Mask>& ms = lists[i];
-              if (ms.empty()) continue;
-              VEP_CHECK(w >= 1 && h >= 1 && w <= mask::kMaxSide && h <= mask::kMaxSide,
-                        "mask: picture size must be 1..65535");
-              gpu::fill_mask_descs(set->h_descs + k, reinterpret_cast<u8*>(dst), size_t(w) * size_t(h) * 3, w, h, ms.data(),
-                                   int(ms.size()));
-              k += int(ms.size());
-            }
-            gpu::MaskPool::run(*set, k, s);
-            VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
-          } catch (...) {
-            pool->release(set);
-            throw;
+          gpu::MaskPool::Lease set = pool_of_current_device<gpu::MaskPool>().acquire();
+          set->reserve(int(nd));
+          int k = 0;
+          for (size_t i = 0; i < pics.size(); ++i) {
+            const uintptr_t dst = std::get<0>(pics[i]);
+            const int w = std::get<1>(pics[i]), h = std::get<2>(pics[i]);
+            const std::vector<mask::Mask>& ms = lists[i];
+            if (ms.empty()) continue;
+            VEP_CHECK(w >= 1 && h >= 1 && w <= mask::kMaxSide && h <= mask::kMaxSide,
+                      "mask: picture size must be 1..65535");
+            gpu::fill_mask_descs(set->h_descs.p + k, reinterpret_cast<u8*>(dst), size_t(w) * size_t(h) * 3, w, h, ms.data(),
+                                 int(ms.size()));
+            k += int(ms.size());
           }
-          pool->release(set);
+          set->run(k, s);
+          VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
         },
         py::arg("pictures"), py::arg("stream"));
   // Pictures (src, w, h, hist, sum_y, energy) on caller-owned device buffers: one launch of the
@@ -2432,71 +2398,44 @@ PYBIND11_MODULE(_vep, m) {
   m.def("tamper_stats",
         [](const std::vector<std::tuple<uintptr_t, int, int, uintptr_t, uintptr_t, uintptr_t>>& pics, int cell,
            uintptr_t stream) {
-          static std::mutex mu;
-          static std::map<int, gpu::TamperPool*>* pools = new std::map<int, gpu::TamperPool*>();  // (never freed)
           const int n = int(pics.size());
           VEP_CHECK(n >= 1 && n <= 65535, "tamper_stats: 1..65535 pictures expected");
           tamper::check_cell(cell);
           py::gil_scoped_release r;
-          int dev = 0;
-          VEP_HIP(hipGetDevice(&dev));
-          gpu::TamperPool* pool;
-          {
-            std::lock_guard<std::mutex> g(mu);
-            gpu::TamperPool*& slot = (*pools)[dev];
-            if (!slot) slot = new gpu::TamperPool();
-            pool = slot;
-          }
           hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-          gpu::TamperPool::Set* set = pool->acquire(n, 0);
-          try {
-            for (int k = 0; k < n; ++k) {
-              const auto& [src, w, h, hist, sum_y, energy] = pics[size_t(k)];
-              VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "tamper: picture size must be 1..65535");
-              gpu::TamperDesc d{};
-              d.src = reinterpret_cast<const u8*>(src);
-              d.src_pitch = u32(w) * 3;
-              d.hist = reinterpret_cast<u32*>(hist);
-              d.sum_y = reinterpret_cast<u32*>(sum_y);
-              d.energy = reinterpret_cast<u32*>(energy);
-              d.w = w;
-              d.h = h;
-              d.cell = cell;
-              gpu::check_tamper(d, size_t(w) * size_t(h) * 3,
-                                size_t(tamper::cells(u32(w), u32(cell))) * tamper::cells(u32(h), u32(cell)));
-              set->h_descs[k] = d;
-            }
-            for (int k = 0; k < n; ++k)
-              VEP_HIP(hipMemsetAsync(set->h_descs[k].hist, 0, size_t(tamper::kBins) * sizeof(u32), s));
-            gpu::TamperPool::run(*set, n, 0, 0, s);
-            VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
-          } catch (...) {
-            pool->release(set);
-            throw;
+          gpu::TamperPool::Lease set = pool_of_current_device<gpu::TamperPool>().acquire();
+          set->reserve(n, 0);
+          for (int k = 0; k < n; ++k) {
+            const auto& [src, w, h, hist, sum_y, energy] = pics[size_t(k)];
+            VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "tamper: picture size must be 1..65535");
+            gpu::TamperDesc d{};
+            d.src = reinterpret_cast<const u8*>(src);
+            d.src_pitch = u32(w) * 3;
+            d.hist = reinterpret_cast<u32*>(hist);
+            d.sum_y = reinterpret_cast<u32*>(sum_y);
+            d.energy = reinterpret_cast<u32*>(energy);
+            d.w = w;
+            d.h = h;
+            d.cell = cell;
+            gpu::check_tamper(d, size_t(w) * size_t(h) * 3,
+                              size_t(tamper::cells(u32(w), u32(cell))) * tamper::cells(u32(h), u32(cell)));
+            set->h_descs.p[k] = d;
           }
-          pool->release(set);
+          for (int k = 0; k < n; ++k)
+            VEP_HIP(hipMemsetAsync(set->h_descs.p[k].hist, 0, size_t(tamper::kBins) * sizeof(u32), s));
+          set->run(n, 0, 0, s);
+          VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
         },
         py::arg("pictures"), py::arg("cell"), py::arg("stream"));
   // JPEG stream of a device BGR24 picture, encoded by the gfx950 kernels on `stream` of the
   // current device (scratch: one process-wide pool per device).
   m.def("jpeg_encode",
         [](uintptr_t bgr, int w, int h, int quality, uintptr_t stream) {
-          static std::mutex mu;
-          static std::map<int, gpu::JpegPool*>* pools = new std::map<int, gpu::JpegPool*>();  // (never freed)
           std::string out;
           {
             py::gil_scoped_release r;
-            int dev = 0;
-            VEP_HIP(hipGetDevice(&dev));
-            gpu::JpegPool* pool;
-            {
-              std::lock_guard<std::mutex> g(mu);
-              gpu::JpegPool*& slot = (*pools)[dev];
-              if (!slot) slot = new gpu::JpegPool();
-              pool = slot;
-            }
             const u8* p = reinterpret_cast<const u8*>(bgr);
-            if (!pool->encode(p, w, h, quality, reinterpret_cast<hipStream_t>(stream), out)) {
+            if (!pool_of_current_device<gpu::JpegPool>().encode(p, w, h, quality, reinterpret_cast<hipStream_t>(stream), out)) {
               // the kernels reported an overflow of their scratch: encode on the host
               std::unique_ptr<u8[]> host(new u8[size_t(w) * size_t(h) * 3]);
               VEP_HIP(hipMemcpyAsync(host.get(), p, size_t(w) * size_t(h) * 3, hipMemcpyDeviceToHost,

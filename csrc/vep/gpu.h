@@ -11,12 +11,11 @@
 
 #include <hip/hip_runtime.h>
 
-#include <condition_variable>
-#include <memory>
-#include <mutex>
+#include <algorithm>
 
 #include "common.h"
 #include "mask.h"
+#include "scratch.h"
 
 namespace vep::gpu {
 
@@ -293,6 +292,78 @@ void launch_avc_deblock(const AvcDesc* d_descs, int n, int max_hmbs, hipStream_t
 // variants: bit 0 High 10 4:2:0, bit 1 8-bit 4:2:2, bit 2 High 10 4:2:2 pictures present
 void launch_avc_hbd(const AvcDesc* d_descs, int n, bool intra, bool dbk, int variants, hipStream_t s);
 
+// ---- per-request scratch of the serving ops below ---------------------------------------------
+// Every op keeps its scratch in a ScratchPool of sets (scratch.h states the contract: up to
+// kScratch sets per pool, one per request in flight, leased for a scope). A Worker owns one pool
+// per op; the ops on caller-owned tensors use one process-wide pool per device. A set is built
+// from the grow-only buffers and the event below, and is used with its device bound to the
+// calling thread: acquire, `reserve` room for the request, fill the host descriptors, `run`.
+//
+// Grow-only buffer of T, in device memory or (kPinned) in pinned host memory. It never shrinks.
+template <class T, bool kPinned>
+struct GrowBuf {
+  T* p = nullptr;
+  size_t cap = 0;  // elements
+  GrowBuf() = default;
+  GrowBuf(const GrowBuf&) = delete;
+  GrowBuf& operator=(const GrowBuf&) = delete;
+  ~GrowBuf() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+  }
+  // Room for n elements. Nothing happens when cap >= n; otherwise the old buffer is freed and
+  // max(n, floor) elements are allocated. cap is set only after the allocation succeeded, so a
+  // buffer whose growth threw is empty and grows again on the next call.
+  void reserve(size_t n, size_t floor = 0) {
+    if (cap >= n) return;
+    if (p) VEP_HIP(kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+    const size_t want = std::max(n, floor);
+    void* q = nullptr;
+    VEP_HIP(kPinned ? hipHostMalloc(&q, want * sizeof(T), hipHostMallocDefault) : hipMalloc(&q, want * sizeof(T)));
+    p = static_cast<T*>(q);
+    cap = want;
+  }
+};
+template <class T>
+using DevBuf = GrowBuf<T, false>;
+template <class T>
+using PinBuf = GrowBuf<T, true>;
+
+// A set's event, created on first use; waiters sleep (several server threads wait at once).
+struct SetEvent {
+  hipEvent_t ev = nullptr;
+  SetEvent() = default;
+  SetEvent(const SetEvent&) = delete;
+  SetEvent& operator=(const SetEvent&) = delete;
+  ~SetEvent() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  void ensure() {
+    if (!ev) VEP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventBlockingSync));
+  }
+  operator hipEvent_t() const { return ev; }
+};
+
+// The part every batched op shares: its descriptor array on the device and in pinned host memory
+// (the caller fills h_descs.p[0..n), `run` copies them up), and the event `run` records last.
+constexpr size_t kDescFloor = 64;
+template <class Desc>
+struct DescSet {
+  DevBuf<Desc> d_descs;
+  PinBuf<Desc> h_descs;
+  SetEvent ev;
+  void reserve_descs(int n) {
+    ev.ensure();
+    d_descs.reserve(size_t(n), kDescFloor);
+    h_descs.reserve(size_t(n), kDescFloor);
+  }
+  bool holds(int n) const { return size_t(n) <= d_descs.cap && size_t(n) <= h_descs.cap; }
+  void upload_descs(int n, hipStream_t s) {
+    VEP_HIP(hipMemcpyAsync(d_descs.p, h_descs.p, size_t(n) * sizeof(Desc), hipMemcpyHostToDevice, s));
+  }
+};
+
 // ---- baseline JPEG encoder (gpu_jpeg.hip; stream format and arithmetic: jpeg.h) -------------
 // One BGR24 picture -> the entropy-coded part of its JPEG stream, byte-identical with
 // jpeg::encode_cpu, in four launches: transform (one workgroup per 16x16 MCU), entropy (one lane
@@ -320,29 +391,19 @@ void launch_jpeg_entropy(const JpegDesc& d, hipStream_t s);
 void launch_jpeg_scan(const JpegDesc& d, hipStream_t s);
 void launch_jpeg_gather(const JpegDesc& d, hipStream_t s);
 
-// Encoder scratch of one device: up to kScratch sets, one per encode in flight, so concurrent
-// requests never share one; a set grows to the largest picture it has seen and is then reused
-// (steady state allocates nothing). Used with the device bound to the calling thread.
-class JpegPool {
+// Encoder scratch of one device (pool contract: above).
+struct JpegSet {
+  DevBuf<u8> dev;      // coefficients | segments | joined stream | lengths | offsets
+  PinBuf<u32> status;  // JpegDesc::status
+  PinBuf<u8> host;     // the joined stream's D2H destination
+  SetEvent ev;
+};
+class JpegPool : public ScratchPool<JpegSet> {
  public:
-  JpegPool();
-  ~JpegPool();
-  JpegPool(const JpegPool&) = delete;
-  JpegPool& operator=(const JpegPool&) = delete;
   // The JPEG stream of the device picture d_bgr (h x w x 3) at `quality` 1..100, encoded on
   // stream `s` (waits for it). False when the kernels reported an overflow: the caller encodes
   // with jpeg::encode_cpu instead.
   bool encode(const u8* d_bgr, int w, int h, int quality, hipStream_t s, std::string& out);
-  static constexpr int kScratch = 4;
-
- private:
-  struct Scratch;
-  Scratch* acquire();
-  void release(Scratch* sc);
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::vector<std::unique_ptr<Scratch>> all_;
-  std::vector<Scratch*> free_;
 };
 
 // ---- area-average downscale and the camera wall (gpu_scale.hip; arithmetic: scale.h) ---------
@@ -368,40 +429,17 @@ void check_scale(const ScaleDesc& d, int canvas_w, int canvas_h);
 // tiles. h_descs is the host copy of d_descs (the grid is sized from it).
 void launch_scale(const ScaleDesc* d_descs, const ScaleDesc* h_descs, int n, hipStream_t s);
 
-// Scale scratch of one device: up to kScratch sets, one per request in flight. A set holds a
-// canvas, a descriptor array (device + pinned host copy) and a pinned upload buffer; each grows
-// to the largest request it has seen and is then reused (steady state allocates nothing). Used
-// with the device bound to the calling thread.
-class ScalePool {
- public:
-  struct Set {
-    u8* canvas = nullptr;         // device
-    size_t canvas_cap = 0;
-    ScaleDesc* d_descs = nullptr; // device
-    ScaleDesc* h_descs = nullptr; // pinned
-    int desc_cap = 0;
-    u8* upload = nullptr;         // pinned: host tiles on their way into the canvas, D2H results
-    size_t upload_cap = 0;
-    hipEvent_t ev = nullptr;
-    ~Set();
-  };
-  ScalePool();
-  ~ScalePool();
-  ScalePool(const ScalePool&) = delete;
-  ScalePool& operator=(const ScalePool&) = delete;
-  // A free set with room for canvas_bytes, ndescs descriptors and upload_bytes (waits for one).
-  Set* acquire(size_t canvas_bytes, int ndescs, size_t upload_bytes);
-  void release(Set* s);
-  // Copies the set's first n host descriptors up, launches them on `s` (no wait).
-  static void run(Set& set, int n, hipStream_t s);
-  static constexpr int kScratch = 4;
-
- private:
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::vector<std::unique_ptr<Set>> all_;
-  std::vector<Set*> free_;
+// Scale scratch of one device (pool contract: above): descriptors, a canvas and a pinned buffer
+// for host tiles on their way into the canvas and for D2H results, both of the exact size asked.
+struct ScaleSet : DescSet<ScaleDesc> {
+  DevBuf<u8> canvas;
+  PinBuf<u8> upload;
+  void reserve(size_t canvas_bytes, int ndescs, size_t upload_bytes);
+  // Copies the first n host descriptors up, launches them on `s` and records the event (no
+  // wait). A caller that enqueues more on `s` for this request records the event again after it.
+  void run(int n, hipStream_t s);
 };
+using ScalePool = ScratchPool<ScaleSet>;
 
 // ---- motion detection (gpu_motion.hip; arithmetic: motion.h) ----------------------------------
 // One picture of a batched motion launch (device memory): a packed BGR24 source compared with
@@ -428,40 +466,18 @@ void check_motion(const MotionDesc& d, size_t src_bytes, size_t bg_samples, size
 // host copy of d_descs (the grid is sized from it).
 void launch_motion(const MotionDesc* d_descs, const MotionDesc* h_descs, int n, hipStream_t s);
 
-// Motion scratch of one device: up to kScratch sets, one per request in flight. A set holds a
-// descriptor array (device + pinned host copy) and a counts buffer (device + pinned host copy);
-// each grows to the largest request it has seen and is then reused. Used with the device bound to
-// the calling thread.
-class MotionPool {
- public:
-  struct Set {
-    MotionDesc* d_descs = nullptr;  // device
-    MotionDesc* h_descs = nullptr;  // pinned
-    int desc_cap = 0;
-    u32* d_counts = nullptr;        // device: the grids of a request, one after another
-    u32* h_counts = nullptr;        // pinned: their copy on the host
-    size_t counts_cap = 0;          // cells
-    hipEvent_t ev = nullptr;
-    ~Set();
-  };
-  MotionPool();
-  ~MotionPool();
-  MotionPool(const MotionPool&) = delete;
-  MotionPool& operator=(const MotionPool&) = delete;
-  // A free set with room for ndescs descriptors and count_cells cells (waits for one).
-  Set* acquire(int ndescs, size_t count_cells);
-  void release(Set* s);
-  // Copies the set's first n host descriptors up, launches them on `s`, then copies the first
-  // count_cells cells down into h_counts and records the set's event (no wait).
-  static void run(Set& set, int n, size_t count_cells, hipStream_t s);
-  static constexpr int kScratch = 4;
-
- private:
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::vector<std::unique_ptr<Set>> all_;
-  std::vector<Set*> free_;
+// Motion scratch of one device (pool contract: above): descriptors and a counts buffer.
+constexpr size_t kResultFloor = 16384;  // words: motion counts, tamper results
+struct MotionSet : DescSet<MotionDesc> {
+  DevBuf<u32> d_counts;  // the grids of a request, one after another
+  PinBuf<u32> h_counts;  // their copy on the host
+  void reserve(int ndescs, size_t count_cells);
+  // Copies the first n host descriptors up, launches them on `s`, then copies the first
+  // count_cells cells down into h_counts (0: the counts are the caller's own buffers) and records
+  // the event (no wait).
+  void run(int n, size_t count_cells, hipStream_t s);
 };
+using MotionPool = ScratchPool<MotionSet>;
 
 // ---- tamper detection (gpu_tamper.hip; arithmetic: tamper.h) -----------------------------------
 // One picture of a batched tamper launch (device memory): the luma histogram, the per-cell luma
@@ -486,43 +502,20 @@ void check_tamper(const TamperDesc& d, size_t src_bytes, size_t grid_cells);
 // host copy of d_descs (the grid is sized from it). The histograms are zeroed by the caller, on `s`.
 void launch_tamper(const TamperDesc* d_descs, const TamperDesc* h_descs, int n, hipStream_t s);
 
-// Tamper scratch of one device: up to kScratch sets, one per request in flight. A set holds a
-// descriptor array and a results buffer (each on the device and in pinned host memory); each grows
-// to the largest request it has seen and is then reused. A request's results are the histograms
-// of all its pictures first (zeroed by one memset), then each picture's two planes. Used with the
-// device bound to the calling thread.
-class TamperPool {
- public:
-  struct Set {
-    TamperDesc* d_descs = nullptr;  // device
-    TamperDesc* h_descs = nullptr;  // pinned
-    int desc_cap = 0;
-    u32* d_res = nullptr;           // device
-    u32* h_res = nullptr;           // pinned: its copy on the host
-    size_t res_cap = 0;             // u32 words
-    hipEvent_t ev = nullptr;
-    ~Set();
-  };
-  TamperPool();
-  ~TamperPool();
-  TamperPool(const TamperPool&) = delete;
-  TamperPool& operator=(const TamperPool&) = delete;
-  // A free set with room for ndescs descriptors and res_words result words (waits for one).
-  Set* acquire(int ndescs, size_t res_words);
-  void release(Set* s);
-  // Copies the set's first n host descriptors up, zeroes the first hist_words words of d_res,
-  // launches on `s`, then copies the first res_words words down into h_res and records the set's
-  // event (no wait). hist_words = res_words = 0: the results are the caller's own buffers, with
-  // the histograms zeroed on `s` already.
-  static void run(Set& set, int n, size_t hist_words, size_t res_words, hipStream_t s);
-  static constexpr int kScratch = 4;
-
- private:
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::vector<std::unique_ptr<Set>> all_;
-  std::vector<Set*> free_;
+// Tamper scratch of one device (pool contract: above): descriptors and a results buffer. A
+// request's results are the histograms of all its pictures first (zeroed by one memset), then
+// each picture's two planes.
+struct TamperSet : DescSet<TamperDesc> {
+  DevBuf<u32> d_res;
+  PinBuf<u32> h_res;  // its copy on the host
+  void reserve(int ndescs, size_t res_words);
+  // Copies the first n host descriptors up, zeroes the first hist_words words of d_res, launches
+  // on `s`, then copies the first res_words words down into h_res and records the event (no
+  // wait). hist_words = res_words = 0: the results are the caller's own buffers, with the
+  // histograms zeroed on `s` already.
+  void run(int n, size_t hist_words, size_t res_words, hipStream_t s);
 };
+using TamperPool = ScratchPool<TamperSet>;
 
 // ---- privacy masks (gpu_mask.hip; arithmetic: mask.h) ------------------------------------------
 // One mask of one picture of a batched mask launch (device memory): the pixel rect x0..x1 x y0..y1
@@ -553,35 +546,14 @@ void launch_mask(const MaskDesc* d_descs, const MaskDesc* h_descs, int n, int le
 // descriptor checked. Returns the number of levels.
 int fill_mask_descs(MaskDesc* out, u8* dst, size_t dst_bytes, int w, int h, const mask::Mask* m, int n);
 
-// Mask descriptors of one device: up to kScratch sets, one per request in flight, each held in
-// pinned host memory and on the device; a set grows to the largest request it has seen and is
-// then reused. Used with the device bound to the calling thread.
-class MaskPool {
- public:
-  struct Set {
-    MaskDesc* d_descs = nullptr;  // device
-    MaskDesc* h_descs = nullptr;  // pinned
-    int desc_cap = 0;
-    hipEvent_t ev = nullptr;
-    ~Set();
-  };
-  MaskPool();
-  ~MaskPool();
-  MaskPool(const MaskPool&) = delete;
-  MaskPool& operator=(const MaskPool&) = delete;
-  Set* acquire(int ndescs);  // a free set with room for ndescs descriptors (waits for one)
-  void release(Set* s);
-  // Copies the set's first n host descriptors up, launches their levels in ascending order on `s`
-  // and records the set's event (no wait).
-  static void run(Set& set, int n, hipStream_t s);
-  static constexpr int kScratch = 4;
-
- private:
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::vector<std::unique_ptr<Set>> all_;
-  std::vector<Set*> free_;
+// Mask descriptors of one device (pool contract: above).
+struct MaskSet : DescSet<MaskDesc> {
+  void reserve(int ndescs) { reserve_descs(ndescs); }
+  // Copies the first n host descriptors up, launches their levels in ascending order on `s` and
+  // records the event (no wait).
+  void run(int n, hipStream_t s);
 };
+using MaskPool = ScratchPool<MaskSet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

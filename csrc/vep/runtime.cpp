@@ -2816,19 +2816,19 @@ void Worker::encode_device(const u8* d_bgr, int w, int h, int quality, std::stri
   out = jpeg::encode_cpu(host.get(), w, h, quality);
 }
 
-void Worker::scale_slot(gpu::ScalePool::Set& set, const FrameRing& ring, int slot, int ow, int oh) {
-  gpu::ScaleDesc& d = set.h_descs[0];
+void Worker::scale_slot(gpu::ScaleSet& set, const FrameRing& ring, int slot, int ow, int oh) {
+  gpu::ScaleDesc& d = set.h_descs.p[0];
   d = gpu::ScaleDesc{};
   d.src = ring.slot_ptr(slot);
   d.sw = ring.width();
   d.sh = ring.height();
   d.src_pitch = u32(ring.width()) * 3;
-  d.dst = set.canvas;
+  d.dst = set.canvas.p;
   d.dst_pitch = u32(ow) * 3;
   d.ow = ow;
   d.oh = oh;
   gpu::check_scale(d, ow, oh);
-  gpu::ScalePool::run(set, 1, serve_stream_);
+  set.run(1, serve_stream_);
 }
 
 static void check_box(int width, int height) {
@@ -2850,18 +2850,13 @@ bool Worker::read_latest_scaled(int cam, i64 after, int width, int height, Frame
     if (!ring->latest(after, meta, &slot)) return false;
     if (dev_.gpu()) {
       dev_.bind();
-      gpu::ScalePool::Set* set = scale_pool_.acquire(n, 1, n);
-      try {
-        scale_slot(*set, *ring, slot, f.w, f.h);
-        VEP_HIP(hipMemcpyAsync(set->upload, set->canvas, n, hipMemcpyDeviceToHost, serve_stream_));
-        VEP_HIP(hipEventRecord(set->ev, serve_stream_));
-        VEP_HIP(hipEventSynchronize(set->ev));
-        std::memcpy(dst.data(), set->upload, n);
-      } catch (...) {
-        scale_pool_.release(set);
-        throw;
-      }
-      scale_pool_.release(set);
+      gpu::ScalePool::Lease set = scale_pool_.acquire();
+      set->reserve(n, 1, n);
+      scale_slot(*set, *ring, slot, f.w, f.h);
+      VEP_HIP(hipMemcpyAsync(set->upload.p, set->canvas.p, n, hipMemcpyDeviceToHost, serve_stream_));
+      VEP_HIP(hipEventRecord(set->ev, serve_stream_));
+      VEP_HIP(hipEventSynchronize(set->ev));
+      std::memcpy(dst.data(), set->upload.p, n);
     } else {
       scale::area_cpu(ring->slot_ptr(slot), ring->width(), ring->height(), size_t(ring->width()) * 3, dst.data(),
                       size_t(f.w) * 3, f.w, f.h);
@@ -2984,73 +2979,68 @@ void Worker::read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int 
   }
   dev_.bind();
   const int cells = g.cols * g.rows;  // (the cells past the last tile are background too)
-  gpu::ScalePool::Set* set = scale_pool_.acquire(canvas_bytes, cells, up_bytes);
-  try {
-    std::vector<int> tile_of;  // descriptor -> tile of the current round
-    for (int round = 0; round < 5; ++round) {
-      // rounds 0..3 scale the tiles that are not settled; round 4 only clears what is left
-      tile_of.clear();
+  gpu::ScalePool::Lease set = scale_pool_.acquire();
+  set->reserve(canvas_bytes, cells, up_bytes);
+  std::vector<int> tile_of;  // descriptor -> tile of the current round
+  for (int round = 0; round < 5; ++round) {
+    // rounds 0..3 scale the tiles that are not settled; round 4 only clears what is left
+    tile_of.clear();
+    for (int t = 0; t < n; ++t) {
+      TileSrc& s = ts[size_t(t)];
+      if (s.done) continue;
+      gpu::ScaleDesc d = cell(t, set->canvas.p);
+      const bool fgn = !foreign.empty() && foreign[size_t(t)].data;
+      if (!fgn && round < 4 && pick(t)) {
+        const scale::Placement p = scale::place(t, g.cols, tw, th, s.ring->width(), s.ring->height());
+        d.src = s.ring->slot_ptr(s.slot);
+        d.sw = s.ring->width();
+        d.sh = s.ring->height();
+        d.src_pitch = u32(d.sw) * 3;
+        d.dx = p.x;
+        d.dy = p.y;
+        d.ow = p.w;
+        d.oh = p.h;
+      } else {
+        s.slot = -1;
+      }
+      gpu::check_scale(d, g.w, g.h);
+      set->h_descs.p[tile_of.size()] = d;
+      tile_of.push_back(t);
+    }
+    if (tile_of.empty()) break;
+    int nd = int(tile_of.size());
+    for (int t = n; t < cells && round == 0; ++t) {
+      set->h_descs.p[nd] = cell(t, set->canvas.p);
+      gpu::check_scale(set->h_descs.p[nd++], g.w, g.h);
+    }
+    set->run(nd, serve_stream_);
+    if (round == 0 && up_bytes) {  // foreign tiles: over their (background) cells, after the launch
+      size_t off = 0;
       for (int t = 0; t < n; ++t) {
-        TileSrc& s = ts[size_t(t)];
-        if (s.done) continue;
-        gpu::ScaleDesc d = cell(t, set->canvas);
-        const bool fgn = !foreign.empty() && foreign[size_t(t)].data;
-        if (!fgn && round < 4 && pick(t)) {
-          const scale::Placement p = scale::place(t, g.cols, tw, th, s.ring->width(), s.ring->height());
-          d.src = s.ring->slot_ptr(s.slot);
-          d.sw = s.ring->width();
-          d.sh = s.ring->height();
-          d.src_pitch = u32(d.sw) * 3;
-          d.dx = p.x;
-          d.dy = p.y;
-          d.ow = p.w;
-          d.oh = p.h;
-        } else {
-          s.slot = -1;
-        }
-        gpu::check_scale(d, g.w, g.h);
-        set->h_descs[tile_of.size()] = d;
-        tile_of.push_back(t);
+        const ForeignTile& f = foreign[size_t(t)];
+        if (!f.data) continue;
+        const size_t row = size_t(f.w) * 3, bytes = row * size_t(f.h);
+        std::memcpy(set->upload.p + off, f.data, bytes);
+        u8* p = set->canvas.p + size_t((t / g.cols) * th + (th - f.h) / 2) * pitch +
+                size_t((t % g.cols) * tw + (tw - f.w) / 2) * 3;
+        VEP_HIP(hipMemcpy2DAsync(p, pitch, set->upload.p + off, row, row, size_t(f.h), hipMemcpyHostToDevice,
+                                 serve_stream_));
+        off += bytes;
       }
-      if (tile_of.empty()) break;
-      int nd = int(tile_of.size());
-      for (int t = n; t < cells && round == 0; ++t) {
-        set->h_descs[nd] = cell(t, set->canvas);
-        gpu::check_scale(set->h_descs[nd++], g.w, g.h);
-      }
-      gpu::ScalePool::run(*set, nd, serve_stream_);
-      if (round == 0 && up_bytes) {  // foreign tiles: over their (background) cells, after the launch
-        size_t off = 0;
-        for (int t = 0; t < n; ++t) {
-          const ForeignTile& f = foreign[size_t(t)];
-          if (!f.data) continue;
-          const size_t row = size_t(f.w) * 3, bytes = row * size_t(f.h);
-          std::memcpy(set->upload + off, f.data, bytes);
-          u8* p = set->canvas + size_t((t / g.cols) * th + (th - f.h) / 2) * pitch +
-                  size_t((t % g.cols) * tw + (tw - f.w) / 2) * 3;
-          VEP_HIP(hipMemcpy2DAsync(p, pitch, set->upload + off, row, row, size_t(f.h), hipMemcpyHostToDevice,
-                                   serve_stream_));
-          off += bytes;
-        }
-      }
-      VEP_HIP(hipEventRecord(set->ev, serve_stream_));
-      VEP_HIP(hipEventSynchronize(set->ev));
-      for (int t : tile_of) {
-        TileSrc& s = ts[size_t(t)];
-        if (s.slot < 0) {
-          s.done = true;  // background or foreign
-        } else if (s.ring->still_valid(s.slot, s.meta.seq)) {
-          s.done = true;
-          seqs_out[size_t(t)] = s.meta.seq;
-        }
+      VEP_HIP(hipEventRecord(set->ev, serve_stream_));  // (again: after the uploads)
+    }
+    VEP_HIP(hipEventSynchronize(set->ev));
+    for (int t : tile_of) {
+      TileSrc& s = ts[size_t(t)];
+      if (s.slot < 0) {
+        s.done = true;  // background or foreign
+      } else if (s.ring->still_valid(s.slot, s.meta.seq)) {
+        s.done = true;
+        seqs_out[size_t(t)] = s.meta.seq;
       }
     }
-    encode_device(set->canvas, g.w, g.h, quality, out);
-  } catch (...) {
-    scale_pool_.release(set);
-    throw;
   }
-  scale_pool_.release(set);
+  encode_device(set->canvas.p, g.w, g.h, quality, out);
 }
 
 bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width,
@@ -3069,15 +3059,10 @@ bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, 
       if (!ring->latest(after, meta, &slot)) return false;
       if (dev_.gpu()) {
         dev_.bind();
-        gpu::ScalePool::Set* set = scale_pool_.acquire(n, 1, 0);
-        try {
-          scale_slot(*set, *ring, slot, f.w, f.h);
-          encode_device(set->canvas, f.w, f.h, quality, out);  // (same stream: ordered after the scale)
-        } catch (...) {
-          scale_pool_.release(set);
-          throw;
-        }
-        scale_pool_.release(set);
+        gpu::ScalePool::Lease set = scale_pool_.acquire();
+        set->reserve(n, 1, 0);
+        scale_slot(*set, *ring, slot, f.w, f.h);
+        encode_device(set->canvas.p, f.w, f.h, quality, out);  // (same stream: ordered after the scale)
       } else {
         std::vector<u8> small(n);
         scale::area_cpu(ring->slot_ptr(slot), ring->width(), ring->height(), size_t(ring->width()) * 3, small.data(),
@@ -3245,34 +3230,30 @@ void Worker::motion_eval(std::vector<MotionEval>& evs) {
     if (todo.empty()) break;
     if (dev_.gpu()) {
       dev_.bind();
-      gpu::MotionPool::Set* set = motion_pool_.acquire(int(todo.size()), total_cells);
-      try {
-        for (size_t k = 0; k < todo.size(); ++k) {
-          MotionEval& e = *todo[k];
-          MotionState& st = e.c->motion;
-          gpu::MotionDesc d{};
-          d.src = e.ring->slot_ptr(e.slot);
-          d.src_pitch = u32(st.w) * 3;
-          d.bg_in = e.primed ? st.bg[st.cur] : nullptr;
-          d.bg_out = st.bg[st.cur ^ 1];
-          d.bg_pitch = motion::pitch_for(u32(st.w));
-          d.counts = set->d_counts + e.at;
-          d.w = st.w;
-          d.h = st.h;
-          d.cell = prm.cell;
-          d.threshold = prm.threshold;
-          d.learn_shift = prm.learn_shift;
-          gpu::check_motion(d, e.ring->slot_bytes(), st.samples, e.cells);
-          set->h_descs[k] = d;
-        }
-        gpu::MotionPool::run(*set, int(todo.size()), total_cells, serve_stream_);
-        VEP_HIP(hipEventSynchronize(set->ev));
-        for (MotionEval* e : todo) e->counts.assign(set->h_counts + e->at, set->h_counts + e->at + e->cells);
-      } catch (...) {
-        motion_pool_.release(set);
-        throw;
+      gpu::MotionPool::Lease set = motion_pool_.acquire();
+      set->reserve(int(todo.size()), total_cells);
+      for (size_t k = 0; k < todo.size(); ++k) {
+        MotionEval& e = *todo[k];
+        MotionState& st = e.c->motion;
+        gpu::MotionDesc d{};
+        d.src = e.ring->slot_ptr(e.slot);
+        d.src_pitch = u32(st.w) * 3;
+        d.bg_in = e.primed ? st.bg[st.cur] : nullptr;
+        d.bg_out = st.bg[st.cur ^ 1];
+        d.bg_pitch = motion::pitch_for(u32(st.w));
+        d.counts = set->d_counts.p + e.at;
+        d.w = st.w;
+        d.h = st.h;
+        d.cell = prm.cell;
+        d.threshold = prm.threshold;
+        d.learn_shift = prm.learn_shift;
+        gpu::check_motion(d, e.ring->slot_bytes(), st.samples, e.cells);
+        set->h_descs.p[k] = d;
       }
-      motion_pool_.release(set);
+      set->run(int(todo.size()), total_cells, serve_stream_);
+      VEP_HIP(hipEventSynchronize(set->ev));
+      const u32* r = set->h_counts.p;
+      for (MotionEval* e : todo) e->counts.assign(r + e->at, r + e->at + e->cells);
     } else {
       for (MotionEval* e : todo) {
         MotionState& st = e->c->motion;
@@ -3472,35 +3453,30 @@ void Worker::tamper_eval(std::vector<TamperEval>& evs, bool set_reference) {
     for (TamperEval* e : todo) e->grid_at += hist_words;  // the planes follow the histograms
     if (dev_.gpu()) {
       dev_.bind();
-      gpu::TamperPool::Set* set = tamper_pool_.acquire(int(todo.size()), res_words);
-      try {
-        for (size_t k = 0; k < todo.size(); ++k) {
-          TamperEval& e = *todo[k];
-          gpu::TamperDesc d{};
-          d.src = e.ring->slot_ptr(e.slot);
-          d.src_pitch = u32(e.w) * 3;
-          d.hist = set->d_res + e.hist_at;
-          d.sum_y = set->d_res + e.grid_at;
-          d.energy = set->d_res + e.grid_at + e.cells;
-          d.w = e.w;
-          d.h = e.h;
-          d.cell = prm.cell;
-          gpu::check_tamper(d, e.ring->slot_bytes(), e.cells);
-          set->h_descs[k] = d;
-        }
-        gpu::TamperPool::run(*set, int(todo.size()), hist_words, res_words, serve_stream_);
-        VEP_HIP(hipEventSynchronize(set->ev));
-        for (TamperEval* e : todo) {
-          const u32* r = set->h_res;
-          e->hist.assign(r + e->hist_at, r + e->hist_at + tamper::kBins);
-          e->sum_y.assign(r + e->grid_at, r + e->grid_at + e->cells);
-          e->energy.assign(r + e->grid_at + e->cells, r + e->grid_at + 2 * e->cells);
-        }
-      } catch (...) {
-        tamper_pool_.release(set);
-        throw;
+      gpu::TamperPool::Lease set = tamper_pool_.acquire();
+      set->reserve(int(todo.size()), res_words);
+      for (size_t k = 0; k < todo.size(); ++k) {
+        TamperEval& e = *todo[k];
+        gpu::TamperDesc d{};
+        d.src = e.ring->slot_ptr(e.slot);
+        d.src_pitch = u32(e.w) * 3;
+        d.hist = set->d_res.p + e.hist_at;
+        d.sum_y = set->d_res.p + e.grid_at;
+        d.energy = set->d_res.p + e.grid_at + e.cells;
+        d.w = e.w;
+        d.h = e.h;
+        d.cell = prm.cell;
+        gpu::check_tamper(d, e.ring->slot_bytes(), e.cells);
+        set->h_descs.p[k] = d;
       }
-      tamper_pool_.release(set);
+      set->run(int(todo.size()), hist_words, res_words, serve_stream_);
+      VEP_HIP(hipEventSynchronize(set->ev));
+      for (TamperEval* e : todo) {
+        const u32* r = set->h_res.p;
+        e->hist.assign(r + e->hist_at, r + e->hist_at + tamper::kBins);
+        e->sum_y.assign(r + e->grid_at, r + e->grid_at + e->cells);
+        e->energy.assign(r + e->grid_at + e->cells, r + e->grid_at + 2 * e->cells);
+      }
     } else {
       for (TamperEval* e : todo) {
         e->hist.resize(size_t(tamper::kBins));

@@ -764,7 +764,7 @@ class Worker {
   // Encode a device picture on the serving stream (host encoder if the kernels report an overflow).
   void encode_device(const u8* d_bgr, int w, int h, int quality, std::string& out);
   // ring slot -> ow x oh at the origin of set's canvas, on the serving stream (no wait)
-  void scale_slot(gpu::ScalePool::Set& set, const FrameRing& ring, int slot, int ow, int oh);
+  void scale_slot(gpu::ScaleSet& set, const FrameRing& ring, int slot, int ow, int oh);
   u8* cons_hwc_ = nullptr;
   void* cons_chw_ = nullptr;
   // consumer snapshots: exclusive while a snapshot is enqueued, shared while a lane enqueues a

@@ -97,3 +97,41 @@ def test_concurrent_encodes():
     for t in ts:
         t.join()
     assert not bad
+
+
+def test_more_callers_than_scratch_sets():
+    """8 threads, twice the pool's sets, 4 encodes each of a 17 x 9 picture: callers wait for a free
+    set, and every stream is the CPU's."""
+    from video_edge_ai_proxy_amd import ops
+
+    kinds = ["noise", "gradient", "checkerboard", "constant"]
+    pics = [picture(kinds[k % 4], 17, 9) for k in range(8)]
+    want = [ops.jpeg_encode_reference(p, 50 + 5 * k) for k, p in enumerate(pics)]
+    dev = [p.cuda() for p in pics]
+    torch.cuda.synchronize()
+    got, errors = {}, []
+
+    def run(k):
+        try:
+            for i in range(4):
+                got[k, i] = ops.jpeg_encode(dev[k], 50 + 5 * k)
+        except Exception as e:
+            errors.append(e)
+
+    ts = [threading.Thread(target=run, args=(k,)) for k in range(8)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errors and len(got) == 32
+    for (k, i), g in got.items():
+        assert g == want[k], f"thread {k} call {i}"
+
+
+def test_scratch_grows_and_comes_back():
+    """16 x 16, then 64 x 48 (a larger scratch), then 16 x 16 again: all three exact."""
+    from video_edge_ai_proxy_amd import ops
+
+    for w, h in ((16, 16), (64, 48), (16, 16)):
+        x = picture("noise", w, h)
+        assert ops.jpeg_encode(x.cuda(), 85) == ops.jpeg_encode_reference(x, 85), f"{w}x{h}"

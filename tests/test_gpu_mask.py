@@ -1,6 +1,8 @@
 """gfx950 privacy masks: byte equality of the kernel with the CPU implementation, inside guarded
 buffers, and the Worker's publish path (run on an MI355X). The CPU implementation is held to the
 independent oracle in tests/test_mask.py."""
+import threading
+
 import numpy as np
 import pytest
 import torch
@@ -135,6 +137,54 @@ def test_batch_of_33():
     for k in range(33):
         want = ops.privacy_mask_reference(torch.from_numpy(a[k]), lists[k]).numpy()
         assert np.array_equal(dev[k].cpu().numpy(), want), f"picture {k}"
+
+
+def test_more_callers_than_scratch_sets():
+    """8 threads, twice the pool's sets, 4 calls each with two overlapping masks: callers wait for
+    a free set, and every result is the CPU's."""
+    from video_edge_ai_proxy_amd import ops
+
+    masks = THREE_LEVELS[:2]
+    a = [mo.picture(mo.KINDS[k % 2], 37, 21, seed=k) for k in range(8)]
+    want = [ops.privacy_mask_reference(torch.from_numpy(x), masks).numpy() for x in a]
+    dev = [torch.from_numpy(x).cuda() for x in a]
+    torch.cuda.synchronize()
+    got, errors = {}, []
+
+    def run(k):
+        try:
+            for i in range(4):
+                got[k, i] = ops.privacy_mask(dev[k].clone(), masks)
+        except Exception as e:
+            errors.append(e)
+
+    ts = [threading.Thread(target=run, args=(k,)) for k in range(8)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errors and len(got) == 32
+    for (k, i), g in got.items():
+        assert np.array_equal(g.cpu().numpy(), want[k]), f"thread {k} call {i}"
+        assert not np.array_equal(want[k], a[k])
+
+
+def test_descriptors_grow_past_the_floor_and_come_back():
+    """One picture with one mask, then 9 pictures with 8 masks each (72 descriptors: more than the
+    64 a set starts with), then the one again: all three exact."""
+    from video_edge_ai_proxy_amd import ops
+
+    eight = [{"x0": 1000 * j, "y0": 500 * j, "x1": 1000 * j + 3000, "y1": 500 * j + 6000,
+              "mode": "fill" if j % 2 else "pixelate", "block": 4, "b": 10 * j, "g": 20 * j, "r": 30 * j}
+             for j in range(8)]
+    a = [mo.picture(mo.KINDS[k % 2], 24, 16, seed=k) for k in range(9)]
+    for n, lists in ((1, [eight[:1]]), (9, [eight] * 9), (1, [eight[:1]])):
+        dev = [torch.from_numpy(x).cuda() for x in a[:n]]
+        ops.privacy_mask_batch(dev, lists)
+        for k in range(n):
+            want = ops.privacy_mask_reference(torch.from_numpy(a[k]), lists[k]).numpy()
+            assert np.array_equal(dev[k].cpu().numpy(), want), f"{n} pictures, picture {k}"
+            assert not np.array_equal(want, a[k])
 
 
 def test_argument_checks():

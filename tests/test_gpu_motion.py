@@ -128,6 +128,54 @@ def test_batch_of_33():
         same(got[k], ops.motion_update_reference(b[k], want0[1], 8, 24, 2), f"picture {k}")
 
 
+def test_more_callers_than_scratch_sets():
+    """8 threads, twice the pool's sets, 4 calls each on 37 x 21 at the smallest cell: callers wait
+    for a free set, and every result is the CPU's."""
+    from video_edge_ai_proxy_amd import ops
+
+    a = [torch.from_numpy(mo.picture("noise", 37, 21, k)) for k in range(8)]
+    b = [torch.from_numpy(mo.picture("noise", 37, 21, 100 + k)) for k in range(8)]
+    bg = [ops.motion_update_reference(x, None, 4, 24, 4)[1] for x in a]
+    want = [ops.motion_update_reference(b[k], bg[k], 4, 24, 4) for k in range(8)]
+    dev = [(b[k].cuda(), bg[k].cuda()) for k in range(8)]
+    torch.cuda.synchronize()
+    got, errors = {}, []
+
+    def run(k):
+        try:
+            for i in range(4):
+                got[k, i] = ops.motion_update(dev[k][0], dev[k][1], 4, 24, 4)
+        except Exception as e:
+            errors.append(e)
+
+    ts = [threading.Thread(target=run, args=(k,)) for k in range(8)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errors and len(got) == 32
+    for (k, i), g in got.items():
+        same(g, want[k], f"thread {k} call {i}")
+        assert int(want[k][0].sum()) > 0
+
+
+def test_descriptors_grow_past_the_floor_and_come_back():
+    """One picture, then 65 in one launch (more than the 64 descriptors a set starts with), then
+    the one again: all three exact."""
+    from video_edge_ai_proxy_amd import ops
+
+    a = [torch.from_numpy(mo.picture("noise", 8, 8, k)) for k in range(65)]
+    b = [torch.from_numpy(mo.picture("noise", 8, 8, 100 + k)) for k in range(65)]
+    bg = [ops.motion_update_reference(x, None, 4, 24, 2)[1] for x in a]
+    want = [ops.motion_update_reference(b[k], bg[k], 4, 24, 2) for k in range(65)]
+    pics = [(b[k].cuda(), bg[k].cuda()) for k in range(65)]
+    for n in (1, 65, 1):
+        got = ops.motion_update_batch(pics[:n], 4, 24, 2)
+        assert len(got) == n
+        for k in range(n):
+            same(got[k], want[k], f"batch of {n}, picture {k}")
+
+
 def test_argument_checks():
     from video_edge_ai_proxy_amd import ops
 

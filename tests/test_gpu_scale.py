@@ -1,5 +1,7 @@
 """gfx950 area-average downscale: byte equality with the CPU implementation (run on an MI355X).
 The CPU implementation is held to the independent oracle in tests/test_scale.py."""
+import threading
+
 import pytest
 import torch
 
@@ -61,6 +63,34 @@ def test_out_argument():
                 torch.empty((119, 199, 3)).cuda(), torch.empty((119, 398, 3), dtype=torch.uint8).cuda()[:, ::2]):
         with pytest.raises(ValueError):
             ops.resize_area(x.cuda(), 199, 119, out=bad)
+
+
+def test_more_callers_than_scratch_sets():
+    """8 threads, twice the pool's sets, 4 calls each from 37 x 21 to 9 x 5: callers wait for a free
+    set, and every result is the CPU's."""
+    from video_edge_ai_proxy_amd import ops
+
+    a = [torch.from_numpy(so.picture(so.KINDS[k % 4], 37, 21, seed=k)) for k in range(8)]
+    want = [ops.resize_area_reference(x, 9, 5) for x in a]
+    dev = [x.cuda() for x in a]
+    torch.cuda.synchronize()
+    got, errors = {}, []
+
+    def run(k):
+        try:
+            for i in range(4):
+                got[k, i] = ops.resize_area(dev[k], 9, 5)
+        except Exception as e:
+            errors.append(e)
+
+    ts = [threading.Thread(target=run, args=(k,)) for k in range(8)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errors and len(got) == 32
+    for (k, i), g in got.items():
+        assert torch.equal(g.cpu(), want[k]), f"thread {k} call {i}"
 
 
 def test_argument_checks():

@@ -90,6 +90,49 @@ def test_batch_of_33():
         same(got[k], ops.tamper_stats_reference(a[k], 8), f"picture {k}")
 
 
+def test_more_callers_than_scratch_sets():
+    """8 threads, twice the pool's sets, 4 calls each on 37 x 21 at the smallest cell: callers wait
+    for a free set, and every result is the CPU's."""
+    from video_edge_ai_proxy_amd import ops
+
+    a = [torch.from_numpy(to.picture(to.KINDS[k % 6], 37, 21, k)) for k in range(8)]
+    want = [ops.tamper_stats_reference(x, 8) for x in a]
+    dev = [x.cuda() for x in a]
+    torch.cuda.synchronize()
+    got, errors = {}, []
+
+    def run(k):
+        try:
+            for i in range(4):
+                got[k, i] = ops.tamper_stats(dev[k], 8)
+        except Exception as e:
+            errors.append(e)
+
+    ts = [threading.Thread(target=run, args=(k,)) for k in range(8)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errors and len(got) == 32
+    for (k, i), g in got.items():
+        same(g, want[k], f"thread {k} call {i}")
+
+
+def test_descriptors_grow_past_the_floor_and_come_back():
+    """One picture, then 65 in one launch (more than the 64 descriptors a set starts with), then
+    the one again: all three exact."""
+    from video_edge_ai_proxy_amd import ops
+
+    a = [torch.from_numpy(to.picture(to.KINDS[k % 6], 8, 8, k)) for k in range(65)]
+    want = [ops.tamper_stats_reference(x, 8) for x in a]
+    dev = [x.cuda() for x in a]
+    for n in (1, 65, 1):
+        got = ops.tamper_stats_batch(dev[:n], 8)
+        assert len(got) == n
+        for k in range(n):
+            same(got[k], want[k], f"batch of {n}, picture {k}")
+
+
 @pytest.mark.parametrize("w,h,cell", [(33, 17, 16), (7, 5, 8), (1, 9, 8), (1921, 3, 16), (300, 260, 128)])
 def test_result_buffers_kept_clean(w, h, cell):
     """The results lie inside guarded buffers pre-filled with a sentinel: every bin and every cell

@@ -50,6 +50,18 @@ def test_more_tiles_than_lanes():
     assert torch.equal(got.cpu(), ops.compose_wall_reference(host(fs), None, 16, 9))
 
 
+def test_descriptors_grow_past_the_floor_and_come_back():
+    """One tile, then 65 tiles of 8 x 8 in 4 x 4 cells (81 cells: more than the 64 descriptors a set
+    starts with), then the one again: all three exact."""
+    from video_edge_ai_proxy_amd import ops
+
+    fs = [so.picture(so.KINDS[t % 4], 8, 8, seed=t) for t in range(65)]
+    d = dev(fs)
+    for n in (1, 65, 1):
+        got = ops.compose_wall(d[:n], None, 4, 4)
+        assert torch.equal(got.cpu(), ops.compose_wall_reference(host(fs[:n]), None, 4, 4)), f"{n} tiles"
+
+
 def test_reused_canvas_has_no_stale_pixels():
     from video_edge_ai_proxy_amd import ops
 

@@ -1,4 +1,5 @@
-"""ThreadSanitizer / AddressSanitizer runs of the native stress driver (csrc/tests/native_stress.cpp).
+"""ThreadSanitizer / AddressSanitizer runs of the native stress driver (csrc/tests/native_stress.cpp)
+and of the scratch pool's stand-alone selftest (csrc/tests/scratch_selftest.cpp).
 
 Host-code sanitizers only (`-Xarch_host -fsanitize=...`; GPU sanitizers are unavailable), CPU
 backend. Building takes about a minute per sanitizer, so the test runs when VEP_SANITIZERS=1
@@ -13,13 +14,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.skipif(os.environ.get("VEP_SANITIZERS") != "1", reason="set VEP_SANITIZERS=1")
-@pytest.mark.parametrize("target", ["tsan", "asan"])
+@pytest.mark.parametrize("target", ["tsan", "asan", "tsan-scratch", "asan-scratch"])
 def test_native_stress_under_sanitizer(target):
     r = subprocess.run(["make", "-C", ROOT, target], capture_output=True, text=True, timeout=900)
     out = r.stdout + r.stderr
     assert r.returncode == 0, out[-4000:]
-    assert "native_stress ok" in out
+    assert ("scratch_selftest ok" if target.endswith("-scratch") else "native_stress ok") in out
     assert "WARNING: ThreadSanitizer" not in out and "ERROR: AddressSanitizer" not in out
+
+
+def test_scratch_selftest():
+    """The scratch pool's locking (csrc/vep/scratch.h), un-instrumented: bounded sets and leases
+    under 16 threads, a set never shared, returned on a throw, moved leases, the wait for a free
+    set, and no growth in steady state."""
+    r = subprocess.run(["make", "-C", ROOT, "scratch-selftest"], capture_output=True, text=True, timeout=300)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-4000:]
+    assert "scratch_selftest ok" in out
 
 
 def test_sanitizer_target_links():
