@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask tsan-scratch asan-scratch scratch-selftest tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -147,6 +147,30 @@ asan-scratch: $(ASAN_DIR)/scratch_selftest
 
 scratch-selftest: build/selftest/scratch_selftest
 	cd /tmp && $(CURDIR)/build/selftest/scratch_selftest
+
+# The stage plan's invariants on real jobs (csrc/tests/stage_plan_selftest.cpp on vep/stage_plan.h,
+# jobs from the cameras of a CPU-backend Worker): a stand-alone host program, no GPU. Linked
+# against the objects csrc/build.py made (default CPU suite), and built from sources under
+# AddressSanitizer + UndefinedBehaviorSanitizer. The shift-base check is off: the codecs that
+# make the jobs shift negative values left in seven places (avc_recon.h filter_samples, which the
+# kernels share, hevc_ctu.cpp, hevc_recon.cpp); the plan itself shifts nothing signed.
+plan-selftest: build
+	mkdir -p build/selftest
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -c csrc/tests/stage_plan_selftest.cpp -Icsrc \
+	  -o build/selftest/stage_plan_selftest.o
+	$(HIPCC) --offload-arch=$(ARCH) build/selftest/stage_plan_selftest.o build/obj/vep__*.o \
+	  -o build/selftest/stage_plan_selftest -lpthread
+	cd /tmp && $(CURDIR)/build/selftest/stage_plan_selftest
+
+$(ASAN_DIR)/stage_plan_selftest: $(SRCS) $(HIP_SRCS) csrc/tests/stage_plan_selftest.cpp $(wildcard csrc/vep/*.h)
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize=shift-base -Xarch_host -fno-sanitize-recover=undefined \
+	  -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc $(SRCS) csrc/tests/stage_plan_selftest.cpp -x hip $(HIP_SRCS) -o $@ -lpthread
+
+asan-plan: $(ASAN_DIR)/stage_plan_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/stage_plan_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

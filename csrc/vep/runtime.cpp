@@ -13,6 +13,7 @@
 #include "color.h"
 #include "jpeg.h"
 #include "scale.h"
+#include "stage_plan.h"
 #include "trace.h"
 
 namespace vep {
@@ -632,7 +633,7 @@ Worker::Worker(const WorkerOptions& o) : opt_(o), dev_(o.device) {
       const char* lc = std::getenv("VEP_LANE_COPY");
       if (lanes_.size() > 1 && lc && std::atoi(lc) == 1)
         VEP_HIP(hipStreamCreateWithFlags(&ln.copy, hipStreamNonBlocking));
-      ln.stage.resize(size_t(stages_));
+      ln.stage = std::vector<Stage>(size_t(stages_));  // (a Stage owns its buffers: not movable)
       for (Stage& st : ln.stage) {
         VEP_HIP(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
         VEP_HIP(hipEventCreate(&st.e0));
@@ -733,16 +734,11 @@ Worker::~Worker() {
   for (auto& lp : lanes_) {
     Lane& ln = *lp;
     for (Stage& st : ln.stage) {
-      dev_.free_pinned(st.err);
-      if (st.mask_h) dev_.free_pinned(st.mask_h);
-      if (st.mask_d) dev_.free(st.mask_d);
-      if (st.h) hostmem::unregister_range(st.h);
-      dev_.free(st.d);
-      dev_.free_pinned(st.h);
       if (st.copied) (void)hipEventDestroy(st.copied);
       if (st.e0) (void)hipEventDestroy(st.e0);
       if (st.e1) (void)hipEventDestroy(st.e1);
     }
+    ln.stage.clear();  // (their buffers go here: lanes drained, device bound, streams still alive)
     if (ln.stream && ln.stream != stream_) (void)hipStreamDestroy(ln.stream);
     if (ln.copy) (void)hipStreamDestroy(ln.copy);
     if (ln.snap_mark) (void)hipEventDestroy(ln.snap_mark);
@@ -1328,11 +1324,11 @@ void Worker::reserve_history(Camera& c, DecodeJob& j) {
 
 namespace {
 
-// Coded-MB bitmask + per-word exclusive prefix, and the raster-order list of sample blocks.
+// Coded-MB bitmask + per-word exclusive prefix, and the raster-order table of sample blocks:
+// table[k] = where(segment, byte offset inside it) of the k-th coded MB's samples.
 // O(coded MBs), not O(picture MBs): a P frame touches a few hundred of 8,160 MBs.
-// seg_off[s] = staging byte offset (relative to the job's payload base) of segment s.
-void build_index(const MbUpdate& u, const std::vector<size_t>& seg_off, u32* mask, u32* prefix,
-                 u32* offsets) {
+template <class T, class Where>
+void build_index(const MbUpdate& u, u32* mask, u32* prefix, T* table, Where where) {
   const int words = (u.mbs() + 31) / 32;
   std::memset(mask, 0, size_t(words) * sizeof(u32));
   const std::vector<i32>* list = &u.coded;
@@ -1347,7 +1343,7 @@ void build_index(const MbUpdate& u, const std::vector<size_t>& seg_off, u32* mas
     mask[mb >> 5] |= 1u << (mb & 31);
     const int s = u.slot[size_t(mb)];
     const u32 g = u.slot_seg[size_t(s)];
-    offsets[k++] = u32(seg_off[g] + size_t(u.block(s) - u.segs[g].base));
+    table[k++] = where(g, size_t(u.block(s) - u.segs[g].base));
   }
   u32 run = 0;
   for (int w = 0; w < words; ++w) {
@@ -1355,349 +1351,170 @@ void build_index(const MbUpdate& u, const std::vector<size_t>& seg_off, u32* mas
     run += u32(__builtin_popcount(mask[w]));
   }
 }
-
-// Direct mode: per coded MB the device address of its samples inside host memory (pinned AU
-// block or staging), instead of an offset into a device-side copy.
-void build_index_ptrs(const MbUpdate& u, const std::vector<const u8*>& seg_dev, u32* mask,
-                      u32* prefix, u64* ptrs) {
-  const int words = (u.mbs() + 31) / 32;
-  std::memset(mask, 0, size_t(words) * sizeof(u32));
-  const std::vector<i32>* list = &u.coded;
-  std::vector<i32> sorted;
-  if (!std::is_sorted(u.coded.begin(), u.coded.end())) {
-    sorted = u.coded;
-    std::sort(sorted.begin(), sorted.end());
-    list = &sorted;
-  }
-  size_t k = 0;
-  for (i32 mb : *list) {
-    mask[mb >> 5] |= 1u << (mb & 31);
-    const int s = u.slot[size_t(mb)];
-    const u32 g = u.slot_seg[size_t(s)];
-    ptrs[k++] = reinterpret_cast<u64>(seg_dev[g] + (u.block(s) - u.segs[g].base));
-  }
-  u32 run = 0;
-  for (int w = 0; w < words; ++w) {
-    prefix[w] = run;
-    run += u32(__builtin_popcount(mask[w]));
-  }
-}
-
-constexpr size_t kPackChunk = size_t(1) << 20;  // bytes per copy task
 
 }  // namespace
 
+void Worker::StagePair::reserve(size_t need) {
+  if (need <= cap) return;
+  release();
+  const size_t want = std::max(need + need / 2, size_t(4) << 20);
+  void* p = nullptr;
+  VEP_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
+  h = static_cast<u8*>(p);
+  VEP_HIP(hipMalloc(&p, want));
+  d = static_cast<u8*>(p);
+  void* hd = nullptr;
+  if (hipHostGetDevicePointer(&hd, h, 0) != hipSuccess) hd = h;
+  h_dev = static_cast<const u8*>(hd);
+  hostmem::register_range(h, want, h_dev);
+  cap = want;  // (only now: a pair whose growth threw is empty and grows again)
+}
+
+void Worker::StagePair::release() {
+  if (cap) hostmem::unregister_range(h);
+  cap = 0;
+  if (d) (void)hipFree(d);
+  if (h) (void)hipHostFree(h);
+  h = d = nullptr;
+  h_dev = nullptr;
+}
+
+// One batch on a lane. Slice bytes stay in host memory: pinned AU blocks as received (hostmem.h),
+// or the stage's pinned half for pageable AUs (one host memcpy). Two ways to the GPU:
+//  * direct (default): decode_convert reads each block straight over PCIe from its host address
+//    (per-MB 64-bit pointer table) — no device copy of the payload at all;
+//  * gather: a gather kernel first pulls the slices into the device half, and the kernel reads
+//    per-MB offsets into that copy.
+// stage_plan.h has the layout of the buffer pair.
 void Worker::launch_gpu(Lane& ln, Stage& st) {
-  const hipStream_t cs = ln.stream;
-  std::vector<DecodeJob>& jobs = st.jobs;
+  const StagePlan pl(st.jobs, {direct_reads_, hevc_tu_window_});
+  check_plan(pl, st);
+  Described ds;
+  const i64 t_res0 = mono_us();
+  reserve_stage(pl, st, ds);
+  const i64 t_res = mono_us() - t_res0;  // (counted as enqueue time, where its parts always were)
+  stage_batch(pl, st);
+  const i64 t_enq0 = mono_us();
+  describe_outputs(pl, st, ds);
+  describe_history(pl, st);
+  for (size_t r = 0; r < pl.avc_rounds.size(); ++r) describe_avc_round(pl, r, st);
+  for (size_t r = 0; r < pl.hevc_rounds.size(); ++r) describe_hevc_round(pl, r, st, ds);
+  describe_masks(st, ds);
+  enqueue(pl, ln, st, ds);
+  add_time(&Timers::enqueue, double(mono_us() - t_enq0 + t_res));
+}
+
+// The checks of a batch that need its cameras' surfaces and rings (StagePlan makes those that
+// need only the jobs).
+void Worker::check_plan(const StagePlan& pl, const Stage& st) {
+  auto surface = [&](int job) -> const Camera::Surface& { return cams_[size_t(st.jobs[size_t(job)].cam)]->surface; };
+  for (int i : pl.outs) {
+    const DecodeJob& j = st.jobs[size_t(i)];
+    const Camera::Surface& sf = surface(i);
+    if (j.out_fields)
+      VEP_CHECK(sf.y8 && sf.bps == 1 && sf.hmbs % 2 == 0, "field pair output without its weave scratch");
+    if (opt_.letterbox_size > 0) VEP_CHECK(j.cam < st.cons_rows, "camera index exceeds consumer batch rows");
+  }
+  for (const StagePlan::AvcPic& a : pl.avc)
+    VEP_CHECK(surface(a.job).bd == a.p->bd && surface(a.job).cf == a.p->cf,
+              "H.264: picture bit depth / chroma format differs from the camera's surfaces");
+  for (const StagePlan::HevcPic& a : pl.hevc) {
+    VEP_CHECK(surface(a.job).bps == (a.p->wide() ? 2 : 1), "HEVC: picture bit depth differs from the camera's surfaces");
+    VEP_CHECK(surface(a.job).slots > st.jobs[size_t(a.job)].hevc_slots, "camera surfaces lack the SAO scratch slot");
+  }
+  for (const StagePlan::HistOut& h : pl.hist) {  // (the plan counted its tiles from the picture's coded size)
+    const DecodeJob& j = st.jobs[size_t(h.job)];
+    const JobOutput& o = j.outputs[size_t(h.out)];
+    const Camera::Surface& sf = surface(h.job);
+    const FrameRing& ring = *cams_[size_t(j.cam)]->ring_;
+    VEP_CHECK(o.slot < sf.slots && o.pic.width == ring.width() && o.pic.height == ring.height() &&
+                  o.pic.coded_width == sf.wmbs * 16 && o.pic.coded_height == sf.hmbs * 16,
+              "history output does not match the camera's surfaces");
+  }
+  for (const DecodeJob& j : st.jobs) {
+    if (!j.ext) continue;
+    const Camera::Surface& sf = cams_[size_t(j.cam)]->surface;
+    VEP_CHECK(j.ext->width <= sf.wmbs * 16 && j.ext->height <= sf.hmbs * 16, "VCN picture exceeds the camera surface");
+  }
+}
+
+// Every allocation of the batch, and nothing later: the buffer pair, the error words (cleared),
+// the mask descriptors (under the lists the cameras have now: publish() commits a slot only if
+// its camera's list is still that one) and each H.265 camera's intra edge exchange.
+void Worker::reserve_stage(const StagePlan& pl, Stage& st, Described& ds) {
+  const size_t n = st.jobs.size();
+  st.buf.reserve(pl.need);  // (the stage's previous batch is complete: nothing reads the old buffers)
+  if (st.err.cap < n) {
+    st.err.reserve(n, 64);
+    void* ed = nullptr;
+    if (hipHostGetDevicePointer(&ed, st.err.p, 0) != hipSuccess) ed = st.err.p;
+    st.err_dev = static_cast<u32*>(ed);
+  }
+  std::memset(st.err.p, 0, n * sizeof(u32));
+  if (snapshot_masks(st.jobs, st.mask_snap)) {
+    size_t nd = 0;
+    for (size_t i = 0; i < n; ++i) {
+      size_t slots_of = st.jobs[i].has_output() ? 1 : 0;
+      for (const JobOutput& o : st.jobs[i].outputs) slots_of += o.ring_slot >= 0 ? 1 : 0;
+      nd += slots_of * size_t(st.mask_snap[i].n);
+    }
+    VEP_CHECK(nd <= 65535, "mask descriptors miscounted");
+    if (nd > 0) {
+      st.mask_h.reserve(nd, 256);
+      st.mask_d.reserve(nd, 256);
+    }
+    ds.nmask = int(nd);
+  }
+  // the cameras' intra edge exchanges (zeroed once: epochs start at 1), one epoch per round
+  ds.hevc_epoch.resize(pl.hevc.size());
+  for (const StagePlan::HevcRound& rd : pl.hevc_rounds) {
+    for (int k : rd.pics) {
+      Camera::Surface& sf = cams_[size_t(st.jobs[size_t(pl.hevc[size_t(k)].job)].cam)]->surface;
+      const size_t words = gpu::hevc_xg_words(sf.wmbs * 16, sf.hmbs * 16);
+      if (sf.hevc_xg_words < words) {
+        dev_.free(sf.hevc_xg);
+        sf.hevc_xg = static_cast<u64*>(dev_.alloc(words * sizeof(u64)));
+        VEP_HIP(hipMemset(sf.hevc_xg, 0, words * sizeof(u64)));
+        sf.hevc_xg_words = words;
+        sf.hevc_epoch = 0;
+      }
+      if (++sf.hevc_epoch == 0) {  // (after 2^32 rounds) never reuse a tag still in the words
+        VEP_HIP(hipMemset(sf.hevc_xg, 0, words * sizeof(u64)));
+        sf.hevc_epoch = 1;
+      }
+      ds.hevc_epoch[size_t(k)] = sf.hevc_epoch;
+    }
+  }
+}
+
+// The pinned half's bulk: gather chunks, then (pack threads) per job the coded-MB bitmask,
+// prefix and per-MB offsets or pointers, then the copies of records and pageable segments.
+void Worker::stage_batch(const StagePlan& pl, Stage& st) {
+  const std::vector<DecodeJob>& jobs = st.jobs;
   const int n = int(jobs.size());
-  st.mask_snap.clear();  // (taken after the conversions are enqueued, below)
-  // Slice bytes stay in host memory: pinned AU blocks as received (hostmem.h), or this stage's
-  // pinned staging buffer for pageable AUs (one host memcpy). Two ways to the GPU:
-  //  * direct (default): decode_convert reads each block straight over PCIe from its host
-  //    address (per-MB 64-bit pointer table) — no device copy of the payload at all;
-  //  * gather: a gather kernel on the copy stream first pulls the slices into device staging,
-  //    and the kernel reads per-MB offsets into that copy.
-  // Layout: [descs][letterbox descs][gather chunks][per job: mask, prefix, offsets|ptrs]
-  // | [per job: staged payload]. Only the header part is copied by SDMA.
-  const bool direct = direct_reads_;
-  const size_t off_desc = 0;
-  const size_t off_lb = al(sizeof(gpu::DecodeDesc) * size_t(n));
-  size_t nchunks = 0;
-  auto chunks_of = [](size_t len) { return (len + gpu::kGatherChunk - 1) / gpu::kGatherChunk; };
-  if (!direct)
-    for (const auto& j : jobs)
-      for (const auto& sg : j.upd.segs) nchunks += chunks_of(sg.len);
-  // record arrays already in pinned pool memory (hostmem::PinnedAllocator) are gathered by the
-  // GPU over PCIe instead of being copied into the staging buffer by the host
-  auto pinned = [](const void* p, size_t len) {
-    return len > 0 && hostmem::device_address(static_cast<const u8*>(p), len) != nullptr;
-  };
-  const size_t off_wv = off_lb + al(sizeof(gpu::LetterboxDesc) * size_t(n));  // field-pair weaves
-  size_t need = off_wv + al(sizeof(gpu::WeaveDesc) * size_t(n));
-  // Frame history: the outputs with a ring slot (reserve_history), by the reconstruction round
-  // (= index of the job picture) that released them; one surface_to_bgr launch after each such
-  // round, before the next round may reuse their surfaces.
-  struct HistOut {
-    int round, job, out;
-  };
-  std::vector<HistOut> hist;
-  for (int i = 0; i < n; ++i)
-    for (size_t k = 0; k < jobs[size_t(i)].outputs.size(); ++k)
-      if (jobs[size_t(i)].outputs[k].ring_slot >= 0) hist.push_back({jobs[size_t(i)].outputs[k].released_by, i, int(k)});
-  const size_t off_hist = need;
-  need += al(sizeof(gpu::SurfaceBgrDesc) * hist.size());
-  std::vector<size_t> mask_off(static_cast<size_t>(n)), pay_off(static_cast<size_t>(n));
-  std::vector<std::vector<size_t>> seg_off(static_cast<size_t>(n));
-  auto words_of = [&](int i) { return size_t(jobs[size_t(i)].upd.mbs() + 31) / 32; };
-  const size_t ent = direct ? sizeof(u64) : sizeof(u32);
-  for (int i = 0; i < n; ++i) {
-    mask_off[size_t(i)] = need;
-    need += 2 * al(words_of(i) * sizeof(u32), 16) +
-            al(size_t(jobs[size_t(i)].upd.nslots) * ent, 16);
+  u8* const h = st.buf.h;
+  auto* gc = reinterpret_cast<gpu::GatherChunk*>(h + pl.gather.off);
+  for (size_t k = 0; k < pl.chunks.size(); ++k) {
+    const StagePlan::Chunk& c = pl.chunks[k];
+    gc[k] = {c.src ? c.src : st.buf.h_dev + c.dst, st.buf.d + c.dst, c.len, 0};
   }
-  // General H.264 pictures: MB records, coefficient blocks and motion vectors of every picture,
-  // plus one AvcDesc array per reconstruction round (round r = r-th picture of each job).
-  struct AvcPic {
-    const avc::Picture* p;
-    int job;
-    size_t off_mbs, off_coef, off_mv, off_wp, off_dbk, off_res, off_xg;
-  };
-  std::vector<AvcPic> apics;
-  int rounds = 0;
-  for (int i = 0; i < n; ++i) rounds = std::max(rounds, int(jobs[size_t(i)].avc.size()));
-  std::vector<size_t> off_round(static_cast<size_t>(rounds));
-  std::vector<std::vector<int>> round_pics(static_cast<size_t>(rounds));
-  for (int r = 0; r < rounds; ++r) {
-    for (int i = 0; i < n; ++i) {
-      const auto& v = jobs[size_t(i)].avc;
-      if (int(v.size()) <= r) continue;
-      const avc::Picture& p = *v[size_t(r)];
-      VEP_CHECK(p.hmbs <= gpu::kAvcMaxRows && p.wmbs <= gpu::kAvcMaxCols,
-                "picture too large for the wavefront kernels");
-      VEP_CHECK(p.wmbs * 16 == jobs[size_t(i)].pic.coded_width &&
-                    p.hmbs * 16 * (p.structure ? 2 : 1) == jobs[size_t(i)].pic.coded_height,  // (a field: half)
-                "picture size differs from the camera's surfaces");
-      AvcPic a{&p, i, 0, 0, 0, 0, 0, 0, 0};
-      auto put = [&](const void* src, size_t bytes) {
-        const size_t o = need;
-        need += al(bytes);
-        if (pinned(src, bytes)) nchunks += chunks_of(bytes);
-        return o;
-      };
-      a.off_mbs = put(p.mbs.data(), p.mbs.size() * sizeof(avc::MbRec));
-      a.off_coef = put(p.coefs.data(), p.coefs.size() * sizeof(i16));
-      a.off_mv = put(p.mvs.data(), p.mvs.size() * sizeof(i16));
-      a.off_wp = put(p.wps.data(), p.wps.size() * sizeof(avc::WpEntry));
-      round_pics[size_t(r)].push_back(int(apics.size()));
-      apics.push_back(a);
-    }
-    off_round[size_t(r)] = need;
-    need += al(round_pics[size_t(r)].size() * sizeof(gpu::AvcDesc));
-  }
-  // General H.265 pictures: reconstruction records of every picture, one HevcDesc array and one
-  // level-range table per round.
-  struct HevcPic {
-    const hevc::GpuPicture* p;
-    int job;
-    size_t off_pu, off_tu, off_coef, off_pcm, off_bsv, off_bsh, off_qp, off_pcmmap, off_cslice, off_slices, off_sao;
-    size_t off_wp, off_ctile;
-  };
-  std::vector<HevcPic> hpics;
-  int hrounds = 0;
-  for (int i = 0; i < n; ++i) hrounds = std::max(hrounds, int(jobs[size_t(i)].hevc.size()));
-  std::vector<size_t> off_hround(static_cast<size_t>(hrounds)), off_hranges(static_cast<size_t>(hrounds));
-  std::vector<std::vector<int>> hround_pics(static_cast<size_t>(hrounds));
-  std::vector<std::vector<gpu::HevcTuRange>> hranges(static_cast<size_t>(hrounds));
-  // per round: level-0 ranges, level-0 blocks, intra (queue) ranges, intra blocks
-  std::vector<std::array<int, 4>> hwork(static_cast<size_t>(hrounds), std::array<int, 4>{0, 0, 0, 0});
-  std::vector<size_t> off_hctr(static_cast<size_t>(hrounds)), off_hpicq(static_cast<size_t>(hrounds));
-  // per round, picture mode (hevc_tu_window_ < 0): {desc, first intra block, intra blocks} per picture
-  std::vector<std::vector<gpu::HevcTuRange>> hpicq(static_cast<size_t>(hrounds));
-  // per round and intra level: first ticket, blocks (the one-launch-per-level mode); per round
-  // and queue window: first ticket, blocks (one ticket counter each)
-  std::vector<std::vector<std::array<int, 2>>> hlevels(static_cast<size_t>(hrounds));
-  std::vector<std::vector<std::array<int, 2>>> hwindows(static_cast<size_t>(hrounds));
-  for (int r = 0; r < hrounds; ++r) {
-    int maxl = 0;
-    for (int i = 0; i < n; ++i) {
-      const auto& v = jobs[size_t(i)].hevc;
-      if (int(v.size()) <= r) continue;
-      const hevc::GpuPicture& p = *v[size_t(r)];
-      VEP_CHECK(((p.width + 15) & ~15) == jobs[size_t(i)].pic.coded_width &&
-                    ((p.height + 15) & ~15) == jobs[size_t(i)].pic.coded_height,
-                "picture size differs from the camera's surfaces");
-      HevcPic a{&p, i, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      auto put = [&](size_t bytes) {
-        const size_t o = need;
-        need += al(std::max<size_t>(bytes, 16));
-        return o;
-      };
-      a.off_pu = put(p.pus.size() * sizeof(hevc::GpuPu));
-      a.off_tu = put(p.tus.size() * sizeof(hevc::GpuTu));
-      a.off_coef = put(p.coefs.size() * sizeof(i16));
-      a.off_pcm = put(p.pcm.size());
-      a.off_bsv = put(p.bs_v.size());
-      a.off_bsh = put(p.bs_h.size());
-      a.off_qp = put(p.qp.size());
-      a.off_pcmmap = put(p.pcm_map.size());
-      a.off_cslice = put(p.ctb_slice.size() * sizeof(u16));
-      a.off_slices = put(p.slices.size() * sizeof(hevc::GpuSlice));
-      a.off_sao = put(p.sao_params.size() * sizeof(hevc::GpuSao));
-      a.off_wp = put(p.wp.size() * sizeof(hevc::GpuWp));
-      a.off_ctile = put(p.ctb_tile.size() * sizeof(u16));
-      maxl = std::max(maxl, int(p.level_begin.size()) - 1);
-      hround_pics[size_t(r)].push_back(int(hpics.size()));
-      hpics.push_back(a);
-    }
-    off_hround[size_t(r)] = need;
-    need += al(hround_pics[size_t(r)].size() * sizeof(gpu::HevcDesc));
-    // level 0 (inter residual + PCM, independent blocks): one range per picture, one wide
-    // launch. Intra levels >= 1: one ticket queue for the whole round, level-major (a block's
-    // producers are at lower levels, so they hold lower tickets).
-    int tickets = 0;
-    for (int l = 0; l < maxl; ++l) {
-      if (l > 0) hlevels[size_t(r)].push_back({tickets, 0});
-      for (size_t k = 0; k < hround_pics[size_t(r)].size(); ++k) {
-        const hevc::GpuPicture& p = *hpics[size_t(hround_pics[size_t(r)][k])].p;
-        if (int(p.level_begin.size()) - 1 <= l) continue;
-        const int b = int(p.level_begin[size_t(l)]), e = int(p.level_begin[size_t(l) + 1]);
-        if (e <= b) continue;
-        if (l == 0) {
-          hranges[size_t(r)].push_back({int(k), b, e - b, hwork[size_t(r)][1]});
-          hwork[size_t(r)][0] += 1;
-          hwork[size_t(r)][1] += e - b;
-        } else {
-          hranges[size_t(r)].push_back({int(k), b, e - b, tickets});
-          hwork[size_t(r)][2] += 1;
-          tickets += e - b;
-          hlevels[size_t(r)].back()[1] += e - b;
-        }
-      }
-    }
-    hwork[size_t(r)][3] = tickets;
-    if (hevc_tu_window_ < 0) {  // one workgroup per picture with intra blocks
-      for (size_t k = 0; k < hround_pics[size_t(r)].size(); ++k) {
-        const hevc::GpuPicture& p = *hpics[size_t(hround_pics[size_t(r)][k])].p;
-        if (p.level_begin.size() < 3) continue;  // (levels 0 .. L-1 plus the end: intra needs L >= 2)
-        const int b = int(p.level_begin[1]), e = int(p.tus.size());
-        if (e > b) hpicq[size_t(r)].push_back({int(k), b, e - b, 0});
-      }
-    }
-    if (hevc_tu_window_ > 0) {  // consecutive levels, hevc_tu_window_ per launch
-      const auto& lv = hlevels[size_t(r)];
-      for (size_t l = 0; l < lv.size(); l += size_t(hevc_tu_window_)) {
-        const size_t e = std::min(lv.size(), l + size_t(hevc_tu_window_));
-        const int first = lv[l][0], last = lv[e - 1][0] + lv[e - 1][1];
-        if (last > first) hwindows[size_t(r)].push_back({first, last - first});
-      }
-    }
-    off_hranges[size_t(r)] = need;
-    need += al(std::max<size_t>(hranges[size_t(r)].size(), 1) * sizeof(gpu::HevcTuRange));
-    off_hctr[size_t(r)] = need;  // the queue windows' ticket counters (zero in the upload)
-    need += al(std::max<size_t>(hwindows[size_t(r)].size(), 1) * sizeof(u32));
-    off_hpicq[size_t(r)] = need;
-    need += al(std::max<size_t>(hpicq[size_t(r)].size(), 1) * sizeof(gpu::HevcTuRange));
-  }
-  const size_t off_gather = need;  // gather chunks: pinned records (+ slices without direct reads)
-  need += al(sizeof(gpu::GatherChunk) * std::max<size_t>(nchunks, 1));
-  need = al(need);
-  const size_t header_bytes = need;
-  for (int i = 0; i < n; ++i) {
-    pay_off[size_t(i)] = need;
-    size_t rel = 0;
-    for (const auto& sg : jobs[size_t(i)].upd.segs) {
-      seg_off[size_t(i)].push_back(rel);
-      rel += al(sg.len, 16);
-    }
-    need += rel;
-  }
-  need = al(need);
-  for (AvcPic& a : apics) {  // device-only scratch (never copied): per-MB loop-filter inputs,
-    a.off_dbk = need;         // intra MBs' residual samples (inter kernel -> intra wavefront)
-    need += al(size_t(a.p->nmbs()) * sizeof(gpu::AvcDbkInfo));
-    a.off_res = need;
-    need += al(size_t(a.p->intra_res) * gpu::kAvcResSamples * sizeof(i16));
-    a.off_xg = need;  // deblock exchange between the wavefront's workgroups
-    need += al(gpu::avc_xg_bytes(a.p->wmbs, a.p->hmbs));
-  }
-  need = al(need);
-  if (need > st.cap) {
-    if (st.h) hostmem::unregister_range(st.h);
-    dev_.free(st.d);
-    dev_.free_pinned(st.h);
-    st.cap = std::max(need + need / 2, size_t(4) << 20);
-    st.h = static_cast<u8*>(dev_.alloc_pinned(st.cap));
-    st.d = static_cast<u8*>(dev_.alloc(st.cap));
-    void* hd_ptr = nullptr;
-    if (hipHostGetDevicePointer(&hd_ptr, st.h, 0) != hipSuccess) hd_ptr = st.h;
-    hostmem::register_range(st.h, st.cap, static_cast<u8*>(hd_ptr));
-  }
-  auto mask_ptr = [&](u8* base, int i) { return reinterpret_cast<u32*>(base + mask_off[size_t(i)]); };
-  auto prefix_ptr = [&](u8* base, int i) {
-    return reinterpret_cast<u32*>(base + mask_off[size_t(i)] + al(words_of(i) * sizeof(u32), 16));
-  };
-  auto table_ptr = [&](u8* base, int i) {
-    return base + mask_off[size_t(i)] + 2 * al(words_of(i) * sizeof(u32), 16);
-  };
-  // Phase 1: where each segment's bytes are readable by the GPU (staging pageable ones).
-  struct CopyTask {
-    const u8* src;
-    u8* dst;
-    size_t len;
-  };
-  std::vector<CopyTask> tasks;
-  auto* gc = reinterpret_cast<gpu::GatherChunk*>(st.h + off_gather);
-  size_t ng = 0;
-  for (const AvcPic& a : apics) {
-    auto add = [&](const void* src, size_t len, size_t off) {
-      if (pinned(src, len)) {  // the GPU pulls it (gather kernel after the header copy)
-        const u8* dv = hostmem::device_address(static_cast<const u8*>(src), len);
-        for (size_t o = 0; o < len; o += gpu::kGatherChunk)
-          gc[ng++] = {dv + o, st.d + off + o, u32(std::min<size_t>(gpu::kGatherChunk, len - o)), 0};
-        records_gathered_ += u64(len);
-        return;
-      }
-      for (size_t o = 0; o < len; o += kPackChunk)
-        tasks.push_back({static_cast<const u8*>(src) + o, st.h + off + o, std::min(kPackChunk, len - o)});
-    };
-    add(a.p->mbs.data(), a.p->mbs.size() * sizeof(avc::MbRec), a.off_mbs);
-    add(a.p->coefs.data(), a.p->coefs.size() * sizeof(i16), a.off_coef);
-    add(a.p->mvs.data(), a.p->mvs.size() * sizeof(i16), a.off_mv);
-    add(a.p->wps.data(), a.p->wps.size() * sizeof(avc::WpEntry), a.off_wp);
-  }
-  for (const HevcPic& a : hpics) {
-    auto add = [&](const void* src, size_t len, size_t off) {
-      for (size_t o = 0; o < len; o += kPackChunk)
-        tasks.push_back({static_cast<const u8*>(src) + o, st.h + off + o, std::min(kPackChunk, len - o)});
-    };
-    const hevc::GpuPicture& p = *a.p;
-    add(p.pus.data(), p.pus.size() * sizeof(hevc::GpuPu), a.off_pu);
-    add(p.tus.data(), p.tus.size() * sizeof(hevc::GpuTu), a.off_tu);
-    add(p.coefs.data(), p.coefs.size() * sizeof(i16), a.off_coef);
-    add(p.pcm.data(), p.pcm.size(), a.off_pcm);
-    add(p.bs_v.data(), p.bs_v.size(), a.off_bsv);
-    add(p.bs_h.data(), p.bs_h.size(), a.off_bsh);
-    add(p.qp.data(), p.qp.size(), a.off_qp);
-    add(p.pcm_map.data(), p.pcm_map.size(), a.off_pcmmap);
-    add(p.ctb_slice.data(), p.ctb_slice.size() * sizeof(u16), a.off_cslice);
-    add(p.slices.data(), p.slices.size() * sizeof(hevc::GpuSlice), a.off_slices);
-    add(p.sao_params.data(), p.sao_params.size() * sizeof(hevc::GpuSao), a.off_sao);
-    add(p.wp.data(), p.wp.size() * sizeof(hevc::GpuWp), a.off_wp);
-    add(p.ctb_tile.data(), p.ctb_tile.size() * sizeof(u16), a.off_ctile);
-  }
-  std::vector<std::vector<const u8*>> seg_dev(static_cast<size_t>(n));
-  for (int i = 0; i < n; ++i) {
-    const auto& segs = jobs[size_t(i)].upd.segs;
-    for (size_t g = 0; g < segs.size(); ++g) {
-      const size_t dst_off = pay_off[size_t(i)] + seg_off[size_t(i)][g];
-      const u8* src = hostmem::device_address(segs[g].base, segs[g].len);
-      if (!src) {  // pageable AU bytes: stage them
-        for (size_t o = 0; o < segs[g].len; o += kPackChunk)
-          tasks.push_back({segs[g].base + o, st.h + dst_off + o,
-                           std::min(kPackChunk, segs[g].len - o)});
-        src = hostmem::device_address(st.h + dst_off, segs[g].len);
-        VEP_CHECK(src, "staging buffer is not registered");
-        pinned_bytes_staged_ += u64(segs[g].len);
-      } else {
-        pinned_bytes_inplace_ += u64(segs[g].len);
-      }
-      seg_dev[size_t(i)].push_back(src);
-      if (!direct)
-        for (size_t o = 0; o < segs[g].len; o += gpu::kGatherChunk)
-          gc[ng++] = {src + o, st.d + dst_off + o,
-                      u32(std::min<size_t>(gpu::kGatherChunk, segs[g].len - o)), 0};
-    }
-  }
-  VEP_CHECK(ng == nchunks, "gather chunk count mismatch");
-  // Phase 2 (per job, pack threads): coded-MB bitmask/prefix + per-MB offsets or pointers.
+  records_gathered_ += pl.bytes_gathered;
+  pinned_bytes_staged_ += pl.bytes_staged;
+  pinned_bytes_inplace_ += pl.bytes_inplace;
   auto index = [&](int i) {
-    if (direct)
-      build_index_ptrs(jobs[size_t(i)].upd, seg_dev[size_t(i)], mask_ptr(st.h, i),
-                       prefix_ptr(st.h, i), reinterpret_cast<u64*>(table_ptr(st.h, i)));
-    else
-      build_index(jobs[size_t(i)].upd, seg_off[size_t(i)], mask_ptr(st.h, i), prefix_ptr(st.h, i),
-                  reinterpret_cast<u32*>(table_ptr(st.h, i)));
+    const StagePlan::Job& jp = pl.jobs[size_t(i)];
+    auto* mask = reinterpret_cast<u32*>(h + jp.mask.off);
+    auto* prefix = reinterpret_cast<u32*>(h + jp.prefix.off);
+    const MbUpdate& u = jobs[size_t(i)].upd;
+    if (pl.set.direct) {  // per MB the device address of its samples in host memory (AU block or pinned half)
+      const u8* staged = st.buf.h_dev + jp.payload;
+      build_index(u, mask, prefix, reinterpret_cast<u64*>(h + jp.table.off), [&](u32 g, size_t o) {
+        return reinterpret_cast<u64>((jp.seg_dev[g] ? jp.seg_dev[g] : staged + jp.seg_rel[g]) + o);
+      });
+    } else {  // per MB the offset of its samples in the device copy of the job's payload
+      build_index(u, mask, prefix, reinterpret_cast<u32*>(h + jp.table.off),
+                  [&](u32 g, size_t o) { return u32(jp.seg_rel[g] + o); });
+    }
   };
   const i64 t_index0 = mono_us();
   {
@@ -1707,73 +1524,58 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
   }
   const i64 t_copy0 = mono_us();
   add_time(&Timers::index, double(t_copy0 - t_index0));
-  auto copy = [&](int t) { std::memcpy(tasks[size_t(t)].dst, tasks[size_t(t)].src, tasks[size_t(t)].len); };
+  const auto& tasks = pl.tasks;
+  auto copy = [&](int t) { std::memcpy(h + tasks[size_t(t)].dst, tasks[size_t(t)].src, tasks[size_t(t)].len); };
   if (pack_pool_ && tasks.size() > 1) pack_pool_->parallel_for(int(tasks.size()), copy);
   else for (int t = 0; t < int(tasks.size()); ++t) copy(t);
-  const i64 t_enq0 = mono_us();
-  add_time(&Timers::copy, double(t_enq0 - t_copy0));
+  add_time(&Timers::copy, double(mono_us() - t_copy0));
+}
 
-  if (st.err_cap < size_t(n)) {
-    if (st.err) dev_.free_pinned(st.err);
-    st.err_cap = std::max<size_t>(size_t(n), 64);
-    st.err = static_cast<u32*>(dev_.alloc_pinned(st.err_cap * sizeof(u32)));
-    void* ed = nullptr;
-    if (hipHostGetDevicePointer(&ed, st.err, 0) != hipSuccess) ed = st.err;
-    st.err_dev = static_cast<const u32*>(ed);
-  }
-  std::memset(st.err, 0, size_t(n) * sizeof(u32));
-  auto* hd = reinterpret_cast<gpu::DecodeDesc*>(st.h + off_desc);
-  auto* hl = reinterpret_cast<gpu::LetterboxDesc*>(st.h + off_lb);
-  auto* hw = reinterpret_cast<gpu::WeaveDesc*>(st.h + off_wv);
-  int nweave = 0, weave_pitch = 0, weave_h = 0;
-  int tiles = 0;
-  // conversion / letterbox descriptors only for jobs that publish a frame (a general-path job
-  // whose pictures all wait in the reorder buffer only reconstructs)
-  std::vector<int> outs;
-  for (int i = 0; i < n; ++i)
-    if (jobs[size_t(i)].has_output()) outs.push_back(i);
-  const int nout = int(outs.size());
-  for (int k = 0; k < nout; ++k) {
-    const int i = outs[size_t(k)];
-    const DecodeJob& j = jobs[size_t(i)];
-    Camera* c = cams_[size_t(j.cam)].get();
-    const size_t words = size_t(j.upd.mbs() + 31) / 32;
+// Conversion, letterbox and weave descriptors, only for jobs that publish a frame (a general-path
+// job whose pictures all wait in the reorder buffer only reconstructs).
+void Worker::describe_outputs(const StagePlan& pl, Stage& st, Described& ds) {
+  u8* const dv = st.buf.d;
+  auto* hd = reinterpret_cast<gpu::DecodeDesc*>(st.buf.h + pl.decode.off);
+  auto* hl = reinterpret_cast<gpu::LetterboxDesc*>(st.buf.h + pl.letterbox.off);
+  auto* hw = reinterpret_cast<gpu::WeaveDesc*>(st.buf.h + pl.weave.off);
+  for (size_t k = 0; k < pl.outs.size(); ++k) {
+    const int i = pl.outs[k];
+    const DecodeJob& j = st.jobs[size_t(i)];
+    const StagePlan::Job& jp = pl.jobs[size_t(i)];
+    const Camera* c = cams_[size_t(j.cam)].get();
+    const Camera::Surface& sf = c->surface;
     gpu::DecodeDesc& d = hd[k];
     const size_t tgt = size_t(j.target());
-    if (j.out_fields) {  // field pair: woven into the 8-bit scratch first (launch_weave below)
-      const Camera::Surface& sf = c->surface;
-      VEP_CHECK(sf.y8 && sf.bps == 1 && sf.hmbs % 2 == 0,
-                "field pair output without its weave scratch");
-      gpu::WeaveDesc& w = hw[nweave++];
+    if (j.out_fields) {  // field pair: woven into the 8-bit scratch first (launch_weave)
+      gpu::WeaveDesc& w = hw[ds.nweave++];
       w.y = sf.y + tgt * sf.slot_y();
       w.uv = sf.uv + tgt * sf.slot_uv();
       w.y8 = sf.y8;
       w.uv8 = sf.uv8;
       w.pitch = sf.wmbs * 16;
       w.height = sf.hmbs * 16;
-      weave_pitch = std::max(weave_pitch, w.pitch);
-      weave_h = std::max(weave_h, w.height);
+      ds.weave_pitch = std::max(ds.weave_pitch, w.pitch);
+      ds.weave_h = std::max(ds.weave_h, w.height);
     }
-    if (c->surface.narrowed() || j.out_fields) {  // Main10 / 4:2:2 / field pair: convert / letterbox the
-                                                // 8-bit frame (launch_narrow / launch_weave below)
-      d.y = c->surface.y8;
-      d.uv = c->surface.uv8;
+    if (sf.narrowed() || j.out_fields) {  // Main10 / 4:2:2 / field pair: convert / letterbox the
+                                          // 8-bit frame (launch_narrow / launch_weave)
+      d.y = sf.y8;
+      d.uv = sf.uv8;
     } else {
-      d.y = c->surface.y + tgt * c->surface.slot_y();
-      d.uv = c->surface.uv + tgt * c->surface.slot_uv();
+      d.y = sf.y + tgt * sf.slot_y();
+      d.uv = sf.uv + tgt * sf.slot_uv();
     }
     d.bgr = c->ring_->slot_ptr(st.slots[size_t(i)]);
-    (void)words;
-    d.mask = mask_ptr(st.d, i);
-    d.prefix = prefix_ptr(st.d, i);
-    if (direct) {
-      d.ptrs = reinterpret_cast<const u64*>(table_ptr(st.d, i));
+    d.mask = reinterpret_cast<const u32*>(dv + jp.mask.off);
+    d.prefix = reinterpret_cast<const u32*>(dv + jp.prefix.off);
+    if (pl.set.direct) {
+      d.ptrs = reinterpret_cast<const u64*>(dv + jp.table.off);
       d.offsets = nullptr;
       d.payload = nullptr;
     } else {
       d.ptrs = nullptr;
-      d.offsets = reinterpret_cast<const u32*>(table_ptr(st.d, i));
-      d.payload = st.d + pay_off[size_t(i)];
+      d.offsets = reinterpret_cast<const u32*>(dv + jp.table.off);
+      d.payload = dv + jp.payload;
     }
     const bool whole = j.general() || j.ext;  // the slot already holds the picture
     d.wmbs = whole ? j.pic.coded_width / 16 : j.upd.width_mbs;
@@ -1784,12 +1586,12 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
     d.crop_left = j.pic.crop_left;
     d.crop_top = j.pic.crop_top;
     d.tiles_x = (d.wmbs + gpu::kTileMbW - 1) / gpu::kTileMbW;
-    d.tile_begin = tiles;
+    d.tile_begin = ds.tiles;
     d.chk_lo = j.pic.spec_lo;
     d.chk_hi = j.pic.spec_hi;
     d.chk_pat = 0x000Du;  // I_PCM header bytes 0D 00
-    d.err = const_cast<u32*>(st.err_dev) + i;
-    tiles += gpu::tiles_for(d.wmbs, d.hmbs);
+    d.err = st.err_dev + i;
+    ds.tiles += gpu::tiles_for(d.wmbs, d.hmbs);
     if (opt_.letterbox_size > 0) {
       gpu::LetterboxDesc& l = hl[k];
       const size_t S = size_t(opt_.letterbox_size);
@@ -1800,7 +1602,6 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
       l.src_h = j.pic.height;
       l.crop_left = j.pic.crop_left;
       l.crop_top = j.pic.crop_top;
-      VEP_CHECK(j.cam < st.cons_rows, "camera index exceeds consumer batch rows");
       l.out_hwc = st.cons_hwc ? st.cons_hwc + size_t(j.cam) * gpu::letterbox_bytes(int(S), opt_.letterbox_format)
                             : nullptr;
       const size_t es = opt_.chw_dtype == gpu::kChwF32 ? 4 : 2;
@@ -1809,276 +1610,249 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
       gpu::fill_letterbox_geometry(l, opt_.letterbox_size, opt_.letterbox_format == gpu::kLbNV12);
     }
   }
-  // history conversions: descriptors in round order; per round {first, count, tiles}
-  // (H.264 rounds 0 .. rounds - 1 run first, then the H.265 rounds: rounds .. rounds + hrounds - 1)
-  std::vector<std::array<int, 3>> hist_round(size_t(rounds + hrounds), std::array<int, 3>{0, 0, 0});
-  {
-    for (HistOut& h : hist) {
-      const DecodeJob& j = jobs[size_t(h.job)];
-      VEP_CHECK(h.round >= 0 && h.round < int(j.avc.empty() ? j.hevc.size() : j.avc.size()),
-                "history output released by a picture outside its job");
-      if (j.avc.empty()) h.round += rounds;
-    }
-    std::stable_sort(hist.begin(), hist.end(), [](const HistOut& a, const HistOut& b) { return a.round < b.round; });
-    auto* hs = reinterpret_cast<gpu::SurfaceBgrDesc*>(st.h + off_hist);
-    for (size_t k = 0; k < hist.size(); ++k) {
-      const DecodeJob& j = jobs[size_t(hist[k].job)];
-      const JobOutput& o = j.outputs[size_t(hist[k].out)];
-      const Camera* c = cams_[size_t(j.cam)].get();
-      const Camera::Surface& sf = c->surface;
-      std::array<int, 3>& hr = hist_round[size_t(hist[k].round)];
-      if (hr[1] == 0) hr[0] = int(k);
-      gpu::SurfaceBgrDesc& d = hs[k];
-      d = gpu::SurfaceBgrDesc{};
-      d.y = sf.y + size_t(o.slot) * sf.slot_y();
-      d.uv = sf.uv + size_t(o.slot) * sf.slot_uv();
-      d.bgr = c->ring_->slot_ptr(o.ring_slot);
-      d.pitch = d.coded_w = sf.wmbs * 16;
-      d.coded_h = sf.hmbs * 16;
-      d.bit_depth = sf.bd;
-      d.chroma_format = sf.cf;
-      d.crop_left = o.pic.crop_left;
-      d.crop_top = o.pic.crop_top;
-      d.out_w = o.pic.width;
-      d.out_h = o.pic.height;
-      d.tile_begin = hr[2];
-      gpu::check_surface_bgr(d);
-      VEP_CHECK(o.slot < sf.slots && d.out_w == c->ring_->width() && d.out_h == c->ring_->height(),
-                "history output does not match the camera's surfaces");
-      hr[1] += 1;
-      hr[2] += gpu::tiles_for(sf.wmbs, sf.hmbs);
-    }
+}
+
+// History conversions, in round order (StagePlan::hist).
+void Worker::describe_history(const StagePlan& pl, Stage& st) {
+  auto* hs = reinterpret_cast<gpu::SurfaceBgrDesc*>(st.buf.h + pl.history.off);
+  for (size_t k = 0; k < pl.hist.size(); ++k) {
+    const DecodeJob& j = st.jobs[size_t(pl.hist[k].job)];
+    const JobOutput& o = j.outputs[size_t(pl.hist[k].out)];
+    const Camera* c = cams_[size_t(j.cam)].get();
+    const Camera::Surface& sf = c->surface;
+    gpu::SurfaceBgrDesc& d = hs[k];
+    d = gpu::SurfaceBgrDesc{};
+    d.y = sf.y + size_t(o.slot) * sf.slot_y();
+    d.uv = sf.uv + size_t(o.slot) * sf.slot_uv();
+    d.bgr = c->ring_->slot_ptr(o.ring_slot);
+    d.pitch = d.coded_w = sf.wmbs * 16;
+    d.coded_h = sf.hmbs * 16;
+    d.bit_depth = sf.bd;
+    d.chroma_format = sf.cf;
+    d.crop_left = o.pic.crop_left;
+    d.crop_top = o.pic.crop_top;
+    d.out_w = o.pic.width;
+    d.out_h = o.pic.height;
+    d.tile_begin = pl.hist[k].tile_begin;
+    gpu::check_surface_bgr(d);
   }
-  auto convert_history = [&](int r) {  // the outputs released by round r's pictures
-    const std::array<int, 3>& hr = hist_round[size_t(r)];
-    if (hr[1] > 0)
-      gpu::launch_surface_to_bgr(reinterpret_cast<const gpu::SurfaceBgrDesc*>(st.d + off_hist) + hr[0], hr[1], hr[2], cs);
+}
+
+void Worker::describe_avc_round(const StagePlan& pl, size_t r, Stage& st) {
+  const StagePlan::AvcRound& rd = pl.avc_rounds[r];
+  u8* const dv = st.buf.d;
+  auto* ad = reinterpret_cast<gpu::AvcDesc*>(st.buf.h + rd.descs.off);
+  int mbs = 0;
+  for (size_t k = 0; k < rd.pics.size(); ++k) {
+    const StagePlan::AvcPic& a = pl.avc[size_t(rd.pics[k])];
+    const Camera::Surface& sf = cams_[size_t(st.jobs[size_t(a.job)].cam)]->surface;
+    gpu::AvcDesc& g = ad[k];
+    g = gpu::AvcDesc{};
+    g.mbs = dv + a.mbs.off;
+    g.coefs = reinterpret_cast<const i16*>(dv + a.coefs.off);
+    g.mvs = reinterpret_cast<const i16*>(dv + a.mvs.off);
+    g.wps = dv + a.wps.off;
+    g.y = sf.y;
+    g.uv = sf.uv;
+    // field pictures address field slots: half a frame slot each (top field rows, then bottom)
+    const size_t per = a.p->structure ? 2 : 1;
+    g.slot_y = sf.slot_y() / per;
+    g.slot_uv = sf.slot_uv() / per;
+    g.wmbs = a.p->wmbs;
+    g.hmbs = a.p->hmbs;
+    g.target = a.p->target;
+    g.constrained = a.p->constrained_intra ? 1 : 0;
+    g.mb_begin = mbs;
+    g.field = a.p->structure;
+    g.err = st.err_dev + a.job;
+    g.dbk = dv + a.dbk.off;
+    g.res = reinterpret_cast<i16*>(dv + a.res.off);
+    g.xg = reinterpret_cast<u64*>(dv + a.xg.off);
+    g.prof = avc_prof_;
+    g.bd = a.p->bd;
+    g.qp_bias = a.p->qp_bias;
+    g.qpc_bias = a.p->qpc_bias;
+    g.cf = a.p->cf;
+    g.ncoef = u32(a.p->coefs.size());
+    g.nres = u32(a.p->intra_res);
+    g.intra_mbs = a.p->intra_mbs;
+    g.deblock = a.p->deblock ? 1 : 0;
+    mbs += a.p->nmbs();
+  }
+}
+
+// An H.265 round's descriptors, TU ranges, zeroed ticket counters and per-picture queues.
+void Worker::describe_hevc_round(const StagePlan& pl, size_t r, Stage& st, const Described& ds) {
+  const StagePlan::HevcRound& rd = pl.hevc_rounds[r];
+  u8* const dv = st.buf.d;
+  auto* hd = reinterpret_cast<gpu::HevcDesc*>(st.buf.h + rd.descs.off);
+  int pus = 0, blks = 0;
+  for (size_t k = 0; k < rd.pics.size(); ++k) {
+    const StagePlan::HevcPic& a = pl.hevc[size_t(rd.pics[k])];
+    const hevc::GpuPicture& p = *a.p;
+    const DecodeJob& j = st.jobs[size_t(a.job)];
+    const Camera::Surface& sf = cams_[size_t(j.cam)]->surface;
+    gpu::HevcDesc& g = hd[k];
+    g = gpu::HevcDesc{};
+    g.y = sf.y;
+    g.uv = sf.uv;
+    g.slot_y = sf.slot_y();
+    g.slot_uv = sf.slot_uv();
+    g.stride = sf.wmbs * 16;
+    g.width = p.width;
+    g.height = p.height;
+    g.log2ctb = p.log2ctb;
+    g.wctb = p.wctb;
+    g.hctb = p.hctb;
+    g.target = p.target;
+    g.cb_qp_offset = p.cb_qp_offset;
+    g.cr_qp_offset = p.cr_qp_offset;
+    g.flags = (p.deblock ? 1 : 0) | (p.sao ? 2 : 0) | (p.pcm_nofilter ? 4 : 0) | (p.tiles_block_sao ? 8 : 0) |
+              (p.wide() ? gpu::kHevcWide : 0);
+    g.bd_y = p.bd_y;
+    g.bd_c = p.bd_c;
+    g.pus = dv + a.pus.off;
+    g.tus = dv + a.tus.off;
+    g.coefs = reinterpret_cast<const i16*>(dv + a.coefs.off);
+    g.pcm = dv + a.pcm.off;
+    g.bs_v = dv + a.bs_v.off;
+    g.bs_h = dv + a.bs_h.off;
+    g.qp = reinterpret_cast<const signed char*>(dv + a.qp.off);
+    g.pcm_map = dv + a.pcm_map.off;
+    g.ctb_slice = reinterpret_cast<const u16*>(dv + a.ctb_slice.off);
+    g.slices = dv + a.slices.off;
+    g.sao = dv + a.sao.off;
+    g.wp = dv + a.wp.off;
+    g.ctb_tile = reinterpret_cast<const u16*>(dv + a.ctb_tile.off);
+    const size_t scratch = size_t(j.hevc_slots);  // the extra surface after the DPB slots
+    g.sao_y = sf.y + scratch * sf.slot_y();
+    g.sao_uv = sf.uv + scratch * sf.slot_uv();
+    g.err = st.err_dev + a.job;
+    g.xg = hevc_tu_window_ == 0 ? nullptr : sf.hevc_xg;  // (per-level launches read the picture)
+    g.xg_h = sf.hmbs * 16;
+    g.epoch = ds.hevc_epoch[size_t(rd.pics[k])];
+    g.nap_max = hevc_tu_nap_;
+    g.npu = int(p.pus.size());
+    g.pu_begin = pus;
+    g.blk_begin = blks;
+    pus += g.npu;
+    blks += p.w4() * p.h4();
+  }
+  if (!rd.tu_ranges.empty())
+    std::memcpy(st.buf.h + rd.ranges.off, rd.tu_ranges.data(), rd.tu_ranges.size() * sizeof(gpu::HevcTuRange));
+  std::memset(st.buf.h + rd.counters.off, 0, std::max<size_t>(rd.windows.size(), 1) * sizeof(u32));
+  if (!rd.pic_queues.empty())
+    std::memcpy(st.buf.h + rd.picq.off, rd.pic_queues.data(), rd.pic_queues.size() * sizeof(gpu::HevcTuRange));
+}
+
+// Privacy masks: every ring slot this batch converts into (the newest frame's and the earlier
+// outputs') gets its camera's masks, under the lists snapshot in reserve_stage.
+void Worker::describe_masks(Stage& st, Described& ds) {
+  if (ds.nmask == 0) return;
+  size_t k = 0;
+  auto add = [&](const Camera& c, const MaskSnap& ms, int slot, int w, int h) {
+    VEP_CHECK(w == c.ring_->width() && h == c.ring_->height(), "masked output does not match the camera's ring");
+    ds.mask_levels = std::max(ds.mask_levels, gpu::fill_mask_descs(st.mask_h.p + k, c.ring_->slot_ptr(slot),
+                                                                   c.ring_->slot_bytes(), w, h, ms.m, ms.n));
+    k += size_t(ms.n);
   };
-  // AVC descriptors (device addresses known only now)
-  for (int r = 0; r < rounds; ++r) {
-    auto* ad = reinterpret_cast<gpu::AvcDesc*>(st.h + off_round[size_t(r)]);
-    int mbs = 0;
-    for (size_t k = 0; k < round_pics[size_t(r)].size(); ++k) {
-      const AvcPic& a = apics[size_t(round_pics[size_t(r)][k])];
-      const Camera* c = cams_[size_t(jobs[size_t(a.job)].cam)].get();
-      gpu::AvcDesc& g = ad[k];
-      g.mbs = st.d + a.off_mbs;
-      g.coefs = reinterpret_cast<const i16*>(st.d + a.off_coef);
-      g.mvs = reinterpret_cast<const i16*>(st.d + a.off_mv);
-      g.wps = st.d + a.off_wp;
-      g.y = c->surface.y;
-      g.uv = c->surface.uv;
-      // field pictures address field slots: half a frame slot each (top field rows, then bottom)
-      const size_t per = a.p->structure ? 2 : 1;
-      g.slot_y = c->surface.slot_y() / per;
-      g.slot_uv = c->surface.slot_uv() / per;
-      g.wmbs = a.p->wmbs;
-      g.hmbs = a.p->hmbs;
-      g.target = a.p->target;
-      g.constrained = a.p->constrained_intra ? 1 : 0;
-      g.mb_begin = mbs;
-      g.field = a.p->structure;
-      g.err = const_cast<u32*>(st.err_dev) + a.job;
-      g.dbk = st.d + a.off_dbk;
-      g.res = reinterpret_cast<i16*>(st.d + a.off_res);
-      g.xg = reinterpret_cast<u64*>(st.d + a.off_xg);
-      g.prof = avc_prof_;
-      g.bd = a.p->bd;
-      g.qp_bias = a.p->qp_bias;
-      g.qpc_bias = a.p->qpc_bias;
-      g.cf = a.p->cf;
-      g.ncoef = u32(a.p->coefs.size());
-      g.nres = u32(a.p->intra_res);
-      g.intra_mbs = a.p->intra_mbs;
-      g.deblock = a.p->deblock ? 1 : 0;
-      VEP_CHECK(c->surface.bd == a.p->bd && c->surface.cf == a.p->cf,
-                "H.264: picture bit depth / chroma format differs from the camera's surfaces");
-      mbs += a.p->nmbs();
-    }
+  for (size_t i = 0; i < st.jobs.size(); ++i) {
+    const DecodeJob& j = st.jobs[i];
+    const MaskSnap& ms = st.mask_snap[i];
+    if (ms.n == 0) continue;
+    const Camera& c = *cams_[size_t(j.cam)];
+    for (const JobOutput& o : j.outputs)
+      if (o.ring_slot >= 0) add(c, ms, o.ring_slot, o.pic.width, o.pic.height);
+    if (j.has_output()) add(c, ms, st.slots[i], j.pic.width, j.pic.height);
   }
-  // HEVC descriptors and level ranges
-  std::vector<std::array<int, 2>> hround_work(static_cast<size_t>(hrounds));  // PUs, 4x4 blocks
-  for (int r = 0; r < hrounds; ++r) {
-    auto* hd2 = reinterpret_cast<gpu::HevcDesc*>(st.h + off_hround[size_t(r)]);
-    int pus = 0, blks = 0;
-    for (size_t k = 0; k < hround_pics[size_t(r)].size(); ++k) {
-      const HevcPic& a = hpics[size_t(hround_pics[size_t(r)][k])];
-      const hevc::GpuPicture& p = *a.p;
-      const DecodeJob& j = jobs[size_t(a.job)];
-      const Camera* c = cams_[size_t(j.cam)].get();
-      gpu::HevcDesc& g = hd2[k];
-      g = gpu::HevcDesc{};
-      g.y = c->surface.y;
-      g.uv = c->surface.uv;
-      g.slot_y = c->surface.slot_y();
-      g.slot_uv = c->surface.slot_uv();
-      g.stride = c->surface.wmbs * 16;
-      g.width = p.width;
-      g.height = p.height;
-      g.log2ctb = p.log2ctb;
-      g.wctb = p.wctb;
-      g.hctb = p.hctb;
-      g.target = p.target;
-      g.cb_qp_offset = p.cb_qp_offset;
-      g.cr_qp_offset = p.cr_qp_offset;
-      g.flags = (p.deblock ? 1 : 0) | (p.sao ? 2 : 0) | (p.pcm_nofilter ? 4 : 0) | (p.tiles_block_sao ? 8 : 0) |
-                (p.wide() ? gpu::kHevcWide : 0);
-      VEP_CHECK(c->surface.bps == (p.wide() ? 2 : 1), "HEVC: picture bit depth differs from the camera's surfaces");
-      g.bd_y = p.bd_y;
-      g.bd_c = p.bd_c;
-      g.pus = st.d + a.off_pu;
-      g.tus = st.d + a.off_tu;
-      g.coefs = reinterpret_cast<const i16*>(st.d + a.off_coef);
-      g.pcm = st.d + a.off_pcm;
-      g.bs_v = st.d + a.off_bsv;
-      g.bs_h = st.d + a.off_bsh;
-      g.qp = reinterpret_cast<const signed char*>(st.d + a.off_qp);
-      g.pcm_map = st.d + a.off_pcmmap;
-      g.ctb_slice = reinterpret_cast<const u16*>(st.d + a.off_cslice);
-      g.slices = st.d + a.off_slices;
-      g.sao = st.d + a.off_sao;
-      g.wp = st.d + a.off_wp;
-      g.ctb_tile = reinterpret_cast<const u16*>(st.d + a.off_ctile);
-      const size_t scratch = size_t(j.hevc_slots);  // the extra surface after the DPB slots
-      VEP_CHECK(c->surface.slots > j.hevc_slots, "camera surfaces lack the SAO scratch slot");
-      g.sao_y = c->surface.y + scratch * c->surface.slot_y();
-      g.sao_uv = c->surface.uv + scratch * c->surface.slot_uv();
-      g.err = const_cast<u32*>(st.err_dev) + a.job;
-      {  // the camera's intra edge exchange (zeroed once: epochs start at 1)
-        Camera::Surface& sf = const_cast<Camera*>(c)->surface;
-        const size_t words = gpu::hevc_xg_words(g.stride, sf.hmbs * 16);
-        if (sf.hevc_xg_words < words) {
-          dev_.free(sf.hevc_xg);
-          sf.hevc_xg = static_cast<u64*>(dev_.alloc(words * sizeof(u64)));
-          VEP_HIP(hipMemset(sf.hevc_xg, 0, words * sizeof(u64)));
-          sf.hevc_xg_words = words;
-          sf.hevc_epoch = 0;
-        }
-        if (++sf.hevc_epoch == 0) {  // (after 2^32 rounds) never reuse a tag still in the words
-          VEP_HIP(hipMemset(sf.hevc_xg, 0, words * sizeof(u64)));
-          sf.hevc_epoch = 1;
-        }
-        g.xg = hevc_tu_window_ == 0 ? nullptr : sf.hevc_xg;  // (per-level launches read the picture)
-        g.xg_h = sf.hmbs * 16;
-        g.epoch = sf.hevc_epoch;
-        g.nap_max = hevc_tu_nap_;
-      }
-      g.npu = int(p.pus.size());
-      g.pu_begin = pus;
-      g.blk_begin = blks;
-      pus += g.npu;
-      blks += p.w4() * p.h4();
-    }
-    hround_work[size_t(r)] = {pus, blks};
-    auto* hr = reinterpret_cast<gpu::HevcTuRange*>(st.h + off_hranges[size_t(r)]);
-    for (size_t k = 0; k < hranges[size_t(r)].size(); ++k) hr[k] = hranges[size_t(r)][k];
-    std::memset(st.h + off_hctr[size_t(r)], 0, std::max<size_t>(hwindows[size_t(r)].size(), 1) * sizeof(u32));
-    if (!hpicq[size_t(r)].empty())
-      std::memcpy(st.h + off_hpicq[size_t(r)], hpicq[size_t(r)].data(), hpicq[size_t(r)].size() * sizeof(gpu::HevcTuRange));
-  }
+  VEP_CHECK(k == size_t(ds.nmask), "mask descriptors miscounted");
+}
+
+// THE RULE: from the first call below that puts work on a stream, nothing follows but HIP enqueue
+// calls and kernel launches: no VEP_CHECK on batch contents, no allocation, no synchronous
+// memset. launch_on gives a batch's ring slots back when launch_gpu throws, and kernels already
+// on the stream would go on writing into them; so whatever can refuse a batch (StagePlan,
+// check_plan, reserve_stage, the describe steps) has run by now, and only a failing HIP call can
+// still throw here.
+void Worker::enqueue(const StagePlan& pl, Lane& ln, Stage& st, const Described& ds) {
+  const hipStream_t cs = ln.stream;
+  const std::vector<DecodeJob>& jobs = st.jobs;
+  u8* const dv = st.buf.d;
+  const auto* chunks = reinterpret_cast<const gpu::GatherChunk*>(dv + pl.gather.off);
+  const int nchunks = int(pl.chunks.size());
   // H2D on the copy stream overlaps the previous batch's kernels on the compute stream: the
-  // small header region by SDMA, the slice payload by the gather kernel (PCIe reads)
+  // small header region by SDMA, the slice payload by the gather kernel (PCIe reads).
   // With several lanes the copy goes on the lane's own stream instead: it then waits for the
   // lane's previous kernels, while the other lanes keep the GPU busy, and no lane ever waits
   // on a queue another lane shares.
-  if (ln.copy) {  // the stage's previous batch has completed (launch_on), so st.d is free
-    VEP_HIP(hipMemcpyAsync(st.d, st.h, header_bytes, hipMemcpyHostToDevice, ln.copy));
-    if (nchunks)
-      gpu::launch_gather(reinterpret_cast<const gpu::GatherChunk*>(st.d + off_gather),
-                         int(nchunks), ln.copy);
-    VEP_HIP(hipEventRecord(st.copied, ln.copy));
-    VEP_HIP(hipStreamWaitEvent(cs, st.copied, 0));
-    VEP_HIP(hipEventRecord(st.e0, cs));
-  } else if (lanes_.size() > 1) {
-    VEP_HIP(hipEventRecord(st.e0, cs));
-    VEP_HIP(hipMemcpyAsync(st.d, st.h, header_bytes, hipMemcpyHostToDevice, cs));
-    if (nchunks)
-      gpu::launch_gather(reinterpret_cast<const gpu::GatherChunk*>(st.d + off_gather),
-                         int(nchunks), cs);
-  } else {
-    VEP_HIP(hipMemcpyAsync(st.d, st.h, header_bytes, hipMemcpyHostToDevice, copy_stream_));
-    if (nchunks)
-      gpu::launch_gather(reinterpret_cast<const gpu::GatherChunk*>(st.d + off_gather),
-                         int(nchunks), copy_stream_);
-    VEP_HIP(hipEventRecord(st.copied, copy_stream_));
+  // (the stage's previous batch has completed, launch_on: the device half is free)
+  const hipStream_t hs = ln.copy ? ln.copy : lanes_.size() > 1 ? cs : copy_stream_;
+  if (hs == cs) VEP_HIP(hipEventRecord(st.e0, cs));
+  VEP_HIP(hipMemcpyAsync(dv, st.buf.h, pl.header_bytes, hipMemcpyHostToDevice, hs));
+  if (nchunks) gpu::launch_gather(chunks, nchunks, hs);
+  if (hs != cs) {
+    VEP_HIP(hipEventRecord(st.copied, hs));
     VEP_HIP(hipStreamWaitEvent(cs, st.copied, 0));
     VEP_HIP(hipEventRecord(st.e0, cs));
   }
-  for (int r = 0; r < rounds; ++r) {
-    const auto* ad = reinterpret_cast<const gpu::AvcDesc*>(st.d + off_round[size_t(r)]);
-    const int np = int(round_pics[size_t(r)].size());
-    int mbs = 0;
-    bool intra = false, dbk = false, narrow = false;
-    int variants = 0;  // High 10 / 4:2:2 pictures by kind (launch_avc_hbd)
-    int max_h = 0;
-    for (int k : round_pics[size_t(r)]) {
-      mbs += apics[size_t(k)].p->nmbs();
-      max_h = std::max(max_h, apics[size_t(k)].p->hmbs);
-      intra |= apics[size_t(k)].p->intra_mbs > 0;
-      dbk |= apics[size_t(k)].p->deblock;
-      const avc::Picture& ap = *apics[size_t(k)].p;
-      if (ap.bd > 8 || ap.cf == 2) variants |= ap.cf != 2 ? 1 : (ap.bd > 8 ? 4 : 2);
-      else narrow = true;
+  auto convert_history = [&](const StagePlan::HistSpan& hs) {  // the outputs a round's pictures released
+    if (hs.count > 0)
+      gpu::launch_surface_to_bgr(reinterpret_cast<const gpu::SurfaceBgrDesc*>(dv + pl.history.off) + hs.first, hs.count,
+                                 hs.tiles, cs);
+  };
+  for (const StagePlan::AvcRound& rd : pl.avc_rounds) {
+    const auto* ad = reinterpret_cast<const gpu::AvcDesc*>(dv + rd.descs.off);
+    const int np = int(rd.pics.size());
+    gpu::launch_avc_inter(ad, np, rd.mbs, cs);
+    if (rd.intra && rd.narrow) gpu::launch_avc_intra(ad, np, rd.max_h, cs);
+    if (rd.dbk) {
+      gpu::launch_avc_bs(ad, np, rd.mbs, cs);
+      if (rd.narrow) gpu::launch_avc_deblock(ad, np, rd.max_h, cs, dbk_packed_);
     }
-    gpu::launch_avc_inter(ad, np, mbs, cs);
-    if (intra && narrow) gpu::launch_avc_intra(ad, np, max_h, cs);
-    if (dbk) {
-      gpu::launch_avc_bs(ad, np, mbs, cs);
-      if (narrow) gpu::launch_avc_deblock(ad, np, max_h, cs, dbk_packed_);
-    }
-    if (variants) gpu::launch_avc_hbd(ad, np, intra, dbk, variants, cs);  // (High 10 / 4:2:2 pictures)
-    convert_history(r);
+    if (rd.variants) gpu::launch_avc_hbd(ad, np, rd.intra, rd.dbk, rd.variants, cs);  // (High 10 / 4:2:2 pictures)
+    convert_history(rd.hist);
   }
-  for (int r = 0; r < hrounds; ++r) {
-    const auto* hd2 = reinterpret_cast<const gpu::HevcDesc*>(st.d + off_hround[size_t(r)]);
-    const auto* hr = reinterpret_cast<const gpu::HevcTuRange*>(st.d + off_hranges[size_t(r)]);
-    const int np = int(hround_pics[size_t(r)].size());
-    bool dbk = false, sao = false;
-    for (int k : hround_pics[size_t(r)]) {
-      dbk |= hpics[size_t(k)].p->deblock;
-      sao |= hpics[size_t(k)].p->sao;
-    }
-    gpu::launch_hevc_mc(hd2, np, hround_work[size_t(r)][0], cs);
-    const auto& hw = hwork[size_t(r)];
-    gpu::launch_hevc_tu(hd2, hr, hw[0], 0, hw[1], cs);
+  for (const StagePlan::HevcRound& rd : pl.hevc_rounds) {
+    const auto* hd = reinterpret_cast<const gpu::HevcDesc*>(dv + rd.descs.off);
+    const auto* hr = reinterpret_cast<const gpu::HevcTuRange*>(dv + rd.ranges.off);
+    const int np = int(rd.pics.size());
+    gpu::launch_hevc_mc(hd, np, rd.pus, cs);
+    gpu::launch_hevc_tu(hd, hr, rd.l0_ranges, 0, rd.l0_blocks, cs);
     if (hevc_tu_window_ < 0) {  // one workgroup per picture: every dependency wait inside it
-      gpu::launch_hevc_tu_pics(hd2, reinterpret_cast<const gpu::HevcTuRange*>(st.d + off_hpicq[size_t(r)]),
-                               int(hpicq[size_t(r)].size()), cs);
+      gpu::launch_hevc_tu_pics(hd, reinterpret_cast<const gpu::HevcTuRange*>(dv + rd.picq.off), int(rd.pic_queues.size()),
+                               cs);
     } else if (hevc_tu_window_ == 0) {  // one launch per intra level (kernel boundaries order the levels)
-      for (const auto& lv : hlevels[size_t(r)]) gpu::launch_hevc_tu(hd2, hr + hw[0], hw[2], lv[0], lv[1], cs);
+      for (const StagePlan::Span& lv : rd.levels)
+        gpu::launch_hevc_tu(hd, hr + rd.l0_ranges, rd.intra_ranges, lv.first, lv.count, cs);
     } else {  // one queue launch per window of levels, in level order on the stream
-      auto* ctr = reinterpret_cast<u32*>(st.d + off_hctr[size_t(r)]);
+      auto* ctr = reinterpret_cast<u32*>(dv + rd.counters.off);
       // (a window of bounded depth runs one wave per block, each taking its block from the
       // window's ticket counter; the whole round keeps the persistent ticket queue)
       const bool persistent = hevc_tu_window_ >= kAllLevels;
-      for (size_t k = 0; k < hwindows[size_t(r)].size(); ++k)
-        gpu::launch_hevc_tu_queue(hd2, hr + hw[0], hw[2], hwindows[size_t(r)][k][0], hwindows[size_t(r)][k][1],
+      for (size_t k = 0; k < rd.windows.size(); ++k)
+        gpu::launch_hevc_tu_queue(hd, hr + rd.l0_ranges, rd.intra_ranges, rd.windows[k].first, rd.windows[k].count,
                                   ctr + k, persistent, cs);
     }
-    if (dbk) {
-      gpu::launch_hevc_deblock(hd2, np, hround_work[size_t(r)][1], 0, cs);
-      gpu::launch_hevc_deblock(hd2, np, hround_work[size_t(r)][1], 1, cs);
+    if (rd.dbk) {
+      gpu::launch_hevc_deblock(hd, np, rd.blks, 0, cs);
+      gpu::launch_hevc_deblock(hd, np, rd.blks, 1, cs);
     }
-    if (sao) gpu::launch_hevc_sao(hd2, np, hround_work[size_t(r)][1], cs);
-    convert_history(rounds + r);
+    if (rd.sao) gpu::launch_hevc_sao(hd, np, rd.blks, cs);
+    convert_history(rd.hist);
   }
   // VCN pictures: the video core's surfaces -> the cameras' NV12 surfaces (device copies on the
   // lane stream, ordered before the conversion; the surfaces return to rocDecode when the batch
   // completes and its jobs are dropped)
-  for (int i = 0; i < n; ++i) {
-    const DecodeJob& j = jobs[size_t(i)];
+  for (const DecodeJob& j : jobs) {
     if (!j.ext) continue;
-    const Camera* c = cams_[size_t(j.cam)].get();
+    const Camera::Surface& sf = cams_[size_t(j.cam)]->surface;
     const vcn::Frame& f = *j.ext;
-    const size_t pitch = size_t(c->surface.wmbs) * 16;
-    VEP_CHECK(size_t(f.width) <= pitch && f.height <= c->surface.hmbs * 16, "VCN picture exceeds the camera surface");
-    VEP_HIP(hipMemcpy2DAsync(c->surface.y, pitch, f.y, f.pitch_y, size_t(f.width), size_t(f.height),
-                             hipMemcpyDefault, cs));
-    VEP_HIP(hipMemcpy2DAsync(c->surface.uv, pitch, f.uv, f.pitch_uv, size_t(f.width), size_t(f.height / 2),
-                             hipMemcpyDefault, cs));
+    const size_t pitch = size_t(sf.wmbs) * 16;
+    VEP_HIP(hipMemcpy2DAsync(sf.y, pitch, f.y, f.pitch_y, size_t(f.width), size_t(f.height), hipMemcpyDefault, cs));
+    VEP_HIP(hipMemcpy2DAsync(sf.uv, pitch, f.uv, f.pitch_uv, size_t(f.width), size_t(f.height / 2), hipMemcpyDefault, cs));
   }
-  gpu::launch_weave(reinterpret_cast<const gpu::WeaveDesc*>(st.d + off_wv), nweave, weave_pitch, weave_h, cs);
-  for (int i : outs) {  // Main10 pictures: the published slot's 8-bit NV12 copy
+  gpu::launch_weave(reinterpret_cast<const gpu::WeaveDesc*>(dv + pl.weave.off), ds.nweave, ds.weave_pitch, ds.weave_h, cs);
+  for (int i : pl.outs) {  // Main10 pictures: the published slot's 8-bit NV12 copy
     const DecodeJob& j = jobs[size_t(i)];
     const Camera::Surface& sf = cams_[size_t(j.cam)]->surface;
     const size_t tgt = size_t(j.target());
@@ -2086,8 +1860,8 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
     gpu::launch_narrow(sf.y + tgt * sf.slot_y(), sf.uv + tgt * sf.slot_uv(), sf.y8, sf.uv8, sf.wmbs * 16,
                        sf.hmbs * 16, sf.bd, sf.cf, cs);
   }
-  gpu::launch_decode_convert(reinterpret_cast<const gpu::DecodeDesc*>(st.d + off_desc), nout, tiles,
-                             cs);
+  const int nout = int(pl.outs.size());
+  gpu::launch_decode_convert(reinterpret_cast<const gpu::DecodeDesc*>(dv + pl.decode.off), nout, ds.tiles, cs);
   if (opt_.letterbox_size > 0) {
     gpu::LetterboxParams p{};
     p.size = opt_.letterbox_size;
@@ -2098,55 +1872,15 @@ void Worker::launch_gpu(Lane& ln, Stage& st) {
     }
     p.pad_value = 114;
     p.format = opt_.letterbox_format;
-    gpu::launch_letterbox(reinterpret_cast<const gpu::LetterboxDesc*>(st.d + off_lb), nout, p,
-                          cs);
+    gpu::launch_letterbox(reinterpret_cast<const gpu::LetterboxDesc*>(dv + pl.letterbox.off), nout, p, cs);
   }
-  // Privacy masks: every ring slot this batch converted into (the newest frame's and the earlier
-  // outputs') is masked in place, behind the conversions on the lane's stream, under the lists
-  // the cameras have now; publish() commits a slot only if its camera's list is still that one.
-  if (snapshot_masks(jobs, st.mask_snap)) {
-    size_t nd = 0;
-    for (int i = 0; i < n; ++i) {
-      size_t slots_of = jobs[size_t(i)].has_output() ? 1 : 0;
-      for (const JobOutput& o : jobs[size_t(i)].outputs) slots_of += o.ring_slot >= 0 ? 1 : 0;
-      nd += slots_of * size_t(st.mask_snap[size_t(i)].n);
-    }
-    if (nd > 0) {
-      if (st.mask_cap < nd) {  // (the stage's previous batch is complete: nothing reads the old buffers)
-        if (st.mask_h) dev_.free_pinned(st.mask_h);
-        st.mask_h = nullptr;
-        if (st.mask_d) dev_.free(st.mask_d);
-        st.mask_d = nullptr;
-        st.mask_cap = 0;
-        const size_t cap = std::max<size_t>(nd, 256);
-        st.mask_h = static_cast<gpu::MaskDesc*>(dev_.alloc_pinned(cap * sizeof(gpu::MaskDesc)));
-        st.mask_d = static_cast<gpu::MaskDesc*>(dev_.alloc(cap * sizeof(gpu::MaskDesc)));
-        st.mask_cap = cap;
-      }
-      size_t k = 0;
-      int top = 0;
-      auto add = [&](const Camera& c, const MaskSnap& ms, int slot, int w, int h) {
-        VEP_CHECK(w == c.ring_->width() && h == c.ring_->height(), "masked output does not match the camera's ring");
-        top = std::max(top, gpu::fill_mask_descs(st.mask_h + k, c.ring_->slot_ptr(slot), c.ring_->slot_bytes(), w, h,
-                                                 ms.m, ms.n));
-        k += size_t(ms.n);
-      };
-      for (int i = 0; i < n; ++i) {
-        const DecodeJob& j = jobs[size_t(i)];
-        const MaskSnap& ms = st.mask_snap[size_t(i)];
-        if (ms.n == 0) continue;
-        const Camera& c = *cams_[size_t(j.cam)];
-        for (const JobOutput& o : j.outputs)
-          if (o.ring_slot >= 0) add(c, ms, o.ring_slot, o.pic.width, o.pic.height);
-        if (j.has_output()) add(c, ms, st.slots[size_t(i)], j.pic.width, j.pic.height);
-      }
-      VEP_CHECK(k == nd && nd <= 65535, "mask descriptors miscounted");
-      VEP_HIP(hipMemcpyAsync(st.mask_d, st.mask_h, nd * sizeof(gpu::MaskDesc), hipMemcpyHostToDevice, cs));
-      for (int level = 0; level < top; ++level) gpu::launch_mask(st.mask_d, st.mask_h, int(nd), level, cs);
-    }
+  // the masks go last on the lane's stream: in place, behind the conversions
+  if (ds.nmask > 0) {
+    VEP_HIP(hipMemcpyAsync(st.mask_d.p, st.mask_h.p, size_t(ds.nmask) * sizeof(gpu::MaskDesc), hipMemcpyHostToDevice, cs));
+    for (int level = 0; level < ds.mask_levels; ++level)
+      gpu::launch_mask(st.mask_d.p, st.mask_h.p, ds.nmask, level, cs);
   }
   VEP_HIP(hipEventRecord(st.e1, cs));
-  add_time(&Timers::enqueue, double(mono_us() - t_enq0));
 }
 
 bool Worker::snapshot_masks(const std::vector<DecodeJob>& jobs, std::vector<MaskSnap>& out) {
@@ -2535,7 +2269,7 @@ void Worker::complete(Lane& ln, Stage& st) {
   add_time(&Timers::wait, double(mono_us() - t0));
   float ms = 0;
   if (hipEventElapsedTime(&ms, st.e0, st.e1) == hipSuccess) ln.gpu_ms.store(ln.gpu_ms.load() + ms);
-  publish(st.jobs, st.slots, st.err, st.mask_snap.size() == st.jobs.size() ? st.mask_snap.data() : nullptr);
+  publish(st.jobs, st.slots, st.err.p, st.mask_snap.size() == st.jobs.size() ? st.mask_snap.data() : nullptr);
   st.jobs.clear();
   st.slots.clear();
   {

@@ -232,6 +232,7 @@ struct DecodeJob {
 void merge_job(DecodeJob& p, DecodeJob&& job);
 
 class Worker;
+struct StagePlan;  // stage_plan.h
 
 // Bounded log ring (docker json-file analog, rtsp_process_manager.go:72-75; Info returns 100).
 class LogRing {
@@ -640,10 +641,22 @@ class Worker {
     int n = 0;
     mask::Mask m[mask::kMaxMasks];
   };
-  struct Stage {  // one pinned + device staging pair and the batch that uses it
+  // A stage's buffer pair: a pinned half the host fills and a device half of the same size. The
+  // pinned half is registered with hostmem, so the GPU can also read staged bytes in place.
+  struct StagePair {
     u8* h = nullptr;
     u8* d = nullptr;
+    const u8* h_dev = nullptr;  // device address of h
     size_t cap = 0;
+    StagePair() = default;
+    StagePair(const StagePair&) = delete;
+    StagePair& operator=(const StagePair&) = delete;
+    ~StagePair() { release(); }
+    void reserve(size_t need);  // grow-only, to max(need + need / 2, 4 MiB)
+    void release();
+  };
+  struct Stage {  // one pinned + device staging pair and the batch that uses it
+    StagePair buf;
     hipEvent_t copied = nullptr, e0 = nullptr, e1 = nullptr;
     std::vector<DecodeJob> jobs;
     std::vector<int> slots;
@@ -653,15 +666,20 @@ class Worker {
     void* cons_chw = nullptr;
     int cons_rows = 0;
     bool active = false;
-    u32* err = nullptr;        // pinned per-job check flags (written by the kernel)
-    const u32* err_dev = nullptr;
-    size_t err_cap = 0;
+    gpu::PinBuf<u32> err;      // per-job check flags (written by the kernels)
+    u32* err_dev = nullptr;    // their device address
     // privacy masks: per job the camera's list and generation at launch; the batch's descriptors
     // (pinned + device, grown to the largest batch seen)
     std::vector<MaskSnap> mask_snap;
-    gpu::MaskDesc* mask_h = nullptr;
-    gpu::MaskDesc* mask_d = nullptr;
-    size_t mask_cap = 0;
+    gpu::PinBuf<gpu::MaskDesc> mask_h;
+    gpu::DevBuf<gpu::MaskDesc> mask_d;
+  };
+  // What reserve / describe hand to enqueue besides the plan.
+  struct Described {
+    std::vector<u32> hevc_epoch;  // per StagePlan::hevc picture: its round's tag in the camera's exchange
+    int tiles = 0;                // conversion tiles of the batch
+    int nweave = 0, weave_pitch = 0, weave_h = 0;
+    int nmask = 0, mask_levels = 0;
   };
   void loop();
   void ensure_surface(Camera& c, const PictureInfo& pi, int slots, int bd = 8, bool weave = false, int cf = 1);
@@ -690,7 +708,17 @@ class Worker {
     hipEvent_t snap_mark = nullptr;  // recorded by snapshot_consumer: the lane's enqueued work
   };
   void prepare(std::vector<DecodeJob>& jobs, std::vector<int>& slots);
+  // One batch on a lane: plan, reserve, stage, describe, enqueue (runtime.cpp, in this order).
   void launch_gpu(Lane& ln, Stage& st);
+  void check_plan(const StagePlan& pl, const Stage& st);
+  void reserve_stage(const StagePlan& pl, Stage& st, Described& ds);
+  void stage_batch(const StagePlan& pl, Stage& st);
+  void describe_outputs(const StagePlan& pl, Stage& st, Described& ds);
+  void describe_history(const StagePlan& pl, Stage& st);
+  void describe_avc_round(const StagePlan& pl, size_t r, Stage& st);
+  void describe_hevc_round(const StagePlan& pl, size_t r, Stage& st, const Described& ds);
+  void describe_masks(Stage& st, Described& ds);
+  void enqueue(const StagePlan& pl, Lane& ln, Stage& st, const Described& ds);
   void lane_loop(Lane& ln);
   void merge_queued(Lane& ln, Batch& b);
   void launch_on(Lane& ln, Batch&& b);  // reuse the lane's oldest stage for batch b

@@ -1,5 +1,7 @@
 """ThreadSanitizer / AddressSanitizer runs of the native stress driver (csrc/tests/native_stress.cpp)
-and of the scratch pool's stand-alone selftest (csrc/tests/scratch_selftest.cpp).
+and of the scratch pool's stand-alone selftest (csrc/tests/scratch_selftest.cpp); the stage plan's
+selftest (csrc/tests/stage_plan_selftest.cpp) un-instrumented (`make asan-plan` runs it under
+AddressSanitizer + UndefinedBehaviorSanitizer).
 
 Host-code sanitizers only (`-Xarch_host -fsanitize=...`; GPU sanitizers are unavailable), CPU
 backend. Building takes about a minute per sanitizer, so the test runs when VEP_SANITIZERS=1
@@ -31,6 +33,17 @@ def test_scratch_selftest():
     out = r.stdout + r.stderr
     assert r.returncode == 0, out[-4000:]
     assert "scratch_selftest ok" in out
+
+
+def test_stage_plan_selftest():
+    """The stage plan's invariants (csrc/vep/stage_plan.h) on real jobs of every kind, planned on
+    the host: regions inside the buffer, aligned, disjoint and in their section; copy tasks and
+    gather chunks tiling their regions; rounds and history outputs complete. Linked against the
+    objects of the build."""
+    r = subprocess.run(["make", "-C", ROOT, "plan-selftest"], capture_output=True, text=True, timeout=600)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-4000:]
+    assert "stage_plan_selftest ok" in out
 
 
 def test_sanitizer_target_links():
