@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -171,6 +171,27 @@ $(ASAN_DIR)/stage_plan_selftest: $(SRCS) $(HIP_SRCS) csrc/tests/stage_plan_selft
 
 asan-plan: $(ASAN_DIR)/stage_plan_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/stage_plan_selftest
+
+# The serving reads' consistent-read rule (csrc/tests/serve_selftest.cpp on vep/ring_read.h, and a
+# CPU-backend Worker for the stored answers): a stand-alone host program, no GPU; its produce steps
+# rewrite the ring themselves, so the retry runs every time. Wired as the plan selftest above.
+serve-selftest: build
+	mkdir -p build/selftest
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -c csrc/tests/serve_selftest.cpp -Icsrc \
+	  -o build/selftest/serve_selftest.o
+	$(HIPCC) --offload-arch=$(ARCH) build/selftest/serve_selftest.o build/obj/vep__*.o \
+	  -o build/selftest/serve_selftest -lpthread
+	cd /tmp && $(CURDIR)/build/selftest/serve_selftest
+
+$(ASAN_DIR)/serve_selftest: $(SRCS) $(HIP_SRCS) csrc/tests/serve_selftest.cpp $(wildcard csrc/vep/*.h)
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize=shift-base -Xarch_host -fno-sanitize-recover=undefined \
+	  -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc $(SRCS) csrc/tests/serve_selftest.cpp -x hip $(HIP_SRCS) -o $@ -lpthread
+
+asan-serve: $(ASAN_DIR)/serve_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/serve_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

@@ -11,8 +11,6 @@
 #include <thread>
 
 #include "color.h"
-#include "jpeg.h"
-#include "scale.h"
 #include "stage_plan.h"
 #include "trace.h"
 
@@ -744,11 +742,7 @@ Worker::~Worker() {
     if (ln.snap_mark) (void)hipEventDestroy(ln.snap_mark);
   }
   if (snap_ev_) (void)hipEventDestroy(snap_ev_);
-  for (auto& b : serve_all_) {
-    dev_.free_pinned(b->h);
-    for (hipEvent_t e : b->ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  serve_pool_.reset();  // (its buffers and events go here: device alive, serving stream not yet destroyed)
   dev_.free(avc_prof_);
   if (stream_) (void)hipStreamDestroy(stream_);
   if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
@@ -2528,913 +2522,6 @@ void Worker::run_batch(std::vector<DecodeJob>& jobs) {
   complete_all();
 }
 
-bool Worker::read_latest(int cam, i64 after, FrameMeta* meta, u8* dst, size_t cap) {
-  std::shared_ptr<Camera> c = camera(cam);
-  if (!c) return false;
-  std::shared_ptr<FrameRing> r = c->ring();
-  return r && read_latest(*r, after, meta, dst, cap);
-}
-
-void Worker::set_wall_max_tiles(int n) {
-  VEP_CHECK(n >= 1 && n <= 65535, "wall: wall_max_tiles must be 1..65535");
-  wall_max_tiles_.store(n);
-}
-
-void Worker::encode_device(const u8* d_bgr, int w, int h, int quality, std::string& out) {
-  if (jpeg_pool_.encode(d_bgr, w, h, quality, serve_stream_, out)) return;
-  // the kernels reported an overflow of their scratch: encode the picture on the host
-  const size_t n = size_t(w) * size_t(h) * 3;
-  std::unique_ptr<u8[]> host(new u8[n]);
-  VEP_HIP(hipMemcpyAsync(host.get(), d_bgr, n, hipMemcpyDeviceToHost, serve_stream_));
-  VEP_HIP(hipStreamSynchronize(serve_stream_));
-  out = jpeg::encode_cpu(host.get(), w, h, quality);
-}
-
-void Worker::scale_slot(gpu::ScaleSet& set, const FrameRing& ring, int slot, int ow, int oh) {
-  gpu::ScaleDesc& d = set.h_descs.p[0];
-  d = gpu::ScaleDesc{};
-  d.src = ring.slot_ptr(slot);
-  d.sw = ring.width();
-  d.sh = ring.height();
-  d.src_pitch = u32(ring.width()) * 3;
-  d.dst = set.canvas.p;
-  d.dst_pitch = u32(ow) * 3;
-  d.ow = ow;
-  d.oh = oh;
-  gpu::check_scale(d, ow, oh);
-  set.run(1, serve_stream_);
-}
-
-static void check_box(int width, int height) {
-  VEP_CHECK(width >= 0 && width <= scale::kMaxSide && height >= 0 && height <= scale::kMaxSide && (width || height),
-            "scale: width and height must be 1..65535");
-}
-
-bool Worker::read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst) {
-  check_box(width, height);
-  std::shared_ptr<Camera> c = camera(cam);
-  if (!c) return false;
-  std::shared_ptr<FrameRing> ring = c->ring();
-  if (!ring) return false;
-  const scale::Size f = scale::fit(ring->width(), ring->height(), width, height);
-  const size_t n = size_t(f.w) * size_t(f.h) * 3;
-  dst.resize(n);
-  for (int attempt = 0; attempt < 4; ++attempt) {
-    int slot;
-    if (!ring->latest(after, meta, &slot)) return false;
-    if (dev_.gpu()) {
-      dev_.bind();
-      gpu::ScalePool::Lease set = scale_pool_.acquire();
-      set->reserve(n, 1, n);
-      scale_slot(*set, *ring, slot, f.w, f.h);
-      VEP_HIP(hipMemcpyAsync(set->upload.p, set->canvas.p, n, hipMemcpyDeviceToHost, serve_stream_));
-      VEP_HIP(hipEventRecord(set->ev, serve_stream_));
-      VEP_HIP(hipEventSynchronize(set->ev));
-      std::memcpy(dst.data(), set->upload.p, n);
-    } else {
-      scale::area_cpu(ring->slot_ptr(slot), ring->width(), ring->height(), size_t(ring->width()) * 3, dst.data(),
-                      size_t(f.w) * 3, f.w, f.h);
-    }
-    if (ring->still_valid(slot, meta->seq)) {
-      meta->width = f.w;
-      meta->height = f.h;
-      return true;
-    }
-  }
-  return false;
-}
-
-void Worker::read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
-                            const std::vector<ForeignTile>& foreign, std::vector<i64>& seqs_out, std::string& out) {
-  VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-  const int n = int(cams.size());
-  VEP_CHECK(n >= 1 && n <= wall_max_tiles(), "wall: the number of tiles must be 1..serving.wall_max_tiles");
-  VEP_CHECK(tw >= 1 && tw <= scale::kMaxSide && th >= 1 && th <= scale::kMaxSide, "wall: tile size must be 1..65535");
-  VEP_CHECK(cols >= 0 && cols <= scale::kMaxSide, "wall: cols out of range");
-  VEP_CHECK(foreign.empty() || int(foreign.size()) == n, "wall: one foreign tile entry per tile expected");
-  const scale::Wall g = scale::wall(n, cols, tw, th);
-  VEP_CHECK(i64(g.cols) * tw <= scale::kMaxSide && i64(g.rows) * th <= scale::kMaxSide,
-            "wall: canvas sides must be <= 65535");
-  struct TileSrc {
-    std::shared_ptr<Camera> cam;
-    std::shared_ptr<FrameRing> ring;
-    FrameMeta meta;
-    int slot = -1;
-    bool done = false;  // consistent, foreign or given up (background)
-  };
-  std::vector<TileSrc> ts((size_t(n)));
-  seqs_out.assign(size_t(n), 0);
-  size_t up_bytes = 0;
-  for (int t = 0; t < n; ++t) {
-    TileSrc& s = ts[size_t(t)];
-    if (!foreign.empty() && foreign[size_t(t)].data) {
-      const ForeignTile& f = foreign[size_t(t)];
-      VEP_CHECK(f.w >= 1 && f.h >= 1 && f.w <= tw && f.h <= th, "wall: foreign tile larger than its cell");
-      up_bytes += size_t(f.w) * size_t(f.h) * 3;
-      seqs_out[size_t(t)] = f.seq;
-      continue;
-    }
-    s.cam = camera(cams[size_t(t)]);
-    if (s.cam) s.ring = s.cam->ring();
-  }
-  const size_t pitch = size_t(g.w) * 3, canvas_bytes = pitch * size_t(g.h);
-  // tile t's descriptor from its ring's newest frame; background only when there is none
-  auto cell = [&](int t, u8* canvas) {
-    gpu::ScaleDesc d{};
-    d.dst = canvas;
-    d.dst_pitch = u32(pitch);
-    d.cx = (t % g.cols) * tw;
-    d.cy = (t / g.cols) * th;
-    d.cw = tw;
-    d.ch = th;
-    return d;
-  };
-  auto pick = [&](int t) {  // newest frame of tile t's ring -> slot / meta; false: background
-    TileSrc& s = ts[size_t(t)];
-    s.slot = -1;
-    return s.ring && s.ring->latest(0, &s.meta, &s.slot);
-  };
-  if (!dev_.gpu()) {
-    std::vector<u8> canvas(canvas_bytes);
-    std::vector<scale::Tile> tiles((size_t(n)));
-    for (int round = 0; round < 4; ++round) {
-      bool again = false;
-      for (int t = 0; t < n; ++t) {
-        TileSrc& s = ts[size_t(t)];
-        scale::Tile& tl = tiles[size_t(t)];
-        if (s.done && round) continue;
-        tl = scale::Tile{};
-        if (!foreign.empty() && foreign[size_t(t)].data) {
-          s.done = true;
-          continue;
-        }
-        if (!pick(t)) {
-          s.done = true;
-          continue;
-        }
-        tl.src = s.ring->slot_ptr(s.slot);
-        tl.sw = s.ring->width();
-        tl.sh = s.ring->height();
-        tl.pitch = size_t(tl.sw) * 3;
-      }
-      // (the host composition is cheap to repeat whole: a round redraws every tile)
-      scale::compose_cpu(tiles.data(), n, g.cols, tw, th, canvas.data(), pitch);
-      for (int t = 0; t < n; ++t) {
-        TileSrc& s = ts[size_t(t)];
-        if (!tiles[size_t(t)].src) continue;
-        if (s.ring->still_valid(s.slot, s.meta.seq)) {
-          s.done = true;
-          seqs_out[size_t(t)] = s.meta.seq;
-        } else {
-          s.done = false;
-          seqs_out[size_t(t)] = 0;
-          again = true;
-        }
-      }
-      if (!again) break;
-      if (round == 3) {  // still inconsistent: those tiles are drawn as background
-        // (only their cells are cleared: the other tiles were checked after they were drawn)
-        for (int t = 0; t < n; ++t) {
-          if (ts[size_t(t)].done) continue;
-          u8* p = canvas.data() + size_t((t / g.cols) * th) * pitch + size_t((t % g.cols) * tw) * 3;
-          for (int y = 0; y < th; ++y) std::memset(p + size_t(y) * pitch, scale::kBackground, size_t(tw) * 3);
-        }
-      }
-    }
-    for (int t = 0; t < n && !foreign.empty(); ++t) {
-      const ForeignTile& f = foreign[size_t(t)];
-      if (!f.data) continue;
-      u8* p = canvas.data() + size_t((t / g.cols) * th + (th - f.h) / 2) * pitch +
-              size_t((t % g.cols) * tw + (tw - f.w) / 2) * 3;
-      for (int y = 0; y < f.h; ++y) std::memcpy(p + size_t(y) * pitch, f.data + size_t(y) * f.w * 3, size_t(f.w) * 3);
-    }
-    out = jpeg::encode_cpu(canvas.data(), g.w, g.h, quality);
-    return;
-  }
-  dev_.bind();
-  const int cells = g.cols * g.rows;  // (the cells past the last tile are background too)
-  gpu::ScalePool::Lease set = scale_pool_.acquire();
-  set->reserve(canvas_bytes, cells, up_bytes);
-  std::vector<int> tile_of;  // descriptor -> tile of the current round
-  for (int round = 0; round < 5; ++round) {
-    // rounds 0..3 scale the tiles that are not settled; round 4 only clears what is left
-    tile_of.clear();
-    for (int t = 0; t < n; ++t) {
-      TileSrc& s = ts[size_t(t)];
-      if (s.done) continue;
-      gpu::ScaleDesc d = cell(t, set->canvas.p);
-      const bool fgn = !foreign.empty() && foreign[size_t(t)].data;
-      if (!fgn && round < 4 && pick(t)) {
-        const scale::Placement p = scale::place(t, g.cols, tw, th, s.ring->width(), s.ring->height());
-        d.src = s.ring->slot_ptr(s.slot);
-        d.sw = s.ring->width();
-        d.sh = s.ring->height();
-        d.src_pitch = u32(d.sw) * 3;
-        d.dx = p.x;
-        d.dy = p.y;
-        d.ow = p.w;
-        d.oh = p.h;
-      } else {
-        s.slot = -1;
-      }
-      gpu::check_scale(d, g.w, g.h);
-      set->h_descs.p[tile_of.size()] = d;
-      tile_of.push_back(t);
-    }
-    if (tile_of.empty()) break;
-    int nd = int(tile_of.size());
-    for (int t = n; t < cells && round == 0; ++t) {
-      set->h_descs.p[nd] = cell(t, set->canvas.p);
-      gpu::check_scale(set->h_descs.p[nd++], g.w, g.h);
-    }
-    set->run(nd, serve_stream_);
-    if (round == 0 && up_bytes) {  // foreign tiles: over their (background) cells, after the launch
-      size_t off = 0;
-      for (int t = 0; t < n; ++t) {
-        const ForeignTile& f = foreign[size_t(t)];
-        if (!f.data) continue;
-        const size_t row = size_t(f.w) * 3, bytes = row * size_t(f.h);
-        std::memcpy(set->upload.p + off, f.data, bytes);
-        u8* p = set->canvas.p + size_t((t / g.cols) * th + (th - f.h) / 2) * pitch +
-                size_t((t % g.cols) * tw + (tw - f.w) / 2) * 3;
-        VEP_HIP(hipMemcpy2DAsync(p, pitch, set->upload.p + off, row, row, size_t(f.h), hipMemcpyHostToDevice,
-                                 serve_stream_));
-        off += bytes;
-      }
-      VEP_HIP(hipEventRecord(set->ev, serve_stream_));  // (again: after the uploads)
-    }
-    VEP_HIP(hipEventSynchronize(set->ev));
-    for (int t : tile_of) {
-      TileSrc& s = ts[size_t(t)];
-      if (s.slot < 0) {
-        s.done = true;  // background or foreign
-      } else if (s.ring->still_valid(s.slot, s.meta.seq)) {
-        s.done = true;
-        seqs_out[size_t(t)] = s.meta.seq;
-      }
-    }
-  }
-  encode_device(set->canvas.p, g.w, g.h, quality, out);
-}
-
-bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width,
-                              int height) {
-  VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-  if (width || height) {
-    check_box(width, height);
-    std::shared_ptr<Camera> c = camera(cam);
-    if (!c) return false;
-    std::shared_ptr<FrameRing> ring = c->ring();
-    if (!ring) return false;
-    const scale::Size f = scale::fit(ring->width(), ring->height(), width, height);
-    const size_t n = size_t(f.w) * size_t(f.h) * 3;
-    for (int attempt = 0; attempt < 4; ++attempt) {
-      int slot;
-      if (!ring->latest(after, meta, &slot)) return false;
-      if (dev_.gpu()) {
-        dev_.bind();
-        gpu::ScalePool::Lease set = scale_pool_.acquire();
-        set->reserve(n, 1, 0);
-        scale_slot(*set, *ring, slot, f.w, f.h);
-        encode_device(set->canvas.p, f.w, f.h, quality, out);  // (same stream: ordered after the scale)
-      } else {
-        std::vector<u8> small(n);
-        scale::area_cpu(ring->slot_ptr(slot), ring->width(), ring->height(), size_t(ring->width()) * 3, small.data(),
-                        size_t(f.w) * 3, f.w, f.h);
-        out = jpeg::encode_cpu(small.data(), f.w, f.h, quality);
-      }
-      if (ring->still_valid(slot, meta->seq)) {
-        meta->width = f.w;
-        meta->height = f.h;
-        return true;
-      }
-    }
-    return false;
-  }
-  std::shared_ptr<Camera> c = camera(cam);
-  if (!c) return false;
-  std::shared_ptr<FrameRing> ring = c->ring();
-  if (!ring) return false;
-  for (int attempt = 0; attempt < 4; ++attempt) {
-    int slot;
-    if (!ring->latest(after, meta, &slot)) return false;
-    const int w = ring->width(), h = ring->height();
-    if (dev_.gpu()) {
-      dev_.bind();
-      if (!jpeg_pool_.encode(ring->slot_ptr(slot), w, h, quality, serve_stream_, out)) {
-        // the kernels reported an overflow of their scratch: encode the frame on the host
-        std::unique_ptr<u8[]> host(new u8[ring->slot_bytes()]);
-        copy_slot(*ring, slot, host.get());
-        out = jpeg::encode_cpu(host.get(), w, h, quality);
-      }
-    } else {
-      out = jpeg::encode_cpu(ring->slot_ptr(slot), w, h, quality);
-    }
-    if (ring->still_valid(slot, meta->seq)) return true;
-  }
-  return false;
-}
-
-// ------------------------------------------------------------------------- motion detection
-
-void Worker::motion_free(MotionState& st) {
-  if (st.bg[0] || st.bg[1]) dev_.bind();
-  dev_.free(st.bg[0]);
-  dev_.free(st.bg[1]);
-  st.bg[0] = st.bg[1] = nullptr;
-  st.samples = 0;
-  st.w = st.h = 0;
-  st.cur = 0;
-  st.have_bg = false;
-  st.seq = 0;
-  st.ring.reset();
-  st.result = MotionResult{};
-}
-
-void Worker::set_motion_params(const motion::Params& p) {
-  motion::check_params(p);
-  {
-    std::lock_guard<std::mutex> g(motion_mu_);
-    motion_params_ = p;
-    ++motion_gen_;  // a model of an older generation counts as none
-  }
-  std::vector<std::shared_ptr<Camera>> cams;
-  {
-    std::lock_guard<std::mutex> g(cams_mu_);
-    cams = cams_;
-  }
-  for (auto& c : cams) {
-    if (!c) continue;
-    std::lock_guard<std::mutex> g(c->motion.mu);
-    motion_free(c->motion);
-  }
-}
-
-motion::Params Worker::motion_params() {
-  std::lock_guard<std::mutex> g(motion_mu_);
-  return motion_params_;
-}
-
-void Worker::motion_reset(int cam) {
-  std::shared_ptr<Camera> c = camera(cam);
-  VEP_CHECK(c, "no such camera");
-  std::lock_guard<std::mutex> g(c->motion.mu);
-  motion_free(c->motion);
-}
-
-// One camera of a motion request. Its state's mutex is held from pick to commit.
-struct Worker::MotionEval {
-  int cam = -1;
-  i64 after = 0;
-  std::shared_ptr<Camera> c;
-  std::shared_ptr<FrameRing> ring;
-  std::unique_lock<std::mutex> lock;
-  FrameMeta meta;
-  int slot = -1;
-  bool pending = false;  // needs (another) evaluation
-  bool primed = false;   // this evaluation has a model to compare with
-  size_t cells = 0, at = 0;  // its grid in the request's counts buffer
-  std::vector<u32> counts;
-  bool ok = false;
-  MotionResult result;
-};
-
-// evs: distinct cameras in ascending index (the order their mutexes are taken in).
-void Worker::motion_eval(std::vector<MotionEval>& evs) {
-  motion::Params prm;
-  u64 gen;
-  // (every camera is looked up before the first state mutex is taken: remove_camera takes a
-  // state's mutex with the camera table locked)
-  for (MotionEval& e : evs) {
-    e.c = camera(e.cam);
-    if (e.c) e.ring = e.c->ring();
-  }
-  for (MotionEval& e : evs) {
-    if (!e.ring) continue;
-    e.lock = std::unique_lock<std::mutex>(e.c->motion.mu);
-    e.pending = !e.c->motion.removed;
-  }
-  {
-    // (after the cameras' mutexes: set_motion_params stores the parameters before it takes them,
-    // so a model built here under older parameters is reset by it afterwards)
-    std::lock_guard<std::mutex> g(motion_mu_);
-    prm = motion_params_;
-    gen = motion_gen_;
-  }
-  const u32 cell = u32(prm.cell);
-  std::vector<MotionEval*> todo;
-  for (int round = 0; round < 4; ++round) {
-    todo.clear();
-    size_t total_cells = 0;
-    for (MotionEval& e : evs) {
-      if (!e.pending) continue;
-      MotionState& st = e.c->motion;
-      if (!e.ring->latest(e.after, &e.meta, &e.slot)) {
-        e.pending = false;
-        continue;
-      }
-      const bool same_ring = st.ring.lock() == e.ring;
-      if (st.gen != gen || !same_ring || st.w != e.ring->width() || st.h != e.ring->height()) {
-        motion_free(st);  // other parameters, a new ring or a new size: prime again
-        st.gen = gen;
-        st.ring = e.ring;
-      }
-      if (st.seq == e.meta.seq && st.seq != 0) {  // evaluated already: one evaluation per frame
-        e.result = st.result;
-        e.ok = true;
-        e.pending = false;
-        continue;
-      }
-      const int w = e.ring->width(), h = e.ring->height();
-      if (!st.bg[0]) {
-        const size_t samples = size_t(motion::pitch_for(u32(w))) * size_t(h);
-        dev_.bind();
-        st.bg[0] = static_cast<u16*>(dev_.alloc(samples * sizeof(u16)));
-        st.bg[1] = static_cast<u16*>(dev_.alloc(samples * sizeof(u16)));
-        st.samples = samples;
-        st.w = w;
-        st.h = h;
-      }
-      e.primed = st.have_bg;
-      e.cells = size_t(motion::cells(u32(w), cell)) * motion::cells(u32(h), cell);
-      e.at = total_cells;
-      total_cells += e.cells;
-      todo.push_back(&e);
-    }
-    if (todo.empty()) break;
-    if (dev_.gpu()) {
-      dev_.bind();
-      gpu::MotionPool::Lease set = motion_pool_.acquire();
-      set->reserve(int(todo.size()), total_cells);
-      for (size_t k = 0; k < todo.size(); ++k) {
-        MotionEval& e = *todo[k];
-        MotionState& st = e.c->motion;
-        gpu::MotionDesc d{};
-        d.src = e.ring->slot_ptr(e.slot);
-        d.src_pitch = u32(st.w) * 3;
-        d.bg_in = e.primed ? st.bg[st.cur] : nullptr;
-        d.bg_out = st.bg[st.cur ^ 1];
-        d.bg_pitch = motion::pitch_for(u32(st.w));
-        d.counts = set->d_counts.p + e.at;
-        d.w = st.w;
-        d.h = st.h;
-        d.cell = prm.cell;
-        d.threshold = prm.threshold;
-        d.learn_shift = prm.learn_shift;
-        gpu::check_motion(d, e.ring->slot_bytes(), st.samples, e.cells);
-        set->h_descs.p[k] = d;
-      }
-      set->run(int(todo.size()), total_cells, serve_stream_);
-      VEP_HIP(hipEventSynchronize(set->ev));
-      const u32* r = set->h_counts.p;
-      for (MotionEval* e : todo) e->counts.assign(r + e->at, r + e->at + e->cells);
-    } else {
-      for (MotionEval* e : todo) {
-        MotionState& st = e->c->motion;
-        e->counts.resize(e->cells);
-        motion::update_cpu(e->ring->slot_ptr(e->slot), st.w, st.h, size_t(st.w) * 3, e->primed ? st.bg[st.cur] : nullptr,
-                           st.bg[st.cur ^ 1], motion::pitch_for(u32(st.w)), prm.cell, prm.threshold, prm.learn_shift,
-                           e->counts.data());
-      }
-    }
-    for (MotionEval* e : todo) {
-      if (!e->ring->still_valid(e->slot, e->meta.seq)) continue;  // redone from the newer frame, same model
-      MotionState& st = e->c->motion;
-      st.cur ^= 1;
-      st.have_bg = true;
-      st.seq = e->meta.seq;
-      MotionResult& r = st.result;
-      r.seq = e->meta.seq;
-      r.width = st.w;
-      r.height = st.h;
-      r.cell = prm.cell;
-      r.cols = int(motion::cells(u32(st.w), cell));
-      r.rows = int(motion::cells(u32(st.h), cell));
-      r.threshold = prm.threshold;
-      r.primed = e->primed;
-      r.counts = std::move(e->counts);
-      r.summary = motion::summarize(r.counts.data(), st.w, st.h, prm.cell, prm.cell_percent, prm.min_cells);
-      e->c->motion_evaluations.fetch_add(1);
-      if (r.summary.motion) e->c->motion_frames.fetch_add(1);
-      e->result = r;
-      e->ok = true;
-      e->pending = false;
-    }
-  }
-  for (MotionEval& e : evs)
-    if (e.lock.owns_lock()) e.lock.unlock();
-}
-
-bool Worker::read_motion(int cam, i64 after, MotionResult& out) {
-  std::vector<MotionEval> evs(1);
-  evs[0].cam = cam;
-  evs[0].after = after;
-  motion_eval(evs);
-  if (!evs[0].ok) return false;
-  out = std::move(evs[0].result);
-  return true;
-}
-
-void Worker::read_motion_many(const std::vector<int>& cams, std::vector<MotionResult>& out, std::vector<char>& ok) {
-  std::vector<int> order(cams);
-  std::sort(order.begin(), order.end());
-  order.erase(std::unique(order.begin(), order.end()), order.end());
-  std::vector<MotionEval> evs(order.size());
-  for (size_t k = 0; k < order.size(); ++k) evs[k].cam = order[k];
-  motion_eval(evs);
-  out.assign(cams.size(), MotionResult{});
-  ok.assign(cams.size(), 0);
-  for (size_t t = 0; t < cams.size(); ++t) {
-    const size_t k = size_t(std::lower_bound(order.begin(), order.end(), cams[t]) - order.begin());
-    if (!evs[k].ok) continue;
-    out[t] = evs[k].result;
-    ok[t] = 1;
-  }
-}
-
-// ------------------------------------------------------------------------- tamper detection
-
-void Worker::set_tamper_params(const tamper::Params& p) {
-  tamper::check_params(p);
-  {
-    std::lock_guard<std::mutex> g(tamper_mu_);
-    tamper_params_ = p;
-    ++tamper_gen_;  // an answer of an older generation counts as none
-  }
-  std::vector<std::shared_ptr<Camera>> cams;
-  {
-    std::lock_guard<std::mutex> g(cams_mu_);
-    cams = cams_;
-  }
-  for (auto& c : cams) {
-    if (!c) continue;
-    TamperState& st = c->tamper;
-    std::lock_guard<std::mutex> g(st.mu);
-    st.seq = 0;
-    st.result = TamperResult{};
-    if (st.have_ref && st.ref.cell != p.cell) {
-      st.have_ref = false;
-      st.ref = tamper::Reference{};
-    }
-  }
-}
-
-tamper::Params Worker::tamper_params() {
-  std::lock_guard<std::mutex> g(tamper_mu_);
-  return tamper_params_;
-}
-
-void Worker::tamper_reset(int cam) {
-  std::shared_ptr<Camera> c = camera(cam);
-  VEP_CHECK(c, "no such camera");
-  TamperState& st = c->tamper;
-  std::lock_guard<std::mutex> g(st.mu);
-  st.seq = 0;
-  st.result = TamperResult{};
-  st.have_ref = false;
-  st.ref = tamper::Reference{};
-}
-
-// One camera of a tamper request. Its state's mutex is held from pick to commit.
-struct Worker::TamperEval {
-  int cam = -1;
-  i64 after = 0;
-  std::shared_ptr<Camera> c;
-  std::shared_ptr<FrameRing> ring;
-  std::unique_lock<std::mutex> lock;
-  FrameMeta meta;
-  int slot = -1;
-  bool pending = false;  // needs (another) evaluation
-  int w = 0, h = 0;
-  size_t cells = 0;      // of its grid
-  size_t hist_at = 0, grid_at = 0;  // its histogram and its two planes in the request's results
-  std::vector<u32> hist, sum_y, energy;
-  bool ok = false;
-  TamperResult result;
-};
-
-// evs: distinct cameras in ascending index (the order their mutexes are taken in).
-void Worker::tamper_eval(std::vector<TamperEval>& evs, bool set_reference) {
-  tamper::Params prm;
-  u64 gen;
-  // (every camera is looked up before the first state mutex is taken, as in motion_eval)
-  for (TamperEval& e : evs) {
-    e.c = camera(e.cam);
-    if (e.c) e.ring = e.c->ring();
-  }
-  for (TamperEval& e : evs) {
-    if (!e.ring) continue;
-    e.lock = std::unique_lock<std::mutex>(e.c->tamper.mu);
-    e.pending = true;
-  }
-  {
-    // (after the cameras' mutexes: set_tamper_params stores the parameters before it takes them,
-    // so an answer built here under older parameters is reset by it afterwards)
-    std::lock_guard<std::mutex> g(tamper_mu_);
-    prm = tamper_params_;
-    gen = tamper_gen_;
-  }
-  const u32 cell = u32(prm.cell);
-  // The stored answer as the camera's reference, and summarised again against it.
-  auto make_reference = [&](TamperState& st) {
-    const TamperResult& r = st.result;
-    st.ref.w = r.width;
-    st.ref.h = r.height;
-    st.ref.cell = r.cell;
-    st.ref.sum_y = r.sum_y;
-    st.ref.energy_total = r.summary.energy_total;
-    st.have_ref = true;
-    st.result.summary = tamper::summarize(r.hist.data(), r.sum_y.data(), r.energy.data(), r.width, r.height, prm, &st.ref);
-  };
-  std::vector<TamperEval*> todo;
-  for (int round = 0; round < 4; ++round) {
-    todo.clear();
-    size_t grid_words = 0;
-    for (TamperEval& e : evs) {
-      if (!e.pending) continue;
-      TamperState& st = e.c->tamper;
-      if (!e.ring->latest(e.after, &e.meta, &e.slot)) {
-        e.pending = false;
-        continue;
-      }
-      if (st.gen != gen || st.ring.lock() != e.ring) {  // other parameters or a new ring: no stored answer
-        st.seq = 0;
-        st.result = TamperResult{};
-        if (st.have_ref && st.ref.cell != prm.cell) {
-          st.have_ref = false;
-          st.ref = tamper::Reference{};
-        }
-        st.gen = gen;
-        st.ring = e.ring;
-      }
-      if (st.seq == e.meta.seq && st.seq != 0) {  // evaluated already: one evaluation per frame
-        if (set_reference) make_reference(st);
-        e.result = st.result;
-        e.ok = true;
-        e.pending = false;
-        continue;
-      }
-      e.w = e.ring->width();
-      e.h = e.ring->height();
-      e.cells = size_t(tamper::cells(u32(e.w), cell)) * tamper::cells(u32(e.h), cell);
-      e.hist_at = todo.size() * size_t(tamper::kBins);
-      e.grid_at = grid_words;
-      grid_words += 2 * e.cells;
-      todo.push_back(&e);
-    }
-    if (todo.empty()) break;
-    const size_t hist_words = todo.size() * size_t(tamper::kBins), res_words = hist_words + grid_words;
-    for (TamperEval* e : todo) e->grid_at += hist_words;  // the planes follow the histograms
-    if (dev_.gpu()) {
-      dev_.bind();
-      gpu::TamperPool::Lease set = tamper_pool_.acquire();
-      set->reserve(int(todo.size()), res_words);
-      for (size_t k = 0; k < todo.size(); ++k) {
-        TamperEval& e = *todo[k];
-        gpu::TamperDesc d{};
-        d.src = e.ring->slot_ptr(e.slot);
-        d.src_pitch = u32(e.w) * 3;
-        d.hist = set->d_res.p + e.hist_at;
-        d.sum_y = set->d_res.p + e.grid_at;
-        d.energy = set->d_res.p + e.grid_at + e.cells;
-        d.w = e.w;
-        d.h = e.h;
-        d.cell = prm.cell;
-        gpu::check_tamper(d, e.ring->slot_bytes(), e.cells);
-        set->h_descs.p[k] = d;
-      }
-      set->run(int(todo.size()), hist_words, res_words, serve_stream_);
-      VEP_HIP(hipEventSynchronize(set->ev));
-      for (TamperEval* e : todo) {
-        const u32* r = set->h_res.p;
-        e->hist.assign(r + e->hist_at, r + e->hist_at + tamper::kBins);
-        e->sum_y.assign(r + e->grid_at, r + e->grid_at + e->cells);
-        e->energy.assign(r + e->grid_at + e->cells, r + e->grid_at + 2 * e->cells);
-      }
-    } else {
-      for (TamperEval* e : todo) {
-        e->hist.resize(size_t(tamper::kBins));
-        e->sum_y.resize(e->cells);
-        e->energy.resize(e->cells);
-        tamper::stats_cpu(e->ring->slot_ptr(e->slot), e->w, e->h, size_t(e->w) * 3, prm.cell, e->hist.data(),
-                          e->sum_y.data(), e->energy.data());
-      }
-    }
-    for (TamperEval* e : todo) {
-      if (!e->ring->still_valid(e->slot, e->meta.seq)) continue;  // redone from the newer frame
-      TamperState& st = e->c->tamper;
-      st.seq = e->meta.seq;
-      TamperResult& r = st.result;
-      r.seq = e->meta.seq;
-      r.width = e->w;
-      r.height = e->h;
-      r.cell = prm.cell;
-      r.cols = int(tamper::cells(u32(e->w), cell));
-      r.rows = int(tamper::cells(u32(e->h), cell));
-      r.hist = std::move(e->hist);
-      r.sum_y = std::move(e->sum_y);
-      r.energy = std::move(e->energy);
-      r.summary = tamper::summarize(r.hist.data(), r.sum_y.data(), r.energy.data(), e->w, e->h, prm,
-                                    st.have_ref ? &st.ref : nullptr);
-      e->c->tamper_evaluations.fetch_add(1);
-      if (r.summary.tampered) e->c->tamper_frames.fetch_add(1);
-      if (set_reference) make_reference(st);
-      e->result = r;
-      e->ok = true;
-      e->pending = false;
-    }
-  }
-  for (TamperEval& e : evs)
-    if (e.lock.owns_lock()) e.lock.unlock();
-}
-
-bool Worker::read_tamper(int cam, i64 after, TamperResult& out) {
-  std::vector<TamperEval> evs(1);
-  evs[0].cam = cam;
-  evs[0].after = after;
-  tamper_eval(evs, false);
-  if (!evs[0].ok) return false;
-  out = std::move(evs[0].result);
-  return true;
-}
-
-void Worker::read_tamper_many(const std::vector<int>& cams, std::vector<TamperResult>& out, std::vector<char>& ok) {
-  std::vector<int> order(cams);
-  std::sort(order.begin(), order.end());
-  order.erase(std::unique(order.begin(), order.end()), order.end());
-  std::vector<TamperEval> evs(order.size());
-  for (size_t k = 0; k < order.size(); ++k) evs[k].cam = order[k];
-  tamper_eval(evs, false);
-  out.assign(cams.size(), TamperResult{});
-  ok.assign(cams.size(), 0);
-  for (size_t t = 0; t < cams.size(); ++t) {
-    const size_t k = size_t(std::lower_bound(order.begin(), order.end(), cams[t]) - order.begin());
-    if (!evs[k].ok) continue;
-    out[t] = evs[k].result;
-    ok[t] = 1;
-  }
-}
-
-bool Worker::tamper_set_reference(int cam) {
-  VEP_CHECK(camera(cam), "no such camera");
-  std::vector<TamperEval> evs(1);
-  evs[0].cam = cam;
-  tamper_eval(evs, true);
-  return evs[0].ok;
-}
-
-void Worker::copy_slot(FrameRing& ring, int slot, u8* dst) {
-  const size_t n = ring.slot_bytes();
-  if (!dev_.gpu()) {
-    std::memcpy(dst, ring.slot_ptr(slot), n);
-    return;
-  }
-  dev_.bind();
-  ServeBuf* b = acquire_serve(n);  // D2H through a pinned pool buffer, as read_latest
-  try {
-    VEP_HIP(hipMemcpyAsync(b->h, ring.slot_ptr(slot), n, hipMemcpyDeviceToHost, serve_stream_));
-    VEP_HIP(hipEventRecord(b->ev[0], serve_stream_));
-    VEP_HIP(hipEventSynchronize(b->ev[0]));
-    std::memcpy(dst, b->h, n);
-  } catch (...) {
-    release_serve(b);
-    throw;
-  }
-  release_serve(b);
-}
-
-std::vector<Worker::HistoryFrame> Worker::read_history(int cam, i64 after, int max_count) {
-  std::vector<HistoryFrame> res;
-  std::shared_ptr<Camera> c = camera(cam);
-  if (!c) return res;
-  std::shared_ptr<FrameRing> r = c->ring();
-  if (!r) return res;
-  // (a ring without a history keeps only its newest frame readable)
-  const int depth = std::max(1, r->history());
-  std::vector<std::pair<FrameMeta, int>> want;
-  r->range(after, max_count > 0 ? std::min(max_count, depth) : depth, want);
-  // newest first: a frame the writer took meanwhile ends the run (it and everything older is
-  // dropped, so the result stays contiguous and ends at the newest frame read)
-  for (size_t k = want.size(); k-- > 0;) {
-    HistoryFrame f;
-    f.meta = want[k].first;
-    f.bytes = r->slot_bytes();
-    f.data.reset(new u8[f.bytes]);
-    copy_slot(*r, want[k].second, f.data.get());
-    if (!r->still_valid(want[k].second, f.meta.seq)) break;
-    res.push_back(std::move(f));
-  }
-  std::reverse(res.begin(), res.end());
-  return res;
-}
-
-Worker::ServeBuf* Worker::acquire_serve(size_t n) {
-  ServeBuf* b = nullptr;
-  {
-    std::unique_lock<std::mutex> g(serve_mu_);
-    if (serve_free_.empty() && serve_all_.size() < size_t(kServeBufs)) {
-      serve_all_.push_back(std::make_unique<ServeBuf>());
-      serve_free_.push_back(serve_all_.back().get());
-    }
-    serve_cv_.wait(g, [&] { return !serve_free_.empty(); });
-    b = serve_free_.back();
-    serve_free_.pop_back();
-  }
-  if (b->cap < n) {  // first use, or a larger ring (resolution change)
-    dev_.free_pinned(b->h);
-    b->h = static_cast<u8*>(dev_.alloc_pinned(n));
-    b->cap = n;
-  }
-  if (!b->ev[0] && dev_.gpu())
-    for (hipEvent_t& e : b->ev)  // waiters sleep: several server threads wait at once
-      VEP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync));
-  return b;
-}
-
-void Worker::release_serve(ServeBuf* b) {
-  {
-    std::lock_guard<std::mutex> g(serve_mu_);
-    serve_free_.push_back(b);
-  }
-  serve_cv_.notify_one();
-}
-
-bool Worker::register_host(void* p, size_t n) {
-  if (!dev_.gpu() || !p || !n) return false;
-  dev_.bind();
-  if (hipHostRegister(p, n, hipHostRegisterDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return true;
-}
-
-void Worker::unregister_host(void* p) {
-  if (!dev_.gpu() || !p) return;
-  dev_.bind();
-  (void)hipHostUnregister(p);
-}
-
-bool Worker::read_latest(FrameRing& rg, i64 after, FrameMeta* meta, u8* dst, size_t cap, bool dst_pinned) {
-  FrameRing* ring = &rg;
-  for (int attempt = 0; attempt < 4; ++attempt) {
-    int slot;
-    if (!ring->latest(after, meta, &slot)) return false;
-    const size_t n = ring->slot_bytes();
-    VEP_CHECK(cap >= n, "read_latest destination too small");
-    if (dev_.gpu() && dst_pinned) {
-      dev_.bind();
-      ServeBuf* b = acquire_serve(0);  // only its completion event: the DMA lands in dst
-      try {
-        VEP_HIP(hipMemcpyAsync(dst, ring->slot_ptr(slot), n, hipMemcpyDeviceToHost, serve_stream_));
-        VEP_HIP(hipEventRecord(b->ev[0], serve_stream_));
-        VEP_HIP(hipEventSynchronize(b->ev[0]));
-      } catch (...) {
-        release_serve(b);
-        throw;
-      }
-      release_serve(b);
-      if (!ring->still_valid(slot, meta->seq)) continue;
-      return true;
-    }
-    if (dev_.gpu() || mock_serve_) {  // (mock: the same pool and chunking, memcpy for the DMA)
-      const bool gpu = dev_.gpu();
-      if (gpu) dev_.bind();
-      ServeBuf* b = acquire_serve(n);
-      const u8* src = ring->slot_ptr(slot);
-      const size_t chunk = (n + kServeChunks - 1) / kServeChunks;
-      try {
-        for (int k = 0; k < kServeChunks; ++k) {
-          const size_t off = size_t(k) * chunk;
-          if (off >= n) break;
-          if (!gpu) {
-            std::memcpy(b->h + off, src + off, std::min(chunk, n - off));
-            continue;
-          }
-          VEP_HIP(hipMemcpyAsync(b->h + off, src + off, std::min(chunk, n - off), hipMemcpyDeviceToHost,
-                                 serve_stream_));
-          VEP_HIP(hipEventRecord(b->ev[k], serve_stream_));
-        }
-        for (int k = 0; k < kServeChunks; ++k) {
-          const size_t off = size_t(k) * chunk;
-          if (off >= n) break;
-          if (gpu) VEP_HIP(hipEventSynchronize(b->ev[k]));
-          std::memcpy(dst + off, b->h + off, std::min(chunk, n - off));
-        }
-      } catch (...) {
-        release_serve(b);
-        throw;
-      }
-      release_serve(b);
-      if (!ring->still_valid(slot, meta->seq)) continue;
-      return true;
-    }
-    std::memcpy(dst, ring->slot_ptr(slot), n);
-    if (ring->still_valid(slot, meta->seq)) return true;
-  }
-  return false;
-}
-
 size_t Worker::snapshot_consumer(void* dst, size_t cap, int rows, hipStream_t stream) {
   VEP_CHECK(opt_.letterbox_size > 0 && cons_hwc_, "consumer batch disabled (letterbox_size is 0)");
   rows = std::clamp(rows, 0, cons_rows_);
@@ -3463,110 +2550,6 @@ size_t Worker::snapshot_consumer(void* dst, size_t cap, int rows, hipStream_t st
   snap_gen_.fetch_add(1);
   if (!stream) VEP_HIP(hipStreamSynchronize(s));
   return n;
-}
-
-void Worker::read_latest_many(std::vector<ReadReq>& reqs) {
-  if (!dev_.gpu()) {
-    for (auto& r : reqs) r.ok = read_latest(*r.ring, r.after, &r.meta, r.dst, r.cap, r.pinned);
-    return;
-  }
-  dev_.bind();
-  std::vector<int> slot(reqs.size(), -1);
-  bool queued = false;
-  for (size_t k = 0; k < reqs.size(); ++k) {
-    ReadReq& r = reqs[k];
-    r.ok = false;
-    if (!r.pinned) {
-      r.ok = read_latest(*r.ring, r.after, &r.meta, r.dst, r.cap, false);
-      continue;
-    }
-    if (!r.ring->latest(r.after, &r.meta, &slot[k])) continue;
-    VEP_CHECK(r.cap >= r.ring->slot_bytes(), "read_latest_many destination too small");
-    VEP_HIP(hipMemcpyAsync(r.dst, r.ring->slot_ptr(slot[k]), r.ring->slot_bytes(), hipMemcpyDeviceToHost,
-                           serve_stream_));
-    queued = true;
-  }
-  if (!queued) return;
-  ServeBuf* b = acquire_serve(0);  // (its completion event)
-  try {
-    VEP_HIP(hipEventRecord(b->ev[0], serve_stream_));
-    VEP_HIP(hipEventSynchronize(b->ev[0]));
-  } catch (...) {
-    release_serve(b);
-    throw;
-  }
-  release_serve(b);
-  for (size_t k = 0; k < reqs.size(); ++k)  // a slot the writer reused meanwhile is not served
-    if (slot[k] >= 0) reqs[k].ok = reqs[k].ring->still_valid(slot[k], reqs[k].meta.seq);
-}
-
-// --------------------------------------------------------------------------- proto encoding
-
-static void put_varint(std::string& s, u64 v) {
-  while (v >= 0x80) {
-    s.push_back(char((v & 0x7f) | 0x80));
-    v >>= 7;
-  }
-  s.push_back(char(v));
-}
-static void put_tag(std::string& s, int field, int wt) { put_varint(s, u64(field) << 3 | u64(wt)); }
-static void put_i64(std::string& s, int field, i64 v) {
-  if (v == 0) return;
-  put_tag(s, field, 0);
-  put_varint(s, u64(v));
-}
-static void put_bool(std::string& s, int field, bool v) {
-  if (!v) return;
-  put_tag(s, field, 0);
-  s.push_back(1);
-}
-static void put_str(std::string& s, int field, const std::string& v) {
-  if (v.empty()) return;
-  put_tag(s, field, 2);
-  put_varint(s, v.size());
-  s += v;
-}
-
-std::pair<std::string, std::string> encode_video_frame(const FrameMeta& m, size_t data_len,
-                                                       const std::string& device_id) {
-  std::string pre, suf;
-  put_i64(pre, 1, m.width);
-  put_i64(pre, 2, m.height);
-  if (data_len) {
-    put_tag(pre, 3, 2);
-    put_varint(pre, data_len);
-  }
-  put_i64(suf, 4, m.timestamp);
-  put_bool(suf, 5, m.is_keyframe);
-  put_i64(suf, 6, m.pts);
-  put_i64(suf, 7, m.dts);
-  if (m.frame_type != '?' && m.frame_type != 0) put_str(suf, 8, std::string(1, m.frame_type));
-  put_bool(suf, 9, m.is_corrupt);
-  if (m.time_base != 0.0) {
-    put_tag(suf, 10, 1);
-    u64 bits;
-    std::memcpy(&bits, &m.time_base, 8);
-    for (int i = 0; i < 8; ++i) suf.push_back(char((bits >> (8 * i)) & 0xff));
-  }
-  if (m.width > 0) {  // ShapeProto{dim: [(H,"0"), (W,"1"), (3,"2")]}
-    std::string shape;
-    const i64 dims[3] = {m.height, m.width, 3};
-    for (int k = 0; k < 3; ++k) {
-      std::string dim;
-      put_i64(dim, 1, dims[k]);
-      put_str(dim, 2, std::string(1, char('0' + k)));
-      put_tag(shape, 2, 2);
-      put_varint(shape, dim.size());
-      shape += dim;
-    }
-    put_tag(suf, 11, 2);
-    put_varint(suf, shape.size());
-    suf += shape;
-  }
-  put_str(suf, 12, device_id);
-  put_i64(suf, 13, m.packet);
-  put_i64(suf, 14, m.keyframe);
-  return {pre, suf};
 }
 
 }  // namespace vep

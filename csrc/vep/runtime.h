@@ -418,7 +418,7 @@ struct WorkerOptions {
   // the default; 0 = off.
   int kf_window_us = -1;
   // CPU backend only (sanitizer runs): serve through the pinned serve-buffer pool with chunked
-  // copies, as the GPU path's D2H does, so its concurrency (acquire_serve / release_serve, chunk
+  // copies, as the GPU path's D2H does, so its concurrency (the pool's leases, chunk
   // hand-off) runs under ThreadSanitizer without a GPU. Also VEP_MOCK_SERVE=1.
   bool mock_serve = false;
   // CPU backend: the reference's per-frame copy chain after the BGR24 conversion
@@ -775,17 +775,17 @@ class Worker {
   // kServeChunks pieces: the host copy of chunk k overlaps the DMA of chunk k+1.
   static constexpr int kServeBufs = 8;
   static constexpr int kServeChunks = 4;
-  struct ServeBuf {
+  struct ServeBuf {  // a set of the pool below (scratch.h), leased for one copy
+    Device* dev = nullptr;  // owner of h
     u8* h = nullptr;
     size_t cap = 0;
-    hipEvent_t ev[kServeChunks] = {};
+    gpu::SetEvent ev[kServeChunks];  // one per chunk (GPU only)
+    ~ServeBuf();
+    void reserve(Device& d, size_t n);  // grow-only pinned room for n bytes; the events on first use
   };
-  ServeBuf* acquire_serve(size_t n);
-  void release_serve(ServeBuf* b);
-  std::mutex serve_mu_;
-  std::condition_variable serve_cv_;
-  std::vector<std::unique_ptr<ServeBuf>> serve_all_;
-  std::vector<ServeBuf*> serve_free_;
+  // (by pointer: ~Worker destroys the sets before the serving stream, with the device alive)
+  using ServePool = ScratchPool<ServeBuf, kServeBufs>;
+  std::unique_ptr<ServePool> serve_pool_ = std::make_unique<ServePool>();
   gpu::JpegPool jpeg_pool_;  // encoder scratch of read_latest_jpeg, one set per request in flight
   gpu::ScalePool scale_pool_;  // canvas + descriptors of the scaled / wall reads, likewise
   std::atomic<int> wall_max_tiles_{64};  // serving.wall_max_tiles
@@ -793,6 +793,8 @@ class Worker {
   void encode_device(const u8* d_bgr, int w, int h, int quality, std::string& out);
   // ring slot -> ow x oh at the origin of set's canvas, on the serving stream (no wait)
   void scale_slot(gpu::ScaleSet& set, const FrameRing& ring, int slot, int ow, int oh);
+  template <class Consume>  // the scaled read of read_latest_scaled and read_latest_jpeg (serve.cpp)
+  bool read_scaled(int cam, i64 after, int width, int height, bool download, FrameMeta* meta, Consume&& consume);
   u8* cons_hwc_ = nullptr;
   void* cons_chw_ = nullptr;
   // consumer snapshots: exclusive while a snapshot is enqueued, shared while a lane enqueues a
@@ -853,16 +855,14 @@ class Worker {
   std::mutex motion_mu_;         // motion_params_ / motion_gen_
   motion::Params motion_params_;
   u64 motion_gen_ = 1;
-  struct MotionEval;
-  void motion_eval(std::vector<MotionEval>& evs);
+  struct MotionOp;  // the motion reads as an op of read_consistent_rounds (ring_read.h, serve.cpp)
   void motion_free(MotionState& st);  // (st.mu held)
   // tamper detection (after motion's members)
   gpu::TamperPool tamper_pool_;  // descriptors + results of the tamper reads, one set per request in flight
   std::mutex tamper_mu_;         // tamper_params_ / tamper_gen_
   tamper::Params tamper_params_;
   u64 tamper_gen_ = 1;
-  struct TamperEval;
-  void tamper_eval(std::vector<TamperEval>& evs, bool set_reference);
+  struct TamperOp;  // likewise
 };
 
 // Protobuf wire encoding of chrys.cloud.videostreaming.v1beta1.VideoFrame

@@ -1,7 +1,8 @@
 """ThreadSanitizer / AddressSanitizer runs of the native stress driver (csrc/tests/native_stress.cpp)
 and of the scratch pool's stand-alone selftest (csrc/tests/scratch_selftest.cpp); the stage plan's
-selftest (csrc/tests/stage_plan_selftest.cpp) un-instrumented (`make asan-plan` runs it under
-AddressSanitizer + UndefinedBehaviorSanitizer).
+selftest (csrc/tests/stage_plan_selftest.cpp) and the serving reads' selftest
+(csrc/tests/serve_selftest.cpp) un-instrumented (`make asan-plan` / `make asan-serve` run them
+under AddressSanitizer + UndefinedBehaviorSanitizer).
 
 Host-code sanitizers only (`-Xarch_host -fsanitize=...`; GPU sanitizers are unavailable), CPU
 backend. Building takes about a minute per sanitizer, so the test runs when VEP_SANITIZERS=1
@@ -44,6 +45,18 @@ def test_stage_plan_selftest():
     out = r.stdout + r.stderr
     assert r.returncode == 0, out[-4000:]
     assert "stage_plan_selftest ok" in out
+
+
+def test_serve_selftest():
+    """The serving reads' consistent-read rule (csrc/vep/ring_read.h), un-instrumented (`make
+    asan-serve` runs it under AddressSanitizer + UndefinedBehaviorSanitizer): a slot rewritten or
+    invalidated during the read is read again from the newer frame and never served or committed,
+    kReadAttempts times at the most; stored answers are not evaluated again. Linked against the
+    objects of the build."""
+    r = subprocess.run(["make", "-C", ROOT, "serve-selftest"], capture_output=True, text=True, timeout=600)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-4000:]
+    assert "serve_selftest ok" in out
 
 
 def test_sanitizer_target_links():
