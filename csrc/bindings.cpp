@@ -13,6 +13,7 @@
 #include "vep/bench_driver.h"
 #include "vep/cabac.h"
 #include "vep/codec.h"
+#include "vep/crop.h"
 #include "vep/gpu.h"
 #include "vep/h264.h"
 #include "vep/hevc_ctu.h"
@@ -218,6 +219,44 @@ static std::vector<MaskTuple> mask_tuples(const std::vector<mask::Mask>& v) {
   std::vector<MaskTuple> out;
   for (const mask::Mask& m : v) out.emplace_back(m.x0, m.y0, m.x1, m.y1, m.mode, m.block, m.b, m.g, m.r);
   return out;
+}
+
+// Crop boxes cross the boundary as tuples (x0, y0, x1, y1) of ints, a pad colour as (b, g, r); an
+// invalid list, output size, fit or colour is a ValueError.
+using BoxTuple = std::tuple<int, int, int, int>;
+using PadTuple = std::tuple<int, int, int>;
+static std::vector<crop::Box> boxes_of(const std::vector<BoxTuple>& v) {
+  std::vector<crop::Box> out;
+  for (const BoxTuple& t : v) {
+    crop::Box b;
+    std::tie(b.x0, b.y0, b.x1, b.y1) = t;
+    out.push_back(b);
+  }
+  try {
+    VEP_CHECK(out.size() <= size_t(crop::kMaxBoxes), "crop: at most 64 boxes per picture");
+    crop::check_list(out.data(), int(out.size()));
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return out;
+}
+static crop::Pad crop_output_of(int ow, int oh, int fit, const PadTuple& pad) {
+  crop::Pad p;
+  std::tie(p.b, p.g, p.r) = pad;
+  try {
+    crop::check_output(ow, oh, fit, p);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return p;
+}
+// (n, oh, ow, 3) over the bytes of px, which the array takes over: no second copy of the crops
+static py::array_t<uint8_t> crops_array(std::vector<u8>& px, size_t n, int ow, int oh) {
+  const std::vector<py::ssize_t> shape = {py::ssize_t(n), py::ssize_t(oh), py::ssize_t(ow), py::ssize_t(3)};
+  if (px.empty()) return py::array_t<uint8_t>(shape);
+  auto* keep = new std::vector<u8>(std::move(px));
+  py::capsule owner(keep, [](void* p) { delete static_cast<std::vector<u8>*>(p); });
+  return py::array_t<uint8_t>(shape, keep->data(), owner);
 }
 
 static tamper::Params tamper_params_of(int cell, int dark_level, int bright_level, int spread_min, int focus_percent,
@@ -1748,6 +1787,77 @@ PYBIND11_MODULE(_vep, m) {
              return mask_tuples(w.privacy_masks(i));
            },
            py::arg("idx"))
+      .def("read_crops",
+           // (meta, ndarray (n, height, width, 3)) of the boxes of the newest frame with seq > after
+           // (seq 0) or of frame `seq`, cut and resized where the frame lies; None if there is no
+           // such frame. ValueError on an invalid list, size, fit or pad colour.
+           [](Worker& w, int i, const std::vector<BoxTuple>& boxes, int width, int height, i64 after, i64 seq, int fit,
+              const PadTuple& pad) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const std::vector<crop::Box> bs = boxes_of(boxes);
+             const crop::Pad p = crop_output_of(width, height, fit, pad);
+             if (after < 0 || seq < 0) throw py::value_error("crop: after and seq must be >= 0");
+             FrameMeta m;
+             std::vector<u8> px;
+             bool ok;
+             {
+               py::gil_scoped_release r;
+               ok = w.read_crops(i, after, seq, bs, width, height, fit, p, &m, px);
+             }
+             if (!ok) return py::none();
+             return py::make_tuple(meta_dict(m), crops_array(px, bs.size(), width, height));
+           },
+           py::arg("idx"), py::arg("boxes"), py::arg("width"), py::arg("height"), py::arg("after") = 0,
+           py::arg("seq") = 0, py::arg("fit") = 0, py::arg("pad") = PadTuple(crop::kPad, crop::kPad, crop::kPad))
+      .def("read_crops_many",
+           // [(meta, ndarray) | None] for requests (idx, after, seq, boxes), a camera may repeat: the
+           // crops of every request in one launch a round. None: an unknown index, no ring, no
+           // such frame, or a frame that stayed inconsistent.
+           [](Worker& w, const std::vector<std::tuple<int, i64, i64, std::vector<BoxTuple>>>& requests, int width,
+              int height, int fit, const PadTuple& pad) {
+             const crop::Pad p = crop_output_of(width, height, fit, pad);
+             std::vector<Worker::CropRequest> reqs(requests.size());
+             for (size_t k = 0; k < requests.size(); ++k) {
+               reqs[k].cam = std::get<0>(requests[k]);
+               reqs[k].after = std::get<1>(requests[k]);
+               reqs[k].seq = std::get<2>(requests[k]);
+               if (reqs[k].after < 0 || reqs[k].seq < 0) throw py::value_error("crop: after and seq must be >= 0");
+               reqs[k].boxes = boxes_of(std::get<3>(requests[k]));
+             }
+             {
+               py::gil_scoped_release r;
+               w.read_crops_many(reqs, width, height, fit, p);
+             }
+             py::list out;
+             for (Worker::CropRequest& r : reqs)
+               out.append(r.ok ? py::object(py::make_tuple(meta_dict(r.meta), crops_array(r.data, r.boxes.size(), width, height)))
+                               : py::object(py::none()));
+             return out;
+           },
+           py::arg("requests"), py::arg("width"), py::arg("height"), py::arg("fit") = 0,
+           py::arg("pad") = PadTuple(crop::kPad, crop::kPad, crop::kPad))
+      .def("read_crop_jpeg",
+           // (meta, bytes): one box as a JPEG, the encoder chained onto the crop on the device.
+           [](Worker& w, int i, const BoxTuple& box, int width, int height, i64 after, i64 seq, int quality, int fit,
+              const PadTuple& pad) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const std::vector<crop::Box> bs = boxes_of({box});
+             const crop::Pad p = crop_output_of(width, height, fit, pad);
+             if (after < 0 || seq < 0) throw py::value_error("crop: after and seq must be >= 0");
+             if (quality < 1 || quality > 100) throw py::value_error("jpeg: quality must be 1..100");
+             FrameMeta m;
+             std::string out;
+             bool ok;
+             {
+               py::gil_scoped_release r;
+               ok = w.read_crop_jpeg(i, after, seq, bs[0], width, height, fit, p, quality, &m, out);
+             }
+             if (!ok) return py::none();
+             return py::make_tuple(meta_dict(m), py::bytes(out));
+           },
+           py::arg("idx"), py::arg("box"), py::arg("width"), py::arg("height"), py::arg("after") = 0,
+           py::arg("seq") = 0, py::arg("quality") = 85, py::arg("fit") = 0,
+           py::arg("pad") = PadTuple(crop::kPad, crop::kPad, crop::kPad))
       .def("read_history",
            // [(meta, ndarray)] of the newest `count` (0 = the camera's history depth) frames with
            // seq > after: ascending, contiguous in seq, ending at the newest frame.
@@ -2391,6 +2501,104 @@ PYBIND11_MODULE(_vep, m) {
           VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
         },
         py::arg("pictures"), py::arg("stream"));
+  // Crops (vep/crop.h) on the host: the arithmetic itself, and the CPU backend's path, the
+  // byte-exact reference of crop_resize.
+  m.def("crop_taps",
+        // (D, [(j, i, w), ...]): the taps of every output index of an axis of s source samples and
+        // o outputs, over the denominator D
+        [](int s, int o) {
+          if (s < 1 || s > crop::kMaxSide || o < 1 || o > crop::kMaxOut)
+            throw py::value_error("crop_taps: source extent must be 1..65535, output extent 1..4096");
+          py::list taps;
+          for (int j = 0; j < o; ++j) {
+            const crop::Taps t = crop::taps(u32(j), u32(s), u32(o));
+            for (u32 i = t.lo; i <= t.hi; ++i) taps.append(py::make_tuple(j, i, crop::weight_of(t, i)));
+          }
+          return py::make_tuple(crop::den(u32(s), u32(o)), taps);
+        },
+        py::arg("s"), py::arg("o"));
+  m.def("crop_fit",
+        // (x, y, w, h): where a letterboxed rect of sw x sh lies in a width x height output
+        [](int sw, int sh, int width, int height) {
+          if (sw < 1 || sh < 1 || sw > crop::kMaxSide || sh > crop::kMaxSide)
+            throw py::value_error("crop_fit: rect size must be 1..65535");
+          crop_output_of(width, height, crop::kLetterbox, PadTuple(0, 0, 0));
+          const crop::Placement p = crop::fitted(sw, sh, width, height, crop::kLetterbox);
+          return py::make_tuple(p.x, p.y, p.w, p.h);
+        },
+        py::arg("sw"), py::arg("sh"), py::arg("width"), py::arg("height"));
+  m.def("crop_pixels",
+        // (x0, y0, x1, y1) in pixels of a box of a w x h picture, rounded outward
+        [](int w, int h, const BoxTuple& box) {
+          if (w < 1 || h < 1 || w > crop::kMaxSide || h > crop::kMaxSide)
+            throw py::value_error("crop_pixels: picture size must be 1..65535");
+          const std::vector<crop::Box> bs = boxes_of({box});
+          const mask::Rect r = crop::to_pixels(w, h, bs[0]);
+          return py::make_tuple(r.x0, r.y0, r.x1, r.y1);
+        },
+        py::arg("width"), py::arg("height"), py::arg("box"));
+  m.def("crop_resize_cpu",
+        // (n, height, width, 3): the boxes of a C-contiguous (H, W, 3) uint8 picture
+        [](py::array_t<uint8_t, py::array::c_style> bgr, const std::vector<BoxTuple>& boxes, int width, int height,
+           int fit, const PadTuple& pad) {
+          if (bgr.ndim() != 3 || bgr.shape(2) != 3 || bgr.shape(0) < 1 || bgr.shape(1) < 1 ||
+              bgr.shape(0) > crop::kMaxSide || bgr.shape(1) > crop::kMaxSide)
+            throw py::value_error("crop_resize_cpu: (H, W, 3) uint8 picture of at most 65535 x 65535 expected");
+          const std::vector<crop::Box> bs = boxes_of(boxes);
+          const crop::Pad p = crop_output_of(width, height, fit, pad);
+          const int h = int(bgr.shape(0)), w = int(bgr.shape(1));
+          py::array_t<uint8_t> o({py::ssize_t(bs.size()), py::ssize_t(height), py::ssize_t(width), py::ssize_t(3)});
+          const u8* src = bgr.data();
+          u8* q = o.mutable_data();
+          {
+            py::gil_scoped_release r;
+            crop::apply_cpu(src, size_t(w) * 3, w, h, bs.data(), int(bs.size()), q, width, height, fit, p);
+          }
+          return o;
+        },
+        py::arg("bgr").noconvert(), py::arg("boxes"), py::arg("width"), py::arg("height"), py::arg("fit") = 0,
+        py::arg("pad") = PadTuple(crop::kPad, crop::kPad, crop::kPad));
+  // Pictures (src, w, h, boxes) on caller-owned device buffers into the caller-owned output `out`
+  // of out_bytes (every crop width x height x 3 packed, one after the other in list order): ONE
+  // launch of the gfx950 crop kernel for all boxes of all pictures, on `stream` of the current
+  // device (descriptors: one process-wide pool per device). src is h x w x 3 packed.
+  m.def("crop_resize",
+        [](const std::vector<std::tuple<uintptr_t, int, int, std::vector<BoxTuple>>>& pics, int width, int height,
+           int fit, const PadTuple& pad, uintptr_t out, size_t out_bytes, uintptr_t stream) {
+          const crop::Pad p = crop_output_of(width, height, fit, pad);
+          std::vector<std::vector<crop::Box>> lists;
+          size_t nd = 0;
+          for (const auto& pc : pics) {
+            const int w = std::get<1>(pc), h = std::get<2>(pc);
+            if (w < 1 || h < 1 || w > crop::kMaxSide || h > crop::kMaxSide)
+              throw py::value_error("crop: picture size must be 1..65535");
+            lists.push_back(boxes_of(std::get<3>(pc)));
+            nd += lists.back().size();
+          }
+          if (nd == 0) return;
+          const size_t one = size_t(width) * size_t(height) * 3;
+          if (nd > 65535) throw py::value_error("crop_resize: at most 65535 boxes per call");
+          if (nd * one > out_bytes) throw py::value_error("crop_resize: output smaller than the crops");
+          py::gil_scoped_release r;
+          hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+          gpu::CropPool::Lease set = pool_of_current_device<gpu::CropPool>().acquire();
+          set->reserve(int(nd), 0, 0);
+          const u32 pw = u32(p.b) | u32(p.g) << 8 | u32(p.r) << 16;
+          size_t k = 0;
+          for (size_t i = 0; i < pics.size(); ++i) {
+            const u8* src = reinterpret_cast<const u8*>(std::get<0>(pics[i]));
+            const int w = std::get<1>(pics[i]), h = std::get<2>(pics[i]);
+            for (const crop::Box& b : lists[i]) {
+              set->h_descs.p[k] = gpu::make_crop_desc(src, size_t(w) * size_t(h) * 3, w, h, crop::to_pixels(w, h, b),
+                                                      reinterpret_cast<u8*>(out) + k * one, one, width, height, fit, pw);
+              ++k;
+            }
+          }
+          set->run(int(nd), 0, s);
+          VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
+        },
+        py::arg("pictures"), py::arg("width"), py::arg("height"), py::arg("fit"), py::arg("pad"), py::arg("out"),
+        py::arg("out_bytes"), py::arg("stream"));
   // Pictures (src, w, h, hist, sum_y, energy) on caller-owned device buffers: one launch of the
   // gfx950 tamper kernel on `stream` of the current device (descriptors: one process-wide pool
   // per device). src is h x w x 3 packed, hist 256 u32 (zeroed here, on the stream), the planes

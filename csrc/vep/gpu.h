@@ -555,6 +555,48 @@ struct MaskSet : DescSet<MaskDesc> {
 };
 using MaskPool = ScratchPool<MaskSet>;
 
+// ---- crops (gpu_crop.hip; arithmetic: crop.h) --------------------------------------------------
+// One box of one picture of a batched crop launch (device memory): the pixel rect x0..x1 x y0..y1
+// of a packed BGR24 picture resampled (reduced, enlarged or both, crop.h) into the rectangle
+// fw x fh at (fx, fy) of its own packed ow x oh output, every other pixel of the output the pad
+// colour; byte-identical with crop::apply_cpu. Pictures, rects and fitted rectangles of one launch
+// may all differ; the outputs of one launch must not overlap.
+struct CropDesc {
+  const VEP_DEV u8* src;  // ph rows of src_pitch bytes (any alignment)
+  VEP_DEV u8* dst;        // this crop's own output: oh rows of ow * 3 bytes, packed (any alignment)
+  u32 src_pitch;          // bytes
+  i32 pw, ph;             // the picture
+  i32 x0, y0, x1, y1;     // crop::to_pixels: 0 <= x0 < x1 <= pw, 0 <= y0 < y1 <= ph
+  u16 ow, oh;             // 1 .. crop::kMaxOut
+  u16 fx, fy, fw, fh;     // crop::fitted: the picture's rectangle in the output
+  u32 pad_bgr;            // b | g << 8 | r << 16
+  u32 pad_;
+};
+static_assert(sizeof(CropDesc) == 64, "CropDesc layout");
+// Throws unless the kernel can run the descriptor without reading outside a picture of src_bytes
+// and without writing outside the crop's own oh * ow * 3 bytes, of which dst_bytes are there (the
+// launch below does not check).
+void check_crop(const CropDesc& d, size_t src_bytes, size_t dst_bytes);
+// One launch for the n crops: grid = (tiles of the largest fitted rectangle + rows of the tallest
+// padded output) x crops. h_descs is the host copy of d_descs (the grid is sized from it).
+void launch_crop(const CropDesc* d_descs, const CropDesc* h_descs, int n, hipStream_t s);
+// The descriptor of one box: the w x h picture at src (src_bytes long, rows of w * 3 bytes) into
+// the ow x oh output at dst (dst_bytes long); pixel rect and fitted rectangle from crop.h, checked.
+CropDesc make_crop_desc(const u8* src, size_t src_bytes, int w, int h, const mask::Rect& rect, u8* dst,
+                        size_t dst_bytes, int ow, int oh, int fit, u32 pad_bgr);
+
+// Crop scratch of one device (pool contract: above): descriptors, the outputs of a request one
+// after the other, and their copy on the host.
+struct CropSet : DescSet<CropDesc> {
+  DevBuf<u8> out;
+  PinBuf<u8> host;
+  void reserve(int ndescs, size_t out_bytes, size_t host_bytes);
+  // Copies the first n host descriptors up, launches them on `s`, then copies the first
+  // down_bytes of `out` into `host` (0: nothing comes down) and records the event (no wait).
+  void run(int n, size_t down_bytes, hipStream_t s);
+};
+using CropPool = ScratchPool<CropSet>;
+
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 
 struct LetterboxDesc {

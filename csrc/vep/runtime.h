@@ -21,6 +21,7 @@
 
 #include "avc.h"
 #include "codec.h"
+#include "crop.h"
 #include "hevc_dec.h"
 #include "hevc_kern.h"
 #include "hostplan.h"
@@ -556,6 +557,30 @@ class Worker {
   // flight when they complete, and resets the camera's motion model and tamper state.
   void set_privacy_masks(int cam, const std::vector<mask::Mask>& masks);
   std::vector<mask::Mask> privacy_masks(int cam);
+  // Crops (crop.h, docs/CROPS.md): the boxes of a frame, cut and resized to ow x oh where the frame
+  // lies, in its ring slot, on the serving stream (CPU backend: crop::apply_cpu on the host ring);
+  // only the crops come down, n packed BGR24 pictures one after the other in dst. seq == 0: the
+  // newest frame with seq > after; seq > 0: that very frame (a detector's boxes belong to the
+  // frame it saw), found in the camera's history, no answer once it has left the ring. A slot the
+  // writer reused (or a mask change invalidated) meanwhile is read again, up to four times, and
+  // what was produced from it is never returned. Crops read the ring slot, so they show the
+  // camera's privacy masks. Throws on an invalid list, size, fit or pad colour.
+  bool read_crops(int cam, i64 after, i64 seq, const std::vector<crop::Box>& boxes, int ow, int oh, int fit,
+                  const crop::Pad& pad, FrameMeta* meta, std::vector<u8>& dst);
+  // Several cameras (a camera may repeat): the crops of every request in ONE launch a round.
+  struct CropRequest {
+    int cam = -1;
+    i64 after = 0, seq = 0;
+    std::vector<crop::Box> boxes;
+    bool ok = false;   // out: false for an unknown camera, no ring, no such frame, still inconsistent
+    FrameMeta meta;    // out
+    std::vector<u8> data;  // out: boxes.size() * oh * ow * 3 bytes
+  };
+  void read_crops_many(std::vector<CropRequest>& reqs, int ow, int oh, int fit, const crop::Pad& pad);
+  // One crop as a JPEG stream: the encoder is chained onto the crop on the device, only the
+  // compressed bytes come down.
+  bool read_crop_jpeg(int cam, i64 after, i64 seq, const crop::Box& box, int ow, int oh, int fit, const crop::Pad& pad,
+                      int quality, FrameMeta* meta, std::string& out);
   void set_wall_max_tiles(int n);
   int wall_max_tiles() const { return wall_max_tiles_.load(); }
   // Frame history: the newest max_count (0 = the camera's depth) frames with seq > after, copied
@@ -863,6 +888,9 @@ class Worker {
   tamper::Params tamper_params_;
   u64 tamper_gen_ = 1;
   struct TamperOp;  // likewise
+  // crops (after tamper's members)
+  gpu::CropPool crop_pool_;  // descriptors + outputs of the crop reads, one set per request in flight
+  struct CropOp;  // likewise
 };
 
 // Protobuf wire encoding of chrys.cloud.videostreaming.v1beta1.VideoFrame

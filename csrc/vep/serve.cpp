@@ -1,9 +1,11 @@
 // The serving reads: the Worker methods that answer a client from a camera's ring (frames, scaled
-// frames, JPEGs, the wall, history, motion and tamper), the serve-buffer pool they copy through, and
-// the VideoFrame wire encoding. Every read follows the consistent-read rule of ring_read.h.
+// frames, JPEGs, the wall, history, motion, tamper and crops), the serve-buffer pool they copy
+// through, and the VideoFrame wire encoding. Every read follows the consistent-read rule of
+// ring_read.h.
 #include <algorithm>
 #include <cstring>
 
+#include "crop.h"
 #include "jpeg.h"
 #include "ring_read.h"
 #include "runtime.h"
@@ -686,6 +688,132 @@ bool Worker::tamper_set_reference(int cam) {
   VEP_CHECK(camera(cam), "no such camera");
   TamperOp op{*this, true};
   return read_camera<TamperOp, TamperResult>(*this, op, cam, 0, nullptr);
+}
+
+// ------------------------------------------------------------------------------------- crops
+
+static u32 pad_word(const crop::Pad& p) { return u32(p.b) | u32(p.g) << 8 | u32(p.r) << 16; }
+
+// The crop reads as an op of read_consistent_rounds: nothing is stored, every request is produced
+// from its slot, all requests of a round in one launch.
+struct Worker::CropOp {
+  struct Eval : ReadEntry {
+    CropRequest* req = nullptr;
+  };
+  Worker& w;
+  int ow, oh, fit;
+  crop::Pad pad;
+  bool stored(Eval&) { return false; }
+  void plan(Eval&) {}
+  void run(std::vector<Eval*>& todo) {
+    const size_t one = size_t(ow) * size_t(oh) * 3;
+    if (!w.dev_.gpu()) {
+      for (Eval* e : todo) {
+        CropRequest& r = *e->req;
+        r.data.resize(r.boxes.size() * one);
+        crop::apply_cpu(e->ring->slot_ptr(e->slot), size_t(e->ring->width()) * 3, e->ring->width(), e->ring->height(),
+                        r.boxes.data(), int(r.boxes.size()), r.data.data(), ow, oh, fit, pad);
+      }
+      return;
+    }
+    size_t nd = 0;
+    for (Eval* e : todo) nd += e->req->boxes.size();
+    VEP_CHECK(nd <= 65535, "crop: at most 65535 boxes per request");
+    for (Eval* e : todo) e->req->data.clear();
+    if (!nd) return;
+    w.dev_.bind();
+    gpu::CropPool::Lease set = w.crop_pool_.acquire();
+    set->reserve(int(nd), nd * one, nd * one);
+    size_t k = 0;
+    for (Eval* e : todo) {
+      const FrameRing& ring = *e->ring;
+      for (const crop::Box& b : e->req->boxes) {
+        set->h_descs.p[k] = gpu::make_crop_desc(ring.slot_ptr(e->slot), ring.slot_bytes(), ring.width(), ring.height(),
+                                                crop::to_pixels(ring.width(), ring.height(), b), set->out.p + k * one,
+                                                one, ow, oh, fit, pad_word(pad));
+        ++k;
+      }
+    }
+    set->run(int(nd), nd * one, w.serve_stream_);
+    VEP_HIP(hipEventSynchronize(set->ev));
+    k = 0;
+    for (Eval* e : todo) {
+      const size_t n = e->req->boxes.size();
+      e->req->data.assign(set->host.p + k * one, set->host.p + (k + n) * one);
+      k += n;
+    }
+  }
+  void commit(Eval& e) {  // the slot proved unchanged
+    e.req->meta = e.meta;
+    e.req->ok = true;
+  }
+};
+
+void Worker::read_crops_many(std::vector<CropRequest>& reqs, int ow, int oh, int fit, const crop::Pad& pad) {
+  crop::check_output(ow, oh, fit, pad);
+  for (CropRequest& r : reqs) {
+    crop::check_list(r.boxes.data(), int(r.boxes.size()));
+    VEP_CHECK(r.after >= 0 && r.seq >= 0, "crop: after and seq must be >= 0");
+    r.ok = false;
+    r.data.clear();
+  }
+  std::vector<CropOp::Eval> evs(reqs.size());
+  for (size_t k = 0; k < reqs.size(); ++k) {
+    CropOp::Eval& e = evs[k];
+    e.req = &reqs[k];
+    e.after = reqs[k].after;
+    e.seq = reqs[k].seq;
+    if (std::shared_ptr<Camera> c = camera(reqs[k].cam)) e.ring = c->ring();
+    e.pending = e.ring != nullptr;
+  }
+  CropOp op{*this, ow, oh, fit, pad};
+  read_consistent_rounds(evs, op);
+  for (CropRequest& r : reqs)
+    if (!r.ok) r.data.clear();  // (produced from a slot that was reused: never returned)
+}
+
+bool Worker::read_crops(int cam, i64 after, i64 seq, const std::vector<crop::Box>& boxes, int ow, int oh, int fit,
+                        const crop::Pad& pad, FrameMeta* meta, std::vector<u8>& dst) {
+  std::vector<CropRequest> reqs(1);
+  reqs[0].cam = cam;
+  reqs[0].after = after;
+  reqs[0].seq = seq;
+  reqs[0].boxes = boxes;
+  read_crops_many(reqs, ow, oh, fit, pad);
+  if (!reqs[0].ok) return false;
+  *meta = reqs[0].meta;
+  dst.swap(reqs[0].data);
+  return true;
+}
+
+bool Worker::read_crop_jpeg(int cam, i64 after, i64 seq, const crop::Box& box, int ow, int oh, int fit,
+                            const crop::Pad& pad, int quality, FrameMeta* meta, std::string& out) {
+  VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  crop::check_box(box);
+  crop::check_output(ow, oh, fit, pad);
+  VEP_CHECK(after >= 0 && seq >= 0, "crop: after and seq must be >= 0");
+  std::shared_ptr<Camera> c = camera(cam);
+  if (!c) return false;
+  std::shared_ptr<FrameRing> ring = c->ring();
+  if (!ring) return false;
+  const int w = ring->width(), h = ring->height();
+  const size_t one = size_t(ow) * size_t(oh) * 3;
+  return read_consistent(*ring, after, seq, meta, [&](int slot, const FrameMeta&) {
+    if (!dev_.gpu()) {
+      std::vector<u8> host(one);
+      crop::apply_cpu(ring->slot_ptr(slot), size_t(w) * 3, w, h, &box, 1, host.data(), ow, oh, fit, pad);
+      out = jpeg::encode_cpu(host.data(), ow, oh, quality);
+      return;
+    }
+    dev_.bind();
+    gpu::CropPool::Lease set = crop_pool_.acquire();
+    set->reserve(1, one, 0);
+    set->h_descs.p[0] = gpu::make_crop_desc(ring->slot_ptr(slot), ring->slot_bytes(), w, h, crop::to_pixels(w, h, box),
+                                            set->out.p, one, ow, oh, fit, pad_word(pad));
+    set->run(1, 0, serve_stream_);
+    // (the same stream, so the encode is ordered after the crop; it waits for the stream)
+    encode_device(set->out.p, ow, oh, quality, out);
+  });
 }
 
 void Worker::copy_slot(FrameRing& ring, int slot, u8* dst) {

@@ -8,6 +8,8 @@
   motion    REST client of the motion detector (--device NAME --rest host:port [--watch])
   tamper    REST client of the tamper detector (--device NAME --rest host:port [--watch] [--set-reference])
   privacy   REST client of a camera's privacy masks (--device NAME --rest host:port [--set JSON | --clear])
+  crop      REST client of crop.jpg: one box of a frame as a JPEG (--device NAME --rest host:port
+            --box x0,y0,x1,y1 --size WxH [--seq N] --out f.jpg)
 """
 from __future__ import annotations
 
@@ -286,6 +288,48 @@ def cmd_privacy(a):
         raise SystemExit(f"privacy: HTTP {e.code} for {a.device!r}{detail}")
 
 
+def crop_url(a) -> str:
+    """The crop.jpg request of ``vep crop``'s arguments (SystemExit on a malformed --box / --size)."""
+    import re
+    import urllib.parse
+
+    m = re.fullmatch(r"(\d+),(\d+),(\d+),(\d+)", a.box.replace(" ", ""))
+    if not m:
+        raise SystemExit("crop: --box is x0,y0,x1,y1 in 1/10000 of the picture")
+    sz = re.fullmatch(r"(\d{1,5})[xX](\d{1,5})", a.size.strip())
+    if not sz:
+        raise SystemExit("crop: --size is WxH")
+    q = {"box": ",".join(m.groups()), "width": sz.group(1), "height": sz.group(2), "fit": a.fit}
+    if a.seq:
+        q["seq"] = str(a.seq)
+    if a.quality is not None:
+        q["quality"] = str(a.quality)
+    return (f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/crop.jpg?"
+            + urllib.parse.urlencode(q, safe=","))
+
+
+def cmd_crop(a):
+    """REST client of ``/api/v1/process/{name}/crop.jpg``: one box of the camera's newest frame (or
+    of frame ``--seq``), cut and resized on the hub's GPU, written to ``--out``."""
+    import json
+    import urllib.error
+    import urllib.request
+
+    try:
+        with urllib.request.urlopen(crop_url(a), timeout=10) as r:
+            jpg, seq = r.read(), r.headers.get("X-Vep-Seq")
+    except urllib.error.HTTPError as e:
+        detail = ""
+        try:
+            detail = ": " + json.loads(e.read()).get("message", "")
+        except ValueError:
+            pass
+        raise SystemExit(f"crop: HTTP {e.code} for {a.device!r}{detail}")
+    with open(a.out, "wb") as f:
+        f.write(jpg)
+    print(f"seq {seq}: {len(jpg)} bytes -> {a.out}", flush=True)
+
+
 def cmd_bench(a, rest):
     """``vep bench ...`` = the repo's bench.py (headline benchmark) with the same flags."""
     import subprocess
@@ -382,6 +426,17 @@ def build_parser():
                     help='a JSON list of masks, e.g. \'[{"x0":0,"y0":0,"x1":2500,"y1":10000,"mode":"pixelate","block":16}]\'')
     pv.add_argument("--clear", action="store_true", help="remove the camera's masks")
     pv.set_defaults(fn=cmd_privacy)
+
+    cr = sub.add_parser("crop", help="one box of a camera's frame as a JPEG, cut and resized on the GPU (REST)")
+    cr.add_argument("--device", required=True)
+    cr.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API")
+    cr.add_argument("--box", required=True, help="x0,y0,x1,y1 in 1/10000 of the picture")
+    cr.add_argument("--size", required=True, help="WxH of the JPEG (each 1..4096)")
+    cr.add_argument("--seq", type=int, default=0, help="that very frame (needs buffer.in_memory); default: the newest")
+    cr.add_argument("--fit", default="stretch", choices=["stretch", "letterbox"])
+    cr.add_argument("--quality", type=int, default=None)
+    cr.add_argument("--out", required=True, help="file to write")
+    cr.set_defaults(fn=cmd_crop)
 
     b = sub.add_parser("bench", help="run bench.py (flags passed through, e.g. --codec h265)")
     b.set_defaults(fn=None)

@@ -105,6 +105,8 @@ class ServingConfig:
     jpeg_quality: int = 85      # frame.jpg / stream.mjpg / Hub.latest_jpeg when a request names none (1..100)
     wall_tile: str = "320x180"  # wall.jpg / wall.mjpg / Hub.wall_jpeg: cell size "WxH" when a request names none
     wall_max_tiles: int = 64    # cameras one wall may show (1..65535)
+    crop_max_boxes: int = 64    # boxes one crop request may name per camera (1..64)
+    crop_max_bytes: int = 64 << 20  # output bytes (boxes x width x height x 3) one crop request may ask for
 
 
 @dataclass
@@ -219,6 +221,12 @@ def validate(cfg: Config) -> None:
         raise ValueError(f"serving.wall_tile: {e}") from None
     if not 1 <= int(cfg.serving.wall_max_tiles) <= 65535:
         raise ValueError(f"serving.wall_max_tiles must be 1..65535, got {cfg.serving.wall_max_tiles}")
+    v = cfg.serving.crop_max_boxes
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 64:
+        raise ValueError(f"serving.crop_max_boxes must be an integer 1..64, got {v!r}")
+    v = cfg.serving.crop_max_bytes
+    if isinstance(v, bool) or not isinstance(v, int) or v < 3:
+        raise ValueError(f"serving.crop_max_bytes must be an integer >= 3, got {v!r}")
     for key, (lo, hi) in MOTION_RANGES.items():
         v = getattr(cfg.motion, key)
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:

@@ -17,7 +17,7 @@ import time
 from dataclasses import dataclass, field
 from typing import Optional
 
-from .. import privacy
+from .. import crops, privacy
 from .._native import gpu_count, native
 from ..config import Config, parse_tile
 from ..utils import now_ms
@@ -79,6 +79,8 @@ class Hub:
         if host_domains is None:
             host_domains = native.plan_host_domains(list(devices), [str(c) for c in (g.host_cpus or [])])
         self.host_domains = host_domains
+        self._crop_lock = threading.Lock()
+        self._crop_counts = [0, 0]  # requests, boxes (Hub.crop_counts, /metrics)
         self.workers = []
         for d, dom in zip(devices, host_domains):
             w = native.Worker(device=d, letterbox_size=int(g.letterbox_size),
@@ -557,6 +559,90 @@ class Hub:
     def privacy_masks(self, name: str) -> list:
         w, cam = self.worker_of(name)
         return privacy.from_native(w.privacy_masks(cam))
+
+    # ------------------------------------------------------------------ crops
+    def _crop_args(self, lists, width, height, after, seq, fit, pad):
+        """A crop request as the native layer takes it; ``ValueError`` on a bad value or one above
+        ``serving.crop_max_boxes`` / ``serving.crop_max_bytes``."""
+        width, height = crops.size(width, height)
+        after, seq = crops.seq_args(after, seq)
+        fit, pad = crops.fit_index(fit), crops.pad_tuple(pad)
+        max_boxes = int(self.cfg.serving.crop_max_boxes)
+        native_lists = [crops.to_native(boxes, max_boxes) for boxes in lists]
+        total = sum(len(b) for b in native_lists) * width * height * 3
+        if total > int(self.cfg.serving.crop_max_bytes):
+            raise ValueError(f"the request asks for {total} bytes of crops, above serving.crop_max_bytes = "
+                             f"{self.cfg.serving.crop_max_bytes}")
+        return native_lists, width, height, after, seq, fit, pad
+
+    def _count_crops(self, boxes: int) -> None:
+        with self._crop_lock:
+            self._crop_counts[0] += 1
+            self._crop_counts[1] += boxes
+
+    def crop_counts(self) -> tuple[int, int]:
+        """(crop requests served or refused for want of a frame, boxes they named) since the start."""
+        with self._crop_lock:
+            return self._crop_counts[0], self._crop_counts[1]
+
+    def crops(self, name: str, boxes, width: int, height: int, after: int = 0, seq: int = 0,
+              fit: str = "stretch", pad=None):
+        """``(seq, ndarray [n, height, width, 3])``: the ``boxes`` (dicts ``{"x0", "y0", "x1",
+        "y1"}`` in 1/10000 of the picture, :mod:`..crops`) of a frame of the camera, cut and resized
+        on its GPU in one kernel launch, in its ring slot; only the crops are copied to the host.
+        ``seq=0``: the newest frame with seq > ``after``; ``seq=N``: that very frame, while
+        ``buffer.in_memory`` still holds it (a detector's boxes belong to the frame it saw).
+        ``None`` when there is no such frame. A box is reduced by area averaging and enlarged
+        bilinearly, exact in integers (docs/CROPS.md); ``fit="letterbox"`` keeps the aspect and pads
+        with ``pad`` ``(b, g, r)``, default 114. Crops read the ring slot, so they show the camera's
+        privacy masks. Refreshes ``last_query``, so asking keeps the camera's lazy decoder awake."""
+        (native_boxes,), width, height, after, seq, fit, pad = self._crop_args([boxes], width, height, after, seq, fit,
+                                                                               pad)
+        w, cam = self.worker_of(name)
+        w.set_last_query(cam, now_ms())
+        self._count_crops(len(native_boxes))
+        r = w.read_crops(cam, native_boxes, width, height, after, seq, fit, pad)
+        return None if r is None else (int(r[0]["seq"]), r[1])
+
+    def crops_many(self, boxes_by_name: dict, width: int, height: int, after: int = 0, fit: str = "stretch",
+                   pad=None) -> dict:
+        """``{name: (seq, ndarray) | None}`` for the newest frame with seq > ``after`` of several
+        cameras, each with its own boxes: one kernel launch per worker covers all of its cameras."""
+        if not isinstance(boxes_by_name, dict):
+            raise ValueError("boxes_by_name must be a dict {name: boxes}")
+        order = list(boxes_by_name)
+        lists, width, height, after, _, fit, pad = self._crop_args([boxes_by_name[n] for n in order], width, height,
+                                                                   after, 0, fit, pad)
+        with self._lock:
+            hs = [self.handle(n) for n in order]
+        now = now_ms()
+        for h in hs:
+            self.workers[h.worker_index].set_last_query(h.cam, now)
+        self._count_crops(sum(len(b) for b in lists))
+        out = {}
+        for wi, w in enumerate(self.workers):
+            mine = [(h, b) for h, b in zip(hs, lists) if h.worker_index == wi]
+            if not mine:
+                continue
+            rs = w.read_crops_many([(h.cam, after, 0, b) for h, b in mine], width, height, fit, pad)
+            for (h, _), r in zip(mine, rs):
+                out[h.name] = None if r is None else (int(r[0]["seq"]), r[1])
+        return {n: out[n] for n in order}
+
+    def crop_jpeg(self, name: str, box, width: int, height: int, after: int = 0, seq: int = 0,
+                  quality: Optional[int] = None, fit: str = "stretch", pad=None):
+        """``(seq, bytes)``: one box of a frame as a baseline JPEG of ``width x height``, the encoder
+        chained onto the crop on the camera's GPU; only compressed bytes are copied. Arguments as
+        :meth:`crops`; ``quality`` 1..100, default ``serving.jpeg_quality``. A digital zoom for any
+        viewer."""
+        q = self._quality(quality)
+        (native_boxes,), width, height, after, seq, fit, pad = self._crop_args([[box]], width, height, after, seq, fit,
+                                                                               pad)
+        w, cam = self.worker_of(name)
+        w.set_last_query(cam, now_ms())
+        self._count_crops(1)
+        r = w.read_crop_jpeg(cam, native_boxes[0], width, height, after, seq, q, fit, pad)
+        return None if r is None else (int(r[0]["seq"]), r[1])
 
     def history(self, name: str, after: int = 0, count: int = 0) -> list:
         """``[(meta, ndarray)]`` of the camera's newest ``count`` (0 = ``buffer.in_memory``) frames

@@ -631,6 +631,17 @@ class ProcessHub:
     def wall_jpeg(self, names=None, cols=None, tile_width=None, tile_height=None, quality=None):
         raise NotImplementedError("the camera wall is not served with gpu.isolation: process")
 
+    # Crops read a ring slot, and with seq=N the ring's history: both live in the worker processes,
+    # so crops are served only by the in-process hub (gpu.isolation: thread).
+    def crops(self, name: str, boxes, width, height, after=0, seq=0, fit="stretch", pad=None):
+        raise NotImplementedError("crops are not served with gpu.isolation: process")
+
+    def crops_many(self, boxes_by_name, width, height, after=0, fit="stretch", pad=None):
+        raise NotImplementedError("crops are not served with gpu.isolation: process")
+
+    def crop_jpeg(self, name: str, box, width, height, after=0, seq=0, quality=None, fit="stretch", pad=None):
+        raise NotImplementedError("crops are not served with gpu.isolation: process")
+
     def wait_decoded(self, name: str, n: int = 1, timeout_s: float = 10.0) -> bool:
         return bool(self._call(name, "wait_decoded", n, timeout_s))
 

@@ -22,6 +22,10 @@
 * :func:`privacy_mask` / :func:`privacy_mask_batch` — fill or pixelate rectangles of BGR24
   pictures in place, one launch per level of overlap for all pictures (the kernel that masks a
   camera's ring slot before it is published), byte-identical with :func:`privacy_mask_reference`.
+* :func:`crop_resize` / :func:`crop_resize_batch` — boxes of BGR24 pictures cut and resized
+  (reduced by area averaging, enlarged bilinearly, stretched or letterboxed) to one output size,
+  every box of every picture in a single launch (the kernel behind ``/crops`` and ``crop.jpg``),
+  byte-identical with :func:`crop_resize_reference`.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -674,6 +678,82 @@ def privacy_mask_reference(bgr: torch.Tensor, masks) -> torch.Tensor:
     out = bgr.detach().cpu().clone().numpy()
     native.mask_apply_cpu(out, privacy.to_native(masks))
     return torch.from_numpy(out)
+
+
+def _check_crop_args(width, height, fit, pad):
+    from .. import crops
+
+    width, height = crops.size(width, height)
+    return width, height, crops.fit_index(fit), crops.pad_tuple(pad)
+
+
+def crop_resize_batch(pictures, boxes_per_picture, width: int, height: int, fit: str = "stretch",
+                      pad=(114, 114, 114), out: torch.Tensor | None = None) -> torch.Tensor:
+    """The boxes (dicts ``{"x0", "y0", "x1", "y1"}`` in 1/10000 of the picture, :mod:`..crops`) of
+    a list of contiguous ``[H, W, 3]`` BGR24 device tensors of any sizes on one device, each with
+    its own list of at most 64 boxes, cut and resized to ``[n, height, width, 3]`` (``n`` the boxes
+    of all pictures, in list order) in ONE kernel launch. A box reduces by area averaging and
+    enlarges bilinearly (half-pixel centres, clamped edges), each axis on its own, exact in
+    integers; ``fit="letterbox"`` keeps the aspect and fills the rest with ``pad`` ``(b, g, r)``.
+    ``out``: a contiguous uint8 tensor of that shape on the pictures' device (a view at any byte
+    offset will do). Byte-identical with :func:`crop_resize_reference`. No CPU fallback."""
+    from .. import crops
+
+    pictures = list(pictures)
+    boxes_per_picture = list(boxes_per_picture)
+    if len(pictures) != len(boxes_per_picture):
+        raise ValueError("boxes_per_picture must hold one list per picture")
+    width, height, fit, pad = _check_crop_args(width, height, fit, pad)
+    device, work, n = None, [], 0
+    for k, (bgr, boxes) in enumerate(zip(pictures, boxes_per_picture)):
+        if not isinstance(bgr, torch.Tensor):
+            raise TypeError(f"pictures[{k}] must be a tensor")
+        w, h = _check_bgr(bgr, f"pictures[{k}]")
+        if not bgr.is_cuda:
+            raise ValueError("bgr must be a device tensor")
+        if device is None:
+            device = bgr.device
+        if bgr.device != device:
+            raise ValueError("the pictures must live on one device")
+        work.append((bgr.data_ptr(), w, h, crops.to_native(boxes)))
+        n += len(work[-1][3])
+    if device is None:
+        if out is None:
+            raise ValueError("pictures must hold at least one picture")
+        device = out.device
+    require_gpu()
+    shape = (n, height, width, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == device and out.dtype == torch.uint8
+            and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on the pictures' device")
+    if n:
+        with torch.cuda.device(device):
+            native.crop_resize(work, width, height, fit, pad, out.data_ptr(), out.numel(),
+                               int(torch.cuda.current_stream(device).cuda_stream))
+    return out
+
+
+def crop_resize(bgr: torch.Tensor, boxes, width: int, height: int, fit: str = "stretch", pad=(114, 114, 114),
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """The boxes of one ``[H, W, 3]`` BGR24 device tensor as ``[n, height, width, 3]``: see
+    :func:`crop_resize_batch`."""
+    return crop_resize_batch([bgr], [boxes], width, height, fit, pad, out)
+
+
+def crop_resize_reference(bgr: torch.Tensor, boxes, width: int, height: int, fit: str = "stretch",
+                          pad=(114, 114, 114)) -> torch.Tensor:
+    """The CPU implementation's result for the same picture (host or device tensor), on the host:
+    the byte-exact oracle of :func:`crop_resize`."""
+    from .. import crops
+
+    if not isinstance(bgr, torch.Tensor):
+        raise TypeError("bgr must be a tensor")
+    _check_bgr(bgr)
+    width, height, fit, pad = _check_crop_args(width, height, fit, pad)
+    return torch.from_numpy(native.crop_resize_cpu(bgr.detach().cpu().numpy(), crops.to_native(boxes), width, height,
+                                                   fit, pad))
 
 
 # ----------------------------------------------------------------------------- references

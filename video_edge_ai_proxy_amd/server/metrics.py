@@ -74,6 +74,14 @@ class HubCollector:
             wf.add_metric([str(d)], w.frames)
             wg.add_metric([str(d)], w.gpu_ms_total)
         yield from (wb, wf, wg)
+        counts = getattr(self.hub, "crop_counts", None)
+        if counts is not None:
+            requests, boxes = counts()
+            cr = CounterMetricFamily("vep_crop_requests", "crop requests (crops, crops_many, crop.jpg)")
+            cr.add_metric([], requests)
+            cb = CounterMetricFamily("vep_crop_boxes", "boxes the crop requests named")
+            cb.add_metric([], boxes)
+            yield from (cr, cb)
         try:
             from .._native import native
 

@@ -18,7 +18,8 @@ docs/WALL.md), ``/api/v1/process/{name}/motion`` and ``/api/v1/motion`` (did any
 motion detection on the GPU, docs/MOTION.md; ``DELETE .../motion`` resets the background),
 ``/api/v1/process/{name}/tamper`` and ``/api/v1/tamper`` (does the camera still show what it should:
 tamper detection on the GPU, docs/TAMPER.md; ``PUT .../tamper/reference`` declares the newest frame
-normal, ``DELETE .../tamper`` forgets it), and the portal itself at ``/`` (replaces the Angular build, which needs a node
+normal, ``DELETE .../tamper`` forgets it), ``POST /api/v1/process/{name}/crops`` and
+``GET .../crop.jpg`` (boxes of a frame cut and resized on the GPU, docs/CROPS.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
 toolchain).
 """
 from __future__ import annotations
@@ -420,6 +421,57 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         except (KeyError, ProcessError):
             return err(404, f"process {name!r} not found")
         return Response(status_code=204)
+
+    # ---- crops: boxes of a frame, cut and resized on the GPU in its ring slot (docs/CROPS.md)
+    @app.post("/api/v1/process/{name}/crops")
+    async def crops_post(name: str, request: Request):
+        from starlette.concurrency import run_in_threadpool
+
+        try:
+            body = json.loads(await request.body() or b"null")
+            if not isinstance(body, dict):
+                raise ValueError("a JSON object expected")
+            unknown = set(body) - {"boxes", "width", "height", "fit", "pad", "after", "seq"}
+            if unknown:
+                raise ValueError(f"unknown field(s): {sorted(unknown)}")
+            for k in ("boxes", "width", "height"):
+                if k not in body:
+                    raise ValueError(f"field {k} is missing")
+            r = await run_in_threadpool(pm.hub.crops, name, body["boxes"], body["width"], body["height"],
+                                        body.get("after", 0), body.get("seq", 0), body.get("fit", "stretch"),
+                                        body.get("pad"))
+        except ValueError as e:  # (invalid JSON included)
+            return err(422, str(e))
+        except NotImplementedError as e:
+            return err(501, str(e))
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        if r is None:
+            return err(404, "no such frame")
+        seq, px = r
+        return Response(content=px.tobytes(), media_type="application/octet-stream",
+                        headers={"X-Vep-Seq": str(seq), "X-Vep-Crops": f"{px.shape[0]},{px.shape[2]},{px.shape[1]}"})
+
+    @app.get("/api/v1/process/{name}/crop.jpg")
+    def crop_jpg(name: str, box: str, width: int, height: int, fit: str = "stretch", quality: int | None = None,
+                 after: int = 0, seq: int = 0):
+        try:
+            try:
+                rect = [int(v) for v in box.split(",")]
+            except ValueError:
+                raise ValueError("box must be x0,y0,x1,y1") from None
+            if len(rect) != 4:
+                raise ValueError("box must be x0,y0,x1,y1")
+            r = pm.hub.crop_jpeg(name, rect, width, height, after, seq, quality, fit)
+        except ValueError as e:
+            return err(422, str(e))
+        except NotImplementedError as e:
+            return err(501, str(e))
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        if r is None:
+            return err(404, "no such frame")
+        return Response(content=r[1], media_type="image/jpeg", headers={"X-Vep-Seq": str(r[0])})
 
     @app.get("/api/v1/tamper")
     def tamper_many(names: str | None = None, grid: int = 0, wake: int = 1):
