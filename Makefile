@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask asan-crop tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask asan-crop asan-overlay tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -129,6 +129,17 @@ $(ASAN_DIR)/crop_selftest: csrc/vep/crop.cpp csrc/tests/crop_selftest.cpp csrc/v
 
 asan-crop: $(ASAN_DIR)/crop_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/crop_selftest
+
+# The CPU on-screen display alone on its edge shapes and closed forms (csrc/tests/overlay_selftest.cpp),
+# likewise: a stand-alone host program, no GPU.
+$(ASAN_DIR)/overlay_selftest: csrc/vep/overlay.cpp csrc/tests/overlay_selftest.cpp csrc/vep/overlay.h csrc/vep/mask.h csrc/vep/common.h
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc csrc/vep/overlay.cpp csrc/tests/overlay_selftest.cpp -o $@
+
+asan-overlay: $(ASAN_DIR)/overlay_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/overlay_selftest
 
 # The scratch pool's locking alone (csrc/tests/scratch_selftest.cpp on vep/scratch.h, which
 # includes no HIP header): a stand-alone host program, no GPU. Under ThreadSanitizer, under

@@ -14,6 +14,7 @@
 #include "vep/cabac.h"
 #include "vep/codec.h"
 #include "vep/crop.h"
+#include "vep/overlay.h"
 #include "vep/gpu.h"
 #include "vep/h264.h"
 #include "vep/hevc_ctu.h"
@@ -257,6 +258,46 @@ static py::array_t<uint8_t> crops_array(std::vector<u8>& px, size_t n, int ow, i
   auto* keep = new std::vector<u8>(std::move(px));
   py::capsule owner(keep, [](void* p) { delete static_cast<std::vector<u8>*>(p); });
   return py::array_t<uint8_t>(shape, keep->data(), owner);
+}
+
+// Overlay items (vep/overlay.h) cross the boundary as tuples (kind, x0, y0, x1, y1, b, g, r, alpha,
+// thickness, fill, scale, has_bg, bg_b, bg_g, bg_r, bg_alpha, text) of ints and one bytes (a text
+// item's origin is (x0, y0)); an invalid list is a ValueError.
+using ItemTuple = std::tuple<int, int, int, int, int, int, int, int, int, int, int, int, int, int, int, int, int, py::bytes>;
+static std::vector<overlay::Item> items_of(const std::vector<ItemTuple>& v) {
+  std::vector<overlay::Item> out;
+  for (const ItemTuple& t : v) {
+    overlay::Item it;
+    py::bytes text;
+    std::tie(it.kind, it.x0, it.y0, it.x1, it.y1, it.b, it.g, it.r, it.alpha, it.thickness, it.fill, it.scale, it.has_bg,
+             it.bg_b, it.bg_g, it.bg_r, it.bg_alpha, text) = t;
+    it.text = std::string(text);
+    out.push_back(std::move(it));
+  }
+  try {
+    VEP_CHECK(out.size() <= size_t(overlay::kMaxItems), "overlay: at most 64 items per picture");
+    overlay::check_list(out.data(), int(out.size()));
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return out;
+}
+static overlay::Meta overlay_meta_of(const py::object& meta) {
+  overlay::Meta m;
+  if (meta.is_none()) return m;
+  py::dict d = meta.cast<py::dict>();
+  if (d.contains("seq")) m.seq = d["seq"].cast<i64>();
+  if (d.contains("timestamp")) m.timestamp = d["timestamp"].cast<i64>();
+  return m;
+}
+// The expansion of a list on a w x h picture; what expand refuses is a ValueError.
+static overlay::Expanded overlay_expand_of(const std::vector<overlay::Item>& items, int w, int h, const std::string& name,
+                                           const overlay::Meta& meta) {
+  try {
+    return overlay::expand(items.data(), int(items.size()), w, h, name, meta);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
 }
 
 static tamper::Params tamper_params_of(int cell, int dark_level, int bright_level, int spread_min, int focus_percent,
@@ -1620,7 +1661,22 @@ PYBIND11_MODULE(_vep, m) {
            // cells (cols 0: ceil(sqrt(n))). foreign[t], if not None, is (seq, ndarray): an already
            // scaled tile of a camera that lives on another worker. seqs[t] is 0 for a tile drawn
            // as background.
-           [](Worker& w, const std::vector<int>& cams, int cols, int tw, int th, int quality, py::object foreign) {
+           // labels (a list of one str per tile, "" for none): drawn at the top-left corner of every
+           // tile that shows a frame (docs/OVERLAY.md); more than 128 labels are a ValueError.
+           [](Worker& w, const std::vector<int>& cams, int cols, int tw, int th, int quality, py::object foreign,
+              py::object labels) {
+             std::vector<std::string> names;
+             if (!labels.is_none()) {
+               names = labels.cast<std::vector<std::string>>();
+               size_t labelled = 0;
+               for (const std::string& l : names) {
+                 if (l.size() > size_t(overlay::kMaxRawText)) throw py::value_error("overlay: a text has at most 256 bytes");
+                 labelled += !l.empty();
+               }
+               if (names.size() != cams.size()) throw py::value_error("wall: one label per tile expected");
+               if (labelled * 2 > size_t(overlay::kMaxPrims))
+                 throw py::value_error("overlay: the wall's labels expand to more than 256 primitives");
+             }
              std::vector<Worker::ForeignTile> ft;
              std::vector<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>> keep;
              if (!foreign.is_none()) {
@@ -1646,12 +1702,46 @@ PYBIND11_MODULE(_vep, m) {
              std::string out;
              {
                py::gil_scoped_release r;
-               w.read_wall_jpeg(cams, cols, tw, th, quality, ft, seqs, out);
+               if (labels.is_none()) w.read_wall_jpeg(cams, cols, tw, th, quality, ft, seqs, out);
+               else w.read_wall_jpeg_labelled(cams, cols, tw, th, quality, ft, names, seqs, out);
              }
              return py::make_tuple(seqs, py::bytes(out));
            },
            py::arg("cams"), py::arg("cols") = 0, py::arg("tile_width") = 320, py::arg("tile_height") = 180,
-           py::arg("quality") = 85, py::arg("foreign") = py::none())
+           py::arg("quality") = 85, py::arg("foreign") = py::none(), py::arg("labels") = py::none())
+      .def("read_overlay_jpeg",
+           // read_latest_jpeg with the overlay items drawn on the picture (docs/OVERLAY.md): {name},
+           // {seq} and {time} come from `name` and the meta of the frame actually encoded.
+           [](Worker& w, int i, const std::vector<ItemTuple>& items, const std::string& name, i64 after, int quality,
+              int width, int height) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const std::vector<overlay::Item> its = items_of(items);
+             if (after < 0) throw py::value_error("overlay: after must be >= 0");
+             if (quality < 1 || quality > 100) throw py::value_error("jpeg: quality must be 1..100");
+             if (width < 0 || width > 65535 || height < 0 || height > 65535)
+               throw py::value_error("scale: width and height must be 1..65535 (0: not given)");
+             FrameMeta m;
+             std::string out;
+             bool ok;
+             std::string refused;
+             {
+               py::gil_scoped_release r;
+               try {
+                 ok = w.read_overlay_jpeg(i, after, quality, its, name, &m, out, width, height);
+               } catch (const Error& e) {
+                 // (only the expansion can refuse a checked list: too many primitives)
+                 if (std::string(e.what()).find("overlay:") == std::string::npos) throw;
+                 refused = e.what();
+                 ok = false;
+               }
+             }
+             if (!refused.empty()) throw py::value_error(refused);
+             if (!ok) return py::none();
+             return py::make_tuple(meta_dict(m), py::bytes(out));
+           },
+           py::arg("idx"), py::arg("items"), py::arg("name") = "", py::arg("after") = 0, py::arg("quality") = 85,
+           py::arg("width") = 0, py::arg("height") = 0)
+      .def("overlay_counts", [](Worker& w) { return w.overlay_counts(); })
       .def_property("wall_max_tiles", &Worker::wall_max_tiles, &Worker::set_wall_max_tiles)
       .def("read_motion",
            // dict of the newest frame with seq > after against the camera's background model
@@ -2599,6 +2689,107 @@ PYBIND11_MODULE(_vep, m) {
         },
         py::arg("pictures"), py::arg("width"), py::arg("height"), py::arg("fit"), py::arg("pad"), py::arg("out"),
         py::arg("out_bytes"), py::arg("stream"));
+  // On-screen display (vep/overlay.h) on the host: the arithmetic itself, and the CPU backend's
+  // path, the byte-exact reference of overlay_draw.
+  m.def("overlay_font", [] {
+    // (95, 8) uint8: the row bytes of the glyphs of 0x20..0x7E, bit 0 the leftmost column
+    py::array_t<uint8_t> a({py::ssize_t(overlay::kGlyphs), py::ssize_t(overlay::kGlyphH)});
+    for (int i = 0; i < overlay::kFontBytes; ++i) a.mutable_data()[i] = overlay::font_byte(u32(i));
+    return a;
+  });
+  m.def("overlay_blend",
+        // blend(d, c, a) elementwise over three uint8 arrays of one shape
+        [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> d,
+           py::array_t<uint8_t, py::array::c_style | py::array::forcecast> c,
+           py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a) {
+          if (d.size() != c.size() || d.size() != a.size()) throw py::value_error("overlay_blend: three arrays of one size expected");
+          py::array_t<uint8_t> o(std::vector<py::ssize_t>(d.shape(), d.shape() + d.ndim()));
+          const uint8_t *pd = d.data(), *pc = c.data(), *pa = a.data();
+          uint8_t* po = o.mutable_data();
+          for (py::ssize_t i = 0; i < d.size(); ++i) po[i] = uint8_t(overlay::blend(pd[i], pc[i], pa[i]));
+          return o;
+        },
+        py::arg("d"), py::arg("c"), py::arg("a"));
+  m.def("overlay_time", [](i64 timestamp) { return overlay::time_text(timestamp); }, py::arg("timestamp"));
+  m.def("overlay_check", [](const std::vector<ItemTuple>& items) { items_of(items); }, py::arg("items"));
+  m.def("overlay_expand",
+        // the primitives of the list on a width x height picture, in order: (0, x0, y0, x1, y1,
+        // (b, g, r), a) for a FILL, (1, ox, oy, k, (b, g, r), a, text) for a TEXT
+        [](int w, int h, const std::vector<ItemTuple>& items, const std::string& name, py::object meta) {
+          const overlay::Expanded e = overlay_expand_of(items_of(items), w, h, name, overlay_meta_of(meta));
+          py::list out;
+          for (const overlay::Prim& p : e.prims) {
+            py::tuple col = py::make_tuple(int(p.bgra & 255u), int((p.bgra >> 8) & 255u), int((p.bgra >> 16) & 255u));
+            const int a = int(p.bgra >> 24);
+            if (p.k == 0)
+              out.append(py::make_tuple(0, int(p.x0), int(p.y0), int(p.x1), int(p.y1), col, a));
+            else
+              out.append(py::make_tuple(1, int(p.x0), int(p.y0), int(p.k), col, a, py::bytes(e.text.substr(p.off, p.len))));
+          }
+          return out;
+        },
+        py::arg("width"), py::arg("height"), py::arg("items"), py::arg("name") = "", py::arg("meta") = py::none());
+  m.def("overlay_draw_cpu",
+        // src (H, W, 3) uint8 rows of any pitch (strides[0]) drawn into dst of the same shape; the
+        // same array for both: in place
+        [](py::array_t<uint8_t> src, py::array_t<uint8_t> dst, const std::vector<ItemTuple>& items, const std::string& name,
+           py::object meta) {
+          auto bad = [](const py::array_t<uint8_t>& a) {
+            return a.ndim() != 3 || a.shape(2) != 3 || a.shape(0) < 1 || a.shape(1) < 1 || a.shape(0) > overlay::kMaxSide ||
+                   a.shape(1) > overlay::kMaxSide || a.strides(2) != 1 || a.strides(1) != 3 || a.strides(0) < a.shape(1) * 3;
+          };
+          if (bad(src) || bad(dst) || src.shape(0) != dst.shape(0) || src.shape(1) != dst.shape(1) || !dst.writeable())
+            throw py::value_error("overlay_draw_cpu: two (H, W, 3) uint8 pictures of one size, rows packed, expected");
+          const int h = int(src.shape(0)), w = int(src.shape(1));
+          const overlay::Expanded e = overlay_expand_of(items_of(items), w, h, name, overlay_meta_of(meta));
+          const u8* s = src.data();
+          u8* d = dst.mutable_data();
+          if (s == d && src.strides(0) != dst.strides(0)) throw py::value_error("overlay_draw_cpu: in place needs equal pitches");
+          const size_t sp = size_t(src.strides(0)), dp = size_t(dst.strides(0));
+          py::gil_scoped_release r;
+          overlay::apply_cpu(s, sp, d, dp, w, h, e.prims.data(), int(e.prims.size()),
+                             reinterpret_cast<const u8*>(e.text.data()), e.text.size());
+        },
+        py::arg("src").noconvert(), py::arg("dst").noconvert(), py::arg("items"), py::arg("name") = "",
+        py::arg("meta") = py::none());
+  // Pictures (src, src_pitch, dst, dst_pitch, w, h, items) on caller-owned device buffers: ONE launch
+  // of the gfx950 overlay kernel for all of them, on `stream` of the current device (scratch: one
+  // process-wide pool per device). dst == src: in place. Rows are packed BGR24 of any pitch.
+  m.def("overlay_draw",
+        [](const std::vector<std::tuple<uintptr_t, size_t, uintptr_t, size_t, int, int, std::vector<ItemTuple>>>& pics,
+           const std::string& name, py::object meta, uintptr_t stream) {
+          const overlay::Meta om = overlay_meta_of(meta);
+          if (pics.size() > 65535) throw py::value_error("overlay_draw: at most 65535 pictures per call");
+          std::vector<overlay::Expanded> ex;
+          size_t nprims = 0, ntext = 0;
+          for (const auto& pc : pics) {
+            const int w = std::get<4>(pc), h = std::get<5>(pc);
+            if (w < 1 || h < 1 || w > overlay::kMaxSide || h > overlay::kMaxSide)
+              throw py::value_error("overlay: picture size must be 1..65535");
+            const size_t sp = std::get<1>(pc), dp = std::get<3>(pc);
+            if (sp < size_t(w) * 3 || dp < size_t(w) * 3 || sp > 0xFFFFFFFFu || dp > 0xFFFFFFFFu)
+              throw py::value_error("overlay: pitch shorter than a row");
+            ex.push_back(overlay_expand_of(items_of(std::get<6>(pc)), w, h, name, om));
+            nprims += ex.back().prims.size();
+            ntext += ex.back().text.size();
+          }
+          if (pics.empty()) return;
+          py::gil_scoped_release r;
+          hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+          gpu::OverlayPool::Lease set = pool_of_current_device<gpu::OverlayPool>().acquire();
+          set->reserve(int(pics.size()), nprims, ntext, 0);
+          size_t prim_at = 0, text_at = 0;
+          for (size_t i = 0; i < pics.size(); ++i) {
+            const auto& [src, sp, dst, dp, w, h, items] = pics[i];
+            (void)items;
+            const size_t row = size_t(w) * 3;
+            set->put(int(i), reinterpret_cast<const u8*>(src), size_t(h - 1) * sp + row, u32(sp), reinterpret_cast<u8*>(dst),
+                     size_t(h - 1) * dp + row, u32(dp), w, h, ex[i], prim_at, text_at);
+          }
+          set->run(int(pics.size()), prim_at, text_at, s);
+          VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
+        },
+        py::arg("pictures"), py::arg("name"), py::arg("meta"), py::arg("stream"));
   // Pictures (src, w, h, hist, sum_y, energy) on caller-owned device buffers: one launch of the
   // gfx950 tamper kernel on `stream` of the current device (descriptors: one process-wide pool
   // per device). src is h x w x 3 packed, hist 256 u32 (zeroed here, on the stream), the planes

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "mask.h"
+#include "overlay.h"
 #include "scratch.h"
 
 namespace vep::gpu {
@@ -596,6 +597,53 @@ struct CropSet : DescSet<CropDesc> {
   void run(int n, size_t down_bytes, hipStream_t s);
 };
 using CropPool = ScratchPool<CropSet>;
+
+// ---- on-screen display (gpu_overlay.hip; arithmetic: overlay.h) --------------------------------
+// One picture of a batched overlay launch (device memory): the packed BGR24 picture at src with
+// its primitives drawn on, written to dst, byte-identical with overlay::apply_cpu. dst == src (and
+// equal pitches): in place; otherwise copy and draw, and the two must not overlap. Pictures of one
+// launch may differ in size; their destinations must not overlap.
+struct OverlayDesc {
+  const VEP_DEV u8* src;    // h rows of src_pitch bytes (any alignment)
+  VEP_DEV u8* dst;          // h rows of dst_pitch bytes (any alignment)
+  const VEP_DEV overlay::Prim* prims;  // the picture's nprims primitives, 16-byte aligned
+  const VEP_DEV u8* text;   // the picture's text pool, text_len bytes of 0x20..0x7E
+  u32 src_pitch, dst_pitch;  // bytes
+  i32 w, h;
+  u32 nprims;               // 0 .. overlay::kMaxPrims
+  u32 text_len;             // 0 .. overlay::kMaxPool
+  u32 pad_[2];
+};
+static_assert(sizeof(OverlayDesc) == 64, "OverlayDesc layout");
+// Throws unless the kernel can run the descriptor without reading outside a source of src_bytes
+// and without writing outside a destination of dst_bytes, with every primitive inside the picture
+// and every text inside the pool (h_prims / h_text: the host copies of prims / text). The launch
+// below does not check.
+void check_overlay(const OverlayDesc& d, size_t src_bytes, size_t dst_bytes, const overlay::Prim* h_prims,
+                   const u8* h_text);
+// One launch for the n pictures: grid = (tiles of the largest picture) x pictures. h_descs is the
+// host copy of d_descs (the grid is sized from it).
+void launch_overlay(const OverlayDesc* d_descs, const OverlayDesc* h_descs, int n, hipStream_t s);
+
+// Overlay scratch of one device (pool contract: above): descriptors, the primitives and the text
+// pools of a request's pictures one after the other (device and pinned), and a picture buffer for
+// the out-of-place copy of a frame.
+struct OverlaySet : DescSet<OverlayDesc> {
+  DevBuf<overlay::Prim> d_prims;
+  PinBuf<overlay::Prim> h_prims;
+  DevBuf<u8> d_text;
+  PinBuf<u8> h_text;
+  DevBuf<u8> picture;
+  void reserve(int ndescs, size_t nprims, size_t text_bytes, size_t picture_bytes);
+  // Descriptor k of the request: the picture at src drawn to dst with e's primitives, which are
+  // appended to the set's host arrays at prim_at / text_at (both advanced). Checked.
+  void put(int k, const u8* src, size_t src_bytes, u32 src_pitch, u8* dst, size_t dst_bytes, u32 dst_pitch, int w, int h,
+           const overlay::Expanded& e, size_t& prim_at, size_t& text_at);
+  // Copies the first n host descriptors, nprims primitives and text_bytes of text up, launches on
+  // `s` and records the event (no wait).
+  void run(int n, size_t nprims, size_t text_bytes, hipStream_t s);
+};
+using OverlayPool = ScratchPool<OverlaySet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

@@ -1,5 +1,6 @@
-// Staging rows of a packed BGR24 picture in LDS, and summing samples out of them: the part the
-// scale kernel (gpu_scale.hip) and the crop kernel (gpu_crop.hip) share. Kernel sources only
+// Staging rows of a packed BGR24 picture in LDS, summing samples out of them and storing rows
+// back: the part the scale kernel (gpu_scale.hip), the crop kernel (gpu_crop.hip) and the overlay
+// kernel (gpu_overlay.hip) share. Kernel sources only
 // (VEP_KERNEL_SOURCE, 256 threads a workgroup).
 //
 // Packed BGR rows start at any byte address, so a row segment is staged with 16-byte loads from
@@ -69,6 +70,41 @@ __device__ __forceinline__ void stage_rows(const VEP_DEV u8* src, u32 src_pitch,
   for (u32 rr = (t >> 5) + kThreads / 32; rr < nr; rr += kThreads / 32) {
     const u32 at = edge(rr, e);
     if (at != ~0u) lds[at] = e;
+  }
+}
+
+// The other direction: nrow rows of nbytes bytes out of LDS (row rr at rr * rowcap + (its global
+// address modulo 16), as stage_rows leaves them) to dst + rr * pitch. 16-byte stores to 16-byte
+// aligned addresses, a row's unaligned head and tail byte by byte: no byte outside the rows' own
+// bytes is written. One vector per thread: nrow * ((nbytes >> 4) + 1) <= kThreads.
+__device__ __forceinline__ void store_rows(VEP_DEV u8* dst, u32 pitch, u32 nrow, u32 nbytes, u32 rowcap, const u8* lds) {
+  const u32 t = threadIdx.x;
+  const u32 vpr = (nbytes >> 4) + 1;  // upper bound of a row's 16-byte vectors
+  if (t < nrow * vpr) {
+    const u32 rr = t / vpr, v = t - rr * vpr;
+    VEP_DEV u8* gp = dst + u64(rr) * pitch;
+    const u32 mis = u32(reinterpret_cast<uintptr_t>(gp)) & 15u;
+    const u32 head = min(nbytes, (16u - mis) & 15u);
+    if (v < ((nbytes - head) >> 4)) {
+      const u32 o = head + v * 16;  // o + 16 <= nbytes
+      *reinterpret_cast<VEP_DEV uint4*>(gp + o) = *reinterpret_cast<const uint4*>(lds + rr * rowcap + mis + o);
+    }
+  }
+  for (u32 rr = t >> 5; rr < nrow; rr += kThreads / 32) {  // 32 byte slots per row, 8 rows per step
+    const u32 slot = t & 31u;
+    VEP_DEV u8* gp = dst + u64(rr) * pitch;
+    const u32 mis = u32(reinterpret_cast<uintptr_t>(gp)) & 15u;
+    const u32 head = min(nbytes, (16u - mis) & 15u);
+    const u32 body = ((nbytes - head) >> 4) << 4;
+    u32 o;
+    if (slot < 16) {
+      if (slot >= head) continue;
+      o = slot;
+    } else {
+      if (slot - 16 >= nbytes - head - body) continue;
+      o = head + body + (slot - 16);
+    }
+    gp[o] = lds[rr * rowcap + mis + o];
   }
 }
 

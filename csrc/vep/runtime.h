@@ -22,6 +22,7 @@
 #include "avc.h"
 #include "codec.h"
 #include "crop.h"
+#include "overlay.h"
 #include "hevc_dec.h"
 #include "hevc_kern.h"
 #include "hostplan.h"
@@ -512,6 +513,23 @@ class Worker {
   };
   void read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
                       const std::vector<ForeignTile>& foreign, std::vector<i64>& seqs_out, std::string& out);
+  // On-screen display (overlay.h, docs/OVERLAY.md). read_latest_jpeg with `items` drawn on the
+  // picture that is encoded: at native size the slot is copied and drawn into pooled scratch in
+  // one launch, scaled the items are drawn in place on the scaled picture, both on the serving
+  // stream with the encoder chained behind, inside the consistent read. Placeholders ({name},
+  // {seq}, {time}) are replaced from the meta of the frame actually picked. The ring slot is never
+  // written.
+  bool read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
+                         const std::string& name, FrameMeta* meta, std::string& out, int width = 0, int height = 0);
+  // read_wall_jpeg with labels[t] (non-empty) drawn at the top-left corner of every tile that
+  // shows a frame, as a text at auto scale for the tile's height over black at alpha 160, clipped
+  // to the tile's cell: one in-place launch on the composed canvas. At most
+  // overlay::kMaxPrims / 2 tiles may carry a label.
+  void read_wall_jpeg_labelled(const std::vector<int>& cams, int cols, int tw, int th, int quality,
+                               const std::vector<ForeignTile>& foreign, const std::vector<std::string>& labels,
+                               std::vector<i64>& seqs_out, std::string& out);
+  // Overlay requests answered and the primitives they drew, since the worker started.
+  std::pair<u64, u64> overlay_counts() const { return {overlay_requests_.load(), overlay_prims_.load()}; }
   // Motion detection (motion.h, docs/MOTION.md): did the newest frame with seq > after differ from
   // the camera's background model? The frame is evaluated where it lies, in its ring slot, on the
   // serving stream (CPU backend: motion::update_cpu on the host ring), from the model plane into
@@ -891,6 +909,12 @@ class Worker {
   // crops (after tamper's members)
   gpu::CropPool crop_pool_;  // descriptors + outputs of the crop reads, one set per request in flight
   struct CropOp;  // likewise
+  // on-screen display (after the crops' members)
+  gpu::OverlayPool overlay_pool_;  // descriptors, primitives, text and a picture, one set per request in flight
+  std::atomic<u64> overlay_requests_{0}, overlay_prims_{0};
+  void wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
+                 const std::vector<ForeignTile>& foreign, const std::vector<std::string>* labels,
+                 std::vector<i64>& seqs_out, std::string& out);
 };
 
 // Protobuf wire encoding of chrys.cloud.videostreaming.v1beta1.VideoFrame

@@ -101,6 +101,53 @@ bool Worker::read_latest_scaled(int cam, i64 after, int width, int height, Frame
 
 void Worker::read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
                             const std::vector<ForeignTile>& foreign, std::vector<i64>& seqs_out, std::string& out) {
+  wall_jpeg(cams, cols, tw, th, quality, foreign, nullptr, seqs_out, out);
+}
+
+void Worker::read_wall_jpeg_labelled(const std::vector<int>& cams, int cols, int tw, int th, int quality,
+                                     const std::vector<ForeignTile>& foreign, const std::vector<std::string>& labels,
+                                     std::vector<i64>& seqs_out, std::string& out) {
+  VEP_CHECK(labels.size() == cams.size(), "wall: one label per tile expected");
+  size_t labelled = 0;
+  for (const std::string& l : labels) {
+    VEP_CHECK(l.size() <= size_t(overlay::kMaxRawText), "overlay: a text has at most 256 bytes");
+    labelled += !l.empty();
+  }
+  VEP_CHECK(labelled * 2 <= size_t(overlay::kMaxPrims), "overlay: the wall's labels expand to more than 256 primitives");
+  wall_jpeg(cams, cols, tw, th, quality, foreign, &labels, seqs_out, out);
+}
+
+// The primitives of the wall's labels on the composed canvas: tile t's label is a text item at
+// (0, 0) of its tw x th cell, expanded there (so it is clipped to the cell) and moved to the cell.
+static overlay::Expanded wall_labels(const std::vector<std::string>& labels, const std::vector<char>& shown, int cols,
+                                     int tw, int th) {
+  overlay::Expanded all;
+  for (size_t t = 0; t < labels.size(); ++t) {
+    if (labels[t].empty() || !shown[t]) continue;
+    overlay::Item it;
+    it.kind = overlay::kTextItem;
+    it.x0 = it.y0 = 0;
+    it.b = it.g = it.r = 255;
+    it.has_bg = 1;
+    it.bg_alpha = 160;
+    it.text = labels[t];
+    overlay::Meta none;
+    const overlay::Expanded e = overlay::expand(&it, 1, tw, th, std::string(), none);
+    const int cx = int(t % size_t(cols)) * tw, cy = int(t / size_t(cols)) * th;
+    for (overlay::Prim p : e.prims) {
+      p.x0 = uint16_t(p.x0 + cx), p.x1 = uint16_t(p.x1 + cx), p.y0 = uint16_t(p.y0 + cy), p.y1 = uint16_t(p.y1 + cy);
+      p.off = uint16_t(p.off + all.text.size());
+      all.prims.push_back(p);
+    }
+    all.text += e.text;
+  }
+  VEP_CHECK(all.prims.size() <= size_t(overlay::kMaxPrims), "overlay: the wall's labels expand to more than 256 primitives");
+  return all;
+}
+
+void Worker::wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
+                       const std::vector<ForeignTile>& foreign, const std::vector<std::string>* labels,
+                       std::vector<i64>& seqs_out, std::string& out) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
   const int n = int(cams.size());
   VEP_CHECK(n >= 1 && n <= wall_max_tiles(), "wall: the number of tiles must be 1..serving.wall_max_tiles");
@@ -148,6 +195,11 @@ void Worker::read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int 
     TileSrc& s = ts[size_t(t)];
     s.slot = -1;
     return s.ring && s.ring->latest(0, &s.meta, &s.slot);
+  };
+  auto shown = [&] {  // the tiles that show a frame, once the rounds are over
+    std::vector<char> v(size_t(n), 0);
+    for (int t = 0; t < n; ++t) v[size_t(t)] = seqs_out[size_t(t)] != 0 || (!foreign.empty() && foreign[size_t(t)].data);
+    return v;
   };
   if (!dev_.gpu()) {
     std::vector<u8> canvas(canvas_bytes);
@@ -202,6 +254,13 @@ void Worker::read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int 
       u8* p = canvas.data() + size_t((t / g.cols) * th + (th - f.h) / 2) * pitch +
               size_t((t % g.cols) * tw + (tw - f.w) / 2) * 3;
       for (int y = 0; y < f.h; ++y) std::memcpy(p + size_t(y) * pitch, f.data + size_t(y) * f.w * 3, size_t(f.w) * 3);
+    }
+    if (labels) {
+      const overlay::Expanded e = wall_labels(*labels, shown(), g.cols, tw, th);
+      overlay_requests_ += 1;
+      overlay_prims_ += e.prims.size();
+      overlay::apply_cpu(canvas.data(), pitch, canvas.data(), pitch, g.w, g.h, e.prims.data(), int(e.prims.size()),
+                         reinterpret_cast<const u8*>(e.text.data()), e.text.size());
     }
     out = jpeg::encode_cpu(canvas.data(), g.w, g.h, quality);
     return;
@@ -269,6 +328,20 @@ void Worker::read_wall_jpeg(const std::vector<int>& cams, int cols, int tw, int 
       }
     }
   }
+  gpu::OverlayPool::Lease osd;  // (held until the encode has waited for the stream)
+  if (labels) {
+    const overlay::Expanded e = wall_labels(*labels, shown(), g.cols, tw, th);
+    overlay_requests_ += 1;
+    overlay_prims_ += e.prims.size();
+    if (!e.prims.empty()) {
+      osd = overlay_pool_.acquire();
+      osd->reserve(1, e.prims.size(), e.text.size(), 0);
+      size_t prim_at = 0, text_at = 0;
+      osd->put(0, set->canvas.p, canvas_bytes, u32(pitch), set->canvas.p, canvas_bytes, u32(pitch), g.w, g.h, e, prim_at,
+               text_at);
+      osd->run(1, prim_at, text_at, serve_stream_);
+    }
+  }
   encode_device(set->canvas.p, g.w, g.h, quality, out);
 }
 
@@ -299,6 +372,74 @@ bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, 
     copy_slot(*ring, slot, host.get());
     out = jpeg::encode_cpu(host.get(), w, h, quality);
   });
+}
+
+bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
+                               const std::string& name, FrameMeta* meta, std::string& out, int width, int height) {
+  VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  VEP_CHECK(width >= 0 && width <= scale::kMaxSide && height >= 0 && height <= scale::kMaxSide,
+            "scale: width and height must be 1..65535");
+  overlay::check_list(items.data(), int(items.size()));
+  std::shared_ptr<Camera> c = camera(cam);
+  if (!c) return false;
+  std::shared_ptr<FrameRing> ring = c->ring();
+  if (!ring) return false;
+  const int w = ring->width(), h = ring->height();
+  const bool scaled = width || height;
+  const scale::Size f = scaled ? scale::fit(w, h, width, height) : scale::Size{w, h};
+  const size_t n = size_t(f.w) * size_t(f.h) * 3, row = size_t(f.w) * 3;
+  size_t drawn = 0;
+  const bool ok = read_consistent(*ring, after, meta, [&](int slot, const FrameMeta& m) {
+    // (the items meet the picture they are drawn on, and the meta of the frame picked this time)
+    const overlay::Expanded e =
+        overlay::expand(items.data(), int(items.size()), f.w, f.h, name, overlay::Meta{m.seq, m.timestamp});
+    const u8* text = reinterpret_cast<const u8*>(e.text.data());
+    drawn = e.prims.size();
+    if (!dev_.gpu()) {
+      std::vector<u8> host(n);
+      if (scaled) {
+        scale::area_cpu(ring->slot_ptr(slot), w, h, size_t(w) * 3, host.data(), row, f.w, f.h);
+        overlay::apply_cpu(host.data(), row, host.data(), row, f.w, f.h, e.prims.data(), int(e.prims.size()), text,
+                           e.text.size());
+      } else {
+        overlay::apply_cpu(ring->slot_ptr(slot), row, host.data(), row, w, h, e.prims.data(), int(e.prims.size()), text,
+                           e.text.size());
+      }
+      out = jpeg::encode_cpu(host.data(), f.w, f.h, quality);
+      return;
+    }
+    dev_.bind();
+    // (every request takes its sets in one order: scale, overlay, encoder)
+    gpu::ScalePool::Lease set;
+    if (scaled) {
+      set = scale_pool_.acquire();
+      set->reserve(n, 1, 0);
+    }
+    gpu::OverlayPool::Lease osd = overlay_pool_.acquire();
+    osd->reserve(1, e.prims.size(), e.text.size(), scaled ? 0 : n);
+    size_t prim_at = 0, text_at = 0;
+    if (scaled) {
+      scale_slot(*set, *ring, slot, f.w, f.h);
+      // (the same stream: drawn after the scale, encoded after the drawing)
+      osd->put(0, set->canvas.p, n, u32(row), set->canvas.p, n, u32(row), f.w, f.h, e, prim_at, text_at);
+      osd->run(1, prim_at, text_at, serve_stream_);
+      encode_device(set->canvas.p, f.w, f.h, quality, out);
+    } else {
+      osd->put(0, ring->slot_ptr(slot), ring->slot_bytes(), u32(row), osd->picture.p, n, u32(row), w, h, e, prim_at,
+               text_at);
+      osd->run(1, prim_at, text_at, serve_stream_);
+      encode_device(osd->picture.p, w, h, quality, out);
+    }
+  });
+  if (ok) {
+    overlay_requests_ += 1;
+    overlay_prims_ += drawn;
+  }
+  if (ok && scaled) {
+    meta->width = f.w;
+    meta->height = f.h;
+  }
+  return ok;
 }
 
 // ------------------------------------------------------------------------- motion detection

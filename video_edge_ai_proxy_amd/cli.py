@@ -106,7 +106,84 @@ def write_frame(path: str, img) -> None:
         f.write(data)
 
 
+def frame_jpg_url(a) -> str:
+    """The frame.jpg request of ``vep frame --overlay / --stamp``."""
+    import urllib.parse
+
+    q = {}
+    if a.overlay:
+        q["overlay"] = "1"
+    if a.stamp:
+        q["stamp"] = "1"
+    for k in ("width", "height"):
+        if getattr(a, k) is not None:
+            q[k] = str(getattr(a, k))
+    return (f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/frame.jpg?"
+            + urllib.parse.urlencode(q))
+
+
+def cmd_frame_osd(a):
+    """``vep frame --overlay / --stamp``: the on-screen display is drawn by the hub (on its GPU) onto
+    the JPEG it serves, so the frame comes from ``frame.jpg`` over REST and is written as it is."""
+    import json
+    import urllib.error
+    import urllib.request
+
+    if not a.out or not a.out.lower().endswith((".jpg", ".jpeg")):
+        raise SystemExit("frame: --overlay / --stamp write a JPEG: --out FILE.jpg")
+    try:
+        with urllib.request.urlopen(frame_jpg_url(a), timeout=10) as r:
+            jpg, seq = r.read(), r.headers.get("X-Vep-Seq")
+    except urllib.error.HTTPError as e:
+        detail = ""
+        try:
+            detail = ": " + json.loads(e.read()).get("message", "")
+        except ValueError:
+            pass
+        raise SystemExit(f"frame: HTTP {e.code} for {a.device!r}{detail}")
+    with open(a.out, "wb") as f:
+        f.write(jpg)
+    print(f"seq {seq}: {len(jpg)} bytes -> {a.out}", flush=True)
+
+
+def cmd_overlay(a):
+    """REST client of ``/api/v1/process/{name}/overlay``: ``--set`` replaces the camera's stored
+    on-screen display list with a JSON list of items (``--ttl-ms``: for that long), ``--clear``
+    removes it; the list in force is printed afterwards."""
+    import json
+    import urllib.error
+    import urllib.parse
+    import urllib.request
+
+    if a.set is not None and a.clear:
+        raise SystemExit("overlay: --set and --clear exclude each other")
+    url = f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/overlay"
+    try:
+        if a.set is not None:
+            try:
+                items = json.loads(a.set)
+            except ValueError as e:
+                raise SystemExit(f"overlay: --set is not JSON: {e}")
+            body = json.dumps({"items": items, "ttl_ms": a.ttl_ms}).encode()
+            req = urllib.request.Request(url, data=body, method="PUT", headers={"Content-Type": "application/json"})
+            urllib.request.urlopen(req, timeout=10).close()
+        elif a.clear:
+            urllib.request.urlopen(urllib.request.Request(url, method="DELETE"), timeout=10).close()
+        with urllib.request.urlopen(url, timeout=10) as r:
+            items = json.loads(r.read()).get("items", [])
+        print(f"{len(items)} item(s)" + "".join("\n  " + json.dumps(i, sort_keys=True) for i in items), flush=True)
+    except urllib.error.HTTPError as e:
+        detail = ""
+        try:
+            detail = ": " + json.loads(e.read()).get("message", "")
+        except ValueError:
+            pass
+        raise SystemExit(f"overlay: HTTP {e.code} for {a.device!r}{detail}")
+
+
 def cmd_frame(a):
+    if a.overlay or a.stamp:
+        return cmd_frame_osd(a)
     import numpy as np
 
     from .server.grpc_server import ImageClient
@@ -398,6 +475,10 @@ def build_parser():
             p.add_argument("--out", default=None, help="write the last frame: .jpg / .jpeg as a JPEG, else PPM")
             p.add_argument("--width", type=int, default=None, help="scale the written frame down to fit this width")
             p.add_argument("--height", type=int, default=None, help="... and / or this height (aspect kept)")
+            p.add_argument("--overlay", action="store_true",
+                           help="draw the camera's stored overlay list (the JPEG then comes from the hub's REST API)")
+            p.add_argument("--stamp", action="store_true", help="draw the camera's name and the frame's time, likewise")
+            p.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API (--overlay / --stamp)")
         if name == "annotate":
             p.add_argument("--type", required=True)
         if name in ("storage", "proxy"):
@@ -426,6 +507,15 @@ def build_parser():
                     help='a JSON list of masks, e.g. \'[{"x0":0,"y0":0,"x1":2500,"y1":10000,"mode":"pixelate","block":16}]\'')
     pv.add_argument("--clear", action="store_true", help="remove the camera's masks")
     pv.set_defaults(fn=cmd_privacy)
+
+    ov = sub.add_parser("overlay", help="show, set or clear a camera's stored on-screen display list (REST)")
+    ov.add_argument("--device", required=True)
+    ov.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API")
+    ov.add_argument("--set", default=None, metavar="JSON",
+                    help='a JSON list of items, e.g. \'[{"x0":1000,"y0":1000,"x1":5000,"y1":8000,"label":"person 87%%"}]\'')
+    ov.add_argument("--ttl-ms", type=int, default=0, help="with --set: drop the items after this many milliseconds")
+    ov.add_argument("--clear", action="store_true", help="remove the camera's list")
+    ov.set_defaults(fn=cmd_overlay)
 
     cr = sub.add_parser("crop", help="one box of a camera's frame as a JPEG, cut and resized on the GPU (REST)")
     cr.add_argument("--device", required=True)

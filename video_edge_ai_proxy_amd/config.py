@@ -142,6 +142,15 @@ TAMPER_RANGES = {"cell": (8, 128), "dark_level": (0, 255), "bright_level": (0, 2
 
 
 @dataclass
+class OverlayConfig:
+    """On-screen display (docs/OVERLAY.md). ``from_annotations``: an ``Annotate`` request that
+    carries a bounding box and the picture size it refers to also becomes a box of its camera's
+    stored overlay list, for ``annotation_ttl_ms`` milliseconds."""
+    from_annotations: bool = False
+    annotation_ttl_ms: int = 1000  # (>= 1)
+
+
+@dataclass
 class Config:
     version: str = "0.1.0"
     title: str = "vep MI355X video edge hub"
@@ -158,6 +167,7 @@ class Config:
     serving: ServingConfig = field(default_factory=ServingConfig)
     motion: MotionConfig = field(default_factory=MotionConfig)
     tamper: TamperConfig = field(default_factory=TamperConfig)
+    overlay: OverlayConfig = field(default_factory=OverlayConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
     bus_tag: str = ""
 
@@ -227,6 +237,11 @@ def validate(cfg: Config) -> None:
     v = cfg.serving.crop_max_bytes
     if isinstance(v, bool) or not isinstance(v, int) or v < 3:
         raise ValueError(f"serving.crop_max_bytes must be an integer >= 3, got {v!r}")
+    if not isinstance(cfg.overlay.from_annotations, bool):
+        raise ValueError(f"overlay.from_annotations must be true or false, got {cfg.overlay.from_annotations!r}")
+    v = cfg.overlay.annotation_ttl_ms
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"overlay.annotation_ttl_ms must be an integer >= 1, got {v!r}")
     for key, (lo, hi) in MOTION_RANGES.items():
         v = getattr(cfg.motion, key)
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:

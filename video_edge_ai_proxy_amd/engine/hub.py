@@ -18,6 +18,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 from .. import crops, privacy
+from .. import overlay as osd
 from .._native import gpu_count, native
 from ..config import Config, parse_tile
 from ..utils import now_ms
@@ -81,6 +82,11 @@ class Hub:
         self.host_domains = host_domains
         self._crop_lock = threading.Lock()
         self._crop_counts = [0, 0]  # requests, boxes (Hub.crop_counts, /metrics)
+        # on-screen display: the stored list of every camera, [(item, deadline | None), ...] with
+        # the deadline on overlay_clock (monotonic seconds); kept here, not persisted
+        self._overlay_lock = threading.Lock()
+        self._overlays: dict[str, list] = {}
+        self.overlay_clock = time.monotonic
         self.workers = []
         for d, dom in zip(devices, host_domains):
             w = native.Worker(device=d, letterbox_size=int(g.letterbox_size),
@@ -168,6 +174,8 @@ class Hub:
             h = self.cameras.pop(name, None)
         if h is None:
             raise CameraNotFound(name)
+        with self._overlay_lock:
+            self._overlays.pop(name, None)
         if self.bus:
             self.bus[h.worker_index].remove(h.cam)
         h.session.stop()
@@ -336,18 +344,91 @@ class Hub:
         return out[0], out[1]
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
-                    width: Optional[int] = None, height: Optional[int] = None):
+                    width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False):
         """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
         Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
         ``quality`` 1..100, default ``serving.jpeg_quality``. With ``width`` and / or ``height``
         the frame is first fitted into that box (aspect kept, never enlarged) and downscaled by
-        area averaging, on the GPU as well; ``meta`` then carries the scaled size."""
+        area averaging, on the GPU as well; ``meta`` then carries the scaled size.
+
+        ``overlay``: ``True`` draws the camera's stored list (:meth:`set_overlay`), a list its
+        items (:mod:`..overlay`, docs/OVERLAY.md); ``stamp`` appends the camera's name and the
+        frame's time. They are drawn on a copy (scaled: on the scaled picture) in one kernel launch
+        on the camera's GPU; the ring slot is never written. With neither, the call and its bytes
+        are what they are without them."""
         q = self._quality(quality)
         bw, bh = self._box(width, height)
+        if not isinstance(stamp, bool):
+            raise ValueError("stamp must be true or false")
         w, cam = self.worker_of(name)
-        if not (bw or bh):
-            return w.read_latest_jpeg(cam, after, q)
-        return w.read_latest_jpeg(cam, after, q, bw, bh)
+        if (overlay is None or overlay is False) and not stamp:
+            if not (bw or bh):
+                return w.read_latest_jpeg(cam, after, q)
+            return w.read_latest_jpeg(cam, after, q, bw, bh)
+        if overlay is None or overlay is False:
+            items = []  # (the stamp alone)
+        elif overlay is True:
+            items = self.overlay(name)
+        else:
+            items = osd.normalize_list(overlay)
+        if stamp:
+            items = items + [osd.STAMP]
+        return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh)
+
+    # ------------------------------------------------------------------ on-screen display
+    def set_overlay(self, name: str, items, ttl_ms: int = 0) -> None:
+        """Replaces the camera's stored overlay list (``latest_jpeg(overlay=True)`` draws it).
+        ``ttl_ms`` > 0: the items are dropped that many milliseconds from now. A bad list is a
+        ``ValueError`` and changes nothing."""
+        norm = osd.normalize_list(items)
+        native.overlay_check(osd.to_native(norm))
+        deadline = self._overlay_deadline(ttl_ms)
+        self.handle(name)
+        with self._overlay_lock:
+            self._overlays[name] = [(it, deadline) for it in norm]
+
+    def add_overlay_item(self, name: str, item, ttl_ms: int = 0) -> None:
+        """Appends one item to the camera's stored list; when the list is full its oldest item
+        makes room."""
+        it = osd.normalize(item)
+        native.overlay_check(osd.to_native([it]))
+        deadline = self._overlay_deadline(ttl_ms)
+        self.handle(name)
+        now = self.overlay_clock()
+        with self._overlay_lock:
+            live = [e for e in self._overlays.get(name, []) if e[1] is None or e[1] > now]
+            live.append((it, deadline))
+            self._overlays[name] = live[-osd.MAX_ITEMS:]
+
+    def _overlay_deadline(self, ttl_ms):
+        if isinstance(ttl_ms, bool) or not isinstance(ttl_ms, int) or ttl_ms < 0:
+            raise ValueError("ttl_ms must be an integer >= 0")
+        return None if ttl_ms == 0 else self.overlay_clock() + ttl_ms / 1000.0
+
+    def overlay(self, name: str) -> list:
+        """The camera's stored list; items past their ``ttl_ms`` are dropped on this read."""
+        self.handle(name)
+        now = self.overlay_clock()
+        with self._overlay_lock:
+            live = [e for e in self._overlays.get(name, []) if e[1] is None or e[1] > now]
+            if live:
+                self._overlays[name] = live
+            else:
+                self._overlays.pop(name, None)
+            return [osd.public(it) for it, _ in live]
+
+    def clear_overlay(self, name: str) -> None:
+        self.handle(name)
+        with self._overlay_lock:
+            self._overlays.pop(name, None)
+
+    def overlay_counts(self) -> tuple:
+        """``(requests, primitives)`` drawn since the hub started (/metrics)."""
+        r = p = 0
+        for w in self.workers:
+            a, b = w.overlay_counts()
+            r, p = r + int(a), p + int(b)
+        return r, p
 
     def latest_scaled(self, name: str, after: int = 0, width: Optional[int] = None,
                       height: Optional[int] = None):
@@ -384,7 +465,7 @@ class Hub:
         return order, gc, gr, tw, th
 
     def wall_jpeg(self, names=None, cols: Optional[int] = None, tile_width: Optional[int] = None,
-                  tile_height: Optional[int] = None, quality: Optional[int] = None):
+                  tile_height: Optional[int] = None, quality: Optional[int] = None, labels: bool = False):
         """``({name: seq}, bytes)``: one JPEG showing the newest frame of every listed camera
         (default: the running cameras, sorted), tile ``t`` fitted into cell ``(t % cols, t // cols)``
         of ``tile_width x tile_height`` (default ``serving.wall_tile``) and centred, ``cols``
@@ -393,9 +474,18 @@ class Hub:
         Rendered by the worker that owns most of the listed cameras (ties: the lowest index): its
         cameras are scaled from their ring slots in one kernel launch; cameras of other workers are
         scaled on their own GPU and only the small tiles travel. A wall refreshes ``last_query``
-        of every camera it shows, so it keeps their lazy decoders awake."""
+        of every camera it shows, so it keeps their lazy decoders awake.
+
+        ``labels``: every tile that shows a frame gets its camera's name at its top-left corner, in
+        one more kernel launch on the composed canvas (docs/OVERLAY.md). A wall whose labels expand
+        to more than 256 primitives (more than 128 tiles) is refused (``overlay.Refused``, a
+        ``ValueError``)."""
         q = self._quality(quality)
+        if not isinstance(labels, bool):
+            raise ValueError("labels must be true or false")
         order, gc, gr, tw, th = self.wall_layout(names, cols, tile_width, tile_height)
+        if labels and 2 * len(order) > osd.MAX_PRIMS:
+            raise osd.Refused(f"the labels of {len(order)} tiles expand to more than {osd.MAX_PRIMS} primitives")
         hs = []
         for n in order:
             h = self.cameras.get(n)
@@ -419,7 +509,11 @@ class Hub:
             r = self.workers[h.worker_index].read_latest_scaled(h.cam, 0, tw, th)
             foreign.append(None if r is None else (int(r[0]["seq"]), r[1]))
             any_foreign = any_foreign or r is not None
-        seqs, jpg = self.workers[home].read_wall_jpeg(cams, gc, tw, th, q, foreign if any_foreign else None)
+        if labels:
+            seqs, jpg = self.workers[home].read_wall_jpeg(cams, gc, tw, th, q, foreign if any_foreign else None,
+                                                          list(order))
+        else:
+            seqs, jpg = self.workers[home].read_wall_jpeg(cams, gc, tw, th, q, foreign if any_foreign else None)
         return {n: int(s) for n, s in zip(order, seqs)}, jpg
 
     # ------------------------------------------------------------------ motion

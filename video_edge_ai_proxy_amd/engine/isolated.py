@@ -568,9 +568,11 @@ class ProcessHub:
         return self._call(name, "latest_frame", after)
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
-                    width: Optional[int] = None, height: Optional[int] = None):
+                    width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False):
         """(meta, JPEG bytes) or None: the worker process scales (width / height given) and encodes
         on its GPU, only the compressed bytes cross the pipe."""
+        if overlay is not None or stamp:
+            raise NotImplementedError("overlays are not served with gpu.isolation: process")
         if width is None and height is None:
             return self._call(name, "latest_jpeg", after, quality)
         return self._call(name, "latest_jpeg", after, quality, width, height)
@@ -628,8 +630,22 @@ class ProcessHub:
     def wall_layout(self, names=None, cols=None, tile_width=None, tile_height=None):
         raise NotImplementedError("the camera wall is not served with gpu.isolation: process")
 
-    def wall_jpeg(self, names=None, cols=None, tile_width=None, tile_height=None, quality=None):
+    def wall_jpeg(self, names=None, cols=None, tile_width=None, tile_height=None, quality=None, labels=False):
         raise NotImplementedError("the camera wall is not served with gpu.isolation: process")
+
+    # An overlay is drawn where the frame lies, by the worker that owns the ring, and its stored
+    # list lives in the in-process hub: served only there (gpu.isolation: thread).
+    def set_overlay(self, name: str, items, ttl_ms=0):
+        raise NotImplementedError("overlays are not served with gpu.isolation: process")
+
+    def add_overlay_item(self, name: str, item, ttl_ms=0):
+        raise NotImplementedError("overlays are not served with gpu.isolation: process")
+
+    def overlay(self, name: str):
+        raise NotImplementedError("overlays are not served with gpu.isolation: process")
+
+    def clear_overlay(self, name: str):
+        raise NotImplementedError("overlays are not served with gpu.isolation: process")
 
     # Crops read a ring slot, and with seq=N the ring's history: both live in the worker processes,
     # so crops are served only by the in-process hub (gpu.isolation: thread).

@@ -756,6 +756,100 @@ def crop_resize_reference(bgr: torch.Tensor, boxes, width: int, height: int, fit
                                                    fit, pad))
 
 
+def _check_overlay_picture(bgr, what: str) -> tuple:
+    """``(width, height, pitch)`` of a ``[H, W, 3]`` uint8 tensor whose rows are packed BGR24 at
+    any byte offset and any pitch ``>= 3 W`` (a contiguous tensor, or a strided view of a buffer)."""
+    if not isinstance(bgr, torch.Tensor):
+        raise TypeError(f"{what} must be a tensor")
+    if bgr.dtype != torch.uint8:
+        raise TypeError(f"{what} must be uint8")
+    if bgr.dim() != 3 or bgr.shape[2] != 3 or bgr.shape[0] < 1 or bgr.shape[1] < 1:
+        raise ValueError(f"{what} must be [H, W, 3], got {tuple(bgr.shape)}")
+    h, w = int(bgr.shape[0]), int(bgr.shape[1])
+    if h > 65535 or w > 65535:
+        raise ValueError(f"{what} is at most 65535 x 65535")
+    pitch = int(bgr.stride(0)) if h > 1 else w * 3
+    if bgr.stride(2) != 1 or (w > 1 and bgr.stride(1) != 3) or pitch < w * 3:
+        raise ValueError(f"{what} must have packed rows: strides (pitch >= 3 W, 3, 1)")
+    return w, h, pitch
+
+
+def _overlay_span(t: torch.Tensor, w: int, h: int, pitch: int) -> tuple:
+    return t.data_ptr(), t.data_ptr() + (h - 1) * pitch + w * 3
+
+
+def overlay_draw_batch(pictures, items_per_picture, outs=None, name: str = "", meta=None):
+    """On-screen display (csrc/vep/overlay.h; the dicts of :mod:`..overlay`) drawn onto a list of
+    ``[H, W, 3]`` BGR24 device tensors of any sizes on one device, each with its own list of at most
+    64 items, in ONE kernel launch. A picture's rows may start at any byte address and have any
+    pitch (a strided view will do). ``outs`` None: IN PLACE; else one tensor (or None: in place) per
+    picture of the same size, which receives the picture with the items drawn on while the picture
+    itself stays as it is; a picture and its output must not overlap. ``name`` and ``meta``
+    (``{"seq", "timestamp"}``) replace ``{name}``, ``{seq}`` and ``{time}``. Returns the tensors
+    drawn on. Byte-identical with :func:`overlay_draw_reference`. No CPU fallback."""
+    from .. import overlay
+
+    pictures = list(pictures)
+    items_per_picture = list(items_per_picture)
+    if len(pictures) != len(items_per_picture):
+        raise ValueError("items_per_picture must hold one list per picture")
+    outs = [None] * len(pictures) if outs is None else list(outs)
+    if len(outs) != len(pictures):
+        raise ValueError("outs must hold one entry per picture")
+    if not isinstance(name, str):
+        raise TypeError("name must be a string")
+    if meta is not None and not isinstance(meta, dict):
+        raise TypeError("meta must be a dict or None")
+    device, work, res, spans = None, [], [], []
+    for k, (bgr, items, out) in enumerate(zip(pictures, items_per_picture, outs)):
+        w, h, pitch = _check_overlay_picture(bgr, f"pictures[{k}]")
+        if not bgr.is_cuda:
+            raise ValueError("bgr must be a device tensor")
+        if device is None:
+            device = bgr.device
+        if bgr.device != device:
+            raise ValueError("the pictures must live on one device")
+        dst, dpitch = bgr, pitch
+        if out is not None:
+            ow, oh, dpitch = _check_overlay_picture(out, f"outs[{k}]")
+            if (ow, oh) != (w, h) or not out.is_cuda or out.device != device:
+                raise ValueError(f"outs[{k}] must be a [{h}, {w}, 3] tensor on the picture's device")
+            dst = out
+            a, b = _overlay_span(bgr, w, h, pitch), _overlay_span(out, w, h, dpitch)
+            if a[0] < b[1] and b[0] < a[1]:
+                raise ValueError(f"pictures[{k}] and outs[{k}] overlap")
+        for s in spans:
+            d = _overlay_span(dst, w, h, dpitch)
+            if d[0] < s[1] and s[0] < d[1]:
+                raise ValueError("the destinations of one call must not overlap")
+        spans.append(_overlay_span(dst, w, h, dpitch))
+        work.append((bgr.data_ptr(), pitch, dst.data_ptr(), dpitch, w, h, overlay.to_native(items)))
+        res.append(dst)
+    if work:
+        require_gpu()
+        with torch.cuda.device(device):
+            native.overlay_draw(work, name, meta, int(torch.cuda.current_stream(device).cuda_stream))
+    return res
+
+
+def overlay_draw(bgr: torch.Tensor, items, out: torch.Tensor | None = None, name: str = "", meta=None) -> torch.Tensor:
+    """The items drawn onto one ``[H, W, 3]`` BGR24 device tensor, in place when ``out`` is None:
+    see :func:`overlay_draw_batch`. Returns the tensor drawn on."""
+    return overlay_draw_batch([bgr], [items], None if out is None else [out], name, meta)[0]
+
+
+def overlay_draw_reference(bgr: torch.Tensor, items, name: str = "", meta=None) -> torch.Tensor:
+    """The CPU implementation's result for the same picture (host or device tensor): a new host
+    tensor, the byte-exact oracle of :func:`overlay_draw`."""
+    from .. import overlay
+
+    _check_overlay_picture(bgr, "bgr")
+    src = bgr.detach().cpu().contiguous().numpy()
+    out = src.copy()
+    native.overlay_draw_cpu(src, out, overlay.to_native(items), name, meta)
+    return torch.from_numpy(out)
+
+
 # ----------------------------------------------------------------------------- references
 
 def nv12_to_bgr_reference(y: torch.Tensor, uv: torch.Tensor, width=None, height=None,

@@ -193,8 +193,25 @@ class ImageService:
                           "start_timestamp must not be older than 7 days and not more than 7 days in the future")
         if self.queue is None or not self.queue.publish(req.SerializeToString()):
             context.abort(grpc.StatusCode.INTERNAL, "failed to publish to msg queue")
+        self._annotation_overlay(req)
         return pb.AnnotateResponse(device_name=req.device_name, start_timestamp=req.start_timestamp,
                                    type=req.type)
+
+    def _annotation_overlay(self, req) -> None:
+        """overlay.from_annotations: the request's bounding box also becomes a box of its camera's
+        stored overlay list (docs/OVERLAY.md). The annotation queue is not touched; a request the
+        overlay cannot use, or a camera this hub does not run, is left alone."""
+        cfg = getattr(self.hub, "cfg", None)
+        if cfg is None or not cfg.overlay.from_annotations:
+            return
+        from .. import overlay
+
+        try:
+            item = overlay.from_annotation(req)
+            if item is not None:
+                self.hub.add_overlay_item(req.device_name, item, int(cfg.overlay.annotation_ttl_ms))
+        except (KeyError, ValueError, NotImplementedError):
+            pass
 
     # ------------------------------------------------------------------ proxy / storage
     def Proxy(self, req, context):

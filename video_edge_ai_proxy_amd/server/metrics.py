@@ -82,6 +82,14 @@ class HubCollector:
             cb = CounterMetricFamily("vep_crop_boxes", "boxes the crop requests named")
             cb.add_metric([], boxes)
             yield from (cr, cb)
+        counts = getattr(self.hub, "overlay_counts", None)
+        if counts is not None:
+            requests, prims = counts()
+            orq = CounterMetricFamily("vep_overlay_requests", "pictures served with an overlay (frame.jpg, stream.mjpg, wall)")
+            orq.add_metric([], requests)
+            opr = CounterMetricFamily("vep_overlay_primitives", "primitives the overlay requests drew")
+            opr.add_metric([], prims)
+            yield from (orq, opr)
         try:
             from .._native import native
 

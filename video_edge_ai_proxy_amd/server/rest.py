@@ -19,7 +19,9 @@ motion detection on the GPU, docs/MOTION.md; ``DELETE .../motion`` resets the ba
 ``/api/v1/process/{name}/tamper`` and ``/api/v1/tamper`` (does the camera still show what it should:
 tamper detection on the GPU, docs/TAMPER.md; ``PUT .../tamper/reference`` declares the newest frame
 normal, ``DELETE .../tamper`` forgets it), ``POST /api/v1/process/{name}/crops`` and
-``GET .../crop.jpg`` (boxes of a frame cut and resized on the GPU, docs/CROPS.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
+``GET .../crop.jpg`` (boxes of a frame cut and resized on the GPU, docs/CROPS.md),
+``PUT / GET / DELETE /api/v1/process/{name}/overlay`` (a camera's stored on-screen display list,
+drawn with ``frame.jpg?overlay=1&stamp=1`` and ``wall.jpg?labels=1``, docs/OVERLAY.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
 toolchain).
 """
 from __future__ import annotations
@@ -33,6 +35,7 @@ from fastapi import FastAPI, Request
 from fastapi.middleware.cors import CORSMiddleware
 from fastapi.responses import HTMLResponse, JSONResponse, Response, StreamingResponse
 
+from .. import overlay as overlay_items
 from ..models import Settings, StreamProcess
 from ..services.process_manager import ProcessError, ProcessManager
 from ..services.settings import SettingsManager
@@ -127,12 +130,23 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return {}
         return {"width": width, "height": height}
 
+    def osd(overlay, stamp) -> dict:
+        """The overlay arguments of latest_jpeg: none when the request names neither, so such a
+        request calls the hub exactly as before."""
+        for v, what in ((overlay, "overlay"), (stamp, "stamp")):
+            if v not in (0, 1):
+                raise ValueError(f"{what} must be 0 or 1")
+        if not (overlay or stamp):
+            return {}
+        return {"overlay": True if overlay else None, "stamp": bool(stamp)}
+
     @app.get("/api/v1/process/{name}/frame.jpg")
     def frame_jpg(name: str, quality: int | None = None, after: int = 0, width: int | None = None,
-                  height: int | None = None):
+                  height: int | None = None, overlay: int = 0, stamp: int = 0):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
+            size.update(osd(overlay, stamp))
         except ValueError as e:
             return err(400, str(e))
         try:
@@ -140,6 +154,10 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             r = pm.hub.latest_jpeg(name, after, q, **size)
         except KeyError:
             return err(404, f"process {name!r} not found")
+        except NotImplementedError as e:
+            return err(501, str(e))
+        except ValueError as e:
+            return err(422, str(e))
         if r is None:
             return err(404, "no frame decoded yet")
         meta, jpg = r
@@ -147,10 +165,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
 
     @app.get("/api/v1/process/{name}/stream.mjpg")
     def stream_mjpg(name: str, fps: float = 10.0, frames: int | None = None, quality: int | None = None,
-                    width: int | None = None, height: int | None = None):
+                    width: int | None = None, height: int | None = None, overlay: int = 0, stamp: int = 0):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
+            size.update(osd(overlay, stamp))
             if not 0 < fps <= 1000:
                 raise ValueError("fps must be in (0, 1000]")
             if frames is not None and frames < 1:
@@ -161,6 +180,10 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             pm.hub.touch(name)
         except KeyError:
             return err(404, f"process {name!r} not found")
+        if "stamp" in size:
+            _, bad = overlay_call(pm.hub.overlay, name)  # (501 before the stream starts)
+            if bad is not None:
+                return bad
 
         def parts():
             # one part per NEW frame (the seq cursor), at most `fps` a second; every part touches
@@ -176,8 +199,8 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                             seq = 0  # the camera started a new ring (restart, resolution change)
                         wait(name, seq, 500)
                     r = pm.hub.latest_jpeg(name, seq, q, **size)
-                except KeyError:
-                    return  # the camera was removed
+                except (KeyError, ValueError):
+                    return  # the camera was removed (or its stored overlay can no longer be drawn)
                 now = time.monotonic()
                 if r is None:
                     if now - last_new > MJPEG_IDLE_S:
@@ -197,10 +220,14 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         return StreamingResponse(parts(), media_type=f"multipart/x-mixed-replace; boundary={MJPEG_BOUNDARY}")
 
     # ---- camera wall: one picture of many cameras, scaled and composed on the GPU (docs/WALL.md)
-    def wall_args(names, cols, tile, quality) -> dict:
+    def wall_args(names, cols, tile, quality, labels=0) -> dict:
         from ..config import parse_tile
 
         a = {"names": None, "cols": None, "tile_width": None, "tile_height": None, "quality": jpeg_quality(quality)}
+        if labels not in (0, 1):
+            raise ValueError("labels must be 0 or 1")
+        if labels:
+            a["labels"] = True  # (absent otherwise: the hub is called exactly as before)
         if names is not None:
             a["names"] = [n for n in names.split(",") if n]
             if not a["names"]:
@@ -221,6 +248,8 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return None, err(501, str(e))
         except KeyError as e:
             return None, err(404, f"process {e.args[0] if e.args else ''!r} not found")
+        except overlay_items.Refused as e:
+            return None, err(422, str(e))
         except ValueError as e:
             # no camera running is "nothing to show" (404); everything else is a bad argument
             return None, err(404 if not pm.hub.cameras else 400, str(e))
@@ -230,9 +259,9 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
 
     @app.get("/api/v1/wall.jpg")
     def wall_jpg(names: str | None = None, cols: int | None = None, tile: str | None = None,
-                 quality: int | None = None):
+                 quality: int | None = None, labels: int = 0):
         try:
-            a = wall_args(names, cols, tile, quality)
+            a = wall_args(names, cols, tile, quality, labels)
         except ValueError as e:
             return err(400, str(e))
         lay, bad = wall_call(pm.hub.wall_layout, a["names"], a["cols"], a["tile_width"], a["tile_height"])
@@ -266,9 +295,9 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
 
     @app.get("/api/v1/wall.mjpg")
     def wall_mjpg(names: str | None = None, cols: int | None = None, tile: str | None = None,
-                  quality: int | None = None, fps: float = 10.0, frames: int | None = None):
+                  quality: int | None = None, fps: float = 10.0, frames: int | None = None, labels: int = 0):
         try:
-            a = wall_args(names, cols, tile, quality)
+            a = wall_args(names, cols, tile, quality, labels)
             if not 0 < fps <= 1000:
                 raise ValueError("fps must be in (0, 1000]")
             if frames is not None and frames < 1:
@@ -421,6 +450,38 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         except (KeyError, ProcessError):
             return err(404, f"process {name!r} not found")
         return Response(status_code=204)
+
+    # ---- on-screen display: a camera's stored list, drawn on served JPEGs (docs/OVERLAY.md)
+    def overlay_call(fn, name, *args):
+        try:
+            return fn(name, *args), None
+        except KeyError:
+            return None, err(404, f"process {name!r} not found")
+        except NotImplementedError as e:
+            return None, err(501, str(e))
+        except ValueError as e:
+            return None, err(422, str(e))
+
+    @app.get("/api/v1/process/{name}/overlay")
+    def overlay_get(name: str):
+        items, bad = overlay_call(pm.hub.overlay, name)
+        return bad if bad is not None else {"items": items}
+
+    @app.put("/api/v1/process/{name}/overlay")
+    async def overlay_put(name: str, request: Request):
+        try:
+            body = json.loads(await request.body() or b"null")
+            if not isinstance(body, dict) or "items" not in body or set(body) - {"items", "ttl_ms"}:
+                raise ValueError('a JSON object {"items": [...], "ttl_ms": N} expected')
+        except ValueError as e:
+            return err(422, str(e))
+        _, bad = overlay_call(pm.hub.set_overlay, name, body["items"], body.get("ttl_ms", 0))
+        return bad if bad is not None else Response(status_code=204)
+
+    @app.delete("/api/v1/process/{name}/overlay")
+    def overlay_delete(name: str):
+        _, bad = overlay_call(pm.hub.clear_overlay, name)
+        return bad if bad is not None else Response(status_code=204)
 
     # ---- crops: boxes of a frame, cut and resized on the GPU in its ring slot (docs/CROPS.md)
     @app.post("/api/v1/process/{name}/crops")
