@@ -64,82 +64,19 @@ tsan: $(TSAN_DIR)/native_stress
 asan: $(ASAN_DIR)/native_stress
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" $(CURDIR)/$(ASAN_DIR)/native_stress
 
-# The CPU JPEG encoder alone on its extreme inputs (csrc/tests/jpeg_selftest.cpp), under
-# AddressSanitizer + UndefinedBehaviorSanitizer: a stand-alone host program, no GPU.
-$(ASAN_DIR)/jpeg_selftest: csrc/vep/jpeg.cpp csrc/tests/jpeg_selftest.cpp csrc/vep/jpeg.h csrc/vep/common.h
+# The CPU implementation of one op alone on its extreme inputs, edge shapes and closed forms
+# (csrc/vep/<op>.cpp driven by csrc/tests/<op>_selftest.cpp), under AddressSanitizer +
+# UndefinedBehaviorSanitizer: a stand-alone host program, no GPU. One rule for every op.
+ASAN_OPS = jpeg scale motion tamper mask crop overlay
+
+$(ASAN_DIR)/%_selftest: csrc/vep/%.cpp csrc/tests/%_selftest.cpp $(wildcard csrc/vep/*.h)
 	mkdir -p $(ASAN_DIR)
 	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
 	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
-	  -Icsrc csrc/vep/jpeg.cpp csrc/tests/jpeg_selftest.cpp -o $@
+	  -Icsrc csrc/vep/$*.cpp csrc/tests/$*_selftest.cpp -o $@
 
-asan-jpeg: $(ASAN_DIR)/jpeg_selftest
-	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/jpeg_selftest
-
-# The CPU scaler and wall composition alone on their edge shapes (csrc/tests/scale_selftest.cpp),
-# likewise: a stand-alone host program, no GPU.
-$(ASAN_DIR)/scale_selftest: csrc/vep/scale.cpp csrc/tests/scale_selftest.cpp csrc/vep/scale.h csrc/vep/common.h
-	mkdir -p $(ASAN_DIR)
-	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
-	  -Icsrc csrc/vep/scale.cpp csrc/tests/scale_selftest.cpp -o $@
-
-asan-scale: $(ASAN_DIR)/scale_selftest
-	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/scale_selftest
-
-# The CPU motion detector alone on its edge shapes (csrc/tests/motion_selftest.cpp), likewise: a
-# stand-alone host program, no GPU.
-$(ASAN_DIR)/motion_selftest: csrc/vep/motion.cpp csrc/tests/motion_selftest.cpp csrc/vep/motion.h csrc/vep/common.h
-	mkdir -p $(ASAN_DIR)
-	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
-	  -Icsrc csrc/vep/motion.cpp csrc/tests/motion_selftest.cpp -o $@
-
-asan-motion: $(ASAN_DIR)/motion_selftest
-	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/motion_selftest
-
-# The CPU tamper detector alone on its edge shapes and closed forms (csrc/tests/tamper_selftest.cpp),
-# likewise: a stand-alone host program, no GPU.
-$(ASAN_DIR)/tamper_selftest: csrc/vep/tamper.cpp csrc/tests/tamper_selftest.cpp csrc/vep/tamper.h csrc/vep/motion.h csrc/vep/common.h
-	mkdir -p $(ASAN_DIR)
-	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
-	  -Icsrc csrc/vep/tamper.cpp csrc/tests/tamper_selftest.cpp -o $@
-
-asan-tamper: $(ASAN_DIR)/tamper_selftest
-	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/tamper_selftest
-
-# The CPU privacy masks alone on their edge shapes and closed forms (csrc/tests/mask_selftest.cpp),
-# likewise: a stand-alone host program, no GPU.
-$(ASAN_DIR)/mask_selftest: csrc/vep/mask.cpp csrc/tests/mask_selftest.cpp csrc/vep/mask.h csrc/vep/common.h
-	mkdir -p $(ASAN_DIR)
-	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
-	  -Icsrc csrc/vep/mask.cpp csrc/tests/mask_selftest.cpp -o $@
-
-asan-mask: $(ASAN_DIR)/mask_selftest
-	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/mask_selftest
-
-# The CPU crops alone on their edge shapes and closed forms (csrc/tests/crop_selftest.cpp), likewise:
-# a stand-alone host program, no GPU.
-$(ASAN_DIR)/crop_selftest: csrc/vep/crop.cpp csrc/tests/crop_selftest.cpp csrc/vep/crop.h csrc/vep/mask.h csrc/vep/scale.h csrc/vep/common.h
-	mkdir -p $(ASAN_DIR)
-	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
-	  -Icsrc csrc/vep/crop.cpp csrc/tests/crop_selftest.cpp -o $@
-
-asan-crop: $(ASAN_DIR)/crop_selftest
-	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/crop_selftest
-
-# The CPU on-screen display alone on its edge shapes and closed forms (csrc/tests/overlay_selftest.cpp),
-# likewise: a stand-alone host program, no GPU.
-$(ASAN_DIR)/overlay_selftest: csrc/vep/overlay.cpp csrc/tests/overlay_selftest.cpp csrc/vep/overlay.h csrc/vep/mask.h csrc/vep/common.h
-	mkdir -p $(ASAN_DIR)
-	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
-	  -Icsrc csrc/vep/overlay.cpp csrc/tests/overlay_selftest.cpp -o $@
-
-asan-overlay: $(ASAN_DIR)/overlay_selftest
-	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/overlay_selftest
+$(ASAN_OPS:%=asan-%): asan-%: $(ASAN_DIR)/%_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/$*_selftest
 
 # The scratch pool's locking alone (csrc/tests/scratch_selftest.cpp on vep/scratch.h, which
 # includes no HIP header): a stand-alone host program, no GPU. Under ThreadSanitizer, under

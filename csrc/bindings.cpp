@@ -2425,21 +2425,11 @@ PYBIND11_MODULE(_vep, m) {
             const auto& [src, w, h, bg_in, bg_out, bg_pitch, counts] = pics[size_t(k)];
             VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "motion: picture size must be 1..65535");
             VEP_CHECK(bg_pitch >= w && bg_pitch <= 65536, "motion: background pitch out of range");
-            gpu::MotionDesc d{};
-            d.src = reinterpret_cast<const u8*>(src);
-            d.src_pitch = u32(w) * 3;
-            d.bg_in = reinterpret_cast<const u16*>(bg_in);
-            d.bg_out = reinterpret_cast<u16*>(bg_out);
-            d.bg_pitch = u32(bg_pitch);
-            d.counts = reinterpret_cast<u32*>(counts);
-            d.w = w;
-            d.h = h;
-            d.cell = cell;
-            d.threshold = threshold;
-            d.learn_shift = learn_shift;
-            gpu::check_motion(d, size_t(w) * size_t(h) * 3, size_t(bg_pitch) * size_t(h),
-                              size_t(motion::cells(u32(w), u32(cell))) * motion::cells(u32(h), u32(cell)));
-            set->h_descs.p[k] = d;
+            set->h_descs.p[k] = gpu::make_motion_desc(
+                reinterpret_cast<const u8*>(src), size_t(w) * size_t(h) * 3, w, h, reinterpret_cast<const u16*>(bg_in),
+                reinterpret_cast<u16*>(bg_out), u32(bg_pitch), size_t(bg_pitch) * size_t(h),
+                reinterpret_cast<u32*>(counts), size_t(motion::cells(u32(w), u32(cell))) * motion::cells(u32(h), u32(cell)),
+                cell, threshold, learn_shift);
           }
           set->run(n, 0, s);
           VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
@@ -2807,18 +2797,10 @@ PYBIND11_MODULE(_vep, m) {
           for (int k = 0; k < n; ++k) {
             const auto& [src, w, h, hist, sum_y, energy] = pics[size_t(k)];
             VEP_CHECK(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "tamper: picture size must be 1..65535");
-            gpu::TamperDesc d{};
-            d.src = reinterpret_cast<const u8*>(src);
-            d.src_pitch = u32(w) * 3;
-            d.hist = reinterpret_cast<u32*>(hist);
-            d.sum_y = reinterpret_cast<u32*>(sum_y);
-            d.energy = reinterpret_cast<u32*>(energy);
-            d.w = w;
-            d.h = h;
-            d.cell = cell;
-            gpu::check_tamper(d, size_t(w) * size_t(h) * 3,
-                              size_t(tamper::cells(u32(w), u32(cell))) * tamper::cells(u32(h), u32(cell)));
-            set->h_descs.p[k] = d;
+            set->h_descs.p[k] = gpu::make_tamper_desc(
+                reinterpret_cast<const u8*>(src), size_t(w) * size_t(h) * 3, w, h, reinterpret_cast<u32*>(hist),
+                reinterpret_cast<u32*>(sum_y), reinterpret_cast<u32*>(energy),
+                size_t(tamper::cells(u32(w), u32(cell))) * tamper::cells(u32(h), u32(cell)), cell);
           }
           for (int k = 0; k < n; ++k)
             VEP_HIP(hipMemsetAsync(set->h_descs.p[k].hist, 0, size_t(tamper::kBins) * sizeof(u32), s));

@@ -466,6 +466,12 @@ void check_motion(const MotionDesc& d, size_t src_bytes, size_t bg_samples, size
 // One launch for the n pictures: grid = (blocks of the largest picture) x pictures. h_descs is the
 // host copy of d_descs (the grid is sized from it).
 void launch_motion(const MotionDesc* d_descs, const MotionDesc* h_descs, int n, hipStream_t s);
+// The descriptor of one picture: the packed w x h picture at src (src_bytes long, rows of w * 3
+// bytes), planes of bg_samples u16 each in rows of bg_pitch samples (bg_in null: prime) and a
+// counts array of count_cells u32; checked.
+MotionDesc make_motion_desc(const u8* src, size_t src_bytes, int w, int h, const u16* bg_in, u16* bg_out, u32 bg_pitch,
+                            size_t bg_samples, u32* counts, size_t count_cells, int cell, int threshold,
+                            int learn_shift);
 
 // Motion scratch of one device (pool contract: above): descriptors and a counts buffer.
 constexpr size_t kResultFloor = 16384;  // words: motion counts, tamper results
@@ -502,6 +508,10 @@ void check_tamper(const TamperDesc& d, size_t src_bytes, size_t grid_cells);
 // One launch for the n pictures: grid = (blocks of the largest picture) x pictures. h_descs is the
 // host copy of d_descs (the grid is sized from it). The histograms are zeroed by the caller, on `s`.
 void launch_tamper(const TamperDesc* d_descs, const TamperDesc* h_descs, int n, hipStream_t s);
+// The descriptor of one picture: the packed w x h picture at src (src_bytes long, rows of w * 3
+// bytes), a histogram of 256 u32 and two grid planes of grid_cells u32 each; checked.
+TamperDesc make_tamper_desc(const u8* src, size_t src_bytes, int w, int h, u32* hist, u32* sum_y, u32* energy,
+                            size_t grid_cells, int cell);
 
 // Tamper scratch of one device (pool contract: above): descriptors and a results buffer. A
 // request's results are the histograms of all its pictures first (zeroed by one memset), then

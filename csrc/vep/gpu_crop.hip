@@ -9,11 +9,11 @@
 // so a thread computes up to kRows output pixels. Both axes run on one tap definition
 // (crop::Taps: consecutive source indices, only the two ends weighing differently), so reducing,
 // enlarging and any mix of the two are the same code:
-//  * the source rows of the tile's footprint are staged in LDS (gpu_stage.h: 16-byte loads from
-//    aligned addresses, byte heads and tails, nothing outside the rect's own bytes is read), as
-//    many rows per barrier as fit; a footprint wider than the buffer goes in segments of kSegPix
-//    pixels, one row at a time;
-//  * a thread sums a staged row horizontally for its column ONCE (sum <= 255 * Dx: 32 bits) and
+//  * the source rows of the tile's footprint are staged in LDS (stage::stage_rows: nothing outside
+//    the rect's own bytes is read), as many rows per barrier as fit; a footprint wider than the
+//    buffer goes in segments of kSegPix pixels, one row at a time;
+//  * a thread sums a staged row horizontally for its column ONCE (stage::sum_weighted, which the
+//    scale kernel shares; sum <= 255 * Dx: 32 bits) and
 //    adds it, weighed, to each of its output rows that has the row among its taps. Reducing, that
 //    is the scale kernel's streaming read (a source row serves one or two output rows);
 //    enlarging, the footprint is small, one staging serves the whole tile and a source row feeds
@@ -21,9 +21,9 @@
 //  * the accumulators are 32 bits while 255 * Dx * Dy fits and 64 bits above (crop::narrow); one
 //    rounding at the end, no float.
 // The tile's bytes are then put together in LDS, every byte at its global address modulo 16, and
-// written row by row: 16-byte stores to 16-byte aligned addresses, the unaligned head and tail of
-// a row byte by byte (crop k of a packed [n, H, W, 3] tensor starts at any byte address). Bytes
-// outside the tile's own rows are NOT WRITTEN AT ALL.
+// written with stage::store_rows (crop k of a packed [n, H, W, 3] tensor starts at any byte
+// address). Bytes outside the tile's own rows are NOT WRITTEN AT ALL. The tile's geometry, the
+// staging and the store live in gpu_stage.h, which the overlay kernel (gpu_overlay.hip) shares.
 //
 // check_crop() proves on the host that every read lies inside the picture and every write inside
 // the crop's own output.
@@ -38,21 +38,17 @@ namespace vep::gpu {
 
 namespace {
 
-constexpr u32 kThreads = stage::kThreads;
-constexpr u32 kLdsBytes = 24576;
-// pixels of one staged segment: 3 bytes each + up to 15 bytes of misalignment fit the buffer
-constexpr u32 kSegPix = (kLdsBytes - 16) / 3;
-static_assert(kSegPix * 3 + 15 <= kLdsBytes, "segment fits LDS");
-constexpr u32 kTileW = 64;                   // a wave spans a tile's row
-constexpr u32 kWaves = kThreads / kTileW;    // 4
-constexpr u32 kRows = 4;                     // output rows of one thread
-constexpr u32 kTileH = kWaves * kRows;       // 16
-constexpr u32 kOutCap = kTileW * 3 + 16;     // a tile row in LDS: its bytes + up to 15 of misalignment
-static_assert(kOutCap % 16 == 0, "tile rows keep their alignment");
-static_assert(kTileH * ((kTileW * 3 >> 4) + 1) <= kThreads, "one 16-byte vector of the tile per thread");
-
-__host__ __device__ inline u32 tiles_x(u32 fw) { return (fw + kTileW - 1) / kTileW; }
-__host__ __device__ inline u32 tiles_of(u32 fw, u32 fh) { return tiles_x(fw) * ((fh + kTileH - 1) / kTileH); }
+using stage::kLdsBytes;
+using stage::kSegPix;
+using stage::kThreads;
+// the tile: kRows output rows of one thread
+using stage::kRows;
+using stage::kTileH;
+using stage::kTileW;
+using stage::kWaves;
+using stage::tiles_of;
+using stage::tiles_x;
+constexpr u32 kOutCap = stage::kTileRowCap;
 
 template <typename Acc>
 __device__ __forceinline__ void crop_tile(const CropDesc& d, u32 j0, u32 j1, u32 k0, u32 k1, u8* lds, u8* olds) {
@@ -65,7 +61,7 @@ __device__ __forceinline__ void crop_tile(const CropDesc& d, u32 j0, u32 j1, u32
   const u32 ra = crop::taps(k0, sh, fh).lo, rz = crop::taps(k1 - 1, sh, fh).hi;
   const u32 npix = ib - ia + 1;
   const bool fits = npix <= kSegPix;
-  const u32 rowcap = fits ? ((npix * 3 + 15 + 15) & ~15u) : kLdsBytes;
+  const u32 rowcap = fits ? stage::rowcap_of(npix) : kLdsBytes;
   const u32 rpp = fits ? kLdsBytes / rowcap : 1;  // rows staged per barrier
   const u32 c = threadIdx.x & (kTileW - 1), q = threadIdx.x / kTileW;
   const u32 j = j0 + c;
@@ -98,8 +94,6 @@ __device__ __forceinline__ void crop_tile(const CropDesc& d, u32 j0, u32 j1, u32
       stage::stage_rows(src, src_pitch, rb, nr, is, (ie - is) * 3, rowcap, lds);
       __syncthreads();
       if (active) {
-        const u32 a = max(tx.lo + 1, is), b = min(tx.hi, ie);  // inner samples [a, b) of this segment
-        const bool has_lo = tx.lo >= is && tx.lo < ie, has_hi = tx.hi != tx.lo && tx.hi >= is && tx.hi < ie;
         for (u32 rr = 0; rr < nr; ++rr) {
           const u32 r = rb + rr;
           bool need = false;
@@ -108,26 +102,7 @@ __device__ __forceinline__ void crop_tile(const CropDesc& d, u32 j0, u32 j1, u32
           if (!need) continue;  // (the same answer in every segment of the row)
           const VEP_DEV u8* g = src + u64(r) * src_pitch + u64(is) * 3;
           const u32 row_off = rr * rowcap + (u32(reinterpret_cast<uintptr_t>(g)) & 15u);
-          const u8* l = lds + row_off;
-          if (a < b) {
-            u32 s0 = 0, s1 = 0, s2 = 0;
-            stage::sum_samples(lds, row_off + (a - is) * 3, b - a, s0, s1, s2);
-            h0 += tx.w_mid * s0;
-            h1 += tx.w_mid * s1;
-            h2 += tx.w_mid * s2;
-          }
-          if (has_lo) {
-            const u8* p = l + (tx.lo - is) * 3;
-            h0 += tx.w_lo * p[0];
-            h1 += tx.w_lo * p[1];
-            h2 += tx.w_lo * p[2];
-          }
-          if (has_hi) {
-            const u8* p = l + (tx.hi - is) * 3;
-            h0 += tx.w_hi * p[0];
-            h1 += tx.w_hi * p[1];
-            h2 += tx.w_hi * p[2];
-          }
+          stage::sum_weighted(lds, row_off, is, ie, tx.lo, tx.hi, tx.w_lo, tx.w_mid, tx.w_hi, h0, h1, h2);
           if (ie == ib + 1) {  // the row is complete
 #pragma unroll
             for (u32 m = 0; m < kRows; ++m) {
@@ -149,60 +124,18 @@ __device__ __forceinline__ void crop_tile(const CropDesc& d, u32 j0, u32 j1, u32
   VEP_DEV u8* dst = d.dst;
   const u32 fx = d.fx, fy = d.fy;
   auto row_ptr = [&](u32 rr) -> VEP_DEV u8* { return dst + (u64(fy + k0 + rr) * ow + fx + j0) * 3; };
-  const u32 dx = crop::den(sw, fw), dy = crop::den(sh, fh);
+  const Acc den = Acc(crop::den(sw, fw)) * crop::den(sh, fh);
 #pragma unroll
   for (u32 m = 0; m < kRows; ++m) {
     const u32 rr = q + m * kWaves;
     if (!active || k0 + rr >= k1) continue;
-    u32 o0, o1, o2;
-    if constexpr (sizeof(Acc) == 4) {
-      const u32 den = dx * dy;
-      o0 = scale::round_div32(acc[m][0], den);
-      o1 = scale::round_div32(acc[m][1], den);
-      o2 = scale::round_div32(acc[m][2], den);
-    } else {
-      const u64 den = u64(dx) * dy;
-      o0 = scale::round_div64(acc[m][0], den);
-      o1 = scale::round_div64(acc[m][1], den);
-      o2 = scale::round_div64(acc[m][2], den);
-    }
     u8* o = olds + rr * kOutCap + (u32(reinterpret_cast<u64>(row_ptr(rr))) & 15u) + c * 3;
-    o[0] = u8(o0);
-    o[1] = u8(o1);
-    o[2] = u8(o2);
+    o[0] = u8(scale::round_div(acc[m][0], den));
+    o[1] = u8(scale::round_div(acc[m][1], den));
+    o[2] = u8(scale::round_div(acc[m][2], den));
   }
   __syncthreads();
-  // The rows go out: whole 16-byte vectors at aligned addresses, one per thread ...
-  const u32 nrow = k1 - k0, nbytes = (j1 - j0) * 3;
-  const u32 t = threadIdx.x;
-  const u32 vpr = (nbytes >> 4) + 1;  // upper bound of a row's 16-byte vectors
-  if (t < nrow * vpr) {
-    const u32 rr = t / vpr, v = t - rr * vpr;
-    VEP_DEV u8* gp = row_ptr(rr);
-    const u32 mis = u32(reinterpret_cast<u64>(gp)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    if (v < ((nbytes - head) >> 4)) {
-      const u32 o = head + v * 16;  // o + 16 <= nbytes
-      *reinterpret_cast<VEP_DEV uint4*>(gp + o) = *reinterpret_cast<const uint4*>(olds + rr * kOutCap + mis + o);
-    }
-  }
-  // ... and a row's head and tail byte by byte: 32 byte slots per row, 8 rows per step
-  for (u32 rr = t >> 5; rr < nrow; rr += kThreads / 32) {
-    const u32 slot = t & 31u;
-    VEP_DEV u8* gp = row_ptr(rr);
-    const u32 mis = u32(reinterpret_cast<u64>(gp)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    const u32 body = ((nbytes - head) >> 4) << 4;
-    u32 o;
-    if (slot < 16) {
-      if (slot >= head) continue;
-      o = slot;
-    } else {
-      if (slot - 16 >= nbytes - head - body) continue;
-      o = head + body + (slot - 16);
-    }
-    gp[o] = olds[rr * kOutCap + mis + o];
-  }
+  stage::store_rows(row_ptr(0), ow * 3, k1 - k0, (j1 - j0) * 3, kOutCap, olds);
 }
 
 __global__ __launch_bounds__(kThreads) void crop_kernel(const CropDesc* __restrict__ descs, u32 fill_base) {

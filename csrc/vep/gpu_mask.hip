@@ -22,7 +22,9 @@
 //
 // Pass 2 (both modes) writes the strip's rows: 16-byte stores to 16-byte aligned addresses, the
 // value of every byte looked up by its pixel's block and its channel, and the unaligned head and
-// tail of every row byte by byte. Bytes outside the rect are NOT WRITTEN AT ALL: a byte that
+// tail of every row byte by byte (the split of a row is stage::split_row, gpu_stage.h, which the
+// staging kernels share; the bytes are generated here, not copied, so the store itself is this
+// kernel's own). Bytes outside the rect are NOT WRITTEN AT ALL: a byte that
 // shares a dword or a 16-byte vector with the rect belongs to the bytewise head or tail of its
 // neighbour, never to a wide store. No float is involved anywhere.
 //
@@ -31,13 +33,14 @@
 #include <algorithm>
 
 #include "gpu.h"
+#include "gpu_stage.h"
 #include "mask.h"
 
 namespace vep::gpu {
 
 namespace {
 
-constexpr u32 kThreads = 256;
+using stage::kThreads;
 constexpr u32 kChunkPix = 512;  // a chunk is at most this wide
 constexpr u32 kFillRows = 16;   // rows of a fill strip
 constexpr u32 kMaxBlocks = kChunkPix / u32(mask::kMinBlock);  // blocks of a chunk
@@ -151,20 +154,17 @@ __global__ __launch_bounds__(kThreads) void mask_kernel(const MaskDesc* __restri
     vals[t] = (fill >> (8 * t)) & 255u;
   }
   __syncthreads();
-  // Pass 2: the strip's rows. Row rr's bytes start at gp(rr); its first `head` bytes and the bytes
-  // after its last whole 16-byte vector go byte by byte.
+  // Pass 2: the strip's rows. Row rr's bytes start at row_ptr(rr); the bytes before its first and
+  // after its last whole 16-byte vector go byte by byte (stage::split_row).
   auto row_ptr = [&](u32 rr) -> VEP_DEV u8* { return dst + u64(sy0 + rr) * pitch + u64(cx0) * 3; };
-  auto head_of = [&](VEP_DEV u8* gp) -> u32 {
-    return min(nbytes, (16u - (u32(reinterpret_cast<u64>(gp)) & 15u)) & 15u);
-  };
   const u32 vpr = (nbytes >> 4) + 1;  // upper bound of a row's 16-byte vectors
   const u32 total = nr * vpr;
   for (u32 item = t; item < total; item += kThreads) {
     const u32 rr = item / vpr, v = item - rr * vpr;
     VEP_DEV u8* gp = row_ptr(rr);
-    const u32 head = head_of(gp);
-    if (v >= ((nbytes - head) >> 4)) continue;
-    const u32 o = head + v * 16;  // o + 16 <= nbytes
+    const stage::RowSplit r = stage::split_row(gp, nbytes);
+    if (v >= r.nvec) continue;
+    const u32 o = r.head + v * 16;  // o + 16 <= nbytes
     u32 p = o / 3, ch = o - p * 3;
     u32 blk = p / bdiv, rem = p - blk * bdiv;
     u32 w4[4];
@@ -193,18 +193,9 @@ __global__ __launch_bounds__(kThreads) void mask_kernel(const MaskDesc* __restri
   }
   // 32 byte slots per row (16 of the head, 16 of the tail), 8 rows per step
   for (u32 rr = t >> 5; rr < nr; rr += kThreads / 32) {
-    const u32 slot = t & 31u;
     VEP_DEV u8* gp = row_ptr(rr);
-    const u32 head = head_of(gp);
-    const u32 body = ((nbytes - head) >> 4) << 4;
     u32 o;
-    if (slot < 16) {
-      if (slot >= head) continue;
-      o = slot;
-    } else {
-      if (slot - 16 >= nbytes - head - body) continue;
-      o = head + body + (slot - 16);
-    }
+    if (!stage::edge_byte(stage::split_row(gp, nbytes), nbytes, t & 31u, o)) continue;
     const u32 p = o / 3, ch = o - p * 3;
     gp[o] = u8(vals[(p / bdiv) * 3 + ch]);
   }

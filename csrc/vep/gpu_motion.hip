@@ -7,12 +7,11 @@
 // A block owns whole cells: one row of the cell grid (`cell` pixel rows) and a chunk of its
 // columns. A chunk is a multiple of lcm(cell, 8) pixels wide, so it starts at a cell boundary and
 // at a 16-byte boundary of the background rows (8 u16 samples). The kernel is a pure stream: per
-// pixel 3 bytes of source and 2 of background in, 2 of background out. Packed BGR rows start at
-// any byte address, so the block stages the source rows of a pass in LDS with 16-byte loads from
-// 16-byte aligned addresses, the unaligned head and tail of every row byte by byte (the scale
-// kernel's staging). A byte keeps its address modulo 16 in LDS, so the LDS stores are aligned
-// too. A thread then takes groups of 8 pixels: 24 source bytes out of aligned LDS dwords, one
-// 16-byte background vector in and one out. The group's changed pixels are added to the block's
+// pixel 3 bytes of source and 2 of background in, 2 of background out. The block stages the source
+// rows of a pass in LDS (stage::stage_rows, gpu_stage.h: a byte keeps its address modulo 16). A
+// thread then takes groups of 8 pixels: 24 source bytes out of aligned LDS dwords, one 16-byte
+// background vector in and one out. The chunk geometry and the groups' lumas are the tamper
+// kernel's too and live in gpu_cells.h. The group's changed pixels are added to the block's
 // per-cell counters in LDS (integer atomics: the sum does not depend on the order), and when the
 // block's rows are done every cell of the block is written once by a plain store, zeros
 // included. Nothing in global memory is written twice or by two blocks.
@@ -23,104 +22,22 @@
 #include <algorithm>
 
 #include "gpu.h"
+#include "gpu_cells.h"
 #include "motion.h"
 
 namespace vep::gpu {
 
 namespace {
 
-constexpr u32 kThreads = 256;
-constexpr u32 kLdsBytes = 24576;
-constexpr u32 kChunkPix = 512;  // a chunk is at most this wide, or one lcm(cell, 8) where that is wider
+using cells::chunk_of;
+using stage::kLdsBytes;
+using stage::kThreads;
 constexpr u32 kMaxItems = 4;    // 8-pixel groups of a thread per pass
-constexpr u32 kMaxCells = kChunkPix / u32(motion::kMinCell);  // cells of a chunk
-
-// Pixels of a chunk: the largest multiple of lcm(cell, 8) that is <= kChunkPix, at least one.
-__host__ __device__ inline u32 chunk_of(u32 cell) {
-  const u32 low = cell & (0u - cell);
-  const u32 unit = cell / (low < 8u ? low : 8u) * 8u;  // lcm(cell, 8) <= 2040
-  return unit >= kChunkPix ? unit : kChunkPix / unit * unit;
-}
-// Every cell in 4..256: a row of the widest chunk fits the staging buffer, a chunk has at most
-// kMaxCells cells, and a pass of one row has at most kThreads * kMaxItems groups.
-constexpr bool chunks_fit() {
-  for (u32 cell = u32(motion::kMinCell); cell <= u32(motion::kMaxCell); ++cell) {
-    const u32 low = cell & (0u - cell);
-    const u32 unit = cell / (low < 8u ? low : 8u) * 8u;
-    const u32 chunk = unit >= kChunkPix ? unit : kChunkPix / unit * unit;
-    if (chunk % cell || chunk % 8u) return false;
-    if (((chunk * 3 + 30) & ~15u) > kLdsBytes) return false;
-    if (chunk / cell > kMaxCells) return false;
-    if (chunk / 8u > kThreads * kMaxItems) return false;
-  }
-  return true;
-}
-static_assert(chunks_fit(), "chunk geometry");
-
-// Rows rb .. rb + nr of the source, pixels from `is` on (nbytes bytes), into LDS: row rr at
-// rr * rowcap + (its address modulo 16).
-__device__ __forceinline__ void stage_rows(const VEP_DEV u8* src, u32 src_pitch, u32 rb, u32 nr, u32 is,
-                                           u32 nbytes, u32 rowcap, u8* lds) {
-  const u32 t = threadIdx.x;
-  const u32 vpr = (nbytes >> 4) + 1;  // upper bound of a row's 16-byte vectors
-  const u32 total = nr * vpr;
-  // Every load of a pass is issued before the first LDS store, so a pass costs one memory
-  // latency: the thread's head / tail byte, then up to six vectors.
-  auto edge = [&](u32 rr, u8& x) -> u32 {  // a byte of row rr's unaligned head or tail
-    const u32 slot = t & 31u;
-    const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
-    const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    const u32 body = ((nbytes - head) >> 4) << 4;
-    u32 o;
-    if (slot < 16) {
-      if (slot >= head) return ~0u;
-      o = slot;
-    } else {
-      if (slot - 16 >= nbytes - head - body) return ~0u;
-      o = head + body + (slot - 16);
-    }
-    x = g[o];
-    return rr * rowcap + mis + o;
-  };
-  auto fetch = [&](u32 item, uint4& x) -> u32 {  // -> LDS offset, ~0u: no vector
-    if (item >= total) return ~0u;
-    const u32 rr = item / vpr, v = item - rr * vpr;
-    const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
-    const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    if (v >= ((nbytes - head) >> 4)) return ~0u;
-    x = *reinterpret_cast<const VEP_DEV uint4*>(g + head + v * 16);
-    return rr * rowcap + mis + head + v * 16;
-  };
-  u8 e = 0;
-  const u32 e_at = (t >> 5) < nr ? edge(t >> 5, e) : ~0u;  // 32 byte slots per row, 8 rows per step
-  for (u32 base = t; base < total; base += kThreads * 6) {
-    uint4 x0 = {}, x1 = {}, x2 = {}, x3 = {}, x4 = {}, x5 = {};
-    const u32 at0 = fetch(base, x0), at1 = fetch(base + kThreads, x1), at2 = fetch(base + 2 * kThreads, x2),
-              at3 = fetch(base + 3 * kThreads, x3), at4 = fetch(base + 4 * kThreads, x4),
-              at5 = fetch(base + 5 * kThreads, x5);
-    if (at0 != ~0u) *reinterpret_cast<uint4*>(lds + at0) = x0;
-    if (at1 != ~0u) *reinterpret_cast<uint4*>(lds + at1) = x1;
-    if (at2 != ~0u) *reinterpret_cast<uint4*>(lds + at2) = x2;
-    if (at3 != ~0u) *reinterpret_cast<uint4*>(lds + at3) = x3;
-    if (at4 != ~0u) *reinterpret_cast<uint4*>(lds + at4) = x4;
-    if (at5 != ~0u) *reinterpret_cast<uint4*>(lds + at5) = x5;
-  }
-  if (e_at != ~0u) lds[e_at] = e;
-  for (u32 rr = (t >> 5) + kThreads / 32; rr < nr; rr += kThreads / 32) {
-    const u32 at = edge(rr, e);
-    if (at != ~0u) lds[at] = e;
-  }
-}
-
-// Lumas of four pixels out of their 12 bytes B G R B | G R B G | R B G R.
-__device__ __forceinline__ void luma4(u32 r0, u32 r1, u32 r2, u32& y0, u32& y1, u32& y2, u32& y3) {
-  y0 = motion::luma(r0 & 255u, (r0 >> 8) & 255u, (r0 >> 16) & 255u);
-  y1 = motion::luma(r0 >> 24, r1 & 255u, (r1 >> 8) & 255u);
-  y2 = motion::luma((r1 >> 16) & 255u, r1 >> 24, r2 & 255u);
-  y3 = motion::luma((r2 >> 8) & 255u, (r2 >> 16) & 255u, r2 >> 24);
-}
+constexpr u32 kMaxCells = cells::kChunkPix / u32(motion::kMinCell);  // cells of a chunk
+// Every cell in 4..256: a chunk has at most kMaxCells cells, a pass of one row has at most
+// kThreads * kMaxItems groups, and a row of the widest chunk fits the staging buffer.
+static_assert(cells::chunks_fit(u32(motion::kMinCell), u32(motion::kMaxCell), kMaxCells, kThreads * kMaxItems, 1),
+              "chunk geometry");
 
 __global__ __launch_bounds__(kThreads) void motion_kernel(const MotionDesc* __restrict__ descs) {
   __shared__ __attribute__((aligned(16))) u8 lds[kLdsBytes + 16];  // (+ 16: the groups' dword reads)
@@ -142,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void motion_kernel(const MotionDesc* __re
   const u32 y0 = gy * cell, y1 = min(h, y0 + cell);      // and rows
   const u32 cw = x1 - x0, nbytes = cw * 3;
   const u32 gpr = (cw + 7) >> 3;                         // 8-pixel groups per row
-  const u32 rowcap = (nbytes + 15 + 15) & ~15u;
+  const u32 rowcap = stage::rowcap_of(cw);
   const u32 rpp = min(kLdsBytes / rowcap, kThreads * kMaxItems / gpr);  // rows per pass, >= 1 (chunks_fit)
   const u32 ncell = (cw + cell - 1) / cell;
   const u32 t = threadIdx.x;
@@ -151,7 +68,7 @@ __global__ __launch_bounds__(kThreads) void motion_kernel(const MotionDesc* __re
   for (u32 rb = y0; rb < y1; rb += rpp) {
     const u32 nr = min(rpp, y1 - rb);
     const u32 total = nr * gpr;
-    stage_rows(src, src_pitch, rb, nr, x0, nbytes, rowcap, lds);
+    stage::stage_rows(src, src_pitch, rb, nr, x0, nbytes, rowcap, lds);
     uint4 b[kMaxItems];
 #pragma unroll
     for (u32 k = 0; k < kMaxItems; ++k) {
@@ -172,26 +89,8 @@ __global__ __launch_bounds__(kThreads) void motion_kernel(const MotionDesc* __re
       const u32 px = x0 + g * 8, n = min(8u, x1 - px);
       const VEP_DEV u8* grow = src + u64(rb + rr) * src_pitch + u64(x0) * 3;
       const u32 off = rr * rowcap + (u32(reinterpret_cast<uintptr_t>(grow)) & 15u) + g * 24;
-      u32 y[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (n == 8) {
-        // 24 bytes out of seven aligned LDS dwords, realigned. The last dword may lie up to 4
-        // bytes past the row: inside the buffer's padding.
-        const u32 sh = off & 3u;
-        const u32* q = reinterpret_cast<const u32*>(lds + (off & ~3u));
-        const u32 d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4], d5 = q[5], d6 = q[6];
-        luma4(__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
-              __builtin_amdgcn_alignbyte(d3, d2, sh), y[0], y[1], y[2], y[3]);
-        luma4(__builtin_amdgcn_alignbyte(d4, d3, sh), __builtin_amdgcn_alignbyte(d5, d4, sh),
-              __builtin_amdgcn_alignbyte(d6, d5, sh), y[4], y[5], y[6], y[7]);
-      } else {
-        // the partial group at the picture's right edge: only its own bytes
-#pragma unroll
-        for (u32 i = 0; i < 8; ++i)
-          if (i < n) {
-            const u8* p = lds + off + i * 3;
-            y[i] = motion::luma(p[0], p[1], p[2]);
-          }
-      }
+      u32 y[8];
+      cells::lumas<false>(lds, off, n, y);
       const u32 bw[4] = {b[k].x, b[k].y, b[k].z, b[k].w};
       u32 o[8];
       u32 ci = (px - x0) / cell, rem = (px - x0) - ci * cell, run = 0;

@@ -7,9 +7,8 @@
 //  * binning: overlay::kMaxPrims equals the thread count, so thread p tests primitive p's
 //    rectangle against the tile; four wave ballots give the 256-bit set of the tile in LDS. An
 //    empty set ends the workgroup at once when the picture is drawn in place;
-//  * the tile's bytes are staged in LDS (gpu_stage.h: 16-byte loads from aligned addresses, byte
-//    heads and tails, nothing outside the tile's own bytes is read), and, when a TEXT is in the
-//    set, the font and the picture's text pool beside them;
+//  * the tile's bytes are staged in LDS (stage::stage_rows: nothing outside the tile's own bytes
+//    is read), and, when a TEXT is in the set, the font and the picture's text pool beside them;
 //  * a wave owns every fourth row of the tile, a lane one column, so a thread holds four pixels
 //    in registers. The workgroup walks the set bits in ascending order; the loop is uniform (the
 //    set goes through readfirstlane), so a primitive's 16 bytes are one wave-uniform load. Each
@@ -17,7 +16,8 @@
 //    read once and written once, however many primitives cover it, and the list order is the
 //    loop order: no second launch, unlike the mask kernel's levels;
 //  * the pixels go back to LDS at their DESTINATION address modulo 16 and out with
-//    stage::store_rows: 16-byte stores to aligned addresses, heads and tails byte by byte.
+//    stage::store_rows. The tile's geometry, the staging and the store live in gpu_stage.h, which
+//    the crop kernel (gpu_crop.hip) shares.
 // A tile's bytes are read and written by its workgroup alone, so drawing in place is race-free.
 // No byte outside the picture's rows is read, none outside a tile is written by that tile.
 //
@@ -34,19 +34,17 @@ namespace vep::gpu {
 
 namespace {
 
-constexpr u32 kThreads = stage::kThreads;
+using stage::kThreads;
 static_assert(kThreads == u32(overlay::kMaxPrims), "thread p bins primitive p");
-constexpr u32 kTileW = 64;                 // a wave spans a tile's row
-constexpr u32 kWaves = kThreads / kTileW;  // 4
-constexpr u32 kRows = 4;                   // pixels of one thread
-constexpr u32 kTileH = kWaves * kRows;     // 16
-constexpr u32 kRowCap = kTileW * 3 + 16;   // a tile row in LDS: its bytes + up to 15 of misalignment
-static_assert(kRowCap % 16 == 0, "tile rows keep their alignment");
-static_assert(kTileH * ((kTileW * 3 >> 4) + 1) <= kThreads, "one 16-byte vector of the tile per thread");
+// the tile (gpu_stage.h, which the crop kernel shares)
+using stage::kRows;
+using stage::kTileH;
+using stage::kTileW;
+using stage::kWaves;
+using stage::tiles_of;
+using stage::tiles_x;
+constexpr u32 kRowCap = stage::kTileRowCap;
 constexpr u32 kFontLds = (u32(overlay::kFontBytes) + 15u) & ~15u;
-
-__host__ __device__ inline u32 tiles_x(u32 w) { return (w + kTileW - 1) / kTileW; }
-__host__ __device__ inline u32 tiles_of(u32 w, u32 h) { return tiles_x(w) * ((h + kTileH - 1) / kTileH); }
 
 __device__ __forceinline__ overlay::Prim unpack(const uint4& r) {
   overlay::Prim p;

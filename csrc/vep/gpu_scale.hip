@@ -7,16 +7,14 @@
 //
 // A picture block owns one output row and a chunk of at most 256 output columns, one thread per
 // output pixel. The source is a pure streaming read (1080p -> 320x180: 36 source pixels per
-// output pixel), and packed BGR rows start at any byte address, so the block stages the source
-// rows of its footprint in LDS with 16-byte loads from 16-byte aligned addresses, the unaligned
-// head and tail of every row byte by byte, several rows per barrier when they fit. A byte keeps
-// its address modulo 16 in LDS, so the LDS stores are aligned too. Each thread then reduces its
-// pixel's footprint horizontally out of LDS (wx weights: ow for every sample but the two at the
-// ends, so the inner loop only adds; sum <= 255 * sw: 32 bits) and
-// accumulates the rows vertically in registers (wy weights), in 32 bits while 255 * sw * sh fits
-// and in 64 bits above (scale::narrow). A footprint wider than the LDS buffer is staged in
-// segments of kSegPix pixels, one row at a time. The staging and the four-samples-at-a-time sum
-// live in gpu_stage.h, which the crop kernel (gpu_crop.hip) shares.
+// output pixel), so the block stages the source rows of its footprint in LDS (stage::stage_rows),
+// several rows per barrier when they fit. Each thread then reduces its pixel's footprint
+// horizontally out of LDS (stage::sum_weighted with the wx weights: ow for every sample but the
+// two at the ends, so the inner loop only adds; sum <= 255 * sw: 32 bits) and accumulates the rows
+// vertically in registers (wy weights), in 32 bits while 255 * sw * sh fits and in 64 bits above
+// (scale::narrow). A footprint wider than the LDS buffer is staged in segments of kSegPix pixels,
+// one row at a time. The staging, the buffer's size and the weighted sum live in gpu_stage.h,
+// which the crop kernel (gpu_crop.hip) shares.
 //
 // Every store is checked against the tile's cell (or the picture's own rectangle when the tile
 // has no cell); check_scale() proves on the host that those lie inside the canvas.
@@ -31,11 +29,9 @@ namespace vep::gpu {
 
 namespace {
 
-constexpr u32 kThreads = stage::kThreads;
-constexpr u32 kLdsBytes = 24576;
-// pixels of one staged segment: 3 bytes each + up to 15 bytes of misalignment fit the buffer
-constexpr u32 kSegPix = (kLdsBytes - 16) / 3;
-static_assert(kSegPix * 3 + 15 <= kLdsBytes, "segment fits LDS");
+using stage::kLdsBytes;
+using stage::kSegPix;
+using stage::kThreads;
 
 __device__ __forceinline__ u32 chunks_of(u32 ow) { return (ow + kThreads - 1) / kThreads; }
 
@@ -49,7 +45,7 @@ __device__ __forceinline__ void scale_block(const ScaleDesc& d, u32 k, u32 j0, u
   const u32 r0 = scale::span_lo(k, sh, oh), r1 = scale::span_hi(k, sh, oh);
   const u32 npix = ib - ia + 1;
   const bool fits = npix <= kSegPix;
-  const u32 rowcap = fits ? ((npix * 3 + 15 + 15) & ~15u) : kLdsBytes;
+  const u32 rowcap = fits ? stage::rowcap_of(npix) : kLdsBytes;
   const u32 rpp = fits ? kLdsBytes / rowcap : 1;  // rows staged per barrier
   const u32 j = j0 + threadIdx.x;
   const bool active = j < j1;
@@ -71,29 +67,10 @@ __device__ __forceinline__ void scale_block(const ScaleDesc& d, u32 k, u32 j0, u
       stage::stage_rows(src, src_pitch, rb, nr, is, (ie - is) * 3, rowcap, lds);
       __syncthreads();
       if (active) {
-        const u32 a = max(lo + 1, is), b = min(hi, ie);  // whole samples [a, b) of this segment
-        const bool has_lo = lo >= is && lo < ie, has_hi = hi != lo && hi >= is && hi < ie;
         for (u32 rr = 0; rr < nr; ++rr) {
           const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
           const u32 row_off = rr * rowcap + (u32(reinterpret_cast<uintptr_t>(g)) & 15u);
-          const u8* l = lds + row_off;
-          u32 s0 = 0, s1 = 0, s2 = 0;
-          if (a < b) stage::sum_samples(lds, row_off + (a - is) * 3, b - a, s0, s1, s2);
-          h0 += ow * s0;
-          h1 += ow * s1;
-          h2 += ow * s2;
-          if (has_lo) {
-            const u8* p = l + (lo - is) * 3;
-            h0 += w_lo * p[0];
-            h1 += w_lo * p[1];
-            h2 += w_lo * p[2];
-          }
-          if (has_hi) {
-            const u8* p = l + (hi - is) * 3;
-            h0 += w_hi * p[0];
-            h1 += w_hi * p[1];
-            h2 += w_hi * p[2];
-          }
+          stage::sum_weighted(lds, row_off, is, ie, lo, hi, w_lo, ow, w_hi, h0, h1, h2);
           if (ie == ib + 1) {  // the row is complete
             const Acc wy = scale::weight(k, rb + rr, sh, oh);
             a0 += wy * h0;
@@ -109,22 +86,11 @@ __device__ __forceinline__ void scale_block(const ScaleDesc& d, u32 k, u32 j0, u
   if (!active) return;
   const i32 x = d.dx + i32(j), y = d.dy + i32(k);
   if (d.cw > 0 && d.ch > 0 && (x < d.cx || x >= d.cx + d.cw || y < d.cy || y >= d.cy + d.ch)) return;
-  u32 o0, o1, o2;
-  if constexpr (sizeof(Acc) == 4) {
-    const u32 den = sw * sh;
-    o0 = scale::round_div32(a0, den);
-    o1 = scale::round_div32(a1, den);
-    o2 = scale::round_div32(a2, den);
-  } else {
-    const u64 den = u64(sw) * sh;
-    o0 = scale::round_div64(a0, den);
-    o1 = scale::round_div64(a1, den);
-    o2 = scale::round_div64(a2, den);
-  }
+  const Acc den = Acc(sw) * sh;
   VEP_DEV u8* q = d.dst + u64(y) * d.dst_pitch + u64(x) * 3;
-  q[0] = u8(o0);
-  q[1] = u8(o1);
-  q[2] = u8(o2);
+  q[0] = u8(scale::round_div(a0, den));
+  q[1] = u8(scale::round_div(a1, den));
+  q[2] = u8(scale::round_div(a2, den));
 }
 
 __global__ __launch_bounds__(kThreads) void scale_kernel(const ScaleDesc* __restrict__ descs, u32 fill_base) {

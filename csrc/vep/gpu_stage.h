@@ -1,12 +1,13 @@
-// Staging rows of a packed BGR24 picture in LDS, summing samples out of them and storing rows
-// back: the part the scale kernel (gpu_scale.hip), the crop kernel (gpu_crop.hip) and the overlay
-// kernel (gpu_overlay.hip) share. Kernel sources only
+// What the kernels on packed BGR24 pictures share: staging rows in LDS, storing rows back out of
+// it, the split of a row into aligned vectors and byte ends that both rest on (the mask kernel,
+// gpu_mask.hip, uses the split alone), the weighted sum of a staged row segment (scale and crop
+// kernels) and the 64 x 16 tile of the crop and overlay kernels. Kernel sources only
 // (VEP_KERNEL_SOURCE, 256 threads a workgroup).
 //
 // Packed BGR rows start at any byte address, so a row segment is staged with 16-byte loads from
 // 16-byte aligned addresses and its unaligned head and tail byte by byte; nothing outside the
 // segment's own bytes is read. A byte keeps its address modulo 16 in LDS, so the LDS stores are
-// aligned too.
+// aligned too. Rows go out the same way: no byte outside a row's own bytes is written.
 #pragma once
 
 #include "gpu.h"
@@ -14,6 +15,47 @@
 namespace vep::gpu::stage {
 
 constexpr u32 kThreads = 256;
+constexpr u32 kLdsBytes = 24576;  // the staging buffer (kernels declare 16 more: the dword reads below)
+// pixels of one staged segment: 3 bytes each + up to 15 bytes of misalignment fit the buffer
+constexpr u32 kSegPix = (kLdsBytes - 16) / 3;
+static_assert(kSegPix * 3 + 15 <= kLdsBytes, "segment fits LDS");
+// bytes between staged rows of npix pixels: a row + up to 15 bytes of misalignment, 16-byte aligned
+__host__ __device__ constexpr u32 rowcap_of(u32 npix) { return (npix * 3 + 15 + 15) & ~15u; }
+
+// The tile of the crop and overlay kernels: a wave owns every fourth row of it, a lane one column.
+constexpr u32 kTileW = 64;                   // a wave spans a tile's row
+constexpr u32 kWaves = kThreads / kTileW;    // 4
+constexpr u32 kRows = 4;                     // pixels of one thread
+constexpr u32 kTileH = kWaves * kRows;       // 16
+constexpr u32 kTileRowCap = kTileW * 3 + 16; // a tile row in LDS: its bytes + up to 15 of misalignment
+static_assert(kTileRowCap % 16 == 0, "tile rows keep their alignment");
+static_assert(kTileH * ((kTileW * 3 >> 4) + 1) <= kThreads, "one 16-byte vector of the tile per thread");
+__host__ __device__ inline u32 tiles_x(u32 w) { return (w + kTileW - 1) / kTileW; }
+__host__ __device__ inline u32 tiles_of(u32 w, u32 h) { return tiles_x(w) * ((h + kTileH - 1) / kTileH); }
+
+// A row of nbytes bytes at g: `head` bytes up to the first 16-byte aligned address, then nvec
+// whole 16-byte vectors, then a tail of fewer than 16 bytes. mis is g modulo 16.
+struct RowSplit {
+  u32 mis, head, nvec;
+};
+__device__ __forceinline__ RowSplit split_row(const VEP_DEV u8* g, u32 nbytes) {
+  const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
+  const u32 head = min(nbytes, (16u - mis) & 15u);
+  return {mis, head, (nbytes - head) >> 4};
+}
+// The row's bytes that no vector covers, by slot: slots 0..15 are the head's, 16..31 the tail's.
+// -> false: the slot is empty; o: the byte's offset in the row.
+__device__ __forceinline__ bool edge_byte(const RowSplit& r, u32 nbytes, u32 slot, u32& o) {
+  const u32 body = r.nvec << 4;
+  if (slot < 16) {
+    if (slot >= r.head) return false;
+    o = slot;
+  } else {
+    if (slot - 16 >= nbytes - r.head - body) return false;
+    o = r.head + body + (slot - 16);
+  }
+  return true;
+}
 
 // Rows rb .. rb + nr of the source, pixels [is, is + nbytes / 3), into LDS: row rr at
 // rr * rowcap + (its address modulo 16).
@@ -26,31 +68,21 @@ __device__ __forceinline__ void stage_rows(const VEP_DEV u8* src, u32 src_pitch,
   // latency: the thread's head / tail byte, then up to six vectors (1080p -> 320x180 stages its
   // six rows of 2.9 KB in one pass).
   auto edge = [&](u32 rr, u8& x) -> u32 {  // a byte of row rr's unaligned head or tail
-    const u32 slot = t & 31u;
     const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
-    const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    const u32 body = ((nbytes - head) >> 4) << 4;
+    const RowSplit r = split_row(g, nbytes);
     u32 o;
-    if (slot < 16) {
-      if (slot >= head) return ~0u;
-      o = slot;
-    } else {
-      if (slot - 16 >= nbytes - head - body) return ~0u;
-      o = head + body + (slot - 16);
-    }
+    if (!edge_byte(r, nbytes, t & 31u, o)) return ~0u;
     x = g[o];
-    return rr * rowcap + mis + o;
+    return rr * rowcap + r.mis + o;
   };
   auto fetch = [&](u32 item, uint4& x) -> u32 {  // -> LDS offset, ~0u: no vector
     if (item >= total) return ~0u;
     const u32 rr = item / vpr, v = item - rr * vpr;
     const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
-    const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    if (v >= ((nbytes - head) >> 4)) return ~0u;
-    x = *reinterpret_cast<const VEP_DEV uint4*>(g + head + v * 16);
-    return rr * rowcap + mis + head + v * 16;
+    const RowSplit r = split_row(g, nbytes);
+    if (v >= r.nvec) return ~0u;
+    x = *reinterpret_cast<const VEP_DEV uint4*>(g + r.head + v * 16);
+    return rr * rowcap + r.mis + r.head + v * 16;
   };
   u8 e = 0;
   const u32 e_at = (t >> 5) < nr ? edge(t >> 5, e) : ~0u;  // 32 byte slots per row, 8 rows per step
@@ -74,37 +106,25 @@ __device__ __forceinline__ void stage_rows(const VEP_DEV u8* src, u32 src_pitch,
 }
 
 // The other direction: nrow rows of nbytes bytes out of LDS (row rr at rr * rowcap + (its global
-// address modulo 16), as stage_rows leaves them) to dst + rr * pitch. 16-byte stores to 16-byte
-// aligned addresses, a row's unaligned head and tail byte by byte: no byte outside the rows' own
-// bytes is written. One vector per thread: nrow * ((nbytes >> 4) + 1) <= kThreads.
+// address modulo 16), as stage_rows leaves them) to dst + rr * pitch. One vector per thread:
+// nrow * ((nbytes >> 4) + 1) <= kThreads.
 __device__ __forceinline__ void store_rows(VEP_DEV u8* dst, u32 pitch, u32 nrow, u32 nbytes, u32 rowcap, const u8* lds) {
   const u32 t = threadIdx.x;
   const u32 vpr = (nbytes >> 4) + 1;  // upper bound of a row's 16-byte vectors
   if (t < nrow * vpr) {
     const u32 rr = t / vpr, v = t - rr * vpr;
     VEP_DEV u8* gp = dst + u64(rr) * pitch;
-    const u32 mis = u32(reinterpret_cast<uintptr_t>(gp)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    if (v < ((nbytes - head) >> 4)) {
-      const u32 o = head + v * 16;  // o + 16 <= nbytes
-      *reinterpret_cast<VEP_DEV uint4*>(gp + o) = *reinterpret_cast<const uint4*>(lds + rr * rowcap + mis + o);
+    const RowSplit r = split_row(gp, nbytes);
+    if (v < r.nvec) {
+      const u32 o = r.head + v * 16;  // o + 16 <= nbytes
+      *reinterpret_cast<VEP_DEV uint4*>(gp + o) = *reinterpret_cast<const uint4*>(lds + rr * rowcap + r.mis + o);
     }
   }
   for (u32 rr = t >> 5; rr < nrow; rr += kThreads / 32) {  // 32 byte slots per row, 8 rows per step
-    const u32 slot = t & 31u;
     VEP_DEV u8* gp = dst + u64(rr) * pitch;
-    const u32 mis = u32(reinterpret_cast<uintptr_t>(gp)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    const u32 body = ((nbytes - head) >> 4) << 4;
+    const RowSplit r = split_row(gp, nbytes);
     u32 o;
-    if (slot < 16) {
-      if (slot >= head) continue;
-      o = slot;
-    } else {
-      if (slot - 16 >= nbytes - head - body) continue;
-      o = head + body + (slot - 16);
-    }
-    gp[o] = lds[rr * rowcap + mis + o];
+    if (edge_byte(r, nbytes, t & 31u, o)) gp[o] = lds[rr * rowcap + r.mis + o];
   }
 }
 
@@ -133,6 +153,32 @@ __device__ __forceinline__ void sum_samples(const u8* lds, u32 off, u32 n, u32& 
     s0 += p[0];
     s1 += p[1];
     s2 += p[2];
+  }
+}
+
+// h0 / h1 / h2 += the weighted B / G / R sum of a row's samples lo .. hi, as far as they lie in
+// the staged segment [is, ie) whose first byte is at row_off of the LDS buffer: w_lo times sample
+// lo, w_mid times every sample between the two ends, w_hi times sample hi (where hi != lo). Only
+// the ends weigh differently, so the inner run only adds.
+__device__ __forceinline__ void sum_weighted(const u8* lds, u32 row_off, u32 is, u32 ie, u32 lo, u32 hi, u32 w_lo,
+                                             u32 w_mid, u32 w_hi, u32& h0, u32& h1, u32& h2) {
+  const u32 a = max(lo + 1, is), b = min(hi, ie);  // inner samples [a, b) of this segment
+  u32 s0 = 0, s1 = 0, s2 = 0;
+  if (a < b) sum_samples(lds, row_off + (a - is) * 3, b - a, s0, s1, s2);
+  h0 += w_mid * s0;
+  h1 += w_mid * s1;
+  h2 += w_mid * s2;
+  if (lo >= is && lo < ie) {
+    const u8* p = lds + row_off + (lo - is) * 3;
+    h0 += w_lo * p[0];
+    h1 += w_lo * p[1];
+    h2 += w_lo * p[2];
+  }
+  if (hi != lo && hi >= is && hi < ie) {
+    const u8* p = lds + row_off + (hi - is) * 3;
+    h0 += w_hi * p[0];
+    h1 += w_hi * p[1];
+    h2 += w_hi * p[2];
   }
 }
 

@@ -7,9 +7,9 @@
 // A block owns whole cells, as in the motion kernel: one row of the cell grid (`cell` pixel rows)
 // and a chunk of its columns, a multiple of lcm(cell, 8) pixels wide, so a chunk starts at a cell
 // boundary. No pixel pair of the energy crosses a cell boundary, so a block needs nothing from
-// another block's cells. The block stages the source rows of a pass in LDS with 16-byte loads from
-// 16-byte aligned addresses, the unaligned head and tail of every row byte by byte; a byte keeps
-// its address modulo 16 in LDS (the motion kernel's staging).
+// another block's cells. The block stages the source rows of a pass in LDS (stage::stage_rows,
+// gpu_stage.h: a byte keeps its address modulo 16). The chunk geometry and the lumas of 8 pixels
+// out of the staged rows are the motion kernel's too and live in gpu_cells.h.
 //
 // A thread owns one column of 8 pixels of the chunk for the block's whole life, and in every pass
 // a segment of the pass's rows, which it walks downwards: it computes the 8 lumas of a row and the
@@ -39,135 +39,21 @@
 #include <algorithm>
 
 #include "gpu.h"
+#include "gpu_cells.h"
 #include "tamper.h"
 
 namespace vep::gpu {
 
 namespace {
 
-constexpr u32 kThreads = 256;
-constexpr u32 kLdsBytes = 24576;  // staged source rows
-constexpr u32 kChunkPix = 512;    // a chunk is at most this wide, or one lcm(cell, 8) where that is wider
-constexpr u32 kMaxCells = kChunkPix / u32(tamper::kMinCell);  // cells of a chunk
-
-// Pixels of a chunk: the largest multiple of lcm(cell, 8) that is <= kChunkPix, at least one.
-__host__ __device__ inline u32 chunk_of(u32 cell) {
-  const u32 low = cell & (0u - cell);
-  const u32 unit = cell / (low < 8u ? low : 8u) * 8u;  // lcm(cell, 8) <= 1016
-  return unit >= kChunkPix ? unit : kChunkPix / unit * unit;
-}
-// bytes between staged rows of cw pixels
-__host__ __device__ constexpr u32 rowcap_of(u32 cw) { return (cw * 3 + 15 + 15) & ~15u; }
+using cells::chunk_of;
+using stage::kLdsBytes;
+using stage::kThreads;
+constexpr u32 kMaxCells = cells::kChunkPix / u32(tamper::kMinCell);  // cells of a chunk
 // Every cell in 8..128: a chunk has at most kMaxCells cells and at most kThreads columns of 8
 // pixels, and at least two rows of the widest chunk fit the staging buffer (a pass that is not
 // the last owns one row less than it stages).
-constexpr bool chunks_fit() {
-  for (u32 cell = u32(tamper::kMinCell); cell <= u32(tamper::kMaxCell); ++cell) {
-    const u32 low = cell & (0u - cell);
-    const u32 unit = cell / (low < 8u ? low : 8u) * 8u;
-    const u32 chunk = unit >= kChunkPix ? unit : kChunkPix / unit * unit;
-    if (chunk % cell || chunk % 8u) return false;
-    if (chunk / cell > kMaxCells) return false;
-    if (chunk / 8u > kThreads) return false;
-    if (kLdsBytes / rowcap_of(chunk) < 2) return false;
-  }
-  return true;
-}
-static_assert(chunks_fit(), "chunk geometry");
-
-// Rows rb .. rb + nr of the source, pixels from `is` on (nbytes bytes), into LDS: row rr at
-// rr * rowcap + (its address modulo 16).
-__device__ __forceinline__ void stage_rows(const VEP_DEV u8* src, u32 src_pitch, u32 rb, u32 nr, u32 is,
-                                           u32 nbytes, u32 rowcap, u8* lds) {
-  const u32 t = threadIdx.x;
-  const u32 vpr = (nbytes >> 4) + 1;  // upper bound of a row's 16-byte vectors
-  const u32 total = nr * vpr;
-  // Every load of a step is issued before the first LDS store, so a step costs one memory
-  // latency: the thread's head / tail byte, then up to six vectors.
-  auto edge = [&](u32 rr, u8& x) -> u32 {  // a byte of row rr's unaligned head or tail
-    const u32 slot = t & 31u;
-    const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
-    const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    const u32 body = ((nbytes - head) >> 4) << 4;
-    u32 o;
-    if (slot < 16) {
-      if (slot >= head) return ~0u;
-      o = slot;
-    } else {
-      if (slot - 16 >= nbytes - head - body) return ~0u;
-      o = head + body + (slot - 16);
-    }
-    x = g[o];
-    return rr * rowcap + mis + o;
-  };
-  auto fetch = [&](u32 item, uint4& x) -> u32 {  // -> LDS offset, ~0u: no vector
-    if (item >= total) return ~0u;
-    const u32 rr = item / vpr, v = item - rr * vpr;
-    const VEP_DEV u8* g = src + u64(rb + rr) * src_pitch + u64(is) * 3;
-    const u32 mis = u32(reinterpret_cast<uintptr_t>(g)) & 15u;
-    const u32 head = min(nbytes, (16u - mis) & 15u);
-    if (v >= ((nbytes - head) >> 4)) return ~0u;
-    x = *reinterpret_cast<const VEP_DEV uint4*>(g + head + v * 16);
-    return rr * rowcap + mis + head + v * 16;
-  };
-  u8 e = 0;
-  const u32 e_at = (t >> 5) < nr ? edge(t >> 5, e) : ~0u;  // 32 byte slots per row, 8 rows per step
-  for (u32 base = t; base < total; base += kThreads * 6) {
-    uint4 x0 = {}, x1 = {}, x2 = {}, x3 = {}, x4 = {}, x5 = {};
-    const u32 at0 = fetch(base, x0), at1 = fetch(base + kThreads, x1), at2 = fetch(base + 2 * kThreads, x2),
-              at3 = fetch(base + 3 * kThreads, x3), at4 = fetch(base + 4 * kThreads, x4),
-              at5 = fetch(base + 5 * kThreads, x5);
-    if (at0 != ~0u) *reinterpret_cast<uint4*>(lds + at0) = x0;
-    if (at1 != ~0u) *reinterpret_cast<uint4*>(lds + at1) = x1;
-    if (at2 != ~0u) *reinterpret_cast<uint4*>(lds + at2) = x2;
-    if (at3 != ~0u) *reinterpret_cast<uint4*>(lds + at3) = x3;
-    if (at4 != ~0u) *reinterpret_cast<uint4*>(lds + at4) = x4;
-    if (at5 != ~0u) *reinterpret_cast<uint4*>(lds + at5) = x5;
-  }
-  if (e_at != ~0u) lds[e_at] = e;
-  for (u32 rr = (t >> 5) + kThreads / 32; rr < nr; rr += kThreads / 32) {
-    const u32 at = edge(rr, e);
-    if (at != ~0u) lds[at] = e;
-  }
-}
-
-// Lumas of four pixels out of their 12 bytes B G R B | G R B G | R B G R.
-__device__ __forceinline__ void luma4(u32 r0, u32 r1, u32 r2, u32& y0, u32& y1, u32& y2, u32& y3) {
-  y0 = motion::luma(r0 & 255u, (r0 >> 8) & 255u, (r0 >> 16) & 255u);
-  y1 = motion::luma(r0 >> 24, r1 & 255u, (r1 >> 8) & 255u);
-  y2 = motion::luma((r1 >> 16) & 255u, r1 >> 24, r2 & 255u);
-  y3 = motion::luma((r2 >> 8) & 255u, (r2 >> 16) & 255u, r2 >> 24);
-}
-
-// The lumas of the n pixels of a column at LDS offset `off`, and in y[8] the next pixel's (only
-// meaningful where that pixel belongs to the block: the caller masks it). Pixels past n are 0.
-__device__ __forceinline__ void lumas9(const u8* lds, u32 off, u32 n, u32 (&y)[9]) {
-  if (n == 8) {
-    // 27 bytes out of eight aligned LDS dwords, realigned. The last dwords may lie up to 8 bytes
-    // past the row: inside the buffer's padding.
-    const u32 sh = off & 3u;
-    const u32* q = reinterpret_cast<const u32*>(lds + (off & ~3u));
-    const u32 d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4], d5 = q[5], d6 = q[6], d7 = q[7];
-    luma4(__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
-          __builtin_amdgcn_alignbyte(d3, d2, sh), y[0], y[1], y[2], y[3]);
-    luma4(__builtin_amdgcn_alignbyte(d4, d3, sh), __builtin_amdgcn_alignbyte(d5, d4, sh),
-          __builtin_amdgcn_alignbyte(d6, d5, sh), y[4], y[5], y[6], y[7]);
-    const u32 r = __builtin_amdgcn_alignbyte(d7, d6, sh);
-    y[8] = motion::luma(r & 255u, (r >> 8) & 255u, (r >> 16) & 255u);
-  } else {
-    // the partial column at the picture's right edge: only its own bytes
-#pragma unroll
-    for (u32 i = 0; i < 8; ++i) {
-      y[i] = 0;
-      if (i < n) {
-        const u8* p = lds + off + i * 3;
-        y[i] = motion::luma(p[0], p[1], p[2]);
-      }
-    }
-    y[8] = 0;
-  }
-}
+static_assert(cells::chunks_fit(u32(tamper::kMinCell), u32(tamper::kMaxCell), kMaxCells, kThreads, 2), "chunk geometry");
 
 __global__ __launch_bounds__(kThreads) void tamper_kernel(const TamperDesc* __restrict__ descs) {
   __shared__ __attribute__((aligned(16))) u8 lds[kLdsBytes + 16];  // (+ 16: the columns' dword reads)
@@ -187,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void tamper_kernel(const TamperDesc* __re
   const u32 y0 = gy * cell, y1 = min(h, y0 + cell);   // and rows
   const u32 cw = x1 - x0, nbytes = cw * 3;
   const u32 gpr = (cw + 7) >> 3;                      // columns of 8 pixels, <= kThreads (chunks_fit)
-  const u32 rowcap = rowcap_of(cw);
+  const u32 rowcap = stage::rowcap_of(cw);
   const u32 rpp = kLdsBytes / rowcap;                 // rows staged per pass, >= 2 (chunks_fit)
   const u32 ncell = (cw + cell - 1) / cell;
   const u32 t = threadIdx.x;
@@ -214,13 +100,13 @@ __global__ __launch_bounds__(kThreads) void tamper_kernel(const TamperDesc* __re
   for (u32 rb = y0; rb < y1;) {
     const u32 ns = min(rpp, y1 - rb);            // rows staged
     const u32 nr = rb + ns == y1 ? ns : ns - 1;  // rows owned: the last staged row opens the next pass
-    stage_rows(src, src_pitch, rb, ns, x0, nbytes, rowcap, lds);
+    stage::stage_rows(src, src_pitch, rb, ns, x0, nbytes, rowcap, lds);
     __syncthreads();
     const u32 nseg = min(nseg_max, nr), rps = (nr + nseg - 1) / nseg;
     const u32 r0 = s * rps, r1 = col ? min(r0 + rps, nr) : 0;  // the thread's rows of this pass
     auto lumas = [&](u32 rr, u32 (&y)[9]) {
       const u32 mis = (base_mis + (rb + rr) * src_pitch) & 15u;
-      lumas9(lds, rr * rowcap + mis + g * 24, n, y);
+      cells::lumas<true>(lds, rr * rowcap + mis + g * 24, n, y);
     };
     u32 cur[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (r0 < r1) lumas(r0, cur);

@@ -48,6 +48,9 @@ VEP_SCALE_HD inline uint32_t round_div32(uint32_t sum, uint32_t den) {
   return q + (r + den / 2 >= den ? 1u : 0u);
 }
 VEP_SCALE_HD inline uint32_t round_div64(uint64_t sum, uint64_t den) { return uint32_t((sum + den / 2) / den); }
+// the one that fits the accumulator's type
+VEP_SCALE_HD inline uint32_t round_div(uint32_t sum, uint32_t den) { return round_div32(sum, den); }
+VEP_SCALE_HD inline uint32_t round_div(uint64_t sum, uint64_t den) { return round_div64(sum, den); }
 
 // Fit sw x sh into a box of bw x bh keeping the aspect ratio, never enlarging. A side of the box
 // that is not given counts as kMaxSide.

@@ -603,20 +603,10 @@ struct Worker::MotionOp {
     for (size_t k = 0; k < todo.size(); ++k) {
       Eval& e = *todo[k];
       MotionState& st = e.c->motion;
-      gpu::MotionDesc d{};
-      d.src = e.ring->slot_ptr(e.slot);
-      d.src_pitch = u32(st.w) * 3;
-      d.bg_in = e.primed ? st.bg[st.cur] : nullptr;
-      d.bg_out = st.bg[st.cur ^ 1];
-      d.bg_pitch = motion::pitch_for(u32(st.w));
-      d.counts = set->d_counts.p + e.at;
-      d.w = st.w;
-      d.h = st.h;
-      d.cell = prm.cell;
-      d.threshold = prm.threshold;
-      d.learn_shift = prm.learn_shift;
-      gpu::check_motion(d, e.ring->slot_bytes(), st.samples, e.cells);
-      set->h_descs.p[k] = d;
+      set->h_descs.p[k] = gpu::make_motion_desc(
+          e.ring->slot_ptr(e.slot), e.ring->slot_bytes(), st.w, st.h, e.primed ? st.bg[st.cur] : nullptr,
+          st.bg[st.cur ^ 1], motion::pitch_for(u32(st.w)), st.samples, set->d_counts.p + e.at, e.cells, prm.cell,
+          prm.threshold, prm.learn_shift);
     }
     set->run(int(todo.size()), total_cells, w.serve_stream_);
     VEP_HIP(hipEventSynchronize(set->ev));
@@ -772,17 +762,9 @@ struct Worker::TamperOp {
     set->reserve(int(todo.size()), res_words);
     for (size_t k = 0; k < todo.size(); ++k) {
       Eval& e = *todo[k];
-      gpu::TamperDesc d{};
-      d.src = e.ring->slot_ptr(e.slot);
-      d.src_pitch = u32(e.w) * 3;
-      d.hist = set->d_res.p + e.hist_at;
-      d.sum_y = set->d_res.p + e.grid_at;
-      d.energy = set->d_res.p + e.grid_at + e.cells;
-      d.w = e.w;
-      d.h = e.h;
-      d.cell = prm.cell;
-      gpu::check_tamper(d, e.ring->slot_bytes(), e.cells);
-      set->h_descs.p[k] = d;
+      u32* res = set->d_res.p;
+      set->h_descs.p[k] = gpu::make_tamper_desc(e.ring->slot_ptr(e.slot), e.ring->slot_bytes(), e.w, e.h, res + e.hist_at,
+                                                res + e.grid_at, res + e.grid_at + e.cells, e.cells, prm.cell);
     }
     set->run(int(todo.size()), hist_words, res_words, w.serve_stream_);
     VEP_HIP(hipEventSynchronize(set->ev));

@@ -1,7 +1,23 @@
-// Host side of the GPU tamper detector: the scratch set (kernel: gpu_tamper.hip).
+// Host side of the GPU tamper detector: the descriptor of a picture and the scratch set (kernel:
+// gpu_tamper.hip).
 #include "gpu.h"
 
 namespace vep::gpu {
+
+TamperDesc make_tamper_desc(const u8* src, size_t src_bytes, int w, int h, u32* hist, u32* sum_y, u32* energy,
+                            size_t grid_cells, int cell) {
+  TamperDesc d{};
+  d.src = src;
+  d.src_pitch = u32(w) * 3;
+  d.hist = hist;
+  d.sum_y = sum_y;
+  d.energy = energy;
+  d.w = w;
+  d.h = h;
+  d.cell = cell;
+  check_tamper(d, src_bytes, grid_cells);
+  return d;
+}
 
 void TamperSet::reserve(int ndescs, size_t res_words) {
   reserve_descs(ndescs);

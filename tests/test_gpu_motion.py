@@ -176,6 +176,60 @@ def test_descriptors_grow_past_the_floor_and_come_back():
             same(got[k], want[k], f"batch of {n}, picture {k}")
 
 
+OFFSET_W, OFFSET_H = 37, 9  # rows of 111 bytes: successive rows differ in alignment as well
+OFFSET_GUARD = 0xA5
+_offset_want = {}
+
+
+def offset_case(cell):
+    """Two pictures and the CPU twin's answers, unprimed and primed: computed once per cell."""
+    from video_edge_ai_proxy_amd import ops
+
+    if cell not in _offset_want:
+        a = torch.from_numpy(mo.picture("noise", OFFSET_W, OFFSET_H, 1))
+        b = torch.from_numpy(mo.picture("noise", OFFSET_W, OFFSET_H, 2))
+        want0 = ops.motion_update_reference(a, None, cell, 24, 4)
+        _offset_want[cell] = (a, b, want0, ops.motion_update_reference(b, want0[1], cell, 24, 4))
+    return _offset_want[cell]
+
+
+def view_at(pic, o):
+    """(flat, view): the picture as a contiguous view that starts at byte address o modulo 16 of a
+    flat device tensor, guard bytes all around it."""
+    n = pic.numel()
+    flat = torch.full((n + 48,), OFFSET_GUARD, dtype=torch.uint8, device="cuda")
+    view = flat[16 + o:16 + o + n].view(pic.shape)
+    view.copy_(pic)
+    assert view.is_contiguous() and view.data_ptr() % 16 == o
+    return flat, view
+
+
+def guard_intact(flat, pic, o):
+    got = flat.cpu().numpy()
+    n = pic.numel()
+    assert (got[:16 + o] == OFFSET_GUARD).all() and (got[16 + o + n:] == OFFSET_GUARD).all(), "guard bytes changed"
+    assert np.array_equal(got[16 + o:16 + o + n], pic.numpy().reshape(-1)), "the source changed"
+
+
+@pytest.mark.parametrize("cell", [4, 16])
+@pytest.mark.parametrize("o", range(16))
+def test_source_at_every_byte_offset(o, cell):
+    """The source starts at every address modulo 16 (its staging never had anything but freshly
+    allocated tensors): unprimed and primed, counts and background are the CPU's, and nothing
+    around the source is written."""
+    from video_edge_ai_proxy_amd import ops
+
+    a, b, want0, want1 = offset_case(cell)
+    fa, va = view_at(a, o)
+    fb, vb = view_at(b, o)
+    got0 = ops.motion_update(va, None, cell, 24, 4)
+    same(got0, want0, f"offset {o} prime")
+    same(ops.motion_update(vb, got0[1], cell, 24, 4), want1, f"offset {o} primed")
+    assert int(want1[0].sum()) > 0
+    guard_intact(fa, a, o)
+    guard_intact(fb, b, o)
+
+
 def test_argument_checks():
     from video_edge_ai_proxy_amd import ops
 

@@ -66,6 +66,41 @@ def test_odd_cells_and_wide_chunks(w, h, cell):
         same(ops.tamper_stats(p.cuda(), cell), ops.tamper_stats_reference(p, cell), f"{kind} {w}x{h}/{cell}")
 
 
+OFFSET_W, OFFSET_H, OFFSET_CELL = 37, 9, 8  # rows of 111 bytes: successive rows differ in alignment as well
+OFFSET_GUARD = 0xA5
+_offset_want = []
+
+
+def offset_case():
+    """The picture and the CPU twin's answer: computed once."""
+    from video_edge_ai_proxy_amd import ops
+
+    if not _offset_want:
+        p = torch.from_numpy(to.picture("noise", OFFSET_W, OFFSET_H, 1))
+        _offset_want.append((p, ops.tamper_stats_reference(p, OFFSET_CELL)))
+    return _offset_want[0]
+
+
+@pytest.mark.parametrize("o", range(16))
+def test_source_at_every_byte_offset(o):
+    """The source is a contiguous view that starts at every address modulo 16 of a flat tensor (its
+    staging never had anything but freshly allocated tensors): all three results are the CPU's,
+    and the guard bytes around the source keep their value."""
+    from video_edge_ai_proxy_amd import ops
+
+    p, want = offset_case()
+    n = p.numel()
+    flat = torch.full((n + 48,), OFFSET_GUARD, dtype=torch.uint8, device="cuda")
+    view = flat[16 + o:16 + o + n].view(p.shape)
+    view.copy_(p)
+    assert view.is_contiguous() and view.data_ptr() % 16 == o
+    same(ops.tamper_stats(view, OFFSET_CELL), want, f"offset {o}")
+    assert int(want[0].sum()) == OFFSET_W * OFFSET_H
+    got = flat.cpu().numpy()
+    assert (got[:16 + o] == OFFSET_GUARD).all() and (got[16 + o + n:] == OFFSET_GUARD).all(), "guard bytes changed"
+    assert np.array_equal(got[16 + o:16 + o + n], p.numpy().reshape(-1)), "the source changed"
+
+
 def test_batch_mixed_sizes():
     """Five pictures of three sizes in one launch, one of them a single cell."""
     from video_edge_ai_proxy_amd import ops
