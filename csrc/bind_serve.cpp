@@ -454,6 +454,37 @@ void bind_worker_serving(py::class_<Worker>& cls) {
       .def("register_host",
            [](Worker& w, uintptr_t addr, size_t n) { return w.register_host(reinterpret_cast<void*>(addr), n); })
       .def("unregister_host", [](Worker& w, uintptr_t addr) { w.unregister_host(reinterpret_cast<void*>(addr)); })
+      .def("read_latest_many_into",
+           // Several cameras' newest frames (raw pixels) into caller memory by one batched read
+           // (Worker::read_latest_many, as the frame bus pump): a list of (idx, after, addr, cap,
+           // pinned) gives a list of (seq, meta), None where there is no newer frame. pinned: the
+           // range is page-locked (allocated so, or register_host()ed).
+           [](Worker& w, const std::vector<std::tuple<int, i64, uintptr_t, size_t, bool>>& items) {
+             std::vector<std::shared_ptr<Camera>> keep;
+             std::vector<std::shared_ptr<FrameRing>> rings;
+             std::vector<Worker::ReadReq> reqs;
+             for (const auto& [i, after, addr, cap, pinned] : items) {
+               keep.push_back(cam_ref(w, i));
+               rings.push_back(keep.back()->ring());
+               VEP_CHECK(rings.back() && addr, "read_latest_many_into: no ring or no destination");
+               VEP_CHECK(cap >= rings.back()->slot_bytes(), "read_latest_many_into: destination too small");
+               Worker::ReadReq r;
+               r.ring = rings.back().get();
+               r.after = after;
+               r.dst = reinterpret_cast<u8*>(addr);
+               r.cap = cap;
+               r.pinned = pinned;
+               reqs.push_back(r);
+             }
+             {
+               py::gil_scoped_release rel;
+               w.read_latest_many(reqs);
+             }
+             py::list out;
+             for (const Worker::ReadReq& r : reqs)
+               out.append(r.ok ? py::object(py::make_tuple(r.meta.seq, meta_dict(r.meta))) : py::object(py::none()));
+             return out;
+           })
       .def("video_frame",
            // Serialized VideoFrame proto, built in place in its final bytes object: header, the
            // slot's pixels (D2H through a pinned pool buffer, GIL released), trailer; the object
