@@ -72,4 +72,5 @@ PYBIND11_MODULE(_vep, m) {
   bind_rpc(m);
   bind_dbk(m);
   bind_hevc_lf(m);
+  bind_recon(m);
 }
