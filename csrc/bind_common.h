@@ -7,6 +7,7 @@
 
 #include "bind_ext.h"
 #include "vep/crop.h"
+#include "vep/dewarp.h"
 #include "vep/overlay.h"
 #include "vep/runtime.h"
 
@@ -239,6 +240,26 @@ inline py::array_t<uint8_t> crops_array(std::vector<u8>& px, size_t n, int ow, i
   py::capsule owner(keep, [](void* p) { delete static_cast<std::vector<u8>*>(p); });
   return py::array_t<uint8_t>(shape, keep->data(), owner);
 }
+
+// A view's mesh (vep/dewarp.h) crosses the boundary as a C-contiguous int32 array of shape
+// (mesh_h(height), mesh_w(width), 2); a bad shape, output size or pad colour is a ValueError.
+using MeshArray = py::array_t<int32_t, py::array::c_style>;
+inline crop::Pad view_output_of(const MeshArray& mesh, int ow, int oh, const PadTuple& pad) {
+  crop::Pad p;
+  std::tie(p.b, p.g, p.r) = pad;
+  try {
+    dewarp::check_output(ow, oh, p);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  if (mesh.ndim() != 3 || mesh.shape(0) != dewarp::mesh_h(oh) || mesh.shape(1) != dewarp::mesh_w(ow) || mesh.shape(2) != 2)
+    throw py::value_error("view: the mesh must be an int32 array of shape (ceil(height / 8) + 1, ceil(width / 8) + 1, 2)");
+  return p;
+}
+inline void view_source_of(int w, int h) {
+  if (w < 1 || h < 1 || w > dewarp::kMaxSrc || h > dewarp::kMaxSrc) throw py::value_error("view: picture size must be 1..8192");
+}
+inline std::vector<i32> mesh_words(const MeshArray& mesh) { return std::vector<i32>(mesh.data(), mesh.data() + mesh.size()); }
 
 // Overlay items (vep/overlay.h) cross the boundary as tuples (kind, x0, y0, x1, y1, b, g, r, alpha,
 // thickness, fill, scale, has_bg, bg_b, bg_g, bg_r, bg_alpha, text) of ints and one bytes (a text

@@ -553,6 +553,62 @@ void bind_ops(py::module_& m) {
         },
         py::arg("pictures"), py::arg("width"), py::arg("height"), py::arg("fit"), py::arg("pad"), py::arg("out"),
         py::arg("out_bytes"), py::arg("stream"));
+  // Views (vep/dewarp.h) on the host: the CPU backend's path, the byte-exact reference of remap.
+  m.def("remap_cpu",
+        // (height, width, 3): a C-contiguous (H, W, 3) uint8 picture sampled through the mesh
+        [](py::array_t<uint8_t, py::array::c_style> bgr, MeshArray mesh, int width, int height, const PadTuple& pad) {
+          if (!is_bgr_picture(bgr)) throw py::value_error("remap_cpu: (H, W, 3) uint8 picture expected");
+          const crop::Pad p = view_output_of(mesh, width, height, pad);
+          const int h = int(bgr.shape(0)), w = int(bgr.shape(1));
+          view_source_of(w, h);
+          py::array_t<uint8_t> o({py::ssize_t(height), py::ssize_t(width), py::ssize_t(3)});
+          const u8* src = bgr.data();
+          const i32* nodes = mesh.data();
+          u8* q = o.mutable_data();
+          {
+            py::gil_scoped_release r;
+            dewarp::apply_cpu(src, size_t(w) * 3, w, h, nodes, width, height, p, q);
+          }
+          return o;
+        },
+        py::arg("bgr").noconvert(), py::arg("mesh").noconvert(), py::arg("width"), py::arg("height"),
+        py::arg("pad") = PadTuple(0, 0, 0));
+  // Views (src, w, h, mesh, width, height) of pictures on caller-owned device buffers into the
+  // caller-owned output `out` of out_bytes (every view width x height x 3 packed, one after the
+  // other in list order): ONE launch of the gfx950 dewarp kernel for all of them, on `stream` of
+  // the current device. The meshes are host arrays: they go up with the descriptors.
+  m.def("remap",
+        [](const std::vector<std::tuple<uintptr_t, int, int, MeshArray, int, int>>& views, const PadTuple& pad, uintptr_t out,
+           size_t out_bytes, uintptr_t stream) {
+          size_t words = 0, bytes = 0;
+          crop::Pad p;
+          for (const auto& v : views) {
+            p = view_output_of(std::get<3>(v), std::get<4>(v), std::get<5>(v), pad);
+            view_source_of(std::get<1>(v), std::get<2>(v));
+            words += size_t(std::get<3>(v).size());
+            bytes += size_t(std::get<4>(v)) * size_t(std::get<5>(v)) * 3;
+          }
+          if (views.empty()) return;
+          if (views.size() > 65535) throw py::value_error("remap: at most 65535 views per call");
+          if (bytes > out_bytes) throw py::value_error("remap: output smaller than the views");
+          on_pooled_set<gpu::DewarpPool>(stream, [&](gpu::DewarpPool::Lease& set, hipStream_t s) {
+            set->reserve(int(views.size()), words, 0, 0);
+            const u32 pw = u32(p.b) | u32(p.g) << 8 | u32(p.r) << 16;
+            size_t mat = 0, oat = 0;
+            for (size_t k = 0; k < views.size(); ++k) {
+              const auto& [src, w, h, mesh, ow, oh] = views[k];
+              const size_t one = size_t(ow) * size_t(oh) * 3;
+              std::memcpy(set->h_mesh.p + mat, mesh.data(), size_t(mesh.size()) * sizeof(i32));
+              set->h_descs.p[k] = gpu::make_dewarp_desc(reinterpret_cast<const u8*>(src), size_t(w) * size_t(h) * 3, w, h,
+                                                        set->d_mesh.p + mat, size_t(mesh.size()) / 2,
+                                                        reinterpret_cast<u8*>(out) + oat, one, ow, oh, pw);
+              mat += size_t(mesh.size());
+              oat += one;
+            }
+            set->run(int(views.size()), words, 0, s);
+          });
+        },
+        py::arg("views"), py::arg("pad"), py::arg("out"), py::arg("out_bytes"), py::arg("stream"));
   // On-screen display (vep/overlay.h) on the host: the arithmetic itself, and the CPU backend's
   // path, the byte-exact reference of overlay_draw.
   m.def("overlay_font", [] {

@@ -349,6 +349,92 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            py::arg("idx"), py::arg("box"), py::arg("width"), py::arg("height"), py::arg("after") = 0,
            py::arg("seq") = 0, py::arg("quality") = 85, py::arg("fit") = 0,
            py::arg("pad") = PadTuple(crop::kPad, crop::kPad, crop::kPad))
+      .def("read_view",
+           // (meta, ndarray (height, width, 3)) of the newest frame with seq > after (seq 0) or of
+           // frame `seq`, sampled through `mesh` (built for a src_width x src_height picture) where
+           // the frame lies; None if there is no such frame; (meta, None) if the frame has another
+           // size than the mesh was built for. ValueError on an invalid mesh, size or pad colour.
+           [](Worker& w, int i, MeshArray mesh, int src_width, int src_height, int width, int height, i64 after, i64 seq,
+              const PadTuple& pad) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const crop::Pad p = view_output_of(mesh, width, height, pad);
+             view_source_of(src_width, src_height);
+             if (after < 0 || seq < 0) throw py::value_error("view: after and seq must be >= 0");
+             const std::vector<i32> words = mesh_words(mesh);
+             FrameMeta m;
+             std::vector<u8> px;
+             int st;
+             {
+               py::gil_scoped_release r;
+               st = w.read_view(i, after, seq, words, src_width, src_height, width, height, p, &m, px);
+             }
+             if (st == Worker::kViewNone) return py::none();
+             if (st == Worker::kViewSize) return py::make_tuple(meta_dict(m), py::none());
+             return py::make_tuple(meta_dict(m), crops_array(px, 1, width, height).attr("reshape")(height, width, 3));
+           },
+           py::arg("idx"), py::arg("mesh").noconvert(), py::arg("src_width"), py::arg("src_height"), py::arg("width"),
+           py::arg("height"), py::arg("after") = 0, py::arg("seq") = 0, py::arg("pad") = PadTuple(0, 0, 0))
+      .def("read_views_many",
+           // [(meta, ndarray) | (meta, None) | None] for requests (idx, after, seq, mesh, src_width,
+           // src_height, width, height), a camera may repeat: every view in one launch a round.
+           [](Worker& w, const std::vector<std::tuple<int, i64, i64, MeshArray, int, int, int, int>>& requests,
+              const PadTuple& pad) {
+             std::vector<Worker::ViewRequest> reqs(requests.size());
+             for (size_t k = 0; k < requests.size(); ++k) {
+               Worker::ViewRequest& r = reqs[k];
+               const MeshArray& mesh = std::get<3>(requests[k]);
+               std::tie(r.cam, r.after, r.seq) = std::make_tuple(std::get<0>(requests[k]), std::get<1>(requests[k]),
+                                                                 std::get<2>(requests[k]));
+               r.src_w = std::get<4>(requests[k]), r.src_h = std::get<5>(requests[k]);
+               r.ow = std::get<6>(requests[k]), r.oh = std::get<7>(requests[k]);
+               view_output_of(mesh, r.ow, r.oh, pad);
+               view_source_of(r.src_w, r.src_h);
+               if (r.after < 0 || r.seq < 0) throw py::value_error("view: after and seq must be >= 0");
+               r.mesh = mesh_words(mesh);
+             }
+             crop::Pad p;
+             std::tie(p.b, p.g, p.r) = pad;
+             {
+               py::gil_scoped_release r;
+               w.read_views_many(reqs, p);
+             }
+             py::list out;
+             for (Worker::ViewRequest& r : reqs) {
+               if (r.status == Worker::kViewNone)
+                 out.append(py::none());
+               else if (r.status == Worker::kViewSize)
+                 out.append(py::make_tuple(meta_dict(r.meta), py::none()));
+               else
+                 out.append(py::make_tuple(meta_dict(r.meta), crops_array(r.data, 1, r.ow, r.oh).attr("reshape")(r.oh, r.ow, 3)));
+             }
+             return out;
+           },
+           py::arg("requests"), py::arg("pad") = PadTuple(0, 0, 0))
+      .def("read_view_jpeg",
+           // (meta, bytes): one view as a JPEG, the encoder chained onto the remap on the device;
+           // None and (meta, None) as read_view.
+           [](Worker& w, int i, MeshArray mesh, int src_width, int src_height, int width, int height, i64 after, i64 seq,
+              int quality, const PadTuple& pad) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const crop::Pad p = view_output_of(mesh, width, height, pad);
+             view_source_of(src_width, src_height);
+             if (after < 0 || seq < 0) throw py::value_error("view: after and seq must be >= 0");
+             if (quality < 1 || quality > 100) throw py::value_error("jpeg: quality must be 1..100");
+             const std::vector<i32> words = mesh_words(mesh);
+             FrameMeta m;
+             std::string out;
+             int st;
+             {
+               py::gil_scoped_release r;
+               st = w.read_view_jpeg(i, after, seq, words, src_width, src_height, width, height, p, quality, &m, out);
+             }
+             if (st == Worker::kViewNone) return py::none();
+             if (st == Worker::kViewSize) return py::make_tuple(meta_dict(m), py::none());
+             return py::make_tuple(meta_dict(m), py::bytes(out));
+           },
+           py::arg("idx"), py::arg("mesh").noconvert(), py::arg("src_width"), py::arg("src_height"), py::arg("width"),
+           py::arg("height"), py::arg("after") = 0, py::arg("seq") = 0, py::arg("quality") = 85,
+           py::arg("pad") = PadTuple(0, 0, 0))
       .def("read_history",
            // [(meta, ndarray)] of the newest `count` (0 = the camera's history depth) frames with
            // seq > after: ascending, contiguous in seq, ending at the newest frame.

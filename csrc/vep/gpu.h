@@ -608,6 +608,51 @@ struct CropSet : DescSet<CropDesc> {
 };
 using CropPool = ScratchPool<CropSet>;
 
+// ---- remapped views (gpu_dewarp.hip; arithmetic: dewarp.h) -------------------------------------
+// One view of one picture of a batched dewarp launch (device memory): the packed BGR24 picture
+// sampled bilinearly through a mesh of source positions (dewarp.h) into its own packed ow x oh
+// output, pixels whose position lies outside the picture the pad colour; byte-identical with
+// dewarp::apply_cpu. Pictures, meshes and sizes of one launch may all differ; the outputs of one
+// launch must not overlap. The mesh's CONTENT is not trusted: the kernel clamps what it loads.
+struct DewarpDesc {
+  const VEP_DEV u8* src;    // ph rows of src_pitch bytes (any alignment)
+  VEP_DEV u8* dst;          // this view's own output: oh rows of ow * 3 bytes, packed (any alignment)
+  const VEP_DEV i32* mesh;  // dewarp::mesh_w(ow) * dewarp::mesh_h(oh) pairs (sx, sy), row-major
+  u32 src_pitch;            // bytes
+  i32 pw, ph;               // the picture, 1 .. dewarp::kMaxSrc
+  u16 ow, oh;               // 1 .. dewarp::kMaxOut
+  u32 pad_bgr;              // b | g << 8 | r << 16
+  u32 pad_;
+};
+static_assert(sizeof(DewarpDesc) == 48, "DewarpDesc layout");
+// Throws unless the kernel can run the descriptor without reading outside a picture of src_bytes
+// or a mesh of mesh_pairs pairs and without writing outside the view's own oh * ow * 3 bytes, of
+// which dst_bytes are there (the launch below does not check).
+void check_dewarp(const DewarpDesc& d, size_t src_bytes, size_t mesh_pairs, size_t dst_bytes);
+// One launch for the n views: grid = tiles of the largest output x views. h_descs is the host copy
+// of d_descs (the grid is sized from it).
+void launch_dewarp(const DewarpDesc* d_descs, const DewarpDesc* h_descs, int n, hipStream_t s);
+// The descriptor of one view, checked: the w x h picture at src (src_bytes long, rows of w * 3
+// bytes) through the mesh at `mesh` (mesh_pairs long) into the ow x oh output at dst.
+DewarpDesc make_dewarp_desc(const u8* src, size_t src_bytes, int w, int h, const i32* mesh, size_t mesh_pairs, u8* dst,
+                            size_t dst_bytes, int ow, int oh, u32 pad_bgr);
+
+// View scratch of one device (pool contract: above): descriptors, the meshes of a request one after
+// the other (they travel with the request: no per-camera device state), the outputs likewise, and
+// their copy on the host.
+struct DewarpSet : DescSet<DewarpDesc> {
+  DevBuf<i32> d_mesh;
+  PinBuf<i32> h_mesh;
+  DevBuf<u8> out;
+  PinBuf<u8> host;
+  void reserve(int ndescs, size_t mesh_words, size_t out_bytes, size_t host_bytes);
+  // Copies the first n host descriptors and the first mesh_words words of h_mesh up, launches the
+  // descriptors on `s`, then copies the first down_bytes of `out` into `host` (0: nothing comes
+  // down) and records the event (no wait).
+  void run(int n, size_t mesh_words, size_t down_bytes, hipStream_t s);
+};
+using DewarpPool = ScratchPool<DewarpSet>;
+
 // ---- on-screen display (gpu_overlay.hip; arithmetic: overlay.h) --------------------------------
 // One picture of a batched overlay launch (device memory): the packed BGR24 picture at src with
 // its primitives drawn on, written to dst, byte-identical with overlay::apply_cpu. dst == src (and

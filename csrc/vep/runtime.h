@@ -599,6 +599,31 @@ class Worker {
   // compressed bytes come down.
   bool read_crop_jpeg(int cam, i64 after, i64 seq, const crop::Box& box, int ow, int oh, int fit, const crop::Pad& pad,
                       int quality, FrameMeta* meta, std::string& out);
+  // Views (dewarp.h, docs/DEWARP.md): a frame sampled through a mesh of source positions (a
+  // dewarped fisheye view, an undistorted picture, any remap) into an ow x oh picture where the
+  // frame lies, in its ring slot, on the serving stream (CPU backend: dewarp::apply_cpu on the host
+  // ring); only the view comes down. `mesh` holds dewarp::mesh_w(ow) * dewarp::mesh_h(oh) pairs and
+  // was built for a src_w x src_h picture: a frame of another size is answered kViewSize and
+  // nothing is produced (the caller rebuilds the mesh). after / seq, the consistent read and the
+  // masks as for the crops. Throws on an invalid size, mesh length or pad colour.
+  enum ViewResult : int { kViewNone = 0, kViewOk = 1, kViewSize = 2 };
+  int read_view(int cam, i64 after, i64 seq, const std::vector<i32>& mesh, int src_w, int src_h, int ow, int oh,
+                const crop::Pad& pad, FrameMeta* meta, std::vector<u8>& dst);
+  // Several cameras (a camera may repeat), each view with its own mesh and size: ONE launch a round.
+  struct ViewRequest {
+    int cam = -1;
+    i64 after = 0, seq = 0;
+    std::vector<i32> mesh;
+    int src_w = 0, src_h = 0, ow = 0, oh = 0;
+    int status = kViewNone;  // out: kViewNone for an unknown camera, no ring, no such frame, still inconsistent
+    FrameMeta meta;          // out
+    std::vector<u8> data;    // out (kViewOk): oh * ow * 3 bytes
+  };
+  void read_views_many(std::vector<ViewRequest>& reqs, const crop::Pad& pad);
+  // One view as a JPEG stream: the encoder is chained onto the remap on the device, only the
+  // compressed bytes come down.
+  int read_view_jpeg(int cam, i64 after, i64 seq, const std::vector<i32>& mesh, int src_w, int src_h, int ow, int oh,
+                     const crop::Pad& pad, int quality, FrameMeta* meta, std::string& out);
   void set_wall_max_tiles(int n);
   int wall_max_tiles() const { return wall_max_tiles_.load(); }
   // Frame history: the newest max_count (0 = the camera's depth) frames with seq > after, copied
@@ -912,6 +937,9 @@ class Worker {
   // on-screen display (after the crops' members)
   gpu::OverlayPool overlay_pool_;  // descriptors, primitives, text and a picture, one set per request in flight
   std::atomic<u64> overlay_requests_{0}, overlay_prims_{0};
+  // views (after the overlay's members)
+  gpu::DewarpPool dewarp_pool_;  // descriptors, meshes and outputs of the view reads, one set per request in flight
+  struct ViewOp;  // as CropOp
   void wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
                  const std::vector<ForeignTile>& foreign, const std::vector<std::string>* labels,
                  std::vector<i64>& seqs_out, std::string& out);

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "crop.h"
+#include "dewarp.h"
 #include "jpeg.h"
 #include "ring_read.h"
 #include "runtime.h"
@@ -937,6 +938,151 @@ bool Worker::read_crop_jpeg(int cam, i64 after, i64 seq, const crop::Box& box, i
     // (the same stream, so the encode is ordered after the crop; it waits for the stream)
     encode_device(set->out.p, ow, oh, quality, out);
   });
+}
+
+// ------------------------------------------------------------------------------------- views
+
+static void check_view_request(const std::vector<i32>& mesh, int src_w, int src_h, int ow, int oh, const crop::Pad& pad,
+                               i64 after, i64 seq) {
+  dewarp::check_output(ow, oh, pad);
+  dewarp::check_source(src_w, src_h);
+  VEP_CHECK(mesh.size() == size_t(dewarp::mesh_w(ow)) * size_t(dewarp::mesh_h(oh)) * 2,
+            "view: the mesh must hold (ceil(width / 8) + 1) * (ceil(height / 8) + 1) pairs");
+  VEP_CHECK(after >= 0 && seq >= 0, "view: after and seq must be >= 0");
+}
+
+// The view reads as an op of read_consistent_rounds: nothing is stored, every request is produced
+// from its slot, all requests of a round in one launch. A frame of another size than the mesh was
+// built for produces nothing and commits kViewSize.
+struct Worker::ViewOp {
+  struct Eval : ReadEntry {
+    ViewRequest* req = nullptr;
+    bool fits = false;  // the frame has the size the mesh was built for
+  };
+  Worker& w;
+  crop::Pad pad;
+  bool stored(Eval&) { return false; }
+  void plan(Eval& e) { e.fits = e.ring->width() == e.req->src_w && e.ring->height() == e.req->src_h; }
+  void run(std::vector<Eval*>& todo) {
+    size_t nd = 0, words = 0, bytes = 0;
+    for (Eval* e : todo) {
+      e->req->data.clear();
+      if (!e->fits) continue;
+      ++nd;
+      words += e->req->mesh.size();
+      bytes += size_t(e->req->ow) * size_t(e->req->oh) * 3;
+    }
+    if (!nd) return;
+    if (!w.dev_.gpu()) {
+      for (Eval* e : todo) {
+        if (!e->fits) continue;
+        ViewRequest& r = *e->req;
+        r.data.resize(size_t(r.ow) * size_t(r.oh) * 3);
+        dewarp::apply_cpu(e->ring->slot_ptr(e->slot), size_t(r.src_w) * 3, r.src_w, r.src_h, r.mesh.data(), r.ow, r.oh, pad,
+                          r.data.data());
+      }
+      return;
+    }
+    VEP_CHECK(nd <= 65535, "view: at most 65535 views per request");
+    w.dev_.bind();
+    gpu::DewarpPool::Lease set = w.dewarp_pool_.acquire();
+    set->reserve(int(nd), words, bytes, bytes);
+    size_t k = 0, mat = 0, oat = 0;
+    for (Eval* e : todo) {
+      if (!e->fits) continue;
+      const ViewRequest& r = *e->req;
+      const FrameRing& ring = *e->ring;
+      const size_t one = size_t(r.ow) * size_t(r.oh) * 3;
+      std::memcpy(set->h_mesh.p + mat, r.mesh.data(), r.mesh.size() * sizeof(i32));
+      set->h_descs.p[k++] = gpu::make_dewarp_desc(ring.slot_ptr(e->slot), ring.slot_bytes(), r.src_w, r.src_h,
+                                                  set->d_mesh.p + mat, r.mesh.size() / 2, set->out.p + oat, one, r.ow,
+                                                  r.oh, pad_word(pad));
+      mat += r.mesh.size();
+      oat += one;
+    }
+    set->run(int(nd), words, bytes, w.serve_stream_);
+    VEP_HIP(hipEventSynchronize(set->ev));
+    oat = 0;
+    for (Eval* e : todo) {
+      if (!e->fits) continue;
+      const size_t one = size_t(e->req->ow) * size_t(e->req->oh) * 3;
+      e->req->data.assign(set->host.p + oat, set->host.p + oat + one);
+      oat += one;
+    }
+  }
+  void commit(Eval& e) {  // the slot proved unchanged
+    e.req->meta = e.meta;
+    e.req->status = e.fits ? kViewOk : kViewSize;
+  }
+};
+
+void Worker::read_views_many(std::vector<ViewRequest>& reqs, const crop::Pad& pad) {
+  for (ViewRequest& r : reqs) {
+    check_view_request(r.mesh, r.src_w, r.src_h, r.ow, r.oh, pad, r.after, r.seq);
+    r.status = kViewNone;
+    r.data.clear();
+  }
+  std::vector<ViewOp::Eval> evs(reqs.size());
+  for (size_t k = 0; k < reqs.size(); ++k) {
+    ViewOp::Eval& e = evs[k];
+    e.req = &reqs[k];
+    e.after = reqs[k].after;
+    e.seq = reqs[k].seq;
+    if (std::shared_ptr<Camera> c = camera(reqs[k].cam)) e.ring = c->ring();
+    e.pending = e.ring != nullptr;
+  }
+  ViewOp op{*this, pad};
+  read_consistent_rounds(evs, op);
+  for (ViewRequest& r : reqs)
+    if (r.status != kViewOk) r.data.clear();  // (produced from a slot that was reused: never returned)
+}
+
+int Worker::read_view(int cam, i64 after, i64 seq, const std::vector<i32>& mesh, int src_w, int src_h, int ow, int oh,
+                      const crop::Pad& pad, FrameMeta* meta, std::vector<u8>& dst) {
+  std::vector<ViewRequest> reqs(1);
+  ViewRequest& r = reqs[0];
+  r.cam = cam;
+  r.after = after;
+  r.seq = seq;
+  r.mesh = mesh;
+  r.src_w = src_w, r.src_h = src_h, r.ow = ow, r.oh = oh;
+  read_views_many(reqs, pad);
+  if (r.status != kViewNone) *meta = r.meta;
+  if (r.status == kViewOk) dst.swap(r.data);
+  return r.status;
+}
+
+int Worker::read_view_jpeg(int cam, i64 after, i64 seq, const std::vector<i32>& mesh, int src_w, int src_h, int ow, int oh,
+                           const crop::Pad& pad, int quality, FrameMeta* meta, std::string& out) {
+  VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  check_view_request(mesh, src_w, src_h, ow, oh, pad, after, seq);
+  std::shared_ptr<Camera> c = camera(cam);
+  if (!c) return kViewNone;
+  std::shared_ptr<FrameRing> ring = c->ring();
+  if (!ring) return kViewNone;
+  if (ring->width() != src_w || ring->height() != src_h) {
+    int slot;
+    return pick_frame(*ring, after, seq, meta, &slot) ? kViewSize : kViewNone;
+  }
+  const size_t one = size_t(ow) * size_t(oh) * 3;
+  const bool ok = read_consistent(*ring, after, seq, meta, [&](int slot, const FrameMeta&) {
+    if (!dev_.gpu()) {
+      std::vector<u8> host(one);
+      dewarp::apply_cpu(ring->slot_ptr(slot), size_t(src_w) * 3, src_w, src_h, mesh.data(), ow, oh, pad, host.data());
+      out = jpeg::encode_cpu(host.data(), ow, oh, quality);
+      return;
+    }
+    dev_.bind();
+    gpu::DewarpPool::Lease set = dewarp_pool_.acquire();
+    set->reserve(1, mesh.size(), one, 0);
+    std::memcpy(set->h_mesh.p, mesh.data(), mesh.size() * sizeof(i32));
+    set->h_descs.p[0] = gpu::make_dewarp_desc(ring->slot_ptr(slot), ring->slot_bytes(), src_w, src_h, set->d_mesh.p,
+                                              mesh.size() / 2, set->out.p, one, ow, oh, pad_word(pad));
+    set->run(1, mesh.size(), 0, serve_stream_);
+    // (the same stream, so the encode is ordered after the remap; it waits for the stream)
+    encode_device(set->out.p, ow, oh, quality, out);
+  });
+  return ok ? kViewOk : kViewNone;
 }
 
 void Worker::copy_slot(FrameRing& ring, int slot, u8* dst) {

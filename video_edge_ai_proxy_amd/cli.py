@@ -10,6 +10,8 @@
   privacy   REST client of a camera's privacy masks (--device NAME --rest host:port [--set JSON | --clear])
   crop      REST client of crop.jpg: one box of a frame as a JPEG (--device NAME --rest host:port
             --box x0,y0,x1,y1 --size WxH [--seq N] --out f.jpg)
+  view      REST client of view.jpg: a dewarped view of a frame as a JPEG (--device NAME --rest host:port
+            --view NAME | --size WxH [--pan D --tilt D --fov D --roll D] --out f.jpg)
 """
 from __future__ import annotations
 
@@ -385,15 +387,14 @@ def crop_url(a) -> str:
             + urllib.parse.urlencode(q, safe=","))
 
 
-def cmd_crop(a):
-    """REST client of ``/api/v1/process/{name}/crop.jpg``: one box of the camera's newest frame (or
-    of frame ``--seq``), cut and resized on the hub's GPU, written to ``--out``."""
+def _fetch_jpeg(what: str, url: str, a) -> None:
+    """GET a JPEG of camera ``a.device`` and write it to ``a.out`` (``vep crop``, ``vep view``)."""
     import json
     import urllib.error
     import urllib.request
 
     try:
-        with urllib.request.urlopen(crop_url(a), timeout=10) as r:
+        with urllib.request.urlopen(url, timeout=10) as r:
             jpg, seq = r.read(), r.headers.get("X-Vep-Seq")
     except urllib.error.HTTPError as e:
         detail = ""
@@ -401,10 +402,43 @@ def cmd_crop(a):
             detail = ": " + json.loads(e.read()).get("message", "")
         except ValueError:
             pass
-        raise SystemExit(f"crop: HTTP {e.code} for {a.device!r}{detail}")
+        raise SystemExit(f"{what}: HTTP {e.code} for {a.device!r}{detail}")
     with open(a.out, "wb") as f:
         f.write(jpg)
     print(f"seq {seq}: {len(jpg)} bytes -> {a.out}", flush=True)
+
+
+def cmd_crop(a):
+    """REST client of ``/api/v1/process/{name}/crop.jpg``: one box of the camera's newest frame (or
+    of frame ``--seq``), cut and resized on the hub's GPU, written to ``--out``."""
+    _fetch_jpeg("crop", crop_url(a), a)
+
+
+def view_url(a) -> str:
+    """The view.jpg request of ``vep view``'s arguments: a stored view (``--view``) or a virtual
+    camera (``--size`` with ``--pan`` / ``--tilt`` / ``--fov`` / ``--roll``)."""
+    import re
+    import urllib.parse
+
+    if a.view is not None:
+        q = {"view": a.view}
+    else:
+        sz = re.fullmatch(r"(\d{1,5})[xX](\d{1,5})", (a.size or "").strip())
+        if not sz:
+            raise SystemExit("view: give --view NAME, or --size WxH of a virtual camera")
+        q = {"pan": a.pan, "tilt": a.tilt, "fov": a.fov, "roll": a.roll, "width": sz.group(1), "height": sz.group(2),
+             "mount": a.mount}
+    if a.seq:
+        q["seq"] = str(a.seq)
+    if a.quality is not None:
+        q["quality"] = str(a.quality)
+    return f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/view.jpg?" + urllib.parse.urlencode(q)
+
+
+def cmd_view(a):
+    """REST client of ``/api/v1/process/{name}/view.jpg``: a dewarped view of a fisheye or
+    wide-angle camera's frame, remapped on the hub's GPU, written to ``--out``."""
+    _fetch_jpeg("view", view_url(a), a)
 
 
 def cmd_bench(a, rest):
@@ -527,6 +561,19 @@ def build_parser():
     cr.add_argument("--quality", type=int, default=None)
     cr.add_argument("--out", required=True, help="file to write")
     cr.set_defaults(fn=cmd_crop)
+
+    vw = sub.add_parser("view", help="a dewarped view of a fisheye / wide-angle camera as a JPEG, remapped on the GPU (REST)")
+    vw.add_argument("--device", required=True)
+    vw.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API")
+    vw.add_argument("--view", default=None, help="the name of a stored view (PUT .../views)")
+    vw.add_argument("--size", default=None, help="WxH of a virtual camera (each 1..4096), with the angles below")
+    for k, d in (("pan", 0.0), ("tilt", 0.0), ("roll", 0.0), ("fov", 90.0)):
+        vw.add_argument(f"--{k}", type=float, default=d, help="degrees")
+    vw.add_argument("--mount", default="wall", choices=["wall", "ceiling"])
+    vw.add_argument("--seq", type=int, default=0, help="that very frame (needs buffer.in_memory); default: the newest")
+    vw.add_argument("--quality", type=int, default=None)
+    vw.add_argument("--out", required=True, help="file to write")
+    vw.set_defaults(fn=cmd_view)
 
     b = sub.add_parser("bench", help="run bench.py (flags passed through, e.g. --codec h265)")
     b.set_defaults(fn=None)

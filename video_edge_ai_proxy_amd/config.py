@@ -107,6 +107,7 @@ class ServingConfig:
     wall_max_tiles: int = 64    # cameras one wall may show (1..65535)
     crop_max_boxes: int = 64    # boxes one crop request may name per camera (1..64)
     crop_max_bytes: int = 64 << 20  # output bytes (boxes x width x height x 3) one crop request may ask for
+    view_max_bytes: int = 256 << 20  # output bytes (width x height x 3, summed) the views of one request may ask for
 
 
 @dataclass
@@ -237,6 +238,9 @@ def validate(cfg: Config) -> None:
     v = cfg.serving.crop_max_bytes
     if isinstance(v, bool) or not isinstance(v, int) or v < 3:
         raise ValueError(f"serving.crop_max_bytes must be an integer >= 3, got {v!r}")
+    v = cfg.serving.view_max_bytes
+    if isinstance(v, bool) or not isinstance(v, int) or v < 3:
+        raise ValueError(f"serving.view_max_bytes must be an integer >= 3, got {v!r}")
     if not isinstance(cfg.overlay.from_annotations, bool):
         raise ValueError(f"overlay.from_annotations must be true or false, got {cfg.overlay.from_annotations!r}")
     v = cfg.overlay.annotation_ttl_ms

@@ -10,6 +10,7 @@ processes/nodes see ``video_edge_ai_proxy_amd.parallel``).
 from __future__ import annotations
 
 import hashlib
+import json
 import logging
 import os
 import threading
@@ -17,7 +18,7 @@ import time
 from dataclasses import dataclass, field
 from typing import Optional
 
-from .. import crops, privacy
+from .. import crops, privacy, views
 from .. import overlay as osd
 from .._native import gpu_count, native
 from ..config import Config, parse_tile
@@ -82,6 +83,12 @@ class Hub:
         self.host_domains = host_domains
         self._crop_lock = threading.Lock()
         self._crop_counts = [0, 0]  # requests, boxes (Hub.crop_counts, /metrics)
+        # views: every camera's (lens, {name: view}), the meshes built last and the frame size
+        # each camera had last (a mesh is built for a source size)
+        self._view_lock = threading.Lock()
+        self._views: dict[str, tuple] = {}
+        self._meshes: dict = {}
+        self._view_count = 0  # requests (Hub.view_counts, /metrics)
         # on-screen display: the stored list of every camera, [(item, deadline | None), ...] with
         # the deadline on overlay_clock (monotonic seconds); kept here, not persisted
         self._overlay_lock = threading.Lock()
@@ -145,10 +152,13 @@ class Hub:
         return self.cfg.buffer.on_disk_folder or os.path.join(self.cfg.data_dir, "archive")
 
     def start_camera(self, name: str, rtsp: str, rtmp: str = "", disk_path: Optional[str] = None,
-                     timeout_ms: int = 5000, reconnect_delay_ms: int = 1000, masks=None) -> CameraHandle:
+                     timeout_ms: int = 5000, reconnect_delay_ms: int = 1000, masks=None, lens_views=None) -> CameraHandle:
         """``masks``: the camera's privacy masks (:mod:`..privacy`), in force before the session
-        starts, so the first frame is already masked."""
+        starts, so the first frame is already masked. ``lens_views``: its ``(lens, {name: view})``
+        (:meth:`set_views`)."""
         native_masks = privacy.to_native(masks)  # (ValueError before anything is created)
+        if lens_views is not None:
+            lens_views = (views.check_lens(lens_views[0]), views.check_views(lens_views[1]))
         with self._lock:
             if name in self.cameras:
                 raise CameraExists(f"camera {name!r} already running")
@@ -164,6 +174,8 @@ class Hub:
                                              self.archiver, timeout_ms, reconnect_delay_ms, 30000)
             h.session.start()
             self.cameras[name] = h
+            if lens_views is not None:
+                self._views[name] = lens_views
             if self.bus:
                 self.bus[wi].add(cam, name)
             log.info("camera %s -> worker %d (device %s) slot %d", name, wi, self.devices[wi], cam)
@@ -176,6 +188,8 @@ class Hub:
             raise CameraNotFound(name)
         with self._overlay_lock:
             self._overlays.pop(name, None)
+        with self._lock:
+            self._views.pop(name, None)
         if self.bus:
             self.bus[h.worker_index].remove(h.cam)
         h.session.stop()
@@ -737,6 +751,152 @@ class Hub:
         self._count_crops(1)
         r = w.read_crop_jpeg(cam, native_boxes[0], width, height, after, seq, q, fit, pad)
         return None if r is None else (int(r[0]["seq"]), r[1])
+
+    # ------------------------------------------------------------------ views
+    _MESH_CACHE = 32  # built meshes kept (least recently used first out)
+
+    def set_views(self, name: str, lens, named_views=None) -> None:
+        """Store the camera's lens and its named views (:mod:`..views`; ``ValueError`` on a bad
+        one). Kept with the camera until :meth:`clear_views` or the camera stops; the process
+        manager stores them beside the camera's record, so they are in force after a restart."""
+        lens, named_views = views.check_lens(lens), views.check_views(named_views or {})
+        with self._lock:
+            self.handle(name)
+            self._views[name] = (lens, named_views)
+
+    def views(self, name: str) -> Optional[dict]:
+        """``{"lens": lens, "views": {name: view}}`` as stored, ``None`` when the camera has none."""
+        with self._lock:
+            self.handle(name)
+            got = self._views.get(name)
+        return None if got is None else {"lens": dict(got[0]), "views": {n: dict(v) for n, v in got[1].items()}}
+
+    def clear_views(self, name: str) -> None:
+        with self._lock:
+            self.handle(name)
+            self._views.pop(name, None)
+
+    def view_counts(self) -> int:
+        """View requests served or refused for want of a frame since the start."""
+        with self._view_lock:
+            return self._view_count
+
+    def _resolve_view(self, name: str, view) -> tuple:
+        """``(lens, view)`` of a stored view's name or an ad-hoc view dict (the virtual PTZ)."""
+        with self._lock:
+            self.handle(name)
+            got = self._views.get(name)
+        if got is None:
+            raise ValueError(f"camera {name!r} has no lens: set its views first")
+        if isinstance(view, str):
+            if view not in got[1]:
+                raise ValueError(f"camera {name!r} has no view {view!r}")
+            view = got[1][view]
+        else:
+            view = views.check_view(view)
+        return got[0], view
+
+    def _check_view_bytes(self, asked: list) -> None:
+        """``ValueError`` when the views of one request ask for more than ``serving.view_max_bytes``."""
+        total = sum(v["width"] * v["height"] * 3 for v in asked)
+        if total > int(self.cfg.serving.view_max_bytes):
+            raise ValueError(f"the request asks for {total} bytes of views, above "
+                             f"serving.view_max_bytes = {self.cfg.serving.view_max_bytes}")
+
+    def _mesh(self, lens: dict, view: dict, src_w: int, src_h: int):
+        key = (json.dumps(lens, sort_keys=True), json.dumps(view, sort_keys=True), src_w, src_h)
+        with self._view_lock:
+            mesh = self._meshes.pop(key, None)
+            if mesh is not None:
+                self._meshes[key] = mesh  # (most recently used last)
+                return mesh
+        mesh = views.build_mesh(lens, view, src_w, src_h)
+        with self._view_lock:
+            self._meshes[key] = mesh
+            while len(self._meshes) > self._MESH_CACHE:
+                self._meshes.pop(next(iter(self._meshes)))
+        return mesh
+
+    def _read_views(self, w, todo: list, after: int, seq: int, pad, read) -> list:
+        """``read(requests)`` for ``[(handle, lens, view)]`` of one worker, with meshes for the
+        size of each camera's ring (no ring yet: no frame, ``None``); a request answered "another
+        size" (the stream changed its size in between) is rebuilt for the size its frame has and
+        asked once more."""
+        sizes = []
+        for h, _, _ in todo:
+            st = w.stats(h.cam)
+            sizes.append((int(st["width"]), int(st["height"])))
+        out = [None] * len(todo)
+        ask = [k for k in range(len(todo)) if sizes[k][0] > 0 and sizes[k][1] > 0]
+        for _ in range(2 if ask else 0):
+            reqs = [(todo[k][0].cam, after, seq, self._mesh(todo[k][1], todo[k][2], *sizes[k]), sizes[k][0], sizes[k][1],
+                     todo[k][2]["width"], todo[k][2]["height"]) for k in ask]
+            again = []
+            for k, r in zip(ask, read(reqs)):
+                if r is not None and r[1] is None:  # the frame has another size than the mesh
+                    sizes[k] = (int(r[0]["width"]), int(r[0]["height"]))
+                    views.size(*sizes[k], views.MAX_SRC, "source")
+                    again.append(k)
+                    r = None
+                out[k] = None if r is None else (int(r[0]["seq"]), r[1])
+            ask = again
+            if not ask:
+                break
+        return out
+
+    def view(self, name: str, view, after: int = 0, seq: int = 0, pad=None):
+        """``(seq, ndarray [height, width, 3])``: a view of a frame of the camera, remapped on its
+        GPU in one kernel launch, in its ring slot; only the view is copied to the host. ``view``
+        is the name of a stored view (:meth:`set_views`) or an ad-hoc view dict (:mod:`..views`): a
+        virtual pan / tilt / zoom. ``after`` / ``seq`` as :meth:`crops`; ``None`` when there is no
+        such frame. Pixels the lens does not see are ``pad`` ``(b, g, r)``, default black. Views
+        read the ring slot, so they show the camera's privacy masks. Refreshes ``last_query``."""
+        return self.views_many({name: view}, after, seq, pad)[name]
+
+    def views_many(self, views_by_name: dict, after: int = 0, seq: int = 0, pad=None) -> dict:
+        """``{name: (seq, ndarray) | None}`` for several cameras, each with its own view: one
+        kernel launch per worker covers all of its cameras."""
+        if not isinstance(views_by_name, dict):
+            raise ValueError("views_by_name must be a dict {name: view}")
+        after, seq = crops.seq_args(after, seq)
+        pad = (0, 0, 0) if pad is None else crops.pad_tuple(pad)
+        order = list(views_by_name)
+        with self._lock:
+            hs = [self.handle(n) for n in order]
+        todo = [(h, *self._resolve_view(h.name, views_by_name[h.name])) for h in hs]
+        self._check_view_bytes([t[2] for t in todo])
+        now = now_ms()
+        for h in hs:
+            self.workers[h.worker_index].set_last_query(h.cam, now)
+        with self._view_lock:
+            self._view_count += 1
+        out = {}
+        for wi, w in enumerate(self.workers):
+            mine = [t for t in todo if t[0].worker_index == wi]
+            if mine:
+                rs = self._read_views(w, mine, after, seq, pad, lambda reqs: w.read_views_many(reqs, pad))
+                out.update({t[0].name: r for t, r in zip(mine, rs)})
+        return {n: out[n] for n in order}
+
+    def view_jpeg(self, name: str, view, after: int = 0, seq: int = 0, quality: Optional[int] = None, pad=None):
+        """``(seq, bytes)``: one view as a baseline JPEG, the encoder chained onto the remap on the
+        camera's GPU; only compressed bytes are copied. Arguments as :meth:`view`; ``quality``
+        1..100, default ``serving.jpeg_quality``."""
+        q = self._quality(quality)
+        after, seq = crops.seq_args(after, seq)
+        pad = (0, 0, 0) if pad is None else crops.pad_tuple(pad)
+        h = self.handle(name)
+        lens, view = self._resolve_view(name, view)
+        self._check_view_bytes([view])
+        w = self.workers[h.worker_index]
+        w.set_last_query(h.cam, now_ms())
+        with self._view_lock:
+            self._view_count += 1
+
+        def read(reqs):
+            return [w.read_view_jpeg(cam, mesh, sw, sh, vw, vh, a, s, q, pad) for cam, a, s, mesh, sw, sh, vw, vh in reqs]
+
+        return self._read_views(w, [(h, lens, view)], after, seq, pad, read)[0]
 
     def history(self, name: str, after: int = 0, count: int = 0) -> list:
         """``[(meta, ndarray)]`` of the camera's newest ``count`` (0 = ``buffer.in_memory``) frames

@@ -341,7 +341,8 @@ class ProcessHub:
         return self.cfg.buffer.on_disk_folder or os.path.join(self.cfg.data_dir, "archive")
 
     def start_camera(self, name: str, rtsp: str, rtmp: str = "", disk_path: Optional[str] = None,
-                     timeout_ms: int = 5000, reconnect_delay_ms: int = 1000, masks=None) -> CameraHandle:
+                     timeout_ms: int = 5000, reconnect_delay_ms: int = 1000, masks=None, lens_views=None) -> CameraHandle:
+        # (lens_views: stored views stay stored; this hub does not serve them)
         masks = privacy.normalize_list(masks)  # (kept with the spec: a fresh child starts the camera masked)
         with self._lock:
             if name in self.cameras:
@@ -657,6 +658,25 @@ class ProcessHub:
 
     def crop_jpeg(self, name: str, box, width, height, after=0, seq=0, quality=None, fit="stretch", pad=None):
         raise NotImplementedError("crops are not served with gpu.isolation: process")
+
+    # Views read a ring slot too: served only by the in-process hub, like the crops.
+    def set_views(self, name: str, lens, named_views=None):
+        raise NotImplementedError("views are not served with gpu.isolation: process")
+
+    def views(self, name: str):
+        raise NotImplementedError("views are not served with gpu.isolation: process")
+
+    def clear_views(self, name: str):
+        raise NotImplementedError("views are not served with gpu.isolation: process")
+
+    def view(self, name: str, view, after=0, seq=0, pad=None):
+        raise NotImplementedError("views are not served with gpu.isolation: process")
+
+    def views_many(self, views_by_name, after=0, seq=0, pad=None):
+        raise NotImplementedError("views are not served with gpu.isolation: process")
+
+    def view_jpeg(self, name: str, view, after=0, seq=0, quality=None, pad=None):
+        raise NotImplementedError("views are not served with gpu.isolation: process")
 
     def wait_decoded(self, name: str, n: int = 1, timeout_s: float = 10.0) -> bool:
         return bool(self._call(name, "wait_decoded", n, timeout_s))

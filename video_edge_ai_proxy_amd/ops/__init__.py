@@ -26,6 +26,10 @@
   (reduced by area averaging, enlarged bilinearly, stretched or letterboxed) to one output size,
   every box of every picture in a single launch (the kernel behind ``/crops`` and ``crop.jpg``),
   byte-identical with :func:`crop_resize_reference`.
+* :func:`remap` / :func:`remap_batch` — BGR24 pictures sampled bilinearly through meshes of source
+  positions (a dewarped fisheye view, an undistorted picture, any per-pixel mapping), every view
+  of the call in a single launch (the kernel behind ``/view`` and ``view.jpg``), byte-identical
+  with :func:`remap_reference`.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -754,6 +758,75 @@ def crop_resize_reference(bgr: torch.Tensor, boxes, width: int, height: int, fit
     width, height, fit, pad = _check_crop_args(width, height, fit, pad)
     return torch.from_numpy(native.crop_resize_cpu(bgr.detach().cpu().numpy(), crops.to_native(boxes), width, height,
                                                    fit, pad))
+
+
+def remap_batch(pictures, meshes, sizes, pad=(0, 0, 0), out: torch.Tensor | None = None):
+    """Views of a list of contiguous ``[H, W, 3]`` BGR24 device tensors (at most 8192 on a side, a
+    picture may repeat) on one device: picture ``k`` sampled bilinearly through ``meshes[k]``
+    (``int32[mesh_h, mesh_w, 2]`` source positions in 1/256 px, :mod:`..views`) into a view of
+    ``sizes[k] = (width, height)``, pixels whose position lies outside the picture ``pad``
+    ``(b, g, r)``; every view of the call in ONE kernel launch, exact in integers. Returns the list
+    of ``[height, width, 3]`` views; they are slices of ``out``, a contiguous uint8 tensor of the
+    views' total bytes on the pictures' device (a view at any byte offset will do; allocated when
+    ``None``). Byte-identical with :func:`remap_reference`. No CPU fallback."""
+    from .. import crops, views
+
+    pictures, meshes, sizes = list(pictures), list(meshes), list(sizes)
+    if not len(pictures) == len(meshes) == len(sizes):
+        raise ValueError("meshes and sizes must hold one entry per picture")
+    pad = crops.pad_tuple(pad)
+    device, work, total = None, [], 0
+    for k, (bgr, mesh, wh) in enumerate(zip(pictures, meshes, sizes)):
+        if not isinstance(bgr, torch.Tensor):
+            raise TypeError(f"pictures[{k}] must be a tensor")
+        w, h = _check_bgr(bgr, f"pictures[{k}]")
+        views.size(w, h, views.MAX_SRC, "source")
+        if not bgr.is_cuda:
+            raise ValueError("bgr must be a device tensor")
+        if device is None:
+            device = bgr.device
+        if bgr.device != device:
+            raise ValueError("the pictures must live on one device")
+        width, height = views.size(*wh)
+        work.append((bgr.data_ptr(), w, h, views.to_native(mesh, width, height), width, height))
+        total += width * height * 3
+    if device is None:
+        return []
+    require_gpu()
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == device and out.dtype == torch.uint8
+            and out.is_contiguous() and out.numel() == total):
+        raise ValueError(f"out must be a contiguous uint8 tensor of {total} elements on the pictures' device")
+    with torch.cuda.device(device):
+        native.remap(work, pad, out.data_ptr(), out.numel(), int(torch.cuda.current_stream(device).cuda_stream))
+    flat, res, at = out.view(-1), [], 0
+    for *_, width, height in work:
+        res.append(flat[at:at + width * height * 3].view(height, width, 3))
+        at += width * height * 3
+    return res
+
+
+def remap(bgr: torch.Tensor, mesh, width: int, height: int, pad=(0, 0, 0), out: torch.Tensor | None = None) -> torch.Tensor:
+    """One ``[H, W, 3]`` BGR24 device tensor through one mesh as ``[height, width, 3]``: see
+    :func:`remap_batch` (``out``: a contiguous uint8 tensor of that shape)."""
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (height, width, 3)):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {(height, width, 3)} on the picture's device")
+    res = remap_batch([bgr], [mesh], [(width, height)], pad, out)[0]
+    return res if out is None else out
+
+
+def remap_reference(bgr: torch.Tensor, mesh, width: int, height: int, pad=(0, 0, 0)) -> torch.Tensor:
+    """The CPU implementation's result for the same picture (host or device tensor), on the host:
+    the byte-exact oracle of :func:`remap`."""
+    from .. import crops, views
+
+    if not isinstance(bgr, torch.Tensor):
+        raise TypeError("bgr must be a tensor")
+    w, h = _check_bgr(bgr)
+    views.size(w, h, views.MAX_SRC, "source")
+    return torch.from_numpy(native.remap_cpu(bgr.detach().cpu().numpy(), views.to_native(mesh, *views.size(width, height)),
+                                             width, height, crops.pad_tuple(pad)))
 
 
 def _check_overlay_picture(bgr, what: str) -> tuple:

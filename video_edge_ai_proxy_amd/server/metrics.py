@@ -82,6 +82,11 @@ class HubCollector:
             cb = CounterMetricFamily("vep_crop_boxes", "boxes the crop requests named")
             cb.add_metric([], boxes)
             yield from (cr, cb)
+        counts = getattr(self.hub, "view_counts", None)
+        if counts is not None:
+            vr = CounterMetricFamily("vep_view_requests", "view requests (view, views_many, view.jpg)")
+            vr.add_metric([], counts())
+            yield vr
         counts = getattr(self.hub, "overlay_counts", None)
         if counts is not None:
             requests, prims = counts()

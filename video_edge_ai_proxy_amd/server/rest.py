@@ -20,6 +20,8 @@ motion detection on the GPU, docs/MOTION.md; ``DELETE .../motion`` resets the ba
 tamper detection on the GPU, docs/TAMPER.md; ``PUT .../tamper/reference`` declares the newest frame
 normal, ``DELETE .../tamper`` forgets it), ``POST /api/v1/process/{name}/crops`` and
 ``GET .../crop.jpg`` (boxes of a frame cut and resized on the GPU, docs/CROPS.md),
+``PUT / GET / DELETE /api/v1/process/{name}/views``, ``GET .../view.jpg`` and ``POST .../view`` (a
+fisheye or wide-angle camera's lens and views, remapped on the GPU, docs/DEWARP.md),
 ``PUT / GET / DELETE /api/v1/process/{name}/overlay`` (a camera's stored on-screen display list,
 drawn with ``frame.jpg?overlay=1&stamp=1`` and ``wall.jpg?labels=1``, docs/OVERLAY.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
 toolchain).
@@ -533,6 +535,76 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         if r is None:
             return err(404, "no such frame")
         return Response(content=r[1], media_type="image/jpeg", headers={"X-Vep-Seq": str(r[0])})
+
+    # ---- views: a fisheye or wide-angle frame remapped on the GPU in its ring slot (docs/DEWARP.md)
+    def view_call(fn, *args):
+        try:
+            return fn(*args), None
+        except ValueError as e:
+            return None, err(422, str(e))
+        except NotImplementedError as e:
+            return None, err(501, str(e))
+        except (KeyError, ProcessError):
+            return None, err(404, f"process {args[0]!r} not found")
+
+    @app.get("/api/v1/process/{name}/views")
+    def views_get(name: str):
+        got, bad = view_call(pm.hub.views, name)
+        return bad if bad is not None else (got or {"lens": None, "views": {}})
+
+    @app.put("/api/v1/process/{name}/views")
+    async def views_put(name: str, request: Request):
+        try:
+            body = json.loads(await request.body() or b"null")
+            if not isinstance(body, dict) or "lens" not in body or set(body) - {"lens", "views"}:
+                raise ValueError('a JSON object {"lens": {...}, "views": {name: {...}}} expected')
+            if body["lens"] is None:
+                raise ValueError("lens must be an object (DELETE clears the views)")
+        except ValueError as e:  # (invalid JSON included)
+            return err(422, str(e))
+        _, bad = view_call(pm.set_views, name, body["lens"], body.get("views") or {})
+        return bad if bad is not None else Response(status_code=204)
+
+    @app.delete("/api/v1/process/{name}/views")
+    def views_delete(name: str):
+        _, bad = view_call(pm.set_views, name, None)
+        return bad if bad is not None else Response(status_code=204)
+
+    @app.get("/api/v1/process/{name}/view.jpg")
+    def view_jpg(name: str, view: str | None = None, pan: float = 0.0, tilt: float = 0.0, fov: float = 90.0,
+                 roll: float = 0.0, width: int | None = None, height: int | None = None, mount: str = "wall",
+                 quality: int | None = None, after: int = 0, seq: int = 0):
+        if view is None:
+            if width is None or height is None:
+                return err(422, "view.jpg needs view=NAME, or width and height of a virtual camera")
+            view = {"type": "ptz", "pan": pan, "tilt": tilt, "fov": fov, "roll": roll, "mount": mount, "width": width,
+                    "height": height}
+        r, bad = view_call(pm.hub.view_jpeg, name, view, after, seq, quality)
+        if bad is not None:
+            return bad
+        if r is None:
+            return err(404, "no such frame")
+        return Response(content=r[1], media_type="image/jpeg", headers={"X-Vep-Seq": str(r[0])})
+
+    @app.post("/api/v1/process/{name}/view")
+    async def view_post(name: str, request: Request):
+        from starlette.concurrency import run_in_threadpool
+
+        try:
+            body = json.loads(await request.body() or b"null")
+            if not isinstance(body, dict) or "view" not in body or set(body) - {"view", "after", "seq", "pad"}:
+                raise ValueError('a JSON object {"view": NAME or {...}, "after": N, "seq": N, "pad": [b, g, r]} expected')
+        except ValueError as e:
+            return err(422, str(e))
+        r, bad = await run_in_threadpool(view_call, pm.hub.view, name, body["view"], body.get("after", 0),
+                                         body.get("seq", 0), body.get("pad"))
+        if bad is not None:
+            return bad
+        if r is None:
+            return err(404, "no such frame")
+        seq, px = r
+        return Response(content=px.tobytes(), media_type="application/octet-stream",
+                        headers={"X-Vep-Seq": str(seq), "X-Vep-View": f"{px.shape[1]},{px.shape[0]}"})
 
     @app.get("/api/v1/tamper")
     def tamper_many(names: str | None = None, grid: int = 0, wake: int = 1):

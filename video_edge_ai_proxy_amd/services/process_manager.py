@@ -13,6 +13,7 @@ Reference parity: server/services/rtsp_process_manager.go —
 New: a camera's privacy masks (``privacy.py``) are stored under ``/privacymasks/<name>``, a prefix
 of their own (the reference-shaped process record stays as it is): :meth:`start` and :meth:`restore`
 start the camera under the stored list, :meth:`stop` deletes it.
+New: a camera's lens and named views (``views.py``) are stored the same way under ``/views/<name>``.
 New: :meth:`restore` re-spawns every stored camera at boot (the reference relied on Docker's
 ``restart: always`` for that — SURVEY.md §5 checkpoint/resume row).
 """
@@ -28,7 +29,7 @@ from typing import Callable, Optional
 from ..engine.hub import CameraExists, CameraNotFound, Hub
 from ..models import (DEFAULT_IMAGE_TAG, PREFIX_RTSP_PROCESS, ContainerState, DockerLogs,
                       RTMPStreamStatus, StreamProcess)
-from .. import privacy
+from .. import privacy, views
 from ..utils import now_ms
 from .storage import KeyNotFound, Storage
 
@@ -36,6 +37,7 @@ log = logging.getLogger("vep.process")
 
 _NAME = re.compile(r"^[A-Za-z0-9_.\-]+$")
 PREFIX_PRIVACY_MASKS = "/privacymasks/"
+PREFIX_VIEWS = "/views/"
 
 
 class ProcessError(RuntimeError):
@@ -107,6 +109,31 @@ class ProcessManager:
             raise ProcessNotFound(f"process {name!r} not found")
         return self.hub.privacy_masks(name)
 
+    def stored_views(self, name: str):
+        """``(lens, {name: view})`` stored for ``name``, ``None`` when none (a corrupt entry counts
+        as none and is logged)."""
+        try:
+            rec = json.loads(self.storage.get(PREFIX_VIEWS, name))
+            return views.check_lens(rec["lens"]), views.check_views(rec["views"])
+        except KeyNotFound:
+            return None
+        except (ValueError, TypeError, KeyError) as e:
+            log.error("corrupt views of %s ignored: %s", name, e)
+            return None
+
+    def set_views(self, name: str, lens, named_views=None) -> None:
+        """Replace a running camera's lens and views (``ValueError`` on a bad one) and store them;
+        ``lens=None`` clears them."""
+        with self._lock:
+            if not self.hub.has(name):
+                raise ProcessNotFound(f"process {name!r} not found")
+            if lens is None:
+                self.hub.clear_views(name)
+                self.storage.delete(PREFIX_VIEWS, name)
+                return
+            self.hub.set_views(name, lens, named_views)
+            self.storage.put(PREFIX_VIEWS, name, json.dumps(self.hub.views(name)).encode())
+
     def unmasked_outputs(self, name: str) -> list:
         """The active outputs of this camera that the masks do NOT cover: ``rtmp`` (the compressed
         stream passed through), ``archive`` (the per-GOP MP4 of the compressed stream) and
@@ -138,7 +165,8 @@ class ProcessManager:
             sp.image_tag = sp.image_tag or DEFAULT_IMAGE_TAG
             try:
                 h = self.hub.start_camera(sp.name, sp.rtsp_endpoint, sp.rtmp_endpoint or "",
-                                          masks=self.stored_masks(sp.name) or None)
+                                          masks=self.stored_masks(sp.name) or None,
+                                          lens_views=self.stored_views(sp.name))
             except (CameraExists, RuntimeError, ValueError) as e:
                 raise ProcessError(str(e))
             if sp.rtmp_endpoint:
@@ -167,6 +195,7 @@ class ProcessManager:
                     raise ProcessNotFound(f"process {name!r} not found")
             self.storage.delete(PREFIX_RTSP_PROCESS, name)
             self.storage.delete(PREFIX_PRIVACY_MASKS, name)
+            self.storage.delete(PREFIX_VIEWS, name)
 
     def info(self, name: str, persist: bool = True) -> StreamProcess:
         if not self.hub.has(name):
@@ -218,7 +247,8 @@ class ProcessManager:
                 continue
             try:
                 self.hub.start_camera(rec.name, rec.rtsp_endpoint, rec.rtmp_endpoint or "",
-                                      masks=self.stored_masks(rec.name) or None)
+                                      masks=self.stored_masks(rec.name) or None,
+                                      lens_views=self.stored_views(rec.name))
                 if rec.rtmp_stream_status and rec.rtmp_stream_status.streaming and rec.rtmp_endpoint:
                     self.hub.set_proxy(rec.name, True)
                 started.append(rec.name)
