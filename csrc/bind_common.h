@@ -6,6 +6,7 @@
 #include <pybind11/stl.h>
 
 #include "bind_ext.h"
+#include "vep/clahe.h"
 #include "vep/crop.h"
 #include "vep/dewarp.h"
 #include "vep/overlay.h"
@@ -260,6 +261,24 @@ inline void view_source_of(int w, int h) {
   if (w < 1 || h < 1 || w > dewarp::kMaxSrc || h > dewarp::kMaxSrc) throw py::value_error("view: picture size must be 1..8192");
 }
 inline std::vector<i32> mesh_words(const MeshArray& mesh) { return std::vector<i32>(mesh.data(), mesh.data() + mesh.size()); }
+
+// Enhancement parameters (vep/clahe.h) cross the boundary as three ints; a bad one is a ValueError.
+inline clahe::Params clahe_params_of(int tile, int clip16, int strength) {
+  const clahe::Params p{tile, clip16, strength};
+  try {
+    clahe::check_params(p);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return p;
+}
+// A serving read's `enhance` argument: None, or the tuple (tile, clip16, strength).
+inline bool enhance_of(const py::object& o, clahe::Params& p) {
+  if (o.is_none()) return false;
+  const auto t = o.cast<std::tuple<int, int, int>>();
+  p = clahe_params_of(std::get<0>(t), std::get<1>(t), std::get<2>(t));
+  return true;
+}
 
 // Overlay items (vep/overlay.h) cross the boundary as tuples (kind, x0, y0, x1, y1, b, g, r, alpha,
 // thickness, fill, scale, has_bg, bg_b, bg_g, bg_r, bg_alpha, text) of ints and one bytes (a text

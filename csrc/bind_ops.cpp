@@ -29,6 +29,41 @@ static void on_pooled_set(uintptr_t stream, Fill&& fill) {
   VEP_HIP(hipEventSynchronize(set->ev));  // the descriptors are reused by the next call
 }
 
+// clahe_device / clahe_device_batch: every picture's descriptor checked against the sizes the
+// caller states, then the three launches on one pooled set.
+using ClahePicture = std::tuple<uintptr_t, size_t, u32, uintptr_t, size_t, u32, int, int, int, int, int, uintptr_t, size_t,
+                                uintptr_t, size_t>;
+static void clahe_run(const std::vector<ClahePicture>& pics, uintptr_t stream) {
+  const int n = int(pics.size());
+  if (n < 1 || pics.size() > 65535) throw py::value_error("clahe: 1..65535 pictures expected");
+  std::vector<gpu::ClaheDesc> descs((size_t(n)));
+  for (int k = 0; k < n; ++k) {
+    const auto& [src, src_bytes, src_pitch, dst, dst_bytes, dst_pitch, w, h, tile, clip16, strength, hist, hist_words, lut,
+                 lut_bytes] = pics[size_t(k)];
+    clahe_params_of(tile, clip16, strength);
+    if (!picture_size_ok(w, h)) throw py::value_error("clahe: picture size must be 1..65535");
+    gpu::ClaheDesc& d = descs[size_t(k)];
+    d = gpu::ClaheDesc{};
+    d.src = reinterpret_cast<const u8*>(src);
+    d.dst = reinterpret_cast<u8*>(dst);
+    d.hist = reinterpret_cast<u32*>(hist);
+    d.lut = reinterpret_cast<u8*>(lut);
+    d.src_pitch = src_pitch;
+    d.dst_pitch = dst_pitch;
+    d.w = w;
+    d.h = h;
+    d.tile = tile;
+    d.clip16 = clip16;
+    d.strength = strength;
+    gpu::check_clahe(d, src_bytes, dst_bytes, hist_words, lut_bytes);
+  }
+  on_pooled_set<gpu::ClahePool>(stream, [&](gpu::ClahePool::Lease& set, hipStream_t s) {
+    set->reserve(n, 0, 0, 0);
+    std::copy(descs.begin(), descs.end(), set->h_descs.p);
+    set->run(n, s);
+  });
+}
+
 // The checked descriptor of one picture of surface_to_bgr / surface_to_bgr_many, in their argument order.
 static gpu::SurfaceBgrDesc surface_bgr_desc(uintptr_t y, uintptr_t uv, int pitch, int coded_w, int coded_h, int bit_depth,
                                             int chroma_format, int crop_left, int crop_top, int out_w, int out_h,
@@ -609,6 +644,61 @@ void bind_ops(py::module_& m) {
           });
         },
         py::arg("views"), py::arg("pad"), py::arg("out"), py::arg("out_bytes"), py::arg("stream"));
+  // Contrast enhancement (vep/clahe.h) on the host: the CPU backend's path, the byte-exact
+  // reference of clahe_device.
+  m.def("clahe_cpu",
+        // (out (H, W, 3) uint8, hist (rows, cols, 256) uint32, lut (rows, cols, 256) uint8)
+        [](py::array_t<uint8_t, py::array::c_style> bgr, int tile, int clip16, int strength) {
+          if (!is_bgr_picture(bgr)) throw py::value_error("clahe_cpu: (H, W, 3) uint8 picture expected");
+          const clahe::Params p = clahe_params_of(tile, clip16, strength);
+          const int h = int(bgr.shape(0)), w = int(bgr.shape(1));
+          const py::ssize_t cols = py::ssize_t(clahe::cells(u32(w), u32(tile))), rows = py::ssize_t(clahe::cells(u32(h), u32(tile)));
+          py::array_t<uint8_t> out({py::ssize_t(h), py::ssize_t(w), py::ssize_t(3)});
+          py::array_t<uint32_t> hist({rows, cols, py::ssize_t(clahe::kBins)});
+          py::array_t<uint8_t> lut({rows, cols, py::ssize_t(clahe::kBins)});
+          const u8* src = bgr.data();
+          u8* q = out.mutable_data();
+          u32* hp = hist.mutable_data();
+          u8* lp = lut.mutable_data();
+          {
+            py::gil_scoped_release r;
+            clahe::hist_cpu(src, w, h, size_t(w) * 3, p.tile, hp);
+            clahe::luts_cpu(hp, w, h, p, lp);
+            clahe::apply_cpu(src, size_t(w) * 3, q, size_t(w) * 3, w, h, p.tile, lp);
+          }
+          return py::make_tuple(out, hist, lut);
+        },
+        py::arg("bgr").noconvert(), py::arg("tile") = 128, py::arg("clip16") = 32, py::arg("strength") = 256);
+  m.def("clahe_lut_cpu",
+        // the LUT (256,) uint8 of one group: its histogram (256,) over n pixels
+        [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> hist, u32 n, int clip16, int strength) {
+          if (hist.ndim() != 1 || hist.shape(0) != clahe::kBins) throw py::value_error("clahe_lut_cpu: hist must have 256 bins");
+          clahe_params_of(clahe::kMinTile, clip16, strength);
+          if (n < 1 || n > clahe::kMaxGroup) throw py::value_error("clahe_lut_cpu: a group has 1..147456 pixels");
+          uint64_t total = 0;
+          for (int v = 0; v < clahe::kBins; ++v) total += hist.data()[v];
+          if (total != n) throw py::value_error("clahe_lut_cpu: the histogram must sum to n");
+          py::array_t<uint8_t> lut = py::array_t<uint8_t>(py::ssize_t(clahe::kBins));
+          clahe::lut_of_group(hist.data(), n, clip16, strength, lut.mutable_data());
+          return lut;
+        },
+        py::arg("hist"), py::arg("n"), py::arg("clip16") = 32, py::arg("strength") = 256);
+  // Pictures (src, src_bytes, src_pitch, dst, dst_bytes, dst_pitch, w, h, tile, clip16, strength,
+  // hist, hist_words, lut, lut_bytes) on caller-owned device buffers: the three gfx950 CLAHE
+  // kernels, each ONE launch for all of them, on `stream` of the current device. dst == src: in
+  // place. The planes are the caller's too, so a test reads the histograms and LUTs back.
+  m.def("clahe_device_batch", &clahe_run, py::arg("pictures"), py::arg("stream"));
+  m.def("clahe_device",
+        [](uintptr_t src, size_t src_bytes, u32 src_pitch, uintptr_t dst, size_t dst_bytes, u32 dst_pitch, int w, int h,
+           int tile, int clip16, int strength, uintptr_t hist, size_t hist_words, uintptr_t lut, size_t lut_bytes,
+           uintptr_t stream) {
+          clahe_run({ClahePicture(src, src_bytes, src_pitch, dst, dst_bytes, dst_pitch, w, h, tile, clip16, strength, hist,
+                                  hist_words, lut, lut_bytes)},
+                    stream);
+        },
+        py::arg("src"), py::arg("src_bytes"), py::arg("src_pitch"), py::arg("dst"), py::arg("dst_bytes"),
+        py::arg("dst_pitch"), py::arg("width"), py::arg("height"), py::arg("tile"), py::arg("clip16"), py::arg("strength"),
+        py::arg("hist"), py::arg("hist_words"), py::arg("lut"), py::arg("lut_bytes"), py::arg("stream"));
   // On-screen display (vep/overlay.h) on the host: the arithmetic itself, and the CPU backend's
   // path, the byte-exact reference of overlay_draw.
   m.def("overlay_font", [] {

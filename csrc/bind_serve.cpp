@@ -26,20 +26,47 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // is none; encoded on the GPU from the ring slot (CPU backend: on the host).
            // width / height (0 = not given): fitted into that box and downscaled first; meta then
            // carries the scaled size.
-           [](Worker& w, int i, i64 after, int quality, int width, int height) -> py::object {
+           // enhance (None, or (tile, clip16, strength)): contrast-enhanced first (docs/ENHANCE.md).
+           [](Worker& w, int i, i64 after, int quality, int width, int height, py::object enhance) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
+             clahe::Params p;
+             const bool eq = enhance_of(enhance, p);
              FrameMeta m;
              std::string out;
              bool ok;
              {
                py::gil_scoped_release r;
-               ok = w.read_latest_jpeg(i, after, quality, &m, out, width, height);
+               ok = w.read_latest_jpeg(i, after, quality, &m, out, width, height, eq ? &p : nullptr);
              }
              if (!ok) return py::none();
              return py::make_tuple(meta_dict(m), py::bytes(out));
            },
            py::arg("idx"), py::arg("after") = 0, py::arg("quality") = 85, py::arg("width") = 0,
-           py::arg("height") = 0)
+           py::arg("height") = 0, py::arg("enhance") = py::none())
+      .def("read_latest_enhanced",
+           // (meta, ndarray) of the newest frame with seq > after, contrast-enhanced (docs/ENHANCE.md)
+           // where it lies; fitted into width x height first when either is given; None if there is none.
+           [](Worker& w, int i, i64 after, int width, int height, int tile, int clip16, int strength) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const clahe::Params p = clahe_params_of(tile, clip16, strength);
+             if (after < 0) throw py::value_error("enhance: after must be >= 0");
+             if (width < 0 || width > 65535 || height < 0 || height > 65535)
+               throw py::value_error("scale: width and height must be 1..65535 (0: not given)");
+             FrameMeta m;
+             std::vector<u8> px;
+             bool ok;
+             {
+               py::gil_scoped_release r;
+               ok = w.read_latest_enhanced(i, after, width, height, p, &m, px);
+             }
+             if (!ok) return py::none();
+             py::array_t<uint8_t> a({py::ssize_t(m.height), py::ssize_t(m.width), py::ssize_t(3)});
+             std::memcpy(a.mutable_data(), px.data(), px.size());
+             return py::make_tuple(meta_dict(m), a);
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("width") = 0, py::arg("height") = 0, py::arg("tile") = 128,
+           py::arg("clip16") = 32, py::arg("strength") = 256)
+      .def("enhance_count", [](Worker& w) { return w.enhance_count(); })
       .def("read_latest_scaled",
            // (meta, ndarray) of the newest frame with seq > after, fitted into width x height
            // (0 = that side not given) and downscaled where it lies; None if there is none.
@@ -114,9 +141,11 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // read_latest_jpeg with the overlay items drawn on the picture (docs/OVERLAY.md): {name},
            // {seq} and {time} come from `name` and the meta of the frame actually encoded.
            [](Worker& w, int i, const std::vector<ItemTuple>& items, const std::string& name, i64 after, int quality,
-              int width, int height) -> py::object {
+              int width, int height, py::object enhance) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              const std::vector<overlay::Item> its = items_of(items);
+             clahe::Params p;
+             const bool eq = enhance_of(enhance, p);
              if (after < 0) throw py::value_error("overlay: after must be >= 0");
              if (quality < 1 || quality > 100) throw py::value_error("jpeg: quality must be 1..100");
              if (width < 0 || width > 65535 || height < 0 || height > 65535)
@@ -128,7 +157,7 @@ void bind_worker_serving(py::class_<Worker>& cls) {
              {
                py::gil_scoped_release r;
                try {
-                 ok = w.read_overlay_jpeg(i, after, quality, its, name, &m, out, width, height);
+                 ok = w.read_overlay_jpeg(i, after, quality, its, name, &m, out, width, height, eq ? &p : nullptr);
                } catch (const Error& e) {
                  // (only the expansion can refuse a checked list: too many primitives)
                  if (std::string(e.what()).find("overlay:") == std::string::npos) throw;
@@ -141,7 +170,7 @@ void bind_worker_serving(py::class_<Worker>& cls) {
              return py::make_tuple(meta_dict(m), py::bytes(out));
            },
            py::arg("idx"), py::arg("items"), py::arg("name") = "", py::arg("after") = 0, py::arg("quality") = 85,
-           py::arg("width") = 0, py::arg("height") = 0)
+           py::arg("width") = 0, py::arg("height") = 0, py::arg("enhance") = py::none())
       .def("overlay_counts", [](Worker& w) { return w.overlay_counts(); })
       .def_property("wall_max_tiles", &Worker::wall_max_tiles, &Worker::set_wall_max_tiles)
       .def("read_motion",

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 
+#include "clahe.h"
 #include "common.h"
 #include "mask.h"
 #include "overlay.h"
@@ -699,6 +700,53 @@ struct OverlaySet : DescSet<OverlayDesc> {
   void run(int n, size_t nprims, size_t text_bytes, hipStream_t s);
 };
 using OverlayPool = ScratchPool<OverlaySet>;
+
+// ---- contrast enhancement (gpu_clahe.hip; arithmetic: clahe.h) ---------------------------------
+// One picture of a batched CLAHE request (device memory): the packed BGR24 picture at src enhanced
+// into dst, byte-identical with clahe::enhance_cpu, in three launches that each cover every picture
+// of the request: per-tile luma histograms, one LUT per tile (of its group), and the blend of four
+// LUTs per pixel. dst == src (and equal pitches): in place; otherwise the two must not overlap and
+// src is never written. Pictures of one request may differ in size and parameters; their
+// destinations and planes must not overlap.
+struct ClaheDesc {
+  const VEP_DEV u8* src;  // h rows of src_pitch bytes (any alignment)
+  VEP_DEV u8* dst;        // h rows of dst_pitch bytes (any alignment)
+  VEP_DEV u32* hist;      // rows x cols x 256 u32, every bin written by the first launch (nothing is zeroed)
+  VEP_DEV u8* lut;        // rows x cols x 256 u8, 4-byte aligned, written by the second launch
+  u32 src_pitch, dst_pitch;  // bytes
+  i32 w, h;
+  i32 tile, clip16, strength;  // clahe::Params
+  u32 pad_;
+};
+static_assert(sizeof(ClaheDesc) == 64, "ClaheDesc layout");
+// tiles of a picture: the words / 256 of its histogram plane and the bytes / 256 of its LUT plane
+size_t clahe_tiles(int w, int h, int tile);
+// Throws unless all three kernels can run the descriptor without touching memory outside a source
+// of src_bytes, a destination of dst_bytes, a histogram plane of hist_words u32 and a LUT plane of
+// lut_bytes, with the planes aligned and all four apart from each other (source and destination
+// may be the same picture). The launch below does not check.
+void check_clahe(const ClaheDesc& d, size_t src_bytes, size_t dst_bytes, size_t hist_words, size_t lut_bytes);
+// The three launches for the n pictures, in order on `s`: grid = (blocks of the largest picture)
+// x pictures each. h_descs is the host copy of d_descs (the grids are sized from it).
+void launch_clahe(const ClaheDesc* d_descs, const ClaheDesc* h_descs, int n, hipStream_t s);
+
+// Enhancement scratch of one device (pool contract: above): descriptors, the histogram and LUT
+// planes of a request's pictures one after the other, a picture for the out-of-place enhancement
+// of a frame, and a pinned buffer for results on their way down.
+struct ClaheSet : DescSet<ClaheDesc> {
+  DevBuf<u32> hist;
+  DevBuf<u8> lut;
+  DevBuf<u8> picture;
+  PinBuf<u8> host;
+  void reserve(int ndescs, size_t tiles, size_t picture_bytes, size_t host_bytes);
+  // Descriptor k: the w x h picture at src (src_bytes long) enhanced into dst (dst_bytes long), its
+  // planes at tile_at tiles into the set's (advanced). Checked.
+  void put(int k, const u8* src, size_t src_bytes, u32 src_pitch, u8* dst, size_t dst_bytes, u32 dst_pitch, int w, int h,
+           const clahe::Params& p, size_t& tile_at);
+  // Copies the first n host descriptors up, launches them on `s` and records the event (no wait).
+  void run(int n, hipStream_t s);
+};
+using ClahePool = ScratchPool<ClaheSet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

@@ -1,6 +1,7 @@
-// What the two kernels on a cell grid share (motion, gpu_motion.hip; tamper, gpu_tamper.hip): the
-// chunk of cell columns a block owns, the proof that every chunk fits a kernel's limits, and the
-// lumas of a group of 8 pixels out of staged rows (gpu_stage.h). Kernel sources only.
+// What the three kernels on a cell grid share (motion, gpu_motion.hip; tamper, gpu_tamper.hip; the
+// tile histograms of the contrast enhancement, gpu_clahe.hip): the chunk of cell columns a block
+// owns, the proof that every chunk fits a kernel's limits, and the lumas of a group of 8 pixels
+// out of staged rows (gpu_stage.h). Kernel sources only.
 #pragma once
 
 #include "gpu_stage.h"

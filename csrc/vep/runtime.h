@@ -493,11 +493,22 @@ class Worker {
   // width / height (0 = not given): the frame is first fitted into that box (scale::fit, never
   // enlarged) and downscaled by area averaging (scale.h) into pooled device scratch, on the
   // serving stream as well. With both 0 the path and the bytes are as without them.
+  // enhance (non-null): the picture that is served is contrast-enhanced first (clahe.h,
+  // docs/ENHANCE.md): after the scale, in place on its canvas, or at native size out of place from
+  // the slot into pooled scratch (the slot is never written); before the overlay and the encoder,
+  // all on the serving stream. The CPU backend runs clahe::enhance_cpu. Null: path and bytes as ever.
   bool read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width = 0,
-                        int height = 0);
+                        int height = 0, const clahe::Params* enhance = nullptr);
   // The same scaled picture as packed BGR24 in host memory (dst is resized to ow * oh * 3; only
   // those bytes are copied off the GPU); meta->width / height are the scaled size.
-  bool read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst);
+  bool read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst,
+                          const clahe::Params* enhance = nullptr);
+  // The enhanced picture as packed BGR24 in host memory: scaled as read_latest_scaled, or with
+  // width = height = 0 at native size.
+  bool read_latest_enhanced(int cam, i64 after, int width, int height, const clahe::Params& p, FrameMeta* meta,
+                            std::vector<u8>& dst);
+  // Enhanced pictures served since the worker started.
+  u64 enhance_count() const { return enhance_requests_.load(); }
   // One picture of several cameras: a wall of scale::wall(n, cols, tw, th) cells, tile t showing
   // the newest frame of camera cams[t] fitted into its cell and centred, background elsewhere,
   // as a JPEG stream. One scale launch fills the canvas from the ring slots; tiles whose slot the
@@ -520,7 +531,8 @@ class Worker {
   // {seq}, {time}) are replaced from the meta of the frame actually picked. The ring slot is never
   // written.
   bool read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
-                         const std::string& name, FrameMeta* meta, std::string& out, int width = 0, int height = 0);
+                         const std::string& name, FrameMeta* meta, std::string& out, int width = 0, int height = 0,
+                         const clahe::Params* enhance = nullptr);
   // read_wall_jpeg with labels[t] (non-empty) drawn at the top-left corner of every tile that
   // shows a frame, as a text at auto scale for the tile's height over black at alpha 160, clipped
   // to the tile's cell: one in-place launch on the composed canvas. At most
@@ -862,7 +874,8 @@ class Worker {
   // ring slot -> ow x oh at the origin of set's canvas, on the serving stream (no wait)
   void scale_slot(gpu::ScaleSet& set, const FrameRing& ring, int slot, int ow, int oh);
   template <class Consume>  // the scaled read of read_latest_scaled and read_latest_jpeg (serve.cpp)
-  bool read_scaled(int cam, i64 after, int width, int height, bool download, FrameMeta* meta, Consume&& consume);
+  bool read_scaled(int cam, i64 after, int width, int height, bool download, FrameMeta* meta,
+                   const clahe::Params* enhance, Consume&& consume);
   u8* cons_hwc_ = nullptr;
   void* cons_chw_ = nullptr;
   // consumer snapshots: exclusive while a snapshot is enqueued, shared while a lane enqueues a
@@ -940,6 +953,11 @@ class Worker {
   // views (after the overlay's members)
   gpu::DewarpPool dewarp_pool_;  // descriptors, meshes and outputs of the view reads, one set per request in flight
   struct ViewOp;  // as CropOp
+  // contrast enhancement (after the views' members)
+  gpu::ClahePool clahe_pool_;  // descriptors, planes and a picture, one set per request in flight
+  std::atomic<u64> enhance_requests_{0};
+  void enhance_device(gpu::ClaheSet& set, const u8* src, size_t src_bytes, u8* dst, size_t dst_bytes, int w, int h,
+                      const clahe::Params& p);
   void wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
                  const std::vector<ForeignTile>& foreign, const std::vector<std::string>* labels,
                  std::vector<i64>& seqs_out, std::string& out);

@@ -1,10 +1,11 @@
 // The serving reads: the Worker methods that answer a client from a camera's ring (frames, scaled
-// frames, JPEGs, the wall, history, motion, tamper and crops), the serve-buffer pool they copy
+// and enhanced frames, JPEGs, the wall, history, motion, tamper and crops), the serve-buffer pool they copy
 // through, and the VideoFrame wire encoding. Every read follows the consistent-read rule of
 // ring_read.h.
 #include <algorithm>
 #include <cstring>
 
+#include "clahe.h"
 #include "crop.h"
 #include "dewarp.h"
 #include "jpeg.h"
@@ -51,11 +52,24 @@ void Worker::scale_slot(gpu::ScaleSet& set, const FrameRing& ring, int slot, int
   set.run(1, serve_stream_);
 }
 
+// Enhancement of the picture that is served (clahe.h, docs/ENHANCE.md): the three launches on the
+// serving stream, behind the scale and ahead of the overlay and the encoder; in place when dst is
+// src. The caller holds the set until it has waited for the stream.
+void Worker::enhance_device(gpu::ClaheSet& set, const u8* src, size_t src_bytes, u8* dst, size_t dst_bytes, int w, int h,
+                            const clahe::Params& p) {
+  size_t tile_at = 0;
+  set.put(0, src, src_bytes, u32(w) * 3, dst, dst_bytes, u32(w) * 3, w, h, p, tile_at);
+  set.run(1, serve_stream_);
+}
+
 // The newest frame with seq > after, fitted into width x height: consume(set, host, f) gets the
 // f.w x f.h picture, on a GPU in set->canvas (scaled on the serving stream, not waited for; the
 // set has `download` times its bytes of pinned room), on the CPU backend in `host` (set null).
+// enhance (non-null): the scaled picture is enhanced in place before consume sees it.
 template <class Consume>
-bool Worker::read_scaled(int cam, i64 after, int width, int height, bool download, FrameMeta* meta, Consume&& consume) {
+bool Worker::read_scaled(int cam, i64 after, int width, int height, bool download, FrameMeta* meta,
+                         const clahe::Params* enhance, Consume&& consume) {
+  if (enhance) clahe::check_params(*enhance);
   VEP_CHECK(width >= 0 && width <= scale::kMaxSide && height >= 0 && height <= scale::kMaxSide && (width || height),
             "scale: width and height must be 1..65535");
   std::shared_ptr<Camera> c = camera(cam);
@@ -71,23 +85,32 @@ bool Worker::read_scaled(int cam, i64 after, int width, int height, bool downloa
       gpu::ScalePool::Lease set = scale_pool_.acquire();
       set->reserve(n, 1, download ? n : 0);
       scale_slot(*set, *ring, slot, f.w, f.h);
+      gpu::ClahePool::Lease eq;  // (after the scale's set; held until consume has waited for the stream)
+      if (enhance) {
+        eq = clahe_pool_.acquire();
+        eq->reserve(1, gpu::clahe_tiles(f.w, f.h, enhance->tile), 0, 0);
+        enhance_device(*eq, set->canvas.p, n, set->canvas.p, n, f.w, f.h, *enhance);
+      }
       consume(set.get(), host, f);
     } else {
       host.resize(n);
       scale::area_cpu(ring->slot_ptr(slot), ring->width(), ring->height(), size_t(ring->width()) * 3, host.data(),
                       size_t(f.w) * 3, f.w, f.h);
+      if (enhance) clahe::enhance_cpu(host.data(), size_t(f.w) * 3, host.data(), size_t(f.w) * 3, f.w, f.h, *enhance);
       consume(nullptr, host, f);
     }
   });
   if (ok) {
     meta->width = f.w;
     meta->height = f.h;
+    if (enhance) enhance_requests_ += 1;
   }
   return ok;
 }
 
-bool Worker::read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst) {
-  return read_scaled(cam, after, width, height, true, meta, [&](gpu::ScaleSet* set, std::vector<u8>& host, scale::Size f) {
+bool Worker::read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst,
+                                const clahe::Params* enhance) {
+  return read_scaled(cam, after, width, height, true, meta, enhance, [&](gpu::ScaleSet* set, std::vector<u8>& host, scale::Size f) {
     if (!set) {
       dst.swap(host);
       return;
@@ -346,11 +369,40 @@ void Worker::wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, i
   encode_device(set->canvas.p, g.w, g.h, quality, out);
 }
 
+bool Worker::read_latest_enhanced(int cam, i64 after, int width, int height, const clahe::Params& p, FrameMeta* meta,
+                                  std::vector<u8>& dst) {
+  if (width || height) return read_latest_scaled(cam, after, width, height, meta, dst, &p);
+  clahe::check_params(p);
+  std::shared_ptr<Camera> c = camera(cam);
+  if (!c) return false;
+  std::shared_ptr<FrameRing> ring = c->ring();
+  if (!ring) return false;
+  const int w = ring->width(), h = ring->height();
+  const size_t n = ring->slot_bytes();
+  const bool ok = read_consistent(*ring, after, meta, [&](int slot, const FrameMeta&) {
+    dst.resize(n);
+    if (!dev_.gpu()) {
+      clahe::enhance_cpu(ring->slot_ptr(slot), size_t(w) * 3, dst.data(), size_t(w) * 3, w, h, p);
+      return;
+    }
+    dev_.bind();
+    gpu::ClahePool::Lease eq = clahe_pool_.acquire();
+    eq->reserve(1, gpu::clahe_tiles(w, h, p.tile), n, n);
+    enhance_device(*eq, ring->slot_ptr(slot), n, eq->picture.p, n, w, h, p);
+    VEP_HIP(hipMemcpyAsync(eq->host.p, eq->picture.p, n, hipMemcpyDeviceToHost, serve_stream_));
+    VEP_HIP(hipEventRecord(eq->ev, serve_stream_));  // (again: after the copy)
+    VEP_HIP(hipEventSynchronize(eq->ev));
+    std::memcpy(dst.data(), eq->host.p, n);
+  });
+  if (ok) enhance_requests_ += 1;
+  return ok;
+}
+
 bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width,
-                              int height) {
+                              int height, const clahe::Params* enhance) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
   if (width || height)
-    return read_scaled(cam, after, width, height, false, meta,
+    return read_scaled(cam, after, width, height, false, meta, enhance,
                        [&](gpu::ScaleSet* set, std::vector<u8>& host, scale::Size f) {
                          // (GPU: the same stream, so the encode is ordered after the scale)
                          if (set) encode_device(set->canvas.p, f.w, f.h, quality, out);
@@ -361,6 +413,25 @@ bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, 
   std::shared_ptr<FrameRing> ring = c->ring();
   if (!ring) return false;
   const int w = ring->width(), h = ring->height();
+  if (enhance) {  // out of place from the slot, which is never written; the encoder chained behind
+    clahe::check_params(*enhance);
+    const size_t n = ring->slot_bytes();
+    const bool ok = read_consistent(*ring, after, meta, [&](int slot, const FrameMeta&) {
+      if (!dev_.gpu()) {
+        std::vector<u8> host(n);
+        clahe::enhance_cpu(ring->slot_ptr(slot), size_t(w) * 3, host.data(), size_t(w) * 3, w, h, *enhance);
+        out = jpeg::encode_cpu(host.data(), w, h, quality);
+        return;
+      }
+      dev_.bind();
+      gpu::ClahePool::Lease eq = clahe_pool_.acquire();
+      eq->reserve(1, gpu::clahe_tiles(w, h, enhance->tile), n, 0);
+      enhance_device(*eq, ring->slot_ptr(slot), n, eq->picture.p, n, w, h, *enhance);
+      encode_device(eq->picture.p, w, h, quality, out);
+    });
+    if (ok) enhance_requests_ += 1;
+    return ok;
+  }
   return read_consistent(*ring, after, meta, [&](int slot, const FrameMeta&) {
     if (!dev_.gpu()) {
       out = jpeg::encode_cpu(ring->slot_ptr(slot), w, h, quality);
@@ -376,8 +447,10 @@ bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, 
 }
 
 bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
-                               const std::string& name, FrameMeta* meta, std::string& out, int width, int height) {
+                               const std::string& name, FrameMeta* meta, std::string& out, int width, int height,
+                               const clahe::Params* enhance) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  if (enhance) clahe::check_params(*enhance);
   VEP_CHECK(width >= 0 && width <= scale::kMaxSide && height >= 0 && height <= scale::kMaxSide,
             "scale: width and height must be 1..65535");
   overlay::check_list(items.data(), int(items.size()));
@@ -398,8 +471,9 @@ bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vecto
     drawn = e.prims.size();
     if (!dev_.gpu()) {
       std::vector<u8> host(n);
-      if (scaled) {
-        scale::area_cpu(ring->slot_ptr(slot), w, h, size_t(w) * 3, host.data(), row, f.w, f.h);
+      if (scaled || enhance) {
+        if (scaled) scale::area_cpu(ring->slot_ptr(slot), w, h, size_t(w) * 3, host.data(), row, f.w, f.h);
+        if (enhance) clahe::enhance_cpu(scaled ? host.data() : ring->slot_ptr(slot), row, host.data(), row, f.w, f.h, *enhance);
         overlay::apply_cpu(host.data(), row, host.data(), row, f.w, f.h, e.prims.data(), int(e.prims.size()), text,
                            e.text.size());
       } else {
@@ -410,21 +484,28 @@ bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vecto
       return;
     }
     dev_.bind();
-    // (every request takes its sets in one order: scale, overlay, encoder)
+    // (every request takes its sets in one order: scale, clahe, overlay, encoder)
     gpu::ScalePool::Lease set;
     if (scaled) {
       set = scale_pool_.acquire();
       set->reserve(n, 1, 0);
     }
+    gpu::ClahePool::Lease eq;
+    if (enhance) {
+      eq = clahe_pool_.acquire();
+      eq->reserve(1, gpu::clahe_tiles(f.w, f.h, enhance->tile), scaled ? 0 : n, 0);
+    }
     gpu::OverlayPool::Lease osd = overlay_pool_.acquire();
-    osd->reserve(1, e.prims.size(), e.text.size(), scaled ? 0 : n);
+    osd->reserve(1, e.prims.size(), e.text.size(), scaled || enhance ? 0 : n);
     size_t prim_at = 0, text_at = 0;
-    if (scaled) {
-      scale_slot(*set, *ring, slot, f.w, f.h);
-      // (the same stream: drawn after the scale, encoded after the drawing)
-      osd->put(0, set->canvas.p, n, u32(row), set->canvas.p, n, u32(row), f.w, f.h, e, prim_at, text_at);
+    if (scaled || enhance) {
+      // (the same stream: enhanced after the scale, drawn after that, encoded after the drawing)
+      u8* pic = scaled ? set->canvas.p : eq->picture.p;  // the scaler's canvas, or the slot's enhanced copy
+      if (scaled) scale_slot(*set, *ring, slot, f.w, f.h);
+      if (enhance) enhance_device(*eq, scaled ? pic : ring->slot_ptr(slot), n, pic, n, f.w, f.h, *enhance);
+      osd->put(0, pic, n, u32(row), pic, n, u32(row), f.w, f.h, e, prim_at, text_at);
       osd->run(1, prim_at, text_at, serve_stream_);
-      encode_device(set->canvas.p, f.w, f.h, quality, out);
+      encode_device(pic, f.w, f.h, quality, out);
     } else {
       osd->put(0, ring->slot_ptr(slot), ring->slot_bytes(), u32(row), osd->picture.p, n, u32(row), w, h, e, prim_at,
                text_at);
@@ -435,6 +516,7 @@ bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vecto
   if (ok) {
     overlay_requests_ += 1;
     overlay_prims_ += drawn;
+    if (enhance) enhance_requests_ += 1;
   }
   if (ok && scaled) {
     meta->width = f.w;

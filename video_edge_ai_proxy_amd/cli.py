@@ -109,7 +109,7 @@ def write_frame(path: str, img) -> None:
 
 
 def frame_jpg_url(a) -> str:
-    """The frame.jpg request of ``vep frame --overlay / --stamp``."""
+    """The frame.jpg request of ``vep frame --overlay / --stamp / --enhance``."""
     import urllib.parse
 
     q = {}
@@ -117,6 +117,11 @@ def frame_jpg_url(a) -> str:
         q["overlay"] = "1"
     if a.stamp:
         q["stamp"] = "1"
+    if a.enhance:
+        q["enhance"] = "clahe"
+        for k in ("clip", "tile", "strength"):
+            if getattr(a, k) is not None:
+                q[k] = str(getattr(a, k))
     for k in ("width", "height"):
         if getattr(a, k) is not None:
             q[k] = str(getattr(a, k))
@@ -132,7 +137,7 @@ def cmd_frame_osd(a):
     import urllib.request
 
     if not a.out or not a.out.lower().endswith((".jpg", ".jpeg")):
-        raise SystemExit("frame: --overlay / --stamp write a JPEG: --out FILE.jpg")
+        raise SystemExit("frame: --overlay / --stamp / --enhance write a JPEG: --out FILE.jpg")
     try:
         with urllib.request.urlopen(frame_jpg_url(a), timeout=10) as r:
             jpg, seq = r.read(), r.headers.get("X-Vep-Seq")
@@ -184,7 +189,9 @@ def cmd_overlay(a):
 
 
 def cmd_frame(a):
-    if a.overlay or a.stamp:
+    if not a.enhance and (a.clip is not None or a.tile is not None or a.strength is not None):
+        raise SystemExit("frame: --clip, --tile and --strength go with --enhance")
+    if a.overlay or a.stamp or a.enhance:
         return cmd_frame_osd(a)
     import numpy as np
 
@@ -512,7 +519,13 @@ def build_parser():
             p.add_argument("--overlay", action="store_true",
                            help="draw the camera's stored overlay list (the JPEG then comes from the hub's REST API)")
             p.add_argument("--stamp", action="store_true", help="draw the camera's name and the frame's time, likewise")
-            p.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API (--overlay / --stamp)")
+            p.add_argument("--enhance", action="store_true",
+                           help="raise the contrast of a dark scene (CLAHE on luma, on the hub's GPU), likewise")
+            p.add_argument("--clip", type=float, default=None, help="--enhance: clip limit 1.0..256.0 (hub default 2.0)")
+            p.add_argument("--tile", type=int, default=None, help="--enhance: tile side 32..256, a multiple of 8 (hub default 128)")
+            p.add_argument("--strength", type=float, default=None, help="--enhance: 0..1 (hub default 1.0)")
+            p.add_argument("--rest", default="127.0.0.1:8080",
+                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance)")
         if name == "annotate":
             p.add_argument("--type", required=True)
         if name in ("storage", "proxy"):

@@ -152,6 +152,15 @@ class OverlayConfig:
 
 
 @dataclass
+class EnhanceConfig:
+    """Hub-wide defaults of the contrast enhancement (``frame.jpg?enhance=clahe``,
+    docs/ENHANCE.md); a request overrides any of them."""
+    tile: int = 128        # 32..256, a multiple of 8
+    clip: float = 2.0      # 1.0..256.0 times the mean bin height
+    strength: float = 1.0  # 0..1
+
+
+@dataclass
 class Config:
     version: str = "0.1.0"
     title: str = "vep MI355X video edge hub"
@@ -169,6 +178,7 @@ class Config:
     motion: MotionConfig = field(default_factory=MotionConfig)
     tamper: TamperConfig = field(default_factory=TamperConfig)
     overlay: OverlayConfig = field(default_factory=OverlayConfig)
+    enhance: EnhanceConfig = field(default_factory=EnhanceConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
     bus_tag: str = ""
 
@@ -246,6 +256,11 @@ def validate(cfg: Config) -> None:
     v = cfg.overlay.annotation_ttl_ms
     if isinstance(v, bool) or not isinstance(v, int) or v < 1:
         raise ValueError(f"overlay.annotation_ttl_ms must be an integer >= 1, got {v!r}")
+    try:
+        from . import enhance
+        enhance.to_native(cfg.enhance.tile, cfg.enhance.clip, cfg.enhance.strength)
+    except ValueError as e:
+        raise ValueError(f"enhance: {e}") from None
     for key, (lo, hi) in MOTION_RANGES.items():
         v = getattr(cfg.motion, key)
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:

@@ -19,6 +19,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 from .. import crops, privacy, views
+from .. import enhance as enhance_params
 from .. import overlay as osd
 from .._native import gpu_count, native
 from ..config import Config, parse_tile
@@ -358,7 +359,8 @@ class Hub:
         return out[0], out[1]
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
-                    width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False):
+                    width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False,
+                    enhance=None):
         """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
         Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
         ``quality`` 1..100, default ``serving.jpeg_quality``. With ``width`` and / or ``height``
@@ -369,13 +371,21 @@ class Hub:
         items (:mod:`..overlay`, docs/OVERLAY.md); ``stamp`` appends the camera's name and the
         frame's time. They are drawn on a copy (scaled: on the scaled picture) in one kernel launch
         on the camera's GPU; the ring slot is never written. With neither, the call and its bytes
-        are what they are without them."""
+        are what they are without them.
+
+        ``enhance``: ``True`` (the hub's ``enhance:`` defaults) or a dict with any of ``tile``,
+        ``clip`` and ``strength`` (:mod:`..enhance`, docs/ENHANCE.md) raises the contrast of a dark
+        scene first, by CLAHE on luma on the camera's GPU: after the scale, before the overlay and
+        the encoder. ``None``: the call and its bytes are what they are without it."""
         q = self._quality(quality)
         bw, bh = self._box(width, height)
         if not isinstance(stamp, bool):
             raise ValueError("stamp must be true or false")
+        eq = enhance_params.from_request(enhance, self.enhance_defaults())
         w, cam = self.worker_of(name)
         if (overlay is None or overlay is False) and not stamp:
+            if eq is not None:
+                return w.read_latest_jpeg(cam, after, q, bw, bh, eq)
             if not (bw or bh):
                 return w.read_latest_jpeg(cam, after, q)
             return w.read_latest_jpeg(cam, after, q, bw, bh)
@@ -387,7 +397,30 @@ class Hub:
             items = osd.normalize_list(overlay)
         if stamp:
             items = items + [osd.STAMP]
+        if eq is not None:
+            return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh, eq)
         return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh)
+
+    # ------------------------------------------------------------------ contrast enhancement
+    def enhance_defaults(self) -> dict:
+        """The hub-wide ``tile``, ``clip`` and ``strength`` (the config's ``enhance:`` section)."""
+        e = self.cfg.enhance
+        return {"tile": e.tile, "clip": e.clip, "strength": e.strength}
+
+    def latest_enhanced(self, name: str, after: int = 0, width: int = 0, height: int = 0, **params):
+        """``(seq, ndarray)`` of the newest frame with seq > after, contrast-enhanced on the camera's
+        GPU (CLAHE on luma, docs/ENHANCE.md), or None; ``width`` / ``height`` (0: not given) fit and
+        downscale it first. ``params``: any of ``tile``, ``clip``, ``strength``; the rest are the
+        hub's defaults. Only the enhanced picture is copied to the host."""
+        eq = enhance_params.from_request(params or True, self.enhance_defaults())
+        bw, bh = self._box(width or None, height or None)
+        w, cam = self.worker_of(name)
+        r = w.read_latest_enhanced(cam, after, bw, bh, *eq)
+        return None if r is None else (int(r[0]["seq"]), r[1])
+
+    def enhance_count(self) -> int:
+        """Enhanced pictures served since the hub started (/metrics)."""
+        return sum(int(w.enhance_count()) for w in self.workers)
 
     # ------------------------------------------------------------------ on-screen display
     def set_overlay(self, name: str, items, ttl_ms: int = 0) -> None:

@@ -569,14 +569,23 @@ class ProcessHub:
         return self._call(name, "latest_frame", after)
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
-                    width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False):
+                    width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False,
+                    enhance=None):
         """(meta, JPEG bytes) or None: the worker process scales (width / height given) and encodes
         on its GPU, only the compressed bytes cross the pipe."""
         if overlay is not None or stamp:
             raise NotImplementedError("overlays are not served with gpu.isolation: process")
+        if enhance is not None and enhance is not False:
+            raise NotImplementedError("enhanced frames are not served with gpu.isolation: process")
         if width is None and height is None:
             return self._call(name, "latest_jpeg", after, quality)
         return self._call(name, "latest_jpeg", after, quality, width, height)
+
+    def latest_enhanced(self, name: str, after: int = 0, width: int = 0, height: int = 0, **params):
+        raise NotImplementedError("enhanced frames are not served with gpu.isolation: process")
+
+    def enhance_count(self) -> int:
+        return 0
 
     def latest_scaled(self, name: str, after: int = 0, width: Optional[int] = None,
                       height: Optional[int] = None):

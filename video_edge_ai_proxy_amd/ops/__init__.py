@@ -30,6 +30,10 @@
   positions (a dewarped fisheye view, an undistorted picture, any per-pixel mapping), every view
   of the call in a single launch (the kernel behind ``/view`` and ``view.jpg``), byte-identical
   with :func:`remap_reference`.
+* :func:`clahe` / :func:`clahe_batch` — BGR24 pictures contrast-enhanced by contrast-limited adaptive
+  histogram equalisation on luma (per-tile histograms, one LUT per tile, four LUTs blended per
+  pixel; three launches for every picture of the call: the kernels behind ``frame.jpg?enhance=clahe``);
+  a host tensor runs the CPU twin, whose bytes are the same.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -921,6 +925,87 @@ def overlay_draw_reference(bgr: torch.Tensor, items, name: str = "", meta=None) 
     out = src.copy()
     native.overlay_draw_cpu(src, out, overlay.to_native(items), name, meta)
     return torch.from_numpy(out)
+
+
+def _per_picture(v, n: int, what: str) -> list:
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError(f"{what} must hold one value per picture")
+        return list(v)
+    return [v] * n
+
+
+def clahe_batch(pictures, tile=128, clip=2.0, strength=1.0, outs=None, planes: bool = False):
+    """Contrast-limited adaptive histogram equalisation on luma (csrc/vep/clahe.h, docs/ENHANCE.md)
+    of a list of ``[H, W, 3]`` BGR24 tensors of any sizes. Device tensors (all on one device) run the
+    three gfx950 kernels, each ONE launch for the whole list; host tensors run the CPU twin, whose
+    bytes are the same. ``tile``, ``clip`` and ``strength`` (:mod:`..enhance`) are one value or one
+    per picture. A device picture's rows may start at any byte address and have any pitch. ``outs``
+    None: a new contiguous tensor per picture; else per picture a tensor of its size that receives
+    the result (the picture itself: IN PLACE), which must not overlap the picture otherwise.
+    Returns the results, with ``planes`` a list of ``(result, hist, lut)``: the ``[rows, cols, 256]``
+    per-tile luma histograms (int64) and LUTs (uint8). No CPU fallback for device tensors."""
+    from .. import enhance
+
+    pictures = list(pictures)
+    n = len(pictures)
+    if not n:
+        raise ValueError("pictures must hold at least one picture")
+    params = [enhance.to_native(t, c, s) for t, c, s in
+              zip(_per_picture(tile, n, "tile"), _per_picture(clip, n, "clip"), _per_picture(strength, n, "strength"))]
+    outs = [None] * n if outs is None else list(outs)
+    if len(outs) != n:
+        raise ValueError("outs must hold one entry per picture")
+    on_device = [isinstance(p, torch.Tensor) and p.is_cuda for p in pictures]
+    if any(on_device) != all(on_device):
+        raise ValueError("the pictures must all be device tensors or all host tensors")
+    res = []
+    if not on_device[0]:
+        for k, (bgr, p, out) in enumerate(zip(pictures, params, outs)):
+            _check_overlay_picture(bgr, f"pictures[{k}]")
+            o, hist, lut = native.clahe_cpu(bgr.detach().contiguous().numpy(), *p)
+            o = torch.from_numpy(o)
+            if out is not None:
+                if not isinstance(out, torch.Tensor) or out.is_cuda or out.dtype != torch.uint8 or out.shape != bgr.shape:
+                    raise ValueError(f"outs[{k}] must be a host uint8 tensor of the picture's shape")
+                out.copy_(o)
+                o = out
+            res.append((o, torch.from_numpy(hist.astype("int64")), torch.from_numpy(lut)) if planes else o)
+        return res
+    device, work, raw, spans = pictures[0].device, [], [], []
+    for k, (bgr, p, out) in enumerate(zip(pictures, params, outs)):
+        w, h, pitch = _check_overlay_picture(bgr, f"pictures[{k}]")
+        if bgr.device != device:
+            raise ValueError("the pictures must live on one device")
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+        ow, oh, dpitch = _check_overlay_picture(out, f"outs[{k}]")
+        if (ow, oh) != (w, h) or not out.is_cuda or out.device != device:
+            raise ValueError(f"outs[{k}] must be a [{h}, {w}, 3] tensor on the picture's device")
+        a, b = _overlay_span(bgr, w, h, pitch), _overlay_span(out, w, h, dpitch)
+        if (a[0] != b[0] or pitch != dpitch) and a[0] < b[1] and b[0] < a[1]:
+            raise ValueError(f"pictures[{k}] and outs[{k}] overlap")
+        for s in spans:
+            if b[0] < s[1] and s[0] < b[1]:
+                raise ValueError("the destinations of one call must not overlap")
+        spans.append(b)
+        cols, rows = -(-w // p[0]), -(-h // p[0])
+        hist = torch.empty((rows, cols, 256), dtype=torch.int32, device=device)
+        lut = torch.empty((rows, cols, 256), dtype=torch.uint8, device=device)
+        work.append((a[0], a[1] - a[0], pitch, b[0], b[1] - b[0], dpitch, w, h, *p,
+                     hist.data_ptr(), hist.numel(), lut.data_ptr(), lut.numel()))
+        raw.append((out, hist, lut))
+    require_gpu()
+    with torch.cuda.device(device):
+        native.clahe_device_batch(work, int(torch.cuda.current_stream(device).cuda_stream))
+    return [(o, _u32(hist), lut) if planes else o for o, hist, lut in raw]
+
+
+def clahe(bgr: torch.Tensor, tile: int = 128, clip: float = 2.0, strength: float = 1.0, out: torch.Tensor | None = None,
+          planes: bool = False):
+    """One ``[H, W, 3]`` BGR24 tensor contrast-enhanced: see :func:`clahe_batch`. A device tensor runs
+    the gfx950 kernels, a host tensor the CPU twin; ``out=bgr`` enhances in place."""
+    return clahe_batch([bgr], tile, clip, strength, None if out is None else [out], planes)[0]
 
 
 # ----------------------------------------------------------------------------- references

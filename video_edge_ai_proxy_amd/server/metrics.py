@@ -95,6 +95,11 @@ class HubCollector:
             opr = CounterMetricFamily("vep_overlay_primitives", "primitives the overlay requests drew")
             opr.add_metric([], prims)
             yield from (orq, opr)
+        count = getattr(self.hub, "enhance_count", None)
+        if count is not None:
+            er = CounterMetricFamily("vep_enhance_requests", "pictures served contrast-enhanced (frame.jpg, stream.mjpg, latest_enhanced)")
+            er.add_metric([], count())
+            yield er
         try:
             from .._native import native
 

@@ -23,7 +23,8 @@ normal, ``DELETE .../tamper`` forgets it), ``POST /api/v1/process/{name}/crops``
 ``PUT / GET / DELETE /api/v1/process/{name}/views``, ``GET .../view.jpg`` and ``POST .../view`` (a
 fisheye or wide-angle camera's lens and views, remapped on the GPU, docs/DEWARP.md),
 ``PUT / GET / DELETE /api/v1/process/{name}/overlay`` (a camera's stored on-screen display list,
-drawn with ``frame.jpg?overlay=1&stamp=1`` and ``wall.jpg?labels=1``, docs/OVERLAY.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
+drawn with ``frame.jpg?overlay=1&stamp=1`` and ``wall.jpg?labels=1``, docs/OVERLAY.md; ``frame.jpg`` and
+``stream.mjpg`` take ``enhance=clahe`` with ``clip``, ``tile`` and ``strength`` for dark scenes, docs/ENHANCE.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
 toolchain).
 """
 from __future__ import annotations
@@ -142,15 +143,33 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return {}
         return {"overlay": True if overlay else None, "stamp": bool(stamp)}
 
+    def enhanced(enhance, clip, tile, strength) -> dict:
+        """The enhancement argument of latest_jpeg (docs/ENHANCE.md): none when the request names
+        none of the four, so such a request calls the hub exactly as before."""
+        from .. import enhance as eq
+
+        if enhance is None and clip is None and tile is None and strength is None:
+            return {}
+        if enhance != "clahe":
+            raise ValueError("enhance must be clahe (clip, tile and strength go with it)")
+        given = {k: v for k, v in (("tile", tile), ("clip", clip), ("strength", strength)) if v is not None}
+        eq.from_request(given or True)  # (a bad value is refused before the hub is asked)
+        return {"enhance": given or True}
+
     @app.get("/api/v1/process/{name}/frame.jpg")
     def frame_jpg(name: str, quality: int | None = None, after: int = 0, width: int | None = None,
-                  height: int | None = None, overlay: int = 0, stamp: int = 0):
+                  height: int | None = None, overlay: int = 0, stamp: int = 0, enhance: str | None = None,
+                  clip: float | None = None, tile: int | None = None, strength: float | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
             size.update(osd(overlay, stamp))
         except ValueError as e:
             return err(400, str(e))
+        try:
+            size.update(enhanced(enhance, clip, tile, strength))
+        except ValueError as e:
+            return err(422, str(e))
         try:
             pm.hub.touch(name)
             r = pm.hub.latest_jpeg(name, after, q, **size)
@@ -167,7 +186,9 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
 
     @app.get("/api/v1/process/{name}/stream.mjpg")
     def stream_mjpg(name: str, fps: float = 10.0, frames: int | None = None, quality: int | None = None,
-                    width: int | None = None, height: int | None = None, overlay: int = 0, stamp: int = 0):
+                    width: int | None = None, height: int | None = None, overlay: int = 0, stamp: int = 0,
+                    enhance: str | None = None, clip: float | None = None, tile: int | None = None,
+                    strength: float | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -179,9 +200,15 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         except ValueError as e:
             return err(400, str(e))
         try:
+            size.update(enhanced(enhance, clip, tile, strength))
+        except ValueError as e:
+            return err(422, str(e))
+        try:
             pm.hub.touch(name)
         except KeyError:
             return err(404, f"process {name!r} not found")
+        if "enhance" in size and not hasattr(pm.hub, "enhance_defaults"):  # (501 before the stream starts)
+            return err(501, "enhanced frames are not served with gpu.isolation: process")
         if "stamp" in size:
             _, bad = overlay_call(pm.hub.overlay, name)  # (501 before the stream starts)
             if bad is not None:
