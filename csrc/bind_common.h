@@ -8,6 +8,7 @@
 #include "bind_ext.h"
 #include "vep/clahe.h"
 #include "vep/crop.h"
+#include "vep/denoise.h"
 #include "vep/dewarp.h"
 #include "vep/overlay.h"
 #include "vep/runtime.h"
@@ -277,6 +278,24 @@ inline bool enhance_of(const py::object& o, clahe::Params& p) {
   if (o.is_none()) return false;
   const auto t = o.cast<std::tuple<int, int, int>>();
   p = clahe_params_of(std::get<0>(t), std::get<1>(t), std::get<2>(t));
+  return true;
+}
+
+// Denoise parameters (vep/denoise.h) cross the boundary as three ints; a bad one is a ValueError.
+inline denoise::Params denoise_params_of(int frames, int level, int strength) {
+  const denoise::Params p{frames, level, strength};
+  try {
+    denoise::check_params(p);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return p;
+}
+// A serving read's `denoise` argument: None, or the tuple (frames, level, strength).
+inline bool denoise_of(const py::object& o, denoise::Params& p) {
+  if (o.is_none()) return false;
+  const auto t = o.cast<std::tuple<int, int, int>>();
+  p = denoise_params_of(std::get<0>(t), std::get<1>(t), std::get<2>(t));
   return true;
 }
 

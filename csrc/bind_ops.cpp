@@ -64,6 +64,44 @@ static void clahe_run(const std::vector<ClahePicture>& pics, uintptr_t stream) {
   });
 }
 
+// denoise_device_batch: every picture's job (its frames (address, bytes, pitch), newest first, and
+// its destination) checked against the sizes the caller states, then one launch on a pooled set.
+using DenoiseFrame = std::tuple<uintptr_t, size_t, u32>;
+using DenoisePicture = std::tuple<std::vector<DenoiseFrame>, uintptr_t, size_t, u32, int, int, int, int>;
+static void denoise_run(const std::vector<DenoisePicture>& pics, uintptr_t stream) {
+  const int n = int(pics.size());
+  if (n < 1 || pics.size() > 65535) throw py::value_error("denoise: 1..65535 pictures expected");
+  std::vector<denoise::Job> jobs((size_t(n)));
+  for (int k = 0; k < n; ++k) {
+    const auto& [frames, dst, dst_bytes, dst_pitch, w, h, level, strength] = pics[size_t(k)];
+    if (frames.empty() || frames.size() > size_t(denoise::kMaxFrames)) throw py::value_error("denoise: 1..8 frames expected");
+    denoise::Job& j = jobs[size_t(k)];
+    j.frames = int(frames.size());
+    for (int f = 0; f < j.frames; ++f) {
+      j.src[f] = reinterpret_cast<const u8*>(std::get<0>(frames[size_t(f)]));
+      j.src_bytes[f] = std::get<1>(frames[size_t(f)]);
+      j.src_pitch[f] = std::get<2>(frames[size_t(f)]);
+    }
+    j.dst = reinterpret_cast<u8*>(dst);
+    j.dst_bytes = dst_bytes;
+    j.dst_pitch = dst_pitch;
+    j.w = w;
+    j.h = h;
+    j.level = level;
+    j.strength = strength;
+    try {
+      denoise::check_job(j);
+    } catch (const Error& e) {
+      throw py::value_error(e.what());
+    }
+  }
+  on_pooled_set<gpu::DenoisePool>(stream, [&](gpu::DenoisePool::Lease& set, hipStream_t s) {
+    set->reserve(n, 0, 0);
+    for (int k = 0; k < n; ++k) set->put(k, jobs[size_t(k)]);
+    set->run(n, s);
+  });
+}
+
 // The checked descriptor of one picture of surface_to_bgr / surface_to_bgr_many, in their argument order.
 static gpu::SurfaceBgrDesc surface_bgr_desc(uintptr_t y, uintptr_t uv, int pitch, int coded_w, int coded_h, int bit_depth,
                                             int chroma_format, int crop_left, int crop_top, int out_w, int out_h,
@@ -699,6 +737,41 @@ void bind_ops(py::module_& m) {
         py::arg("src"), py::arg("src_bytes"), py::arg("src_pitch"), py::arg("dst"), py::arg("dst_bytes"),
         py::arg("dst_pitch"), py::arg("width"), py::arg("height"), py::arg("tile"), py::arg("clip16"), py::arg("strength"),
         py::arg("hist"), py::arg("hist_words"), py::arg("lut"), py::arg("lut_bytes"), py::arg("stream"));
+  // Temporal denoising (vep/denoise.h) on the host: the CPU backend's path, the byte-exact
+  // reference of denoise_device_batch. frames (K, H, W, 3), frames[0] the newest -> (H, W, 3).
+  m.def("denoise_cpu",
+        [](py::array_t<uint8_t, py::array::c_style> frames, int level, int strength) {
+          if (frames.ndim() != 4 || frames.shape(0) < 1 || frames.shape(0) > denoise::kMaxFrames || frames.shape(3) != 3 ||
+              !picture_size_ok(frames.shape(2), frames.shape(1)))
+            throw py::value_error("denoise_cpu: (K, H, W, 3) uint8 frames expected, K 1..8");
+          denoise_params_of(2, level, strength);
+          denoise::Job j;
+          j.frames = int(frames.shape(0));
+          j.h = int(frames.shape(1));
+          j.w = int(frames.shape(2));
+          const size_t row = size_t(j.w) * 3, bytes = row * size_t(j.h);
+          py::array_t<uint8_t> out({py::ssize_t(j.h), py::ssize_t(j.w), py::ssize_t(3)});
+          for (int k = 0; k < j.frames; ++k) {
+            j.src[k] = frames.data() + size_t(k) * bytes;
+            j.src_bytes[k] = bytes;
+            j.src_pitch[k] = u32(row);
+          }
+          j.dst = out.mutable_data();
+          j.dst_bytes = bytes;
+          j.dst_pitch = u32(row);
+          j.level = level;
+          j.strength = strength;
+          {
+            py::gil_scoped_release r;
+            denoise::denoise_cpu(j);
+          }
+          return out;
+        },
+        py::arg("frames").noconvert(), py::arg("level") = 8, py::arg("strength") = 256);
+  // Pictures ([(src, src_bytes, src_pitch), ...] newest first, dst, dst_bytes, dst_pitch, w, h,
+  // level, strength) on caller-owned device buffers: the gfx950 denoise kernel, ONE launch for all
+  // of them, on `stream` of the current device. Out of place only.
+  m.def("denoise_device_batch", &denoise_run, py::arg("pictures"), py::arg("stream"));
   // On-screen display (vep/overlay.h) on the host: the arithmetic itself, and the CPU backend's
   // path, the byte-exact reference of overlay_draw.
   m.def("overlay_font", [] {

@@ -2,6 +2,32 @@
 // wall, overlay, motion, tamper, privacy masks, crops, history and the serialized VideoFrames.
 #include "bind_common.h"
 
+// A serving read with the GIL released. What the read refuses about the request itself (an overlay
+// that expands to too many primitives, a denoise request on a ring without history) is a ValueError.
+template <class Read>
+static bool serve_released(Read&& read) {
+  std::string refused;
+  bool ok = false;
+  {
+    py::gil_scoped_release r;
+    try {
+      ok = read();
+    } catch (const Error& e) {
+      const std::string what = e.what();
+      if (what.find("overlay:") == std::string::npos && what.find("denoise:") == std::string::npos) throw;
+      refused = what;
+    }
+  }
+  if (!refused.empty()) throw py::value_error(refused);
+  return ok;
+}
+// The meta of a denoised read says how many frames were blended.
+static py::dict denoised_meta(const FrameMeta& m, bool denoised, int frames) {
+  py::dict d = meta_dict(m);
+  if (denoised) d["denoise_frames"] = frames;
+  return d;
+}
+
 void bind_worker_serving(py::class_<Worker>& cls) {
   cls
       .def("read_latest",
@@ -27,22 +53,48 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // width / height (0 = not given): fitted into that box and downscaled first; meta then
            // carries the scaled size.
            // enhance (None, or (tile, clip16, strength)): contrast-enhanced first (docs/ENHANCE.md).
-           [](Worker& w, int i, i64 after, int quality, int width, int height, py::object enhance) -> py::object {
+           // denoise (None, or (frames, level, strength)): blended with the ring's earlier frames before
+           // anything else (docs/DENOISE.md); meta then carries denoise_frames, how many were used.
+           [](Worker& w, int i, i64 after, int quality, int width, int height, py::object enhance,
+              py::object denoise) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              clahe::Params p;
              const bool eq = enhance_of(enhance, p);
+             denoise::Params dp;
+             const bool dn = denoise_of(denoise, dp);
              FrameMeta m;
              std::string out;
-             bool ok;
-             {
-               py::gil_scoped_release r;
-               ok = w.read_latest_jpeg(i, after, quality, &m, out, width, height, eq ? &p : nullptr);
-             }
+             int used = 0;
+             const bool ok = serve_released([&] {
+               return w.read_latest_jpeg(i, after, quality, &m, out, width, height, eq ? &p : nullptr, dn ? &dp : nullptr, &used);
+             });
              if (!ok) return py::none();
-             return py::make_tuple(meta_dict(m), py::bytes(out));
+             return py::make_tuple(denoised_meta(m, dn, used), py::bytes(out));
            },
            py::arg("idx"), py::arg("after") = 0, py::arg("quality") = 85, py::arg("width") = 0,
-           py::arg("height") = 0, py::arg("enhance") = py::none())
+           py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none())
+      .def("read_latest_denoised",
+           // (meta, ndarray) of the newest frame with seq > after, blended with up to frames - 1 earlier
+           // frames of the ring (docs/DENOISE.md); fitted into width x height afterwards when either is
+           // given; None if there is none. meta carries denoise_frames.
+           [](Worker& w, int i, i64 after, int width, int height, int frames, int level, int strength) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const denoise::Params p = denoise_params_of(frames, level, strength);
+             if (after < 0) throw py::value_error("denoise: after must be >= 0");
+             if (width < 0 || width > 65535 || height < 0 || height > 65535)
+               throw py::value_error("scale: width and height must be 1..65535 (0: not given)");
+             FrameMeta m;
+             std::vector<u8> px;
+             int used = 0;
+             if (!serve_released([&] { return w.read_latest_denoised(i, after, width, height, p, &m, px, &used); }))
+               return py::none();
+             py::array_t<uint8_t> a({py::ssize_t(m.height), py::ssize_t(m.width), py::ssize_t(3)});
+             std::memcpy(a.mutable_data(), px.data(), px.size());
+             return py::make_tuple(denoised_meta(m, true, used), a);
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("width") = 0, py::arg("height") = 0, py::arg("frames") = 4,
+           py::arg("level") = 8, py::arg("strength") = 256)
+      .def("denoise_count", [](Worker& w) { return w.denoise_count(); })
       .def("read_latest_enhanced",
            // (meta, ndarray) of the newest frame with seq > after, contrast-enhanced (docs/ENHANCE.md)
            // where it lies; fitted into width x height first when either is given; None if there is none.
@@ -70,21 +122,23 @@ void bind_worker_serving(py::class_<Worker>& cls) {
       .def("read_latest_scaled",
            // (meta, ndarray) of the newest frame with seq > after, fitted into width x height
            // (0 = that side not given) and downscaled where it lies; None if there is none.
-           [](Worker& w, int i, i64 after, int width, int height) -> py::object {
+           // denoise (None, or (frames, level, strength)): denoised first (docs/DENOISE.md).
+           [](Worker& w, int i, i64 after, int width, int height, py::object denoise) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
+             denoise::Params dp;
+             const bool dn = denoise_of(denoise, dp);
              FrameMeta m;
              std::vector<u8> px;
-             bool ok;
-             {
-               py::gil_scoped_release r;
-               ok = w.read_latest_scaled(i, after, width, height, &m, px);
-             }
+             int used = 0;
+             const bool ok = serve_released(
+                 [&] { return w.read_latest_scaled(i, after, width, height, &m, px, nullptr, dn ? &dp : nullptr, &used); });
              if (!ok) return py::none();
              py::array_t<uint8_t> a({py::ssize_t(m.height), py::ssize_t(m.width), py::ssize_t(3)});
              std::memcpy(a.mutable_data(), px.data(), px.size());
-             return py::make_tuple(meta_dict(m), a);
+             return py::make_tuple(denoised_meta(m, dn, used), a);
            },
-           py::arg("idx"), py::arg("after") = 0, py::arg("width") = 0, py::arg("height") = 0)
+           py::arg("idx"), py::arg("after") = 0, py::arg("width") = 0, py::arg("height") = 0,
+           py::arg("denoise") = py::none())
       .def("read_wall_jpeg",
            // (seqs, bytes): one JPEG of the newest frames of `cams` (camera indices; -1 = an empty
            // tile), tile t fitted into cell t of a cols-wide grid of tile_width x tile_height
@@ -141,36 +195,30 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // read_latest_jpeg with the overlay items drawn on the picture (docs/OVERLAY.md): {name},
            // {seq} and {time} come from `name` and the meta of the frame actually encoded.
            [](Worker& w, int i, const std::vector<ItemTuple>& items, const std::string& name, i64 after, int quality,
-              int width, int height, py::object enhance) -> py::object {
+              int width, int height, py::object enhance, py::object denoise) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              const std::vector<overlay::Item> its = items_of(items);
              clahe::Params p;
              const bool eq = enhance_of(enhance, p);
+             denoise::Params dp;
+             const bool dn = denoise_of(denoise, dp);
              if (after < 0) throw py::value_error("overlay: after must be >= 0");
              if (quality < 1 || quality > 100) throw py::value_error("jpeg: quality must be 1..100");
              if (width < 0 || width > 65535 || height < 0 || height > 65535)
                throw py::value_error("scale: width and height must be 1..65535 (0: not given)");
              FrameMeta m;
              std::string out;
-             bool ok;
-             std::string refused;
-             {
-               py::gil_scoped_release r;
-               try {
-                 ok = w.read_overlay_jpeg(i, after, quality, its, name, &m, out, width, height, eq ? &p : nullptr);
-               } catch (const Error& e) {
-                 // (only the expansion can refuse a checked list: too many primitives)
-                 if (std::string(e.what()).find("overlay:") == std::string::npos) throw;
-                 refused = e.what();
-                 ok = false;
-               }
-             }
-             if (!refused.empty()) throw py::value_error(refused);
+             int used = 0;
+             // (of a checked list only the expansion can be refused: too many primitives)
+             const bool ok = serve_released([&] {
+               return w.read_overlay_jpeg(i, after, quality, its, name, &m, out, width, height, eq ? &p : nullptr,
+                                          dn ? &dp : nullptr, &used);
+             });
              if (!ok) return py::none();
-             return py::make_tuple(meta_dict(m), py::bytes(out));
+             return py::make_tuple(denoised_meta(m, dn, used), py::bytes(out));
            },
            py::arg("idx"), py::arg("items"), py::arg("name") = "", py::arg("after") = 0, py::arg("quality") = 85,
-           py::arg("width") = 0, py::arg("height") = 0, py::arg("enhance") = py::none())
+           py::arg("width") = 0, py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none())
       .def("overlay_counts", [](Worker& w) { return w.overlay_counts(); })
       .def_property("wall_max_tiles", &Worker::wall_max_tiles, &Worker::set_wall_max_tiles)
       .def("read_motion",

@@ -15,6 +15,7 @@
 
 #include "clahe.h"
 #include "common.h"
+#include "denoise.h"
 #include "mask.h"
 #include "overlay.h"
 #include "scratch.h"
@@ -747,6 +748,45 @@ struct ClaheSet : DescSet<ClaheDesc> {
   void run(int n, hipStream_t s);
 };
 using ClahePool = ScratchPool<ClaheSet>;
+
+// ---- temporal denoising (gpu_denoise.hip; arithmetic: denoise.h) --------------------------------
+// One picture of a batched denoise request (device memory): `frames` packed BGR24 frames of one
+// size, src[0] the newest, blended into dst, byte-identical with denoise::denoise_cpu, in ONE launch
+// for every picture of the request. Out of place only: dst overlaps no source, and a source (a ring
+// slot) is never written. Pictures of one request may differ in size, frames and parameters; their
+// destinations must not overlap.
+struct DenoiseDesc {
+  const VEP_DEV u8* src[denoise::kMaxFrames];  // h rows of src_pitch[k] bytes each (any alignment)
+  VEP_DEV u8* dst;                             // h rows of dst_pitch bytes (any alignment)
+  u32 src_pitch[denoise::kMaxFrames];          // bytes
+  u32 dst_pitch;
+  i32 w, h;
+  i32 frames, level, strength;  // K, T, S of denoise.h
+  u32 recip9t;                  // denoise::reciprocal(9 * level)
+  u32 pad_;
+};
+static_assert(sizeof(DenoiseDesc) == 136, "DenoiseDesc layout");
+// The descriptor of a job (denoise::Job: sources, destination and their sizes), checked by
+// denoise::check_job: every access of the kernel lies inside a source or the destination, the
+// destination overlaps no source, and K, T and S are in range. The launch below does not check.
+DenoiseDesc check_denoise(const denoise::Job& j);
+// One launch for the n pictures on `s`: grid = (tiles of the largest picture) x pictures.
+// h_descs is the host copy of d_descs (the grid is sized from it).
+void launch_denoise(const DenoiseDesc* d_descs, const DenoiseDesc* h_descs, int n, hipStream_t s);
+
+// Denoise scratch of one device (pool contract: above): descriptors, a picture that receives a
+// frame's denoised copy (where the ring slot stood for the stages behind), and a pinned buffer
+// for results on their way down.
+struct DenoiseSet : DescSet<DenoiseDesc> {
+  DevBuf<u8> picture;
+  PinBuf<u8> host;
+  void reserve(int ndescs, size_t picture_bytes, size_t host_bytes);
+  // Descriptor k from a checked job.
+  void put(int k, const denoise::Job& j);
+  // Copies the first n host descriptors up, launches them on `s` and records the event (no wait).
+  void run(int n, hipStream_t s);
+};
+using DenoisePool = ScratchPool<DenoiseSet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

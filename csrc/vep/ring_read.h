@@ -53,6 +53,33 @@ bool read_consistent(const FrameRing& ring, i64 after, FrameMeta* meta, Produce&
   return read_consistent(ring, after, 0, meta, produce);
 }
 
+// Several slots of one ring (the temporal denoise, denoise.h): the rule above over all of them.
+//   pick   ring.range(after, frames)   the newest min(frames, available) frames with seq > after,
+//          contiguous in seq and ending at the newest; none: no answer. Fewer than asked for
+//          (start-up, or just after FrameRing::invalidate) means fewer are used;
+//   produce(have, *meta) from all of them   have[0] is the newest, *meta its meta;
+//   check  ring.still_valid for EVERY one of those slots.
+// One reused slot spoils the read: it starts again from the then newest frames, kReadAttempts
+// times in all. After invalidate() no earlier frame is readable, so what a privacy-mask change
+// withdrew is never blended into a later picture. *used: how many frames the good read used.
+template <class Produce>
+bool read_consistent_frames(const FrameRing& ring, i64 after, int frames, FrameMeta* meta, int* used, Produce&& produce) {
+  std::vector<std::pair<FrameMeta, int>> have;
+  for (int attempt = 0; attempt < kReadAttempts; ++attempt) {
+    if (ring.range(after, frames, have) < 1) return false;
+    std::reverse(have.begin(), have.end());  // newest first
+    *meta = have.front().first;
+    produce(have, *meta);
+    bool good = true;
+    for (const auto& f : have) good = good && ring.still_valid(f.second, f.first.seq);
+    if (good) {
+      *used = int(have.size());
+      return true;
+    }
+  }
+  return false;
+}
+
 // One ring of a batched read; an op's entry type derives from it.
 struct ReadEntry {
   std::shared_ptr<FrameRing> ring;

@@ -497,12 +497,25 @@ class Worker {
   // docs/ENHANCE.md): after the scale, in place on its canvas, or at native size out of place from
   // the slot into pooled scratch (the slot is never written); before the overlay and the encoder,
   // all on the serving stream. The CPU backend runs clahe::enhance_cpu. Null: path and bytes as ever.
+  // denoise (non-null): the frame is first blended with the ring's earlier frames (denoise.h,
+  // docs/DENOISE.md) into pooled scratch at native size, which then stands where the ring slot
+  // stood: denoise, scale, enhance, overlay, encoder, all on the serving stream; *denoise_frames
+  // is how many frames were used (fewer than asked for while the ring holds fewer; 1: the
+  // identity). A ring without history throws. Null: path and bytes as ever.
   bool read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width = 0,
-                        int height = 0, const clahe::Params* enhance = nullptr);
+                        int height = 0, const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
+                        int* denoise_frames = nullptr);
   // The same scaled picture as packed BGR24 in host memory (dst is resized to ow * oh * 3; only
   // those bytes are copied off the GPU); meta->width / height are the scaled size.
   bool read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst,
-                          const clahe::Params* enhance = nullptr);
+                          const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
+                          int* denoise_frames = nullptr);
+  // The denoised picture as packed BGR24 in host memory: scaled as read_latest_scaled, or with
+  // width = height = 0 at native size.
+  bool read_latest_denoised(int cam, i64 after, int width, int height, const denoise::Params& p, FrameMeta* meta,
+                            std::vector<u8>& dst, int* denoise_frames = nullptr);
+  // Denoised pictures served since the worker started.
+  u64 denoise_count() const { return denoise_requests_.load(); }
   // The enhanced picture as packed BGR24 in host memory: scaled as read_latest_scaled, or with
   // width = height = 0 at native size.
   bool read_latest_enhanced(int cam, i64 after, int width, int height, const clahe::Params& p, FrameMeta* meta,
@@ -532,7 +545,8 @@ class Worker {
   // written.
   bool read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
                          const std::string& name, FrameMeta* meta, std::string& out, int width = 0, int height = 0,
-                         const clahe::Params* enhance = nullptr);
+                         const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
+                         int* denoise_frames = nullptr);
   // read_wall_jpeg with labels[t] (non-empty) drawn at the top-left corner of every tile that
   // shows a frame, as a text at auto scale for the tile's height over black at alpha 160, clipped
   // to the tile's cell: one in-place launch on the composed canvas. At most
@@ -873,6 +887,8 @@ class Worker {
   void encode_device(const u8* d_bgr, int w, int h, int quality, std::string& out);
   // ring slot -> ow x oh at the origin of set's canvas, on the serving stream (no wait)
   void scale_slot(gpu::ScaleSet& set, const FrameRing& ring, int slot, int ow, int oh);
+  // the same from any packed sw x sh picture on the device (the denoised copy of a frame)
+  void scale_picture(gpu::ScaleSet& set, const u8* src, int sw, int sh, int ow, int oh);
   template <class Consume>  // the scaled read of read_latest_scaled and read_latest_jpeg (serve.cpp)
   bool read_scaled(int cam, i64 after, int width, int height, bool download, FrameMeta* meta,
                    const clahe::Params* enhance, Consume&& consume);
@@ -958,6 +974,21 @@ class Worker {
   std::atomic<u64> enhance_requests_{0};
   void enhance_device(gpu::ClaheSet& set, const u8* src, size_t src_bytes, u8* dst, size_t dst_bytes, int w, int h,
                       const clahe::Params& p);
+  // temporal denoise (after the enhancement's members)
+  gpu::DenoisePool denoise_pool_;  // descriptors and a picture, one set per request in flight
+  std::atomic<u64> denoise_requests_{0};
+  // One denoised read: what is asked of the picture behind the denoise, and where it goes (a JPEG
+  // of `quality`, or raw BGR when jpeg is null).
+  struct DenoisedRead {
+    const denoise::Params* dn = nullptr;
+    int width = 0, height = 0;
+    const clahe::Params* enhance = nullptr;
+    const std::vector<overlay::Item>* items = nullptr;  // with `name`: the overlay
+    const std::string* name = nullptr;
+    int quality = 0;
+  };
+  bool read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta* meta, int* used, std::string* jpeg,
+                     std::vector<u8>* raw);
   void wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
                  const std::vector<ForeignTile>& foreign, const std::vector<std::string>* labels,
                  std::vector<i64>& seqs_out, std::string& out);

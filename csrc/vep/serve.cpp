@@ -1,5 +1,5 @@
 // The serving reads: the Worker methods that answer a client from a camera's ring (frames, scaled
-// and enhanced frames, JPEGs, the wall, history, motion, tamper and crops), the serve-buffer pool they copy
+// enhanced and denoised frames, JPEGs, the wall, history, motion, tamper and crops), the serve-buffer pool they copy
 // through, and the VideoFrame wire encoding. Every read follows the consistent-read rule of
 // ring_read.h.
 #include <algorithm>
@@ -7,6 +7,7 @@
 
 #include "clahe.h"
 #include "crop.h"
+#include "denoise.h"
 #include "dewarp.h"
 #include "jpeg.h"
 #include "ring_read.h"
@@ -38,12 +39,16 @@ void Worker::encode_device(const u8* d_bgr, int w, int h, int quality, std::stri
 }
 
 void Worker::scale_slot(gpu::ScaleSet& set, const FrameRing& ring, int slot, int ow, int oh) {
+  scale_picture(set, ring.slot_ptr(slot), ring.width(), ring.height(), ow, oh);
+}
+
+void Worker::scale_picture(gpu::ScaleSet& set, const u8* src, int sw, int sh, int ow, int oh) {
   gpu::ScaleDesc& d = set.h_descs.p[0];
   d = gpu::ScaleDesc{};
-  d.src = ring.slot_ptr(slot);
-  d.sw = ring.width();
-  d.sh = ring.height();
-  d.src_pitch = u32(ring.width()) * 3;
+  d.src = src;
+  d.sw = sw;
+  d.sh = sh;
+  d.src_pitch = u32(sw) * 3;
   d.dst = set.canvas.p;
   d.dst_pitch = u32(ow) * 3;
   d.ow = ow;
@@ -109,7 +114,15 @@ bool Worker::read_scaled(int cam, i64 after, int width, int height, bool downloa
 }
 
 bool Worker::read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst,
-                                const clahe::Params* enhance) {
+                                const clahe::Params* enhance, const denoise::Params* denoise, int* denoise_frames) {
+  if (denoise) {
+    DenoisedRead rq;
+    rq.dn = denoise;
+    rq.width = width;
+    rq.height = height;
+    rq.enhance = enhance;
+    return read_denoised(cam, after, rq, meta, denoise_frames, nullptr, &dst);
+  }
   return read_scaled(cam, after, width, height, true, meta, enhance, [&](gpu::ScaleSet* set, std::vector<u8>& host, scale::Size f) {
     if (!set) {
       dst.swap(host);
@@ -398,9 +411,145 @@ bool Worker::read_latest_enhanced(int cam, i64 after, int width, int height, con
   return ok;
 }
 
+// A denoised read (denoise.h, docs/DENOISE.md): the newest frames of the ring, read under the
+// multi-slot rule of ring_read.h, are blended into the denoise set's picture at native size, and
+// from there on that picture stands where the ring slot stands in the other reads: scaled into
+// the scaler's canvas, enhanced and drawn on in place, then encoded or copied down, all on the
+// serving stream. The ring's slots are only read. The CPU backend does the same on the host.
+bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta* meta, int* used, std::string* jpeg,
+                           std::vector<u8>* raw) {
+  denoise::check_params(*rq.dn);
+  if (rq.enhance) clahe::check_params(*rq.enhance);
+  VEP_CHECK(rq.width >= 0 && rq.width <= scale::kMaxSide && rq.height >= 0 && rq.height <= scale::kMaxSide,
+            "scale: width and height must be 1..65535");
+  if (rq.items) overlay::check_list(rq.items->data(), int(rq.items->size()));
+  std::shared_ptr<Camera> c = camera(cam);
+  if (!c) return false;
+  std::shared_ptr<FrameRing> ring = c->ring();
+  if (!ring) return false;
+  VEP_CHECK(ring->history() >= 2, "denoise: the camera's ring keeps no history: buffer.in_memory must be 2 or more");
+  const int w = ring->width(), h = ring->height();
+  const bool scaled = rq.width || rq.height;
+  const scale::Size f = scaled ? scale::fit(w, h, rq.width, rq.height) : scale::Size{w, h};
+  const size_t native = ring->slot_bytes(), n = size_t(f.w) * size_t(f.h) * 3, row = size_t(f.w) * 3;
+  size_t drawn = 0;
+  int count = 0;
+  const bool ok = read_consistent_frames(
+      *ring, after, std::min(rq.dn->frames, ring->history()), meta, &count,
+      [&](const std::vector<std::pair<FrameMeta, int>>& have, const FrameMeta& m) {
+        denoise::Job j;
+        j.frames = int(have.size());
+        for (int k = 0; k < j.frames; ++k) {
+          j.src[k] = ring->slot_ptr(have[size_t(k)].second);
+          j.src_bytes[k] = native;
+          j.src_pitch[k] = u32(w) * 3;
+        }
+        j.dst_bytes = native;
+        j.dst_pitch = u32(w) * 3;
+        j.w = w;
+        j.h = h;
+        j.level = rq.dn->level;
+        j.strength = rq.dn->strength;
+        overlay::Expanded e;  // (the items meet the picture they are drawn on, and the newest frame's meta)
+        if (rq.items)
+          e = overlay::expand(rq.items->data(), int(rq.items->size()), f.w, f.h, *rq.name, overlay::Meta{m.seq, m.timestamp});
+        const u8* text = reinterpret_cast<const u8*>(e.text.data());
+        drawn = e.prims.size();
+        if (!dev_.gpu()) {
+          std::vector<u8> pic(native);
+          j.dst = pic.data();
+          denoise::denoise_cpu(j);
+          if (scaled) {
+            std::vector<u8> small(n);
+            scale::area_cpu(pic.data(), w, h, size_t(w) * 3, small.data(), row, f.w, f.h);
+            pic.swap(small);
+          }
+          if (rq.enhance) clahe::enhance_cpu(pic.data(), row, pic.data(), row, f.w, f.h, *rq.enhance);
+          if (rq.items)
+            overlay::apply_cpu(pic.data(), row, pic.data(), row, f.w, f.h, e.prims.data(), int(e.prims.size()), text,
+                               e.text.size());
+          if (jpeg) *jpeg = jpeg::encode_cpu(pic.data(), f.w, f.h, rq.quality);
+          else raw->swap(pic);
+          return;
+        }
+        dev_.bind();
+        // (every request takes its sets in one order: denoise, scale, clahe, overlay, encoder)
+        gpu::DenoisePool::Lease dn = denoise_pool_.acquire();
+        dn->reserve(1, native, raw ? n : 0);
+        gpu::ScalePool::Lease set;
+        if (scaled) {
+          set = scale_pool_.acquire();
+          set->reserve(n, 1, 0);
+        }
+        gpu::ClahePool::Lease eq;
+        if (rq.enhance) {
+          eq = clahe_pool_.acquire();
+          eq->reserve(1, gpu::clahe_tiles(f.w, f.h, rq.enhance->tile), 0, 0);
+        }
+        gpu::OverlayPool::Lease osd;
+        if (rq.items) {
+          osd = overlay_pool_.acquire();
+          osd->reserve(1, e.prims.size(), e.text.size(), 0);
+        }
+        // (the same stream: every stage is ordered behind the one before)
+        j.dst = dn->picture.p;
+        dn->put(0, j);
+        dn->run(1, serve_stream_);
+        u8* pic = dn->picture.p;
+        if (scaled) {
+          scale_picture(*set, pic, w, h, f.w, f.h);
+          pic = set->canvas.p;
+        }
+        if (rq.enhance) enhance_device(*eq, pic, n, pic, n, f.w, f.h, *rq.enhance);
+        if (rq.items) {
+          size_t prim_at = 0, text_at = 0;
+          osd->put(0, pic, n, u32(row), pic, n, u32(row), f.w, f.h, e, prim_at, text_at);
+          osd->run(1, prim_at, text_at, serve_stream_);
+        }
+        if (jpeg) {
+          encode_device(pic, f.w, f.h, rq.quality, *jpeg);
+          return;
+        }
+        VEP_HIP(hipMemcpyAsync(dn->host.p, pic, n, hipMemcpyDeviceToHost, serve_stream_));
+        VEP_HIP(hipEventRecord(dn->ev, serve_stream_));  // (again: after the copy)
+        VEP_HIP(hipEventSynchronize(dn->ev));
+        raw->assign(dn->host.p, dn->host.p + n);
+      });
+  if (!ok) return false;
+  if (used) *used = count;
+  meta->width = f.w;
+  meta->height = f.h;
+  denoise_requests_ += 1;
+  if (rq.enhance) enhance_requests_ += 1;
+  if (rq.items) {
+    overlay_requests_ += 1;
+    overlay_prims_ += drawn;
+  }
+  return true;
+}
+
+bool Worker::read_latest_denoised(int cam, i64 after, int width, int height, const denoise::Params& p, FrameMeta* meta,
+                                  std::vector<u8>& dst, int* denoise_frames) {
+  DenoisedRead rq;
+  rq.dn = &p;
+  rq.width = width;
+  rq.height = height;
+  return read_denoised(cam, after, rq, meta, denoise_frames, nullptr, &dst);
+}
+
 bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width,
-                              int height, const clahe::Params* enhance) {
+                              int height, const clahe::Params* enhance, const denoise::Params* denoise,
+                              int* denoise_frames) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  if (denoise) {
+    DenoisedRead rq;
+    rq.dn = denoise;
+    rq.width = width;
+    rq.height = height;
+    rq.enhance = enhance;
+    rq.quality = quality;
+    return read_denoised(cam, after, rq, meta, denoise_frames, &out, nullptr);
+  }
   if (width || height)
     return read_scaled(cam, after, width, height, false, meta, enhance,
                        [&](gpu::ScaleSet* set, std::vector<u8>& host, scale::Size f) {
@@ -448,8 +597,19 @@ bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, 
 
 bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
                                const std::string& name, FrameMeta* meta, std::string& out, int width, int height,
-                               const clahe::Params* enhance) {
+                               const clahe::Params* enhance, const denoise::Params* denoise, int* denoise_frames) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+  if (denoise) {
+    DenoisedRead rq;
+    rq.dn = denoise;
+    rq.width = width;
+    rq.height = height;
+    rq.enhance = enhance;
+    rq.items = &items;
+    rq.name = &name;
+    rq.quality = quality;
+    return read_denoised(cam, after, rq, meta, denoise_frames, &out, nullptr);
+  }
   if (enhance) clahe::check_params(*enhance);
   VEP_CHECK(width >= 0 && width <= scale::kMaxSide && height >= 0 && height <= scale::kMaxSide,
             "scale: width and height must be 1..65535");

@@ -109,7 +109,7 @@ def write_frame(path: str, img) -> None:
 
 
 def frame_jpg_url(a) -> str:
-    """The frame.jpg request of ``vep frame --overlay / --stamp / --enhance``."""
+    """The frame.jpg request of ``vep frame --overlay / --stamp / --enhance / --denoise``."""
     import urllib.parse
 
     q = {}
@@ -120,6 +120,11 @@ def frame_jpg_url(a) -> str:
     if a.enhance:
         q["enhance"] = "clahe"
         for k in ("clip", "tile", "strength"):
+            if getattr(a, k) is not None:
+                q[k] = str(getattr(a, k))
+    if a.denoise:
+        q["denoise"] = "1"
+        for k in ("nr_frames", "nr_level", "nr_strength"):
             if getattr(a, k) is not None:
                 q[k] = str(getattr(a, k))
     for k in ("width", "height"):
@@ -137,7 +142,7 @@ def cmd_frame_osd(a):
     import urllib.request
 
     if not a.out or not a.out.lower().endswith((".jpg", ".jpeg")):
-        raise SystemExit("frame: --overlay / --stamp / --enhance write a JPEG: --out FILE.jpg")
+        raise SystemExit("frame: --overlay / --stamp / --enhance / --denoise write a JPEG: --out FILE.jpg")
     try:
         with urllib.request.urlopen(frame_jpg_url(a), timeout=10) as r:
             jpg, seq = r.read(), r.headers.get("X-Vep-Seq")
@@ -191,7 +196,9 @@ def cmd_overlay(a):
 def cmd_frame(a):
     if not a.enhance and (a.clip is not None or a.tile is not None or a.strength is not None):
         raise SystemExit("frame: --clip, --tile and --strength go with --enhance")
-    if a.overlay or a.stamp or a.enhance:
+    if not a.denoise and (a.nr_frames is not None or a.nr_level is not None or a.nr_strength is not None):
+        raise SystemExit("frame: --nr-frames, --nr-level and --nr-strength go with --denoise")
+    if a.overlay or a.stamp or a.enhance or a.denoise:
         return cmd_frame_osd(a)
     import numpy as np
 
@@ -524,8 +531,14 @@ def build_parser():
             p.add_argument("--clip", type=float, default=None, help="--enhance: clip limit 1.0..256.0 (hub default 2.0)")
             p.add_argument("--tile", type=int, default=None, help="--enhance: tile side 32..256, a multiple of 8 (hub default 128)")
             p.add_argument("--strength", type=float, default=None, help="--enhance: 0..1 (hub default 1.0)")
+            p.add_argument("--denoise", action="store_true",
+                           help="blend the frame with the camera's earlier frames where the picture stands still "
+                                "(on the hub's GPU; needs buffer.in_memory >= 2), likewise")
+            p.add_argument("--nr-frames", type=int, default=None, help="--denoise: frames blended, 2..8 (hub default 4)")
+            p.add_argument("--nr-level", type=int, default=None, help="--denoise: noise floor 1..64 luma levels (hub default 8)")
+            p.add_argument("--nr-strength", type=float, default=None, help="--denoise: 0..1 (hub default 1.0)")
             p.add_argument("--rest", default="127.0.0.1:8080",
-                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance)")
+                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance / --denoise)")
         if name == "annotate":
             p.add_argument("--type", required=True)
         if name in ("storage", "proxy"):

@@ -161,6 +161,15 @@ class EnhanceConfig:
 
 
 @dataclass
+class DenoiseConfig:
+    """Hub-wide defaults of the temporal denoise (``frame.jpg?denoise=1``, docs/DENOISE.md); a
+    request overrides any of them. Needs ``buffer.in_memory`` >= 2."""
+    frames: int = 4        # 2..8 of the ring's newest frames
+    level: int = 8         # the noise floor, 1..64 luma levels
+    strength: float = 1.0  # 0..1
+
+
+@dataclass
 class Config:
     version: str = "0.1.0"
     title: str = "vep MI355X video edge hub"
@@ -179,6 +188,7 @@ class Config:
     tamper: TamperConfig = field(default_factory=TamperConfig)
     overlay: OverlayConfig = field(default_factory=OverlayConfig)
     enhance: EnhanceConfig = field(default_factory=EnhanceConfig)
+    denoise: DenoiseConfig = field(default_factory=DenoiseConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
     bus_tag: str = ""
 
@@ -261,6 +271,11 @@ def validate(cfg: Config) -> None:
         enhance.to_native(cfg.enhance.tile, cfg.enhance.clip, cfg.enhance.strength)
     except ValueError as e:
         raise ValueError(f"enhance: {e}") from None
+    try:
+        from . import denoise
+        denoise.to_native(cfg.denoise.frames, cfg.denoise.level, cfg.denoise.strength)
+    except ValueError as e:
+        raise ValueError(f"denoise: {e}") from None
     for key, (lo, hi) in MOTION_RANGES.items():
         v = getattr(cfg.motion, key)
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:

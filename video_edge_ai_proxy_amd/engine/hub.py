@@ -19,6 +19,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 from .. import crops, privacy, views
+from .. import denoise as denoise_params
 from .. import enhance as enhance_params
 from .. import overlay as osd
 from .._native import gpu_count, native
@@ -360,7 +361,7 @@ class Hub:
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
                     width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False,
-                    enhance=None):
+                    enhance=None, denoise=None):
         """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
         Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
         ``quality`` 1..100, default ``serving.jpeg_quality``. With ``width`` and / or ``height``
@@ -376,14 +377,24 @@ class Hub:
         ``enhance``: ``True`` (the hub's ``enhance:`` defaults) or a dict with any of ``tile``,
         ``clip`` and ``strength`` (:mod:`..enhance`, docs/ENHANCE.md) raises the contrast of a dark
         scene first, by CLAHE on luma on the camera's GPU: after the scale, before the overlay and
-        the encoder. ``None``: the call and its bytes are what they are without it."""
+        the encoder. ``None``: the call and its bytes are what they are without it.
+
+        ``denoise``: ``True`` (the hub's ``denoise:`` defaults) or a dict with any of ``frames``,
+        ``level`` and ``strength`` (:mod:`..denoise`, docs/DENOISE.md) first blends the frame with the
+        ring's earlier frames where the picture stands still, on the camera's GPU: ahead of the
+        scale, the enhancement, the overlay and the encoder. ``meta["denoise_frames"]`` says how many
+        frames were used. Needs ``buffer.in_memory`` >= 2 (else a ``ValueError``). ``None``: the call
+        and its bytes are what they are without it."""
         q = self._quality(quality)
         bw, bh = self._box(width, height)
         if not isinstance(stamp, bool):
             raise ValueError("stamp must be true or false")
         eq = enhance_params.from_request(enhance, self.enhance_defaults())
+        dn = denoise_params.from_request(denoise, self.denoise_defaults())
         w, cam = self.worker_of(name)
         if (overlay is None or overlay is False) and not stamp:
+            if dn is not None:
+                return w.read_latest_jpeg(cam, after, q, bw, bh, eq, dn)
             if eq is not None:
                 return w.read_latest_jpeg(cam, after, q, bw, bh, eq)
             if not (bw or bh):
@@ -397,6 +408,8 @@ class Hub:
             items = osd.normalize_list(overlay)
         if stamp:
             items = items + [osd.STAMP]
+        if dn is not None:
+            return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh, eq, dn)
         if eq is not None:
             return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh, eq)
         return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh)
@@ -421,6 +434,28 @@ class Hub:
     def enhance_count(self) -> int:
         """Enhanced pictures served since the hub started (/metrics)."""
         return sum(int(w.enhance_count()) for w in self.workers)
+
+    # ------------------------------------------------------------------ temporal denoise
+    def denoise_defaults(self) -> dict:
+        """The hub-wide ``frames``, ``level`` and ``strength`` (the config's ``denoise:`` section)."""
+        d = self.cfg.denoise
+        return {"frames": d.frames, "level": d.level, "strength": d.strength}
+
+    def latest_denoised(self, name: str, after: int = 0, width: int = 0, height: int = 0, **params):
+        """``(seq, ndarray)`` of the newest frame with seq > after, blended on the camera's GPU with
+        the ring's earlier frames where the picture stands still (docs/DENOISE.md), or None;
+        ``width`` / ``height`` (0: not given) fit and downscale the result. ``params``: any of
+        ``frames``, ``level``, ``strength``; the rest are the hub's defaults. Only the denoised
+        picture is copied to the host. Needs ``buffer.in_memory`` >= 2 (else a ``ValueError``)."""
+        dn = denoise_params.from_request(params or True, self.denoise_defaults())
+        bw, bh = self._box(width or None, height or None)
+        w, cam = self.worker_of(name)
+        r = w.read_latest_denoised(cam, after, bw, bh, *dn)
+        return None if r is None else (int(r[0]["seq"]), r[1])
+
+    def denoise_count(self) -> int:
+        """Denoised pictures served since the hub started (/metrics)."""
+        return sum(int(w.denoise_count()) for w in self.workers)
 
     # ------------------------------------------------------------------ on-screen display
     def set_overlay(self, name: str, items, ttl_ms: int = 0) -> None:

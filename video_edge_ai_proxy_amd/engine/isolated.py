@@ -570,13 +570,15 @@ class ProcessHub:
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
                     width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False,
-                    enhance=None):
+                    enhance=None, denoise=None):
         """(meta, JPEG bytes) or None: the worker process scales (width / height given) and encodes
         on its GPU, only the compressed bytes cross the pipe."""
         if overlay is not None or stamp:
             raise NotImplementedError("overlays are not served with gpu.isolation: process")
         if enhance is not None and enhance is not False:
             raise NotImplementedError("enhanced frames are not served with gpu.isolation: process")
+        if denoise is not None and denoise is not False:
+            raise NotImplementedError("denoised frames are not served with gpu.isolation: process")
         if width is None and height is None:
             return self._call(name, "latest_jpeg", after, quality)
         return self._call(name, "latest_jpeg", after, quality, width, height)
@@ -585,6 +587,12 @@ class ProcessHub:
         raise NotImplementedError("enhanced frames are not served with gpu.isolation: process")
 
     def enhance_count(self) -> int:
+        return 0
+
+    def latest_denoised(self, name: str, after: int = 0, width: int = 0, height: int = 0, **params):
+        raise NotImplementedError("denoised frames are not served with gpu.isolation: process")
+
+    def denoise_count(self) -> int:
         return 0
 
     def latest_scaled(self, name: str, after: int = 0, width: Optional[int] = None,

@@ -34,6 +34,10 @@
   histogram equalisation on luma (per-tile histograms, one LUT per tile, four LUTs blended per
   pixel; three launches for every picture of the call: the kernels behind ``frame.jpg?enhance=clahe``);
   a host tensor runs the CPU twin, whose bytes are the same.
+* :func:`denoise` / :func:`denoise_batch` — the K newest BGR24 frames of a picture blended where the
+  luma around a pixel stands still (3 x 3 sums of absolute luma differences, integer weights; one
+  launch for every picture of the call: the kernel behind ``frame.jpg?denoise=1``); host tensors run
+  the CPU twin, whose bytes are the same.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -1006,6 +1010,91 @@ def clahe(bgr: torch.Tensor, tile: int = 128, clip: float = 2.0, strength: float
     """One ``[H, W, 3]`` BGR24 tensor contrast-enhanced: see :func:`clahe_batch`. A device tensor runs
     the gfx950 kernels, a host tensor the CPU twin; ``out=bgr`` enhances in place."""
     return clahe_batch([bgr], tile, clip, strength, None if out is None else [out], planes)[0]
+
+
+def _frame_list(frames, what: str) -> list:
+    """The K ``[H, W, 3]`` frames of one picture, newest first: a ``[K, H, W, 3]`` tensor's or a list's."""
+    if isinstance(frames, torch.Tensor):
+        if frames.dim() != 4:
+            raise ValueError(f"{what} must be [K, H, W, 3] or a list of [H, W, 3] tensors")
+        frames = list(frames.unbind(0))
+    frames = list(frames)
+    if not 1 <= len(frames) <= 8:
+        raise ValueError(f"{what} must hold 1..8 frames")
+    return frames
+
+
+def denoise_batch(frame_lists, levels=8, strengths=1.0, outs=None):
+    """Temporal denoising (csrc/vep/denoise.h, docs/DENOISE.md) of a list of pictures, each given as
+    its K newest frames, newest first: a ``[K, H, W, 3]`` BGR24 tensor or a list of K ``[H, W, 3]``
+    tensors of one size, K 1..8. A pixel is averaged with the earlier frames where the luma around
+    it stands still. Device tensors (all on one device) run the gfx950 kernel, ONE launch for the
+    whole list; host tensors run the CPU twin, whose bytes are the same. ``levels`` (1..64) and
+    ``strengths`` (0..1) are one value or one per picture; pictures may differ in size and K. A
+    device frame's rows may start at any byte address and have any pitch. ``outs`` None: a new
+    contiguous tensor per picture; else per picture a tensor of its size that receives the result
+    and overlaps none of its frames (out of place only). No CPU fallback for device tensors."""
+    from .. import denoise as params
+
+    lists = [_frame_list(f, f"frame_lists[{k}]") for k, f in enumerate(frame_lists)]
+    n = len(lists)
+    if not n:
+        raise ValueError("frame_lists must hold at least one picture")
+    native_params = [params.to_native(2, lv, st)[1:] for lv, st in
+                     zip(_per_picture(levels, n, "levels"), _per_picture(strengths, n, "strengths"))]
+    outs = [None] * n if outs is None else list(outs)
+    if len(outs) != n:
+        raise ValueError("outs must hold one entry per picture")
+    on_device = [isinstance(f, torch.Tensor) and f.is_cuda for fl in lists for f in fl]
+    if any(on_device) != all(on_device):
+        raise ValueError("the frames must all be device tensors or all host tensors")
+    res = []
+    if not on_device[0]:
+        for k, (fl, (level, strength), out) in enumerate(zip(lists, native_params, outs)):
+            shapes = {(_check_overlay_picture(f, f"frame_lists[{k}]")[:2]) for f in fl}
+            if len(shapes) != 1:
+                raise ValueError(f"frame_lists[{k}]: the frames of a picture must have one size")
+            o = torch.from_numpy(native.denoise_cpu(torch.stack([f.detach() for f in fl]).contiguous().numpy(), level, strength))
+            if out is not None:
+                if not isinstance(out, torch.Tensor) or out.is_cuda or out.dtype != torch.uint8 or out.shape != o.shape:
+                    raise ValueError(f"outs[{k}] must be a host uint8 tensor of the picture's shape")
+                out.copy_(o)
+                o = out
+            res.append(o)
+        return res
+    device, work, spans = lists[0][0].device, [], []
+    for k, (fl, (level, strength), out) in enumerate(zip(lists, native_params, outs)):
+        w, h, _ = _check_overlay_picture(fl[0], f"frame_lists[{k}][0]")
+        srcs = []
+        for i, f in enumerate(fl):
+            fw, fh, pitch = _check_overlay_picture(f, f"frame_lists[{k}][{i}]")
+            if (fw, fh) != (w, h) or f.device != device:
+                raise ValueError(f"frame_lists[{k}]: the frames of a picture must have one size and live on one device")
+            srcs.append(_overlay_span(f, w, h, pitch) + (pitch,))
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+        ow, oh, dpitch = _check_overlay_picture(out, f"outs[{k}]")
+        if (ow, oh) != (w, h) or not out.is_cuda or out.device != device:
+            raise ValueError(f"outs[{k}] must be a [{h}, {w}, 3] tensor on the frames' device")
+        b = _overlay_span(out, w, h, dpitch)
+        if any(a[0] < b[1] and b[0] < a[1] for a in srcs):
+            raise ValueError(f"outs[{k}] overlaps a frame of its picture")
+        if any(b[0] < s[1] and s[0] < b[1] for s in spans):
+            raise ValueError("the destinations of one call must not overlap")
+        spans.append(b)
+        work.append(([(a[0], a[1] - a[0], a[2]) for a in srcs], b[0], b[1] - b[0], dpitch, w, h, level, strength))
+        res.append(out)
+    require_gpu()
+    with torch.cuda.device(device):
+        native.denoise_device_batch(work, int(torch.cuda.current_stream(device).cuda_stream))
+    return res
+
+
+def denoise(frames, level: int = 8, strength: float = 1.0, out: torch.Tensor | None = None):
+    """The K newest frames of one picture, newest first (a ``[K, H, W, 3]`` tensor or a list of
+    ``[H, W, 3]`` tensors), temporally denoised into one ``[H, W, 3]`` tensor: see
+    :func:`denoise_batch`. Device tensors run the gfx950 kernel, host tensors the CPU twin."""
+    return denoise_batch([frames], level, strength, None if out is None else [out])[0]
 
 
 # ----------------------------------------------------------------------------- references

@@ -100,6 +100,11 @@ class HubCollector:
             er = CounterMetricFamily("vep_enhance_requests", "pictures served contrast-enhanced (frame.jpg, stream.mjpg, latest_enhanced)")
             er.add_metric([], count())
             yield er
+        count = getattr(self.hub, "denoise_count", None)
+        if count is not None:
+            dr = CounterMetricFamily("vep_denoise_requests", "pictures served temporally denoised (frame.jpg, stream.mjpg, latest_denoised)")
+            dr.add_metric([], count())
+            yield dr
         try:
             from .._native import native
 

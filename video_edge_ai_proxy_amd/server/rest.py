@@ -24,7 +24,8 @@ normal, ``DELETE .../tamper`` forgets it), ``POST /api/v1/process/{name}/crops``
 fisheye or wide-angle camera's lens and views, remapped on the GPU, docs/DEWARP.md),
 ``PUT / GET / DELETE /api/v1/process/{name}/overlay`` (a camera's stored on-screen display list,
 drawn with ``frame.jpg?overlay=1&stamp=1`` and ``wall.jpg?labels=1``, docs/OVERLAY.md; ``frame.jpg`` and
-``stream.mjpg`` take ``enhance=clahe`` with ``clip``, ``tile`` and ``strength`` for dark scenes, docs/ENHANCE.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
+``stream.mjpg`` take ``enhance=clahe`` with ``clip``, ``tile`` and ``strength`` for dark scenes, docs/ENHANCE.md,
+and ``denoise=1`` with ``nr_frames``, ``nr_level`` and ``nr_strength`` for noisy ones, docs/DENOISE.md), and the portal itself at ``/`` (replaces the Angular build, which needs a node
 toolchain).
 """
 from __future__ import annotations
@@ -156,10 +157,31 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         eq.from_request(given or True)  # (a bad value is refused before the hub is asked)
         return {"enhance": given or True}
 
+    def denoised(denoise, nr_frames, nr_level, nr_strength) -> dict:
+        """The denoise argument of latest_jpeg (docs/DENOISE.md): none when the request names none
+        of the four, so such a request calls the hub exactly as before."""
+        from .. import denoise as dn
+
+        if denoise in (None, 0) and nr_frames is None and nr_level is None and nr_strength is None:
+            return {}
+        if denoise != 1:
+            raise ValueError("denoise must be 0 or 1 (nr_frames, nr_level and nr_strength go with denoise=1)")
+        given = {k: v for k, v in (("frames", nr_frames), ("level", nr_level), ("strength", nr_strength)) if v is not None}
+        dn.from_request(given or True)  # (a bad value is refused before the hub is asked)
+        return {"denoise": given or True}
+
+    def frame_headers(meta) -> dict:
+        h = {"X-Vep-Seq": str(meta["seq"])}
+        if "denoise_frames" in meta:
+            h["X-Vep-Denoise-Frames"] = str(meta["denoise_frames"])
+        return h
+
     @app.get("/api/v1/process/{name}/frame.jpg")
     def frame_jpg(name: str, quality: int | None = None, after: int = 0, width: int | None = None,
                   height: int | None = None, overlay: int = 0, stamp: int = 0, enhance: str | None = None,
-                  clip: float | None = None, tile: int | None = None, strength: float | None = None):
+                  clip: float | None = None, tile: int | None = None, strength: float | None = None,
+                  denoise: int | None = None, nr_frames: int | None = None, nr_level: int | None = None,
+                  nr_strength: float | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -168,6 +190,7 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return err(400, str(e))
         try:
             size.update(enhanced(enhance, clip, tile, strength))
+            size.update(denoised(denoise, nr_frames, nr_level, nr_strength))
         except ValueError as e:
             return err(422, str(e))
         try:
@@ -182,13 +205,14 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         if r is None:
             return err(404, "no frame decoded yet")
         meta, jpg = r
-        return Response(content=jpg, media_type="image/jpeg", headers={"X-Vep-Seq": str(meta["seq"])})
+        return Response(content=jpg, media_type="image/jpeg", headers=frame_headers(meta))
 
     @app.get("/api/v1/process/{name}/stream.mjpg")
     def stream_mjpg(name: str, fps: float = 10.0, frames: int | None = None, quality: int | None = None,
                     width: int | None = None, height: int | None = None, overlay: int = 0, stamp: int = 0,
                     enhance: str | None = None, clip: float | None = None, tile: int | None = None,
-                    strength: float | None = None):
+                    strength: float | None = None, denoise: int | None = None, nr_frames: int | None = None,
+                    nr_level: int | None = None, nr_strength: float | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -201,6 +225,7 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return err(400, str(e))
         try:
             size.update(enhanced(enhance, clip, tile, strength))
+            size.update(denoised(denoise, nr_frames, nr_level, nr_strength))
         except ValueError as e:
             return err(422, str(e))
         try:
@@ -209,6 +234,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return err(404, f"process {name!r} not found")
         if "enhance" in size and not hasattr(pm.hub, "enhance_defaults"):  # (501 before the stream starts)
             return err(501, "enhanced frames are not served with gpu.isolation: process")
+        if "denoise" in size:  # (501 and 422 before the stream starts)
+            if not hasattr(pm.hub, "denoise_defaults"):
+                return err(501, "denoised frames are not served with gpu.isolation: process")
+            if pm.hub.cfg.history_depth < 2:
+                return err(422, "denoise needs the ring's history: buffer.in_memory must be 2 or more")
         if "stamp" in size:
             _, bad = overlay_call(pm.hub.overlay, name)  # (501 before the stream starts)
             if bad is not None:
@@ -240,7 +270,8 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                 meta, jpg = r
                 seq, last_new = meta["seq"], now
                 yield (f"--{MJPEG_BOUNDARY}\r\nContent-Type: image/jpeg\r\nContent-Length: {len(jpg)}\r\n"
-                       f"X-Vep-Seq: {seq}\r\n\r\n").encode() + jpg + b"\r\n"
+                       f"X-Vep-Seq: {seq}\r\n" + (f"X-Vep-Denoise-Frames: {meta['denoise_frames']}\r\n" if "denoise_frames" in meta else "")
+                       + "\r\n").encode() + jpg + b"\r\n"
                 sent += 1
                 due = max(due + 1.0 / fps, now)
                 if (frames is None or sent < frames) and due > now:
