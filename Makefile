@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask asan-crop asan-overlay asan-dewarp asan-clahe asan-denoise tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask asan-crop asan-overlay asan-dewarp asan-clahe asan-denoise tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve flow-selftest asan-flow tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -151,6 +151,27 @@ $(ASAN_DIR)/serve_selftest: $(SRCS) $(HIP_SRCS) csrc/tests/serve_selftest.cpp $(
 
 asan-serve: $(ASAN_DIR)/serve_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/serve_selftest
+
+# The block matching's packed key and the multi-slot rounds of the consistent-read rule
+# (csrc/tests/flow_selftest.cpp on vep/flow.h and vep/ring_read.h): a stand-alone host program, no
+# GPU. Wired as the serve selftest above.
+flow-selftest: build
+	mkdir -p build/selftest
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -c csrc/tests/flow_selftest.cpp -Icsrc \
+	  -o build/selftest/flow_selftest.o
+	$(HIPCC) --offload-arch=$(ARCH) build/selftest/flow_selftest.o build/obj/vep__*.o \
+	  -o build/selftest/flow_selftest -lpthread
+	cd /tmp && $(CURDIR)/build/selftest/flow_selftest
+
+$(ASAN_DIR)/flow_selftest: $(SRCS) $(HIP_SRCS) csrc/tests/flow_selftest.cpp $(wildcard csrc/vep/*.h)
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize=shift-base -Xarch_host -fno-sanitize-recover=undefined \
+	  -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc $(SRCS) csrc/tests/flow_selftest.cpp -x hip $(HIP_SRCS) -o $@ -lpthread
+
+asan-flow: $(ASAN_DIR)/flow_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/flow_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

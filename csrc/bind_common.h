@@ -181,6 +181,90 @@ inline py::dict tamper_dict(const TamperResult& r) {
   return d;
 }
 
+// Flow records cross the boundary as a (rows, cols, 4) int16 array: vx, vy, best, zero of every
+// block (a SAD is at most 16320).
+inline py::array_t<int16_t> flow_grid(const flow::Record* r, py::ssize_t rows, py::ssize_t cols) {
+  py::array_t<int16_t> a({rows, cols, py::ssize_t(4)});
+  int16_t* o = a.mutable_data();
+  for (py::ssize_t i = 0; i < rows * cols; ++i, o += 4) {
+    o[0] = r[i].vx;
+    o[1] = r[i].vy;
+    o[2] = int16_t(r[i].best);
+    o[3] = int16_t(r[i].zero);
+  }
+  return a;
+}
+
+inline py::dict flow_summary_dict(const flow::Summary& s, int decimate) {
+  py::dict d;
+  d["moving"] = s.moving;
+  d["sum_vx"] = s.sum_vx;
+  d["sum_vy"] = s.sum_vy;
+  // the mean vector of the moving blocks in picture pixels per gap
+  d["mean"] = py::make_tuple(s.moving ? double(s.sum_vx) * decimate / s.moving : 0.0,
+                             s.moving ? double(s.sum_vy) * decimate / s.moving : 0.0);
+  py::list dirs;
+  for (int v : s.dirs) dirs.append(v);
+  d["dirs"] = dirs;
+  if (s.has_box)
+    d["box"] = py::make_tuple(s.x, s.y, s.w, s.h);
+  else
+    d["box"] = py::none();
+  d["motion"] = s.motion;
+  py::dict g;
+  g["vx"] = s.global_vx;
+  g["vy"] = s.global_vy;
+  g["count"] = s.global_count;
+  g["percent"] = s.global_percent;
+  d["global"] = g;
+  d["camera_moved"] = s.camera_moved;
+  return d;
+}
+
+inline py::dict flow_dict(const FlowResult& r) {
+  py::dict d = flow_summary_dict(r.summary, r.decimate ? r.decimate : 1);
+  d["seq"] = r.seq;
+  d["prev_seq"] = r.prev_seq;
+  d["primed"] = r.primed;
+  d["width"] = r.width;
+  d["height"] = r.height;
+  d["decimate"] = r.decimate;
+  d["range"] = r.range;
+  d["gap"] = r.gap;
+  d["cols"] = r.cols;
+  d["rows"] = r.rows;
+  d["block_px"] = flow::kBlock * r.decimate;
+  d["grid"] = flow_grid(r.records.data(), r.rows, r.cols);
+  return d;
+}
+
+inline flow::Params flow_params_of(int decimate, int range, int gap, int min_gain, int min_blocks, int global_percent) {
+  flow::Params p;
+  p.decimate = decimate;
+  p.range = range;
+  p.gap = gap;
+  p.min_gain = min_gain;
+  p.min_blocks = min_blocks;
+  p.global_percent = global_percent;
+  try {
+    flow::check_params(p);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return p;
+}
+
+inline py::dict flow_params_dict(const flow::Params& p) {
+  py::dict d;
+  d["decimate"] = p.decimate;
+  d["range"] = p.range;
+  d["gap"] = p.gap;
+  d["min_gain"] = p.min_gain;
+  d["min_blocks"] = p.min_blocks;
+  d["global_percent"] = p.global_percent;
+  return d;
+}
+
 // Privacy masks cross the boundary as tuples (x0, y0, x1, y1, mode, block, b, g, r) of ints; an
 // invalid list is a ValueError.
 using MaskTuple = std::tuple<int, int, int, int, int, int, int, int, int>;

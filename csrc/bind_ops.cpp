@@ -102,6 +102,46 @@ static void denoise_run(const std::vector<DenoisePicture>& pics, uintptr_t strea
   });
 }
 
+// flow_device_batch: every picture's job (newer and older frame as (address, bytes, pitch), its two
+// luma planes of plane_bytes each, its records) checked against the sizes the caller states, then
+// the two launches on a pooled set.
+using FlowFrame = std::tuple<uintptr_t, size_t, u32>;
+using FlowPicture = std::tuple<FlowFrame, FlowFrame, uintptr_t, uintptr_t, size_t, uintptr_t, size_t, int, int>;
+static void flow_run(const std::vector<FlowPicture>& pics, int decimate, int range, uintptr_t stream) {
+  const int n = int(pics.size());
+  if (n < 1 || pics.size() > 65535) throw py::value_error("flow: 1..65535 pictures expected");
+  std::vector<gpu::FlowDesc> descs((size_t(n)));
+  for (int k = 0; k < n; ++k) {
+    const auto& [newer, older, plane0, plane1, plane_bytes, records, record_count, w, h] = pics[size_t(k)];
+    flow::Job j;
+    const FlowFrame* fr[2] = {&newer, &older};
+    const uintptr_t planes[2] = {plane0, plane1};
+    for (int f = 0; f < 2; ++f) {
+      j.src[f] = reinterpret_cast<const u8*>(std::get<0>(*fr[f]));
+      j.src_bytes[f] = std::get<1>(*fr[f]);
+      j.src_pitch[f] = std::get<2>(*fr[f]);
+      j.plane[f] = reinterpret_cast<u8*>(planes[f]);
+      j.plane_bytes[f] = plane_bytes;
+    }
+    j.records = reinterpret_cast<flow::Record*>(records);
+    j.record_count = record_count;
+    j.w = w;
+    j.h = h;
+    j.decimate = decimate;
+    j.range = range;
+    try {
+      descs[size_t(k)] = gpu::check_flow(j);
+    } catch (const Error& e) {
+      throw py::value_error(e.what());
+    }
+  }
+  on_pooled_set<gpu::FlowPool>(stream, [&](gpu::FlowPool::Lease& set, hipStream_t s) {
+    set->reserve(n, 0, 0);
+    std::copy(descs.begin(), descs.end(), set->h_descs.p);
+    set->run(n, decimate, range, 0, s);
+  });
+}
+
 // The checked descriptor of one picture of surface_to_bgr / surface_to_bgr_many, in their argument order.
 static gpu::SurfaceBgrDesc surface_bgr_desc(uintptr_t y, uintptr_t uv, int pitch, int coded_w, int coded_h, int bit_depth,
                                             int chroma_format, int crop_left, int crop_top, int out_w, int out_h,
@@ -772,6 +812,75 @@ void bind_ops(py::module_& m) {
   // level, strength) on caller-owned device buffers: the gfx950 denoise kernel, ONE launch for all
   // of them, on `stream` of the current device. Out of place only.
   m.def("denoise_device_batch", &denoise_run, py::arg("pictures"), py::arg("stream"));
+  // Motion vectors by block matching (vep/flow.h) on the host: the CPU backend's path, the
+  // byte-exact reference of flow_device_batch. Two (H, W, 3) pictures -> (the two luma planes
+  // (2, h', w'), the records as a (rows, cols, 4) int16 array of vx, vy, best, zero).
+  m.def("flow_cpu",
+        [](py::array_t<uint8_t, py::array::c_style> newer, py::array_t<uint8_t, py::array::c_style> older, int decimate,
+           int range) {
+          if (!is_bgr_picture(newer) || !is_bgr_picture(older))
+            throw py::value_error("flow_cpu: (H, W, 3) uint8 pictures of at most 65535 x 65535 expected");
+          if (newer.shape(0) != older.shape(0) || newer.shape(1) != older.shape(1))
+            throw py::value_error("flow_cpu: the pictures differ in size");
+          flow_params_of(decimate, range, 1, 0, 1, 1);
+          const int h = int(newer.shape(0)), w = int(newer.shape(1));
+          const u32 pw = flow::plane_side(u32(w), u32(decimate)), ph = flow::plane_side(u32(h), u32(decimate));
+          const size_t pitch = flow::plane_pitch(pw), rows = flow::blocks(ph), cols = flow::blocks(pw);
+          std::vector<u8> plane((2 * pitch * ph) + 16);
+          u8* p0 = plane.data() + ((16 - (reinterpret_cast<uintptr_t>(plane.data()) & 15u)) & 15u);
+          std::vector<flow::Record> records(std::max<size_t>(rows * cols, 1));
+          flow::Job j;
+          j.src[0] = newer.data();
+          j.src[1] = older.data();
+          for (int k = 0; k < 2; ++k) {
+            j.src_bytes[k] = size_t(w) * h * 3;
+            j.src_pitch[k] = u32(w) * 3;
+            j.plane[k] = p0 + size_t(k) * pitch * ph;
+            j.plane_bytes[k] = pitch * ph;
+          }
+          j.records = records.data();
+          j.record_count = records.size();
+          j.w = w;
+          j.h = h;
+          j.decimate = decimate;
+          j.range = range;
+          {
+            py::gil_scoped_release r;
+            flow::flow_cpu(j);
+          }
+          py::array_t<uint8_t> planes({py::ssize_t(2), py::ssize_t(ph), py::ssize_t(pw)});
+          for (u32 k = 0; k < 2; ++k)
+            for (u32 y = 0; y < ph; ++y)
+              std::memcpy(planes.mutable_data() + (size_t(k) * ph + y) * pw, j.plane[k] + size_t(y) * pitch, pw);
+          return py::make_tuple(planes, flow_grid(records.data(), py::ssize_t(rows), py::ssize_t(cols)));
+        },
+        py::arg("newer").noconvert(), py::arg("older").noconvert(), py::arg("decimate") = 2, py::arg("range") = 7);
+  m.def("flow_summarize",
+        // what a client asks about a (rows, cols, 4) int16 record grid (flow::summarize)
+        [](py::array_t<int16_t, py::array::c_style> grid, int decimate, int min_gain, int min_blocks, int global_percent) {
+          if (grid.ndim() != 3 || grid.shape(2) != 4) throw py::value_error("flow_summarize: a (rows, cols, 4) int16 grid expected");
+          flow_params_of(decimate, 1, 1, min_gain, min_blocks, global_percent);
+          const py::ssize_t n = grid.shape(0) * grid.shape(1);
+          std::vector<flow::Record> records((size_t(n)));
+          const int16_t* g = grid.data();
+          for (py::ssize_t i = 0; i < n; ++i, g += 4) {
+            if (g[0] < -flow::kMaxRange || g[0] > flow::kMaxRange || g[1] < -flow::kMaxRange || g[1] > flow::kMaxRange || g[2] < 0 ||
+                g[3] < 0)
+              throw py::value_error("flow_summarize: a record is out of range");
+            records[size_t(i)] = flow::Record{int8_t(g[0]), int8_t(g[1]), uint16_t(g[2]), uint16_t(g[3]), 0};
+          }
+          return flow_summary_dict(flow::summarize(records.data(), int(grid.shape(1)), int(grid.shape(0)), decimate, min_gain,
+                                                   min_blocks, global_percent),
+                                   decimate);
+        },
+        py::arg("grid"), py::arg("decimate") = 2, py::arg("min_gain") = 4, py::arg("min_blocks") = 4,
+        py::arg("global_percent") = 60);
+  // Pictures ((newer, bytes, pitch), (older, bytes, pitch), plane0, plane1, plane_bytes, records,
+  // record_count, w, h) on caller-owned device buffers: the gfx950 flow kernels, TWO launches for
+  // all of them, on `stream` of the current device. A plane holds h' rows of flow_plane_pitch(w')
+  // bytes at a 16-byte aligned address, the records rows x cols entries of 8 bytes.
+  m.def("flow_device_batch", &flow_run, py::arg("pictures"), py::arg("decimate"), py::arg("range"), py::arg("stream"));
+  m.def("flow_plane_pitch", [](int pw) { return flow::plane_pitch(u32(std::max(pw, 0))); }, py::arg("plane_width"));
   // On-screen display (vep/overlay.h) on the host: the arithmetic itself, and the CPU backend's
   // path, the byte-exact reference of overlay_draw.
   m.def("overlay_font", [] {

@@ -3,7 +3,8 @@
 #include "bind_common.h"
 
 // A serving read with the GIL released. What the read refuses about the request itself (an overlay
-// that expands to too many primitives, a denoise request on a ring without history) is a ValueError.
+// that expands to too many primitives, a denoise or flow request on a ring without history) is a
+// ValueError.
 template <class Read>
 static bool serve_released(Read&& read) {
   std::string refused;
@@ -14,7 +15,9 @@ static bool serve_released(Read&& read) {
       ok = read();
     } catch (const Error& e) {
       const std::string what = e.what();
-      if (what.find("overlay:") == std::string::npos && what.find("denoise:") == std::string::npos) throw;
+      if (what.find("overlay:") == std::string::npos && what.find("denoise:") == std::string::npos &&
+          what.find("flow:") == std::string::npos)
+        throw;
       refused = what;
     }
   }
@@ -341,6 +344,42 @@ void bind_worker_serving(py::class_<Worker>& cls) {
              w.tamper_reset(i);
            },
            py::arg("idx"))
+      .def("read_flow",
+           // dict of the newest frame with seq > after against the frame `gap` before it: the block
+           // vectors and what flow::summarize derives from them (docs/FLOW.md), None if there is no
+           // such frame. primed False (an empty grid): the ring holds no earlier frame to match. A
+           // pair is evaluated once, on the GPU from its ring slots (CPU backend: on the host); later
+           // calls get the stored answer. ValueError when the ring keeps too little history.
+           [](Worker& w, int i, i64 after) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             FlowResult r;
+             if (!serve_released([&] { return w.read_flow(i, after, r); })) return py::none();
+             return flow_dict(r);
+           },
+           py::arg("idx"), py::arg("after") = 0)
+      .def("read_flow_many",
+           // [dict | None] of the newest pairs of `cams`, every evaluation of a round in one launch pair.
+           [](Worker& w, const std::vector<int>& cams) {
+             std::vector<FlowResult> rs;
+             std::vector<char> ok;
+             serve_released([&] {
+               w.read_flow_many(cams, rs, ok);
+               return true;
+             });
+             py::list out;
+             for (size_t k = 0; k < rs.size(); ++k) out.append(ok[k] ? py::object(flow_dict(rs[k])) : py::object(py::none()));
+             return out;
+           },
+           py::arg("cams"))
+      .def("set_flow_params",
+           [](Worker& w, int decimate, int range, int gap, int min_gain, int min_blocks, int global_percent) {
+             const flow::Params p = flow_params_of(decimate, range, gap, min_gain, min_blocks, global_percent);
+             py::gil_scoped_release rel;
+             w.set_flow_params(p);
+           },
+           py::arg("decimate") = 2, py::arg("range") = 7, py::arg("gap") = 1, py::arg("min_gain") = 4,
+           py::arg("min_blocks") = 4, py::arg("global_percent") = 60)
+      .def_property_readonly("flow_params", [](Worker& w) { return flow_params_dict(w.flow_params()); })
       .def("set_privacy_masks",
            [](Worker& w, int i, const std::vector<MaskTuple>& masks) {
              std::shared_ptr<Camera> keep = cam_ref(w, i);

@@ -165,6 +165,8 @@ void bind_worker(py::module_& m) {
              d["motion_frames"] = c.motion_frames.load();
              d["tamper_evaluations"] = c.tamper_evaluations.load();
              d["tamper_frames_tampered"] = c.tamper_frames.load();
+             d["flow_evaluations"] = c.flow_evaluations.load();
+             d["flow_frames"] = c.flow_frames.load();
              d["masked_frames"] = c.masked_frames.load();
              d["mask_dropped"] = c.mask_dropped.load();
              py::list hist;

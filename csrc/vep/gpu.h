@@ -16,6 +16,7 @@
 #include "clahe.h"
 #include "common.h"
 #include "denoise.h"
+#include "flow.h"
 #include "mask.h"
 #include "overlay.h"
 #include "scratch.h"
@@ -787,6 +788,54 @@ struct DenoiseSet : DescSet<DenoiseDesc> {
   void run(int n, hipStream_t s);
 };
 using DenoisePool = ScratchPool<DenoiseSet>;
+
+// ---- motion vectors by block matching (gpu_flow.hip; arithmetic: flow.h) -------------------------
+// One picture of a batched flow request (device memory): the newest frame src[0] and an earlier
+// one src[1], both w x h, become the decimated luma planes plane[0] and plane[1] (first launch),
+// and every 8 x 8 block of plane[0] is searched for in plane[1] (second launch): `records`,
+// byte-identical with flow::flow_cpu. Pictures of one request may differ in size; decimate and range
+// hold for the request. The sources (ring slots) are never written.
+struct FlowDesc {
+  const VEP_DEV u8* src[2];  // h rows of src_pitch[k] bytes each (any alignment)
+  VEP_DEV u8* plane[2];      // ph rows of plane_pitch bytes, 16-byte aligned; padding never written
+  VEP_DEV uint2* records;    // flow::blocks(ph) x flow::blocks(pw) flow::Record, every one written once
+  u32 src_pitch[2];          // bytes
+  u32 plane_pitch;           // flow::plane_pitch(pw)
+  i32 w, h;
+  i32 pw, ph;                // the planes: w / decimate, h / decimate
+  i32 decimate, range;
+  u32 pad_;
+};
+static_assert(sizeof(FlowDesc) == 80, "FlowDesc layout");
+// The descriptor of a job (flow::Job: sources, planes, records and their sizes), checked by
+// flow::check_job: every access of both kernels lies inside a source, a plane or the records. The
+// launches below do not check.
+FlowDesc check_flow(const flow::Job& j);
+// Two launches for the n pictures on `s`: planes (grid = tiles of the largest picture x pictures x
+// the two frames), then the search (grid = tiles of the largest grid x pictures). h_descs is the
+// host copy of d_descs (the grids are sized from it); decimate and range are those of every job.
+void launch_flow(const FlowDesc* d_descs, const FlowDesc* h_descs, int n, int decimate, int range, hipStream_t s);
+
+// Flow scratch of one device (pool contract: above): descriptors, the luma planes and records of
+// a request, one picture after another, and the records' copy on the host.
+struct FlowSet : DescSet<FlowDesc> {
+  DevBuf<u8> planes;
+  DevBuf<flow::Record> d_records;
+  PinBuf<flow::Record> h_records;
+  // bytes of one picture's two planes (each a multiple of 256, so every plane stays aligned)
+  static size_t plane_bytes(int w, int h, int decimate);
+  void reserve(int ndescs, size_t plane_bytes, size_t records);
+  // Descriptor k: the two w x h frames against the set's planes at plane_at and records at
+  // record_at (both advanced). Checked. records null: the set's own d_records.
+  void put(int k, const u8* newer, const u8* older, size_t src_bytes, u32 pitch_newer, u32 pitch_older, int w, int h,
+           int decimate, int range, size_t& plane_at, size_t& record_at, flow::Record* records = nullptr,
+           size_t record_count = 0);
+  // Copies the first n host descriptors up, launches both kernels on `s`, then copies the first
+  // `records` records down into h_records (0: they are the caller's own buffers) and records the
+  // event (no wait).
+  void run(int n, int decimate, int range, size_t records, hipStream_t s);
+};
+using FlowPool = ScratchPool<FlowSet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

@@ -91,11 +91,39 @@ struct ReadEntry {
   bool ok = false;       // answered, from a stored result or a committed round
 };
 
+// One ring of a batched read over several slots (the block matching, flow.h): the entry asks for
+// `frames` frames and gets the ring's newest min(frames, available), newest first. `after` decides
+// only whether the newest frame answers (its seq > after); the EARLIER frames are picked whatever
+// `after` is, since what the op makes of them is stored per newest seq for every caller, and a
+// caller polling with the last seq it saw must get what a caller with after = 0 gets. (Unlike
+// read_consistent_frames, whose `after` also bounds the earlier frames.) meta and slot are those of
+// the newest.
+struct FramesEntry : ReadEntry {
+  int frames = 1;
+  std::vector<std::pair<FrameMeta, int>> have;
+};
+
+// The pick and the check of an entry of the rounds below: one slot, or every slot of `have`.
+inline bool pick_entry(ReadEntry& e) { return pick_frame(*e.ring, e.after, e.seq, &e.meta, &e.slot); }
+inline bool entry_valid(const ReadEntry& e) { return e.ring->still_valid(e.slot, e.meta.seq); }
+inline bool pick_entry(FramesEntry& e) {
+  if (e.ring->range(0, e.frames, e.have) < 1 || e.have.back().first.seq <= e.after) return false;
+  std::reverse(e.have.begin(), e.have.end());
+  e.meta = e.have.front().first;
+  e.slot = e.have.front().second;
+  return true;
+}
+inline bool entry_valid(const FramesEntry& e) {
+  bool good = true;
+  for (const auto& f : e.have) good = good && e.ring->still_valid(f.second, f.first.seq);
+  return good;
+}
+
 // Several rings, one launch a round. Up to kReadAttempts rounds; in each, every pending entry
-// picks its frame (pick_frame; none: dropped, not ok) and the op either answers it from a stored
+// picks its frame or frames (pick_entry; none: dropped, not ok) and the op either answers it from a stored
 // result (op.stored(e) true: ok, never run) or plans it (op.plan(e)); op.run(todo) then produces
-// for all planned entries at once, and op.commit(e) is called for those whose slot proved
-// unchanged (ok). The others go into the next round; an entry still pending after the last round
+// for all planned entries at once, and op.commit(e) is called for those whose slot, or every one
+// of whose slots (FramesEntry), proved unchanged (ok). The others go into the next round; an entry still pending after the last round
 // ends not ok and is never committed.
 template <class Entry, class Op>
 void read_consistent_rounds(std::vector<Entry>& entries, Op& op) {
@@ -104,7 +132,7 @@ void read_consistent_rounds(std::vector<Entry>& entries, Op& op) {
     todo.clear();
     for (Entry& e : entries) {
       if (!e.pending) continue;
-      if (!pick_frame(*e.ring, e.after, e.seq, &e.meta, &e.slot)) {
+      if (!pick_entry(e)) {
         e.pending = false;
       } else if (op.stored(e)) {
         e.ok = true;
@@ -117,7 +145,7 @@ void read_consistent_rounds(std::vector<Entry>& entries, Op& op) {
     if (todo.empty()) return;
     op.run(todo);
     for (Entry* e : todo) {
-      if (!e->ring->still_valid(e->slot, e->meta.seq)) continue;  // redone from the newer frame
+      if (!entry_valid(*e)) continue;  // redone from the newer frame
       op.commit(*e);
       e->ok = true;
       e->pending = false;

@@ -799,6 +799,12 @@ void Worker::remove_camera(int idx) {
     motion_free(c->motion);
     c->motion.removed = true;  // (a reader that still holds the camera allocates nothing)
   }
+  {
+    std::lock_guard<std::mutex> fg(c->flow.mu);
+    c->flow.removed = true;  // (nor does one evaluate or store an answer)
+    c->flow.seq = 0;
+    c->flow.result = FlowResult{};
+  }
   c.reset();
 }
 

@@ -167,6 +167,26 @@ struct TamperState {
   tamper::Reference ref;       // the grid of the frame an operator declared normal
 };
 
+// What read_flow answers about one frame pair (flow.h has the arithmetic).
+struct FlowResult {
+  i64 seq = 0, prev_seq = 0;   // the newest frame and the one `gap` frames before it (0: none)
+  int width = 0, height = 0;
+  int decimate = 0, range = 0, gap = 0, cols = 0, rows = 0;
+  bool primed = false;         // false: no earlier frame to match against; the grid is empty
+  flow::Summary summary;
+  std::vector<flow::Record> records;  // rows x cols
+};
+
+// A camera's flow state: the last answer. Nothing lives on the device.
+struct FlowState {
+  std::mutex mu;               // one evaluation of the camera at a time
+  bool removed = false;        // the camera left its worker: nothing is evaluated or stored any more
+  u64 gen = 0;                 // Worker::set_flow_params generation the answer was built under
+  std::weak_ptr<FrameRing> ring;  // the ring `seq` counts in
+  i64 seq = 0;                 // the newest frame of the pair last evaluated, 0: none
+  FlowResult result;           // its answer
+};
+
 // One picture that left the reorder buffer during a job (frame history, Camera::history): a
 // job of several pictures publishes each of them, not only the newest.
 struct JobOutput {
@@ -386,6 +406,9 @@ class Camera {
   u64 mask_gen = 0;
   std::atomic<u64> masked_frames{0};  // committed frames that had at least one mask
   std::atomic<u64> mask_dropped{0};   // frames given up because the list changed while they were in flight
+  // motion vectors (Worker::read_flow; last again): frame pairs evaluated, and those with motion.
+  std::atomic<u64> flow_evaluations{0}, flow_frames{0};
+  FlowState flow;
 };
 
 struct WorkerOptions {
@@ -594,6 +617,25 @@ class Worker {
   bool tamper_set_reference(int cam);
   // Drops the camera's reference and its stored answer.
   void tamper_reset(int cam);
+  // Motion vectors (flow.h, docs/FLOW.md): which way did the content of the newest frame with
+  // seq > after move since the frame `gap` frames before it? Both frames are read where they lie,
+  // in their ring slots, on the serving stream (CPU backend: flow::flow_cpu on the host ring); only
+  // the records (8 bytes a block) come down and flow::summarize runs on the host. Every slot used
+  // must still hold its frame afterwards, or the read starts again (ring_read.h). A frame pair is
+  // evaluated once, whoever asks, and `after` bounds the newest frame only: the earlier one is picked
+  // whatever `after` is, so every caller gets the same answer about a frame. primed = false with an empty grid, not an error: the ring holds
+  // fewer than gap + 1 readable frames (start-up, or FrameRing::invalidate after a privacy-mask
+  // change: what it withdrew is never matched against). Throws when the ring keeps no more than
+  // `gap` frames. False when there is no frame.
+  bool read_flow(int cam, i64 after, FlowResult& out);
+  // The newest pair of several cameras, every camera that needs an evaluation in ONE launch pair
+  // a round. ok[k] is false as in read_tamper_many. Throws as read_flow does, for the WHOLE request,
+  // when one of its cameras' rings keeps too little history (buffer.in_memory holds for every
+  // camera of a hub, so the others would be refused as well).
+  void read_flow_many(const std::vector<int>& cams, std::vector<FlowResult>& out, std::vector<char>& ok);
+  // Parameters are per worker: validates and resets every stored answer.
+  void set_flow_params(const flow::Params& p);
+  flow::Params flow_params();
   // Privacy masks (mask.h, docs/PRIVACY.md): the camera's list, applied in its ring slot after the
   // BGR24 conversion and before the commit, so no consumer of the ring sees an unmasked pixel of a
   // masked region. set_privacy_masks throws on an invalid list; an empty list clears. A change
@@ -989,6 +1031,12 @@ class Worker {
   };
   bool read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta* meta, int* used, std::string* jpeg,
                      std::vector<u8>* raw);
+  // motion vectors (after the denoise's members)
+  gpu::FlowPool flow_pool_;  // descriptors, planes and records of the flow reads, one set per request in flight
+  std::mutex flow_mu_;       // flow_params_ / flow_gen_
+  flow::Params flow_params_;
+  u64 flow_gen_ = 1;
+  struct FlowOp;  // as MotionOp, over several slots of a ring
   void wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
                  const std::vector<ForeignTile>& foreign, const std::vector<std::string>* labels,
                  std::vector<i64>& seqs_out, std::string& out);

@@ -733,8 +733,8 @@ void Worker::motion_reset(int cam) {
 }
 
 // One camera of a motion or tamper request. Its state's mutex is held from pick to commit.
-template <class Result>
-struct CamEval : ReadEntry {
+template <class Result, class Entry = ReadEntry>
+struct CamEval : Entry {
   int cam = -1;
   std::shared_ptr<Camera> c;
   std::unique_lock<std::mutex> lock;
@@ -1054,6 +1054,177 @@ bool Worker::tamper_set_reference(int cam) {
   VEP_CHECK(camera(cam), "no such camera");
   TamperOp op{*this, true};
   return read_camera<TamperOp, TamperResult>(*this, op, cam, 0, nullptr);
+}
+
+// ---------------------------------------------------------------------------- motion vectors
+
+void Worker::set_flow_params(const flow::Params& p) {
+  flow::check_params(p);
+  {
+    std::lock_guard<std::mutex> g(flow_mu_);
+    flow_params_ = p;
+    ++flow_gen_;  // an answer of an older generation counts as none
+  }
+  std::vector<std::shared_ptr<Camera>> cams;
+  {
+    std::lock_guard<std::mutex> g(cams_mu_);
+    cams = cams_;
+  }
+  for (auto& c : cams) {
+    if (!c) continue;
+    std::lock_guard<std::mutex> g(c->flow.mu);
+    c->flow.seq = 0;
+    c->flow.result = FlowResult{};
+  }
+}
+
+flow::Params Worker::flow_params() {
+  std::lock_guard<std::mutex> g(flow_mu_);
+  return flow_params_;
+}
+
+struct Worker::FlowOp {
+  struct Eval : CamEval<FlowResult, FramesEntry> {
+    int w = 0, h = 0;
+    bool primed = false;  // the ring held the frame `gap` before the newest, of the same size
+    i64 prev_seq = 0;
+    size_t blocks = 0;    // of its grid (0 unless primed)
+    size_t at = 0;        // its records in the request's
+    std::vector<flow::Record> records;
+  };
+  Worker& w;
+  std::vector<Eval>* evs = nullptr;
+  flow::Params prm;
+  u64 gen = 0;
+  static FlowState& state(Camera& c) { return c.flow; }
+  static bool live(Camera& c) { return !c.flow.removed; }
+  void snapshot() {
+    std::lock_guard<std::mutex> g(w.flow_mu_);
+    prm = w.flow_params_;
+    gen = w.flow_gen_;
+    for (Eval& e : *evs) e.frames = prm.gap + 1;
+  }
+  bool stored(Eval& e) {
+    FlowState& st = e.c->flow;
+    if (st.gen != gen || st.ring.lock() != e.ring) {  // other parameters or a new ring: no stored answer
+      st.seq = 0;
+      st.result = FlowResult{};
+      st.gen = gen;
+      st.ring = e.ring;
+    }
+    if (st.seq != e.meta.seq || st.seq == 0) return false;
+    e.result = st.result;  // evaluated already: one evaluation per frame pair
+    return true;
+  }
+  void plan(Eval& e) {
+    VEP_CHECK(e.ring->history() > prm.gap,
+              "flow: the camera's ring keeps too little history: buffer.in_memory must be larger than flow.gap");
+    e.w = e.ring->width();
+    e.h = e.ring->height();
+    const size_t gap = size_t(prm.gap);
+    e.primed = e.have.size() > gap && e.have[gap].first.width == e.meta.width && e.have[gap].first.height == e.meta.height;
+    e.prev_seq = e.primed ? e.have[gap].first.seq : 0;
+    // only the slots that are used have to stay valid: the newest, and the earlier one when primed
+    if (e.primed) e.have[1] = e.have[gap];
+    e.have.resize(e.primed ? 2 : 1);
+    const u32 d = u32(prm.decimate);
+    e.blocks = e.primed ? size_t(flow::blocks(flow::plane_side(u32(e.w), d))) * flow::blocks(flow::plane_side(u32(e.h), d)) : 0;
+  }
+  void run(std::vector<Eval*>& todo) {
+    size_t records = 0, planes = 0;
+    int n = 0;
+    for (Eval* e : todo) {
+      e->at = records;
+      records += e->blocks;
+      if (!e->primed) continue;
+      planes += gpu::FlowSet::plane_bytes(e->w, e->h, prm.decimate);
+      ++n;
+    }
+    if (!n) return;
+    if (!w.dev_.gpu()) {
+      std::vector<u8> plane[2];
+      for (Eval* e : todo) {
+        if (!e->primed) continue;
+        const size_t half = gpu::FlowSet::plane_bytes(e->w, e->h, prm.decimate) / 2;
+        e->records.assign(std::max<size_t>(e->blocks, 1), flow::Record{});
+        flow::Job j;
+        for (int k = 0; k < 2; ++k) {
+          plane[k].resize(half + 16);
+          j.src[k] = e->ring->slot_ptr(e->have[size_t(k)].second);
+          j.src_bytes[k] = e->ring->slot_bytes();
+          j.src_pitch[k] = u32(e->w) * 3;
+          j.plane[k] = plane[k].data() + ((16 - (reinterpret_cast<uintptr_t>(plane[k].data()) & 15u)) & 15u);
+          j.plane_bytes[k] = half;
+        }
+        j.records = e->records.data();
+        j.record_count = e->records.size();
+        j.w = e->w;
+        j.h = e->h;
+        j.decimate = prm.decimate;
+        j.range = prm.range;
+        flow::flow_cpu(j);
+        e->records.resize(e->blocks);
+      }
+      return;
+    }
+    w.dev_.bind();
+    gpu::FlowPool::Lease set = w.flow_pool_.acquire();
+    set->reserve(n, planes, records);
+    size_t plane_at = 0, record_at = 0;
+    int k = 0;
+    for (Eval* e : todo) {
+      if (!e->primed) continue;
+      set->put(k++, e->ring->slot_ptr(e->have[0].second), e->ring->slot_ptr(e->have[1].second), e->ring->slot_bytes(),
+               u32(e->w) * 3, u32(e->w) * 3, e->w, e->h, prm.decimate, prm.range, plane_at, record_at);
+    }
+    set->run(n, prm.decimate, prm.range, records, w.serve_stream_);
+    VEP_HIP(hipEventSynchronize(set->ev));
+    const flow::Record* r = set->h_records.p;
+    for (Eval* e : todo) e->records.assign(r + e->at, r + e->at + e->blocks);
+  }
+  void commit(Eval& e) {
+    FlowState& st = e.c->flow;
+    st.seq = e.meta.seq;
+    FlowResult& r = st.result;
+    r = FlowResult{};
+    r.seq = e.meta.seq;
+    r.prev_seq = e.prev_seq;
+    r.width = e.w;
+    r.height = e.h;
+    r.decimate = prm.decimate;
+    r.range = prm.range;
+    r.gap = prm.gap;
+    r.primed = e.primed;
+    if (e.primed) {
+      r.cols = int(flow::blocks(flow::plane_side(u32(e.w), u32(prm.decimate))));
+      r.rows = int(flow::blocks(flow::plane_side(u32(e.h), u32(prm.decimate))));
+      r.records = std::move(e.records);
+      e.c->flow_evaluations.fetch_add(1);
+    }
+    r.summary = flow::summarize(r.records.data(), r.cols, r.rows, prm.decimate, prm.min_gain, prm.min_blocks, prm.global_percent);
+    if (r.summary.motion) e.c->flow_frames.fetch_add(1);
+    e.result = r;
+  }
+};
+
+bool Worker::read_flow(int cam, i64 after, FlowResult& out) {
+  std::vector<FlowResult> res;
+  std::vector<char> ok;
+  FlowOp op{*this};
+  read_each_once<FlowOp::Eval>({cam}, after, res, ok, [&](std::vector<FlowOp::Eval>& evs) {
+    op.evs = &evs;
+    eval_cameras(*this, evs, op);
+  });
+  if (ok[0]) out = std::move(res[0]);
+  return ok[0] != 0;
+}
+
+void Worker::read_flow_many(const std::vector<int>& cams, std::vector<FlowResult>& out, std::vector<char>& ok) {
+  FlowOp op{*this};
+  read_each_once<FlowOp::Eval>(cams, 0, out, ok, [&](std::vector<FlowOp::Eval>& evs) {
+    op.evs = &evs;
+    eval_cameras(*this, evs, op);
+  });
 }
 
 // ------------------------------------------------------------------------------------- crops

@@ -6,6 +6,7 @@
   farm      synthetic RTSP camera farm (H.264 I_PCM/P_Skip streams) for tests and benchmarks
   list | frame | annotate | storage | proxy   gRPC clients (examples/*.py analogs)
   motion    REST client of the motion detector (--device NAME --rest host:port [--watch])
+  flow      REST client of the block motion vectors (--device NAME --rest host:port [--watch])
   tamper    REST client of the tamper detector (--device NAME --rest host:port [--watch] [--set-reference])
   privacy   REST client of a camera's privacy masks (--device NAME --rest host:port [--set JSON | --clear])
   crop      REST client of crop.jpg: one box of a frame as a JPEG (--device NAME --rest host:port
@@ -263,14 +264,15 @@ def format_motion(m: dict) -> str:
             f"active {m.get('active', 0)} box {box}")
 
 
-def cmd_motion(a):
-    """REST client of ``/api/v1/process/{name}/motion``: one line per new evaluated frame."""
+def cmd_motion(a, what="motion", fmt=format_motion):
+    """REST client of ``/api/v1/process/{name}/motion`` (and of ``.../flow``): one line per new
+    evaluated frame."""
     import json
     import urllib.error
     import urllib.parse
     import urllib.request
 
-    base = f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/motion"
+    base = f"http://{a.rest}/api/v1/process/{urllib.parse.quote(a.device, safe='')}/{what}"
     seq, idle = 0, 0
     while True:
         try:
@@ -278,18 +280,34 @@ def cmd_motion(a):
                 m = json.loads(r.read())
         except urllib.error.HTTPError as e:
             if e.code != 404 or b"not found" in e.read():
-                raise SystemExit(f"motion: HTTP {e.code} for {a.device!r}")
+                raise SystemExit(f"{what}: HTTP {e.code} for {a.device!r}")
             m = None  # no newer frame yet
         if m is not None:
             seq, idle = int(m["seq"]), 0
-            print(format_motion(m), flush=True)
+            print(fmt(m), flush=True)
             if not a.watch:
                 return
         else:
             idle += 1
             if not a.watch and idle * a.interval > 10.0:
-                raise SystemExit(f"motion: no frame of {a.device!r} within 10 s")
+                raise SystemExit(f"{what}: no frame of {a.device!r} within 10 s")
         time.sleep(a.interval)
+
+
+def format_flow(m: dict) -> str:
+    """One line per evaluated frame pair of ``vep flow``."""
+    box = "-" if m.get("box") is None else "{},{} {}x{}".format(*m["box"])
+    flag = "MOTION" if m.get("motion") else ("still" if m.get("primed") else "primed")
+    g = m.get("global") or {}
+    cam = f" CAMERA MOVED {g.get('vx', 0)},{g.get('vy', 0)} ({g.get('percent', 0)} %)" if m.get("camera_moved") else ""
+    mean = m.get("mean") or [0.0, 0.0]
+    return (f"seq {m['seq']} {flag} moving {m.get('moving', 0)} mean {mean[0]:+.1f},{mean[1]:+.1f} px "
+            f"dirs {' '.join(str(v) for v in m.get('dirs') or [])} box {box}{cam}")
+
+
+def cmd_flow(a):
+    """REST client of ``/api/v1/process/{name}/flow``: one line per new evaluated frame pair."""
+    cmd_motion(a, "flow", format_flow)
 
 
 def format_tamper(m: dict) -> str:
@@ -551,6 +569,13 @@ def build_parser():
     m.add_argument("--watch", action="store_true", help="keep printing, one line per new evaluated frame")
     m.add_argument("--interval", type=float, default=0.1, help="seconds between polls")
     m.set_defaults(fn=cmd_motion)
+
+    fl = sub.add_parser("flow", help="which way does it move: the hub's block motion vectors of one camera (REST)")
+    fl.add_argument("--device", required=True)
+    fl.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API")
+    fl.add_argument("--watch", action="store_true", help="keep printing, one line per new evaluated frame pair")
+    fl.add_argument("--interval", type=float, default=0.1, help="seconds between polls")
+    fl.set_defaults(fn=cmd_flow)
 
     t = sub.add_parser("tamper", help="does the camera still show what it should: the hub's tamper detection (REST)")
     t.add_argument("--device", required=True)

@@ -170,6 +170,19 @@ class DenoiseConfig:
 
 
 @dataclass
+class FlowConfig:
+    """Motion vectors by block matching (docs/FLOW.md; ``Hub.flow``, ``/api/v1/flow``). The
+    parameters hold for every camera of the hub. The defaults are design choices, not measured
+    thresholds. Needs ``buffer.in_memory`` > ``gap``."""
+    decimate: int = 2         # the luma plane's decimation: 1, 2 or 4
+    range: int = 7            # the search range in samples of the plane (1..15)
+    gap: int = 1              # the earlier frame lies this many frames before the newest (1..7)
+    min_gain: int = 4         # a block moves when its SAD fell by this per sample (0..255)
+    min_blocks: int = 4       # motion when this many blocks move (>= 1)
+    global_percent: int = 60  # camera_moved when this share of the blocks has one vector (1..100)
+
+
+@dataclass
 class Config:
     version: str = "0.1.0"
     title: str = "vep MI355X video edge hub"
@@ -189,6 +202,7 @@ class Config:
     overlay: OverlayConfig = field(default_factory=OverlayConfig)
     enhance: EnhanceConfig = field(default_factory=EnhanceConfig)
     denoise: DenoiseConfig = field(default_factory=DenoiseConfig)
+    flow: FlowConfig = field(default_factory=FlowConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
     bus_tag: str = ""
 
@@ -276,6 +290,8 @@ def validate(cfg: Config) -> None:
         denoise.to_native(cfg.denoise.frames, cfg.denoise.level, cfg.denoise.strength)
     except ValueError as e:
         raise ValueError(f"denoise: {e}") from None
+    from . import flow
+    flow.to_native({k: getattr(cfg.flow, k) for k in flow.DEFAULTS})
     for key, (lo, hi) in MOTION_RANGES.items():
         v = getattr(cfg.motion, key)
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:

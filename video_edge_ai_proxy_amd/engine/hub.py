@@ -21,6 +21,7 @@ from typing import Optional
 from .. import crops, privacy, views
 from .. import denoise as denoise_params
 from .. import enhance as enhance_params
+from .. import flow as flow_params
 from .. import overlay as osd
 from .._native import gpu_count, native
 from ..config import Config, parse_tile
@@ -110,6 +111,7 @@ class Hub:
             t = cfg.tamper
             w.set_tamper_params(int(t.cell), int(t.dark_level), int(t.bright_level), int(t.spread_min),
                                 int(t.focus_percent), int(t.shift_level), int(t.shift_percent))
+            w.set_flow_params(**flow_params.to_native({k: getattr(cfg.flow, k) for k in flow_params.DEFAULTS}))
             w.start()
             self.workers.append(w)
         # Consumer batch: with letterbox_size > 0 every worker letterboxes each frame it publishes
@@ -711,6 +713,44 @@ class Hub:
         """Drop the camera's reference and its stored answer."""
         w, cam = self.worker_of(name)
         w.tamper_reset(cam)
+
+    # ------------------------------------------------------------------ motion vectors
+    def flow(self, name: str, after: int = 0, grid: bool = False, wake: bool = True) -> Optional[dict]:
+        """Which way did the camera's picture move between the frame ``flow.gap`` frames back and
+        the newest frame with seq > after? ``None`` when there is no such frame, else a dict of
+        ``seq, prev_seq, primed, blocks, block_px, moving, mean, dirs, box, motion, global,
+        camera_moved`` (docs/FLOW.md), with ``grid`` also ``vx``, ``vy``, ``best`` and ``zero`` as
+        flat lists. Both frames are matched on the camera's GPU, in their ring slots, once however
+        many clients ask. ``primed`` false (an empty grid): the ring holds no earlier frame yet, or
+        a privacy-mask change withdrew it. ``ValueError`` when ``buffer.in_memory`` <= ``flow.gap``.
+        ``wake`` as in :meth:`tamper`."""
+        w, cam = self.worker_of(name)
+        if wake:
+            w.set_last_query(cam, now_ms())
+        r = w.read_flow(cam, int(after))
+        return None if r is None else flow_params.response(r, grid)
+
+    def flow_many(self, names=None, grid: bool = False, wake: bool = True) -> dict:
+        """``{name: dict | None}`` for the newest frame pair of every listed camera (default: the
+        running cameras, sorted): one launch pair per worker covers all of its cameras that need
+        an evaluation. ``None``: the camera has no frame yet. ``ValueError`` for the whole request
+        when ``buffer.in_memory`` <= ``flow.gap`` (it holds for every camera of the hub). ``wake`` as
+        in :meth:`tamper`."""
+        with self._lock:
+            order = sorted(self.cameras) if names is None else list(names)
+            hs = [self.handle(n) for n in order]
+        if wake:
+            now = now_ms()
+            for h in hs:
+                self.workers[h.worker_index].set_last_query(h.cam, now)
+        out = {}
+        for wi, w in enumerate(self.workers):
+            mine = [h for h in hs if h.worker_index == wi]
+            if not mine:
+                continue
+            for h, r in zip(mine, w.read_flow_many([h.cam for h in mine])):
+                out[h.name] = None if r is None else flow_params.response(r, grid)
+        return {n: out[n] for n in order}
 
     # ------------------------------------------------------------------ privacy masks
     def set_privacy_masks(self, name: str, masks) -> None:

@@ -632,6 +632,18 @@ class ProcessHub:
     def tamper_reset(self, name: str) -> None:
         self._call(name, "tamper_reset")
 
+    def flow(self, name: str, after: int = 0, grid: bool = False, wake: bool = True):
+        """dict or None: matched on the worker process's GPU, only the answer crosses the pipe."""
+        return self._call(name, "flow", after, grid, wake)
+
+    def flow_many(self, names=None, grid: bool = False, wake: bool = True) -> dict:
+        """{name: dict | None}: forwarded per name (the rings live in the worker processes), so
+        here every camera is one pipe call and one launch pair of its own, not one pair per worker."""
+        order = sorted(self.cameras) if names is None else list(names)
+        for n in order:
+            self.handle(n)
+        return {n: self._call(n, "flow", 0, grid, wake) for n in order}
+
     def set_privacy_masks(self, name: str, masks) -> None:
         masks = privacy.normalize_list(masks)
         with self._lock:

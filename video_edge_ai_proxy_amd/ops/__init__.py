@@ -38,6 +38,10 @@
   luma around a pixel stands still (3 x 3 sums of absolute luma differences, integer weights; one
   launch for every picture of the call: the kernel behind ``frame.jpg?denoise=1``); host tensors run
   the CPU twin, whose bytes are the same.
+* :func:`block_flow` / :func:`block_flow_batch` — motion vectors of a BGR24 picture against an earlier
+  one by exhaustive 8 x 8 block matching on decimated luma (packed 8-bit SADs; two launches for every
+  pair of the call: the kernels behind ``/flow``); host tensors run the CPU twin, whose bytes are the
+  same.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -1095,6 +1099,75 @@ def denoise(frames, level: int = 8, strength: float = 1.0, out: torch.Tensor | N
     ``[H, W, 3]`` tensors), temporally denoised into one ``[H, W, 3]`` tensor: see
     :func:`denoise_batch`. Device tensors run the gfx950 kernel, host tensors the CPU twin."""
     return denoise_batch([frames], level, strength, None if out is None else [out])[0]
+
+
+def block_flow_batch(pairs, decimate: int = 2, range: int = 7, planes: bool = False):
+    """Motion vectors by exhaustive block matching (csrc/vep/flow.h, docs/FLOW.md) of a list of
+    ``(newer, older)`` pairs of ``[H, W, 3]`` BGR24 tensors of one size: per pair the record grid as a
+    ``[rows, cols, 4]`` int16 tensor of ``vx, vy, best, zero`` per 8 x 8 block of the luma plane
+    decimated by ``decimate`` (1, 2 or 4), searched over ``|vx|, |vy| <= range`` (1..15). The vector
+    says how the content moved from ``older`` to ``newer``, in samples of the plane. Device tensors
+    (all on one device) run the gfx950 kernels, TWO launches for the whole list; host tensors run the
+    CPU twin, whose bytes are the same. Pairs may differ in size; a device picture's rows may start at
+    any byte address and have any pitch. A picture too small for one block gives an empty grid.
+    ``planes``: also return the two luma planes, ``(grid, [2, h', w'] uint8)`` per pair. No CPU
+    fallback for device tensors."""
+    from .. import flow as params
+
+    decimate, range = params.check_match(decimate, range)
+    pairs = [tuple(p) for p in pairs]
+    if not pairs or any(len(p) != 2 for p in pairs):
+        raise ValueError("pairs must hold at least one (newer, older) pair")
+    on_device = [isinstance(f, torch.Tensor) and f.is_cuda for p in pairs for f in p]
+    if any(on_device) != all(on_device):
+        raise ValueError("the pictures must all be device tensors or all host tensors")
+    res = []
+    if not on_device[0]:
+        for k, (a, b) in enumerate(pairs):
+            if _check_overlay_picture(a, f"pairs[{k}][0]")[:2] != _check_overlay_picture(b, f"pairs[{k}][1]")[:2]:
+                raise ValueError(f"pairs[{k}]: the pictures of a pair must have one size")
+            pl, grid = native.flow_cpu(a.detach().contiguous().numpy(), b.detach().contiguous().numpy(), decimate, range)
+            res.append((torch.from_numpy(grid), torch.from_numpy(pl)) if planes else torch.from_numpy(grid))
+        return res
+    device, work, keep = pairs[0][0].device, [], []
+    for k, (a, b) in enumerate(pairs):
+        w, h, pa = _check_overlay_picture(a, f"pairs[{k}][0]")
+        bw, bh, pb = _check_overlay_picture(b, f"pairs[{k}][1]")
+        if (bw, bh) != (w, h) or a.device != device or b.device != device:
+            raise ValueError(f"pairs[{k}]: the pictures of a pair must have one size and live on one device")
+        pw, ph = w // decimate, h // decimate
+        pitch = native.flow_plane_pitch(pw)
+        half = (pitch * ph + 255) & ~255
+        plane = torch.empty(max(2 * half, 256), dtype=torch.uint8, device=device)
+        grid = torch.empty((ph // 8, pw // 8, 4), dtype=torch.int16, device=device)
+        records = torch.empty(max(grid.numel() // 4, 1) * 8, dtype=torch.uint8, device=device)
+        sa, sb = _overlay_span(a, w, h, pa), _overlay_span(b, w, h, pb)
+        work.append(((sa[0], sa[1] - sa[0], pa), (sb[0], sb[1] - sb[0], pb), plane.data_ptr(), plane.data_ptr() + half,
+                     half, records.data_ptr(), records.numel() // 8, w, h))
+        keep.append((plane, records, grid, pw, ph, pitch, half))
+    require_gpu()
+    with torch.cuda.device(device):
+        native.flow_device_batch(work, decimate, range, int(torch.cuda.current_stream(device).cuda_stream))
+    for plane, records, grid, pw, ph, pitch, half in keep:
+        n = grid.numel() // 4
+        if n:  # i8 vx, i8 vy, u16 best, u16 zero, u16 0 -> int16 vx, vy, best, zero
+            r = records[:n * 8].view(n, 8)
+            grid.view(n, 4)[:, :2] = r[:, :2].view(torch.int8).to(torch.int16)
+            grid.view(n, 4)[:, 2:] = r[:, 2:6].contiguous().view(torch.int16)
+        if planes:
+            two = torch.stack([plane[i * half:i * half + pitch * ph].view(ph, pitch)[:, :pw] for i in (0, 1)]) if ph and pw \
+                else torch.empty((2, ph, pw), dtype=torch.uint8, device=device)
+            res.append((grid, two))
+        else:
+            res.append(grid)
+    return res
+
+
+def block_flow(newer: torch.Tensor, older: torch.Tensor, decimate: int = 2, range: int = 7, planes: bool = False):
+    """The block motion vectors from ``older`` to ``newer`` (two ``[H, W, 3]`` BGR24 tensors of one
+    size) as a ``[rows, cols, 4]`` int16 tensor of ``vx, vy, best, zero``: see :func:`block_flow_batch`.
+    Device tensors run the gfx950 kernels, host tensors the CPU twin."""
+    return block_flow_batch([(newer, older)], decimate, range, planes)[0]
 
 
 # ----------------------------------------------------------------------------- references

@@ -35,6 +35,9 @@ class HubCollector:
         tev = CounterMetricFamily("vep_tamper_evaluations", "frames evaluated by the tamper detector", labels=labels)
         tfr = CounterMetricFamily("vep_tamper_frames_tampered", "evaluated frames flagged as tampered",
                                   labels=labels)
+        fev = CounterMetricFamily("vep_flow_evaluations", "frame pairs block-matched for motion vectors", labels=labels)
+        ffr = CounterMetricFamily("vep_flow_frames_with_motion", "matched frame pairs that showed motion",
+                                  labels=labels)
         pmf = CounterMetricFamily("vep_privacy_masked_frames", "published frames that had at least one privacy mask",
                                   labels=labels)
         pdr = CounterMetricFamily("vep_privacy_dropped_frames",
@@ -56,6 +59,8 @@ class HubCollector:
             mfr.add_metric(lv, st.get("motion_frames", 0))
             tev.add_metric(lv, st.get("tamper_evaluations", 0))
             tfr.add_metric(lv, st.get("tamper_frames_tampered", 0))
+            fev.add_metric(lv, st.get("flow_evaluations", 0))
+            ffr.add_metric(lv, st.get("flow_frames", 0))
             pmf.add_metric(lv, st.get("masked_frames", 0))
             pdr.add_metric(lv, st.get("mask_dropped", 0))
             hist, bounds = st.get("latency_hist"), st.get("latency_bounds_ms")
@@ -65,7 +70,7 @@ class HubCollector:
                     acc += c
                     buckets.append((str(b / 1000.0) if b != float("inf") else "+Inf", acc))
                 lat.add_metric(lv, buckets, st.get("latency_sum_ms", 0) / 1000.0)
-        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr, tev, tfr, pmf, pdr)
+        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr, tev, tfr, fev, ffr, pmf, pdr)
         wb = CounterMetricFamily("vep_worker_batches", "batched decode launches", labels=["device"])
         wf = CounterMetricFamily("vep_worker_frames", "frames decoded by the worker", labels=["device"])
         wg = CounterMetricFamily("vep_worker_gpu_ms", "GPU time of decode batches (ms)", labels=["device"])

@@ -482,6 +482,21 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return err(404, f"process {name!r} not found")
         return Response(status_code=204)
 
+    # ---- motion vectors: the newest frame block-matched against an earlier one, from the ring slots (docs/FLOW.md)
+    @app.get("/api/v1/process/{name}/flow")
+    def flow(name: str, after: int = 0, grid: int = 0, wake: int = 1):
+        if after < 0 or grid not in (0, 1) or wake not in (0, 1):
+            return err(400, "after must be >= 0, grid and wake 0 or 1")
+        try:
+            r = pm.hub.flow(name, after, bool(grid), bool(wake))
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        except ValueError as e:  # (the ring keeps too little history)
+            return err(422, str(e))
+        if r is None:
+            return err(404, "no newer frame decoded yet")
+        return JSONResponse(content=r, headers={"X-Vep-Seq": str(r["seq"])})
+
     # ---- privacy masks: written into the ring slot before a frame is published (docs/PRIVACY.md)
     @app.get("/api/v1/process/{name}/privacy")
     def privacy_get(name: str):
@@ -682,6 +697,28 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         cams = []
         for n, r in res.items():
             cams.append({"name": n, **(r if r is not None else {"seq": 0, "tampered": False, "causes": []})})
+        return {"cameras": cams}
+
+    @app.get("/api/v1/flow")
+    def flow_many(names: str | None = None, grid: int = 0, wake: int = 1):
+        if grid not in (0, 1) or wake not in (0, 1):
+            return err(400, "grid and wake must be 0 or 1")
+        order = None
+        if names is not None:
+            order = [n for n in names.split(",") if n]
+            if not order:
+                return err(400, "names must list at least one camera")
+        elif not pm.hub.cameras:
+            return err(404, "no camera running")
+        try:
+            res = pm.hub.flow_many(order, bool(grid), bool(wake))
+        except KeyError as e:
+            return err(404, f"process {e.args[0] if e.args else ''!r} not found")
+        except ValueError as e:
+            return err(422, str(e))
+        cams = []
+        for n, r in res.items():
+            cams.append({"name": n, **(r if r is not None else {"seq": 0, "primed": False, "motion": False})})
         return {"cameras": cams}
 
     @app.get("/api/v1/processlist")
