@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask asan-crop asan-overlay asan-dewarp asan-clahe asan-denoise tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve flow-selftest asan-flow tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask asan-crop asan-overlay asan-dewarp asan-clahe asan-denoise tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve flow-selftest asan-flow objects-selftest asan-objects tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -172,6 +172,26 @@ $(ASAN_DIR)/flow_selftest: $(SRCS) $(HIP_SRCS) csrc/tests/flow_selftest.cpp $(wi
 
 asan-flow: $(ASAN_DIR)/flow_selftest
 	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/flow_selftest
+
+# The moving-object boxes' CPU twin, job check and capacity bound (csrc/tests/objects_selftest.cpp on
+# vep/objects.h): a stand-alone host program, no GPU. Wired as the flow selftest above.
+objects-selftest: build
+	mkdir -p build/selftest
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -c csrc/tests/objects_selftest.cpp -Icsrc \
+	  -o build/selftest/objects_selftest.o
+	$(HIPCC) --offload-arch=$(ARCH) build/selftest/objects_selftest.o build/obj/vep__*.o \
+	  -o build/selftest/objects_selftest -lpthread
+	cd /tmp && $(CURDIR)/build/selftest/objects_selftest
+
+$(ASAN_DIR)/objects_selftest: $(SRCS) $(HIP_SRCS) csrc/tests/objects_selftest.cpp $(wildcard csrc/vep/*.h)
+	mkdir -p $(ASAN_DIR)
+	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize=shift-base -Xarch_host -fno-sanitize-recover=undefined \
+	  -Xarch_host -fno-omit-frame-pointer \
+	  -Icsrc $(SRCS) csrc/tests/objects_selftest.cpp -x hip $(HIP_SRCS) -o $@ -lpthread
+
+asan-objects: $(ASAN_DIR)/objects_selftest
+	cd /tmp && ASAN_OPTIONS="detect_leaks=1" UBSAN_OPTIONS="print_stacktrace=1" $(CURDIR)/$(ASAN_DIR)/objects_selftest
 
 # the native gRPC endpoint's hostile-client stress alone (csrc/tests/rpc_stress.cpp)
 tsan-rpc: $(TSAN_DIR)/native_stress

@@ -265,6 +265,82 @@ inline py::dict flow_params_dict(const flow::Params& p) {
   return d;
 }
 
+// Objects records cross the boundary as an (n, 6) int64 array: label, area, x0, y0, x1, y1 in plane
+// samples, sorted by label.
+inline py::array_t<int64_t> objects_records(const objects::Record* r, py::ssize_t n) {
+  py::array_t<int64_t> a({n, py::ssize_t(6)});
+  int64_t* o = a.mutable_data();
+  for (py::ssize_t i = 0; i < n; ++i, o += 6) {
+    const uint32_t v[6] = {r[i].label, r[i].area, r[i].x0, r[i].y0, r[i].x1, r[i].y1};
+    for (int k = 0; k < 6; ++k) o[k] = v[k];
+  }
+  return a;
+}
+
+inline py::dict objects_summary_dict(const objects::Summary& s) {
+  py::dict d;
+  d["count"] = s.count;
+  py::list objs;
+  for (const objects::Object& o : s.objects) {
+    py::dict e;
+    e["label"] = o.label;
+    e["area"] = o.area;
+    e["box"] = py::make_tuple(o.x, o.y, o.w, o.h);
+    objs.append(e);
+  }
+  d["objects"] = objs;
+  d["truncated"] = s.truncated;
+  d["area"] = s.area;
+  if (s.has_box)
+    d["box"] = py::make_tuple(s.x, s.y, s.w, s.h);
+  else
+    d["box"] = py::none();
+  d["motion"] = s.motion;
+  return d;
+}
+
+inline py::dict objects_dict(const ObjectsResult& r) {
+  py::dict d = objects_summary_dict(r.summary);
+  d["seq"] = r.seq;
+  d["prev_seq"] = r.prev_seq;
+  d["primed"] = r.primed;
+  d["width"] = r.width;
+  d["height"] = r.height;
+  d["decimate"] = r.decimate;
+  d["gap"] = r.gap;
+  d["records"] = objects_records(r.records.data(), py::ssize_t(r.records.size()));
+  return d;
+}
+
+inline objects::Params objects_params_of(int decimate, int threshold, int gap, int open, int grow, int min_area, int max_objects) {
+  objects::Params p;
+  p.decimate = decimate;
+  p.threshold = threshold;
+  p.gap = gap;
+  p.open = open;
+  p.grow = grow;
+  p.min_area = min_area;
+  p.max_objects = max_objects;
+  try {
+    objects::check_params(p);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return p;
+}
+
+inline py::dict objects_params_dict(const objects::Params& p) {
+  py::dict d;
+  d["decimate"] = p.decimate;
+  d["threshold"] = p.threshold;
+  d["gap"] = p.gap;
+  d["open"] = p.open;
+  d["grow"] = p.grow;
+  d["min_area"] = p.min_area;
+  d["max_objects"] = p.max_objects;
+  return d;
+}
+
 // Privacy masks cross the boundary as tuples (x0, y0, x1, y1, mode, block, b, g, r) of ints; an
 // invalid list is a ValueError.
 using MaskTuple = std::tuple<int, int, int, int, int, int, int, int, int>;

@@ -142,6 +142,60 @@ static void flow_run(const std::vector<FlowPicture>& pics, int decimate, int ran
   });
 }
 
+// objects_device_batch: every picture's job (newer and older frame as (address, bytes, pitch), its
+// two luma planes of plane_bytes each, mask (words), label and area planes (samples each), records
+// (capacity), count) checked against the sizes the caller states, then the six launches on a pooled set.
+using ObjectsPicture = std::tuple<FlowFrame, FlowFrame, uintptr_t, uintptr_t, size_t, uintptr_t, size_t, uintptr_t, uintptr_t,
+                                  size_t, uintptr_t, size_t, uintptr_t, int, int>;
+static void objects_run(const std::vector<ObjectsPicture>& pics, int decimate, int threshold, int open, int grow, int min_area,
+                        uintptr_t stream) {
+  const int n = int(pics.size());
+  if (n < 1 || pics.size() > 65535) throw py::value_error("objects: 1..65535 pictures expected");
+  std::vector<gpu::ObjectsJobDescs> descs((size_t(n)));
+  for (int k = 0; k < n; ++k) {
+    const auto& [newer, older, plane0, plane1, plane_bytes, mask, mask_count, labels, area, sample_count, records,
+                 record_count, count, w, h] = pics[size_t(k)];
+    objects::Job j;
+    const FlowFrame* fr[2] = {&newer, &older};
+    const uintptr_t planes[2] = {plane0, plane1};
+    for (int f = 0; f < 2; ++f) {
+      j.src[f] = reinterpret_cast<const u8*>(std::get<0>(*fr[f]));
+      j.src_bytes[f] = std::get<1>(*fr[f]);
+      j.src_pitch[f] = std::get<2>(*fr[f]);
+      j.plane[f] = reinterpret_cast<u8*>(planes[f]);
+      j.plane_bytes[f] = plane_bytes;
+    }
+    j.mask = reinterpret_cast<u64*>(mask);
+    j.mask_count = mask_count;
+    j.labels = reinterpret_cast<u32*>(labels);
+    j.area = reinterpret_cast<u32*>(area);
+    j.sample_count = sample_count;
+    j.records = reinterpret_cast<objects::Record*>(records);
+    j.record_count = record_count;
+    j.count = reinterpret_cast<u32*>(count);
+    j.w = w;
+    j.h = h;
+    j.decimate = decimate;
+    j.threshold = threshold;
+    j.open = open;
+    j.grow = grow;
+    j.min_area = min_area;
+    try {
+      descs[size_t(k)] = gpu::check_objects(j);
+    } catch (const Error& e) {
+      throw py::value_error(e.what());
+    }
+  }
+  on_pooled_set<gpu::ObjectsPool>(stream, [&](gpu::ObjectsPool::Lease& set, hipStream_t s) {
+    set->reserve(n, 0, 0);
+    for (int k = 0; k < n; ++k) {
+      set->h_luma.p[k] = descs[size_t(k)].luma;
+      set->h_descs.p[k] = descs[size_t(k)].objects;
+    }
+    set->run(n, decimate, s, false);
+  });
+}
+
 // The checked descriptor of one picture of surface_to_bgr / surface_to_bgr_many, in their argument order.
 static gpu::SurfaceBgrDesc surface_bgr_desc(uintptr_t y, uintptr_t uv, int pitch, int coded_w, int coded_h, int bit_depth,
                                             int chroma_format, int crop_left, int crop_top, int out_w, int out_h,
@@ -881,6 +935,88 @@ void bind_ops(py::module_& m) {
   // bytes at a 16-byte aligned address, the records rows x cols entries of 8 bytes.
   m.def("flow_device_batch", &flow_run, py::arg("pictures"), py::arg("decimate"), py::arg("range"), py::arg("stream"));
   m.def("flow_plane_pitch", [](int pw) { return flow::plane_pitch(u32(std::max(pw, 0))); }, py::arg("plane_width"));
+  // Moving-object boxes (vep/objects.h) on the host: the CPU backend's path, the byte-exact
+  // reference of objects_device_batch. Two (H, W, 3) pictures -> (records (n, 6) int64 sorted by
+  // label, the label plane (h', w') uint32, the packed mask (h', words) uint64).
+  m.def("objects_cpu",
+        [](py::array_t<uint8_t, py::array::c_style> newer, py::array_t<uint8_t, py::array::c_style> older, int decimate,
+           int threshold, int open, int grow, int min_area) {
+          if (!is_bgr_picture(newer) || !is_bgr_picture(older))
+            throw py::value_error("objects_cpu: (H, W, 3) uint8 pictures of at most 65535 x 65535 expected");
+          if (newer.shape(0) != older.shape(0) || newer.shape(1) != older.shape(1))
+            throw py::value_error("objects_cpu: the pictures differ in size");
+          objects_params_of(decimate, threshold, 1, open, grow, min_area, 1);
+          const int h = int(newer.shape(0)), w = int(newer.shape(1));
+          const u32 pw = flow::plane_side(u32(w), u32(decimate)), ph = flow::plane_side(u32(h), u32(decimate));
+          const size_t pitch = flow::plane_pitch(pw), words = objects::mask_words(pw);
+          std::vector<u8> plane((2 * pitch * ph) + 16);
+          u8* p0 = plane.data() + ((16 - (reinterpret_cast<uintptr_t>(plane.data()) & 15u)) & 15u);
+          py::array_t<uint64_t> mask({py::ssize_t(ph), py::ssize_t(words)});
+          py::array_t<uint32_t> labels({py::ssize_t(ph), py::ssize_t(pw)});
+          std::vector<u64> mask_none(1);
+          std::vector<u32> area(size_t(pw) * ph + 1), labels_none(1);
+          std::vector<objects::Record> records(std::max<size_t>(size_t(objects::capacity(pw, ph, u32(min_area))), 1));
+          u32 count = 0;
+          objects::Job j;
+          j.src[0] = newer.data();
+          j.src[1] = older.data();
+          for (int k = 0; k < 2; ++k) {
+            j.src_bytes[k] = size_t(w) * h * 3;
+            j.src_pitch[k] = u32(w) * 3;
+            j.plane[k] = p0 + size_t(k) * pitch * ph;
+            j.plane_bytes[k] = pitch * ph;
+          }
+          // (an empty array may have no address of its own)
+          j.mask = mask.size() ? mask.mutable_data() : mask_none.data();
+          j.mask_count = size_t(mask.size());
+          j.labels = labels.size() ? labels.mutable_data() : labels_none.data();
+          j.area = area.data();
+          j.sample_count = size_t(pw) * ph;
+          j.records = records.data();
+          j.record_count = records.size();
+          j.count = &count;
+          j.w = w;
+          j.h = h;
+          j.decimate = decimate;
+          j.threshold = threshold;
+          j.open = open;
+          j.grow = grow;
+          j.min_area = min_area;
+          {
+            py::gil_scoped_release r;
+            objects::objects_cpu(j);
+          }
+          return py::make_tuple(objects_records(records.data(), py::ssize_t(count)), labels, mask);
+        },
+        py::arg("newer").noconvert(), py::arg("older").noconvert(), py::arg("decimate") = 2, py::arg("threshold") = 24,
+        py::arg("open") = 1, py::arg("grow") = 1, py::arg("min_area") = 64);
+  m.def("objects_summarize",
+        // what a client asks about an (n, 6) int64 record array sorted by label (objects::summarize)
+        [](py::array_t<int64_t, py::array::c_style> recs, int decimate, int max_objects, int w, int h) {
+          if (recs.ndim() != 2 || recs.shape(1) != 6) throw py::value_error("objects_summarize: an (n, 6) int64 array expected");
+          objects_params_of(decimate, 0, 1, 0, 0, objects::kMinArea, max_objects);
+          if (!picture_size_ok(w, h)) throw py::value_error("objects_summarize: picture size must be 1..65535");
+          std::vector<objects::Record> records((size_t(recs.shape(0))));
+          const int64_t* g = recs.data();
+          for (size_t i = 0; i < records.size(); ++i, g += 6) {
+            for (int k = 0; k < 6; ++k)
+              if (g[k] < 0 || g[k] > int64_t(0xFFFFFFFF)) throw py::value_error("objects_summarize: a record is out of range");
+            records[i] = objects::Record{u32(g[0]), u32(g[1]), u32(g[2]), u32(g[3]), u32(g[4]), u32(g[5])};
+          }
+          try {
+            return objects_summary_dict(objects::summarize(records.data(), records.size(), decimate, max_objects, w, h));
+          } catch (const Error& e) {
+            throw py::value_error(e.what());
+          }
+        },
+        py::arg("records"), py::arg("decimate") = 2, py::arg("max_objects") = 32, py::arg("width") = 65535,
+        py::arg("height") = 65535);
+  // Pictures ((newer, bytes, pitch), (older, bytes, pitch), plane0, plane1, plane_bytes, mask,
+  // mask_words, labels, area, samples, records, record_capacity, count, w, h) on caller-owned
+  // device buffers: the luma kernel and the five objects kernels, SIX launches for all of them, on
+  // `stream` of the current device. The records come in any order; the count word says how many.
+  m.def("objects_device_batch", &objects_run, py::arg("pictures"), py::arg("decimate"), py::arg("threshold"), py::arg("open"),
+        py::arg("grow"), py::arg("min_area"), py::arg("stream"));
   // On-screen display (vep/overlay.h) on the host: the arithmetic itself, and the CPU backend's
   // path, the byte-exact reference of overlay_draw.
   m.def("overlay_font", [] {

@@ -3,8 +3,8 @@
 #include "bind_common.h"
 
 // A serving read with the GIL released. What the read refuses about the request itself (an overlay
-// that expands to too many primitives, a denoise or flow request on a ring without history) is a
-// ValueError.
+// that expands to too many primitives, a denoise, flow or objects request on a ring without history)
+// is a ValueError.
 template <class Read>
 static bool serve_released(Read&& read) {
   std::string refused;
@@ -16,7 +16,7 @@ static bool serve_released(Read&& read) {
     } catch (const Error& e) {
       const std::string what = e.what();
       if (what.find("overlay:") == std::string::npos && what.find("denoise:") == std::string::npos &&
-          what.find("flow:") == std::string::npos)
+          what.find("flow:") == std::string::npos && what.find("objects:") == std::string::npos)
         throw;
       refused = what;
     }
@@ -380,6 +380,41 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            py::arg("decimate") = 2, py::arg("range") = 7, py::arg("gap") = 1, py::arg("min_gain") = 4,
            py::arg("min_blocks") = 4, py::arg("global_percent") = 60)
       .def_property_readonly("flow_params", [](Worker& w) { return flow_params_dict(w.flow_params()); })
+      .def("read_objects",
+           // dict of the newest frame with seq > after against the frame `gap` before it: the moving
+           // regions' records (an (n, 6) int64 array sorted by label) and what objects::summarize
+           // derives from them (docs/OBJECTS.md); None, primed False, the single evaluation of a pair
+           // and the ValueError as read_flow.
+           [](Worker& w, int i, i64 after) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             ObjectsResult r;
+             if (!serve_released([&] { return w.read_objects(i, after, r); })) return py::none();
+             return objects_dict(r);
+           },
+           py::arg("idx"), py::arg("after") = 0)
+      .def("read_objects_many",
+           // [dict | None] of the newest pairs of `cams`, every evaluation of a round in one set of launches.
+           [](Worker& w, const std::vector<int>& cams) {
+             std::vector<ObjectsResult> rs;
+             std::vector<char> ok;
+             serve_released([&] {
+               w.read_objects_many(cams, rs, ok);
+               return true;
+             });
+             py::list out;
+             for (size_t k = 0; k < rs.size(); ++k) out.append(ok[k] ? py::object(objects_dict(rs[k])) : py::object(py::none()));
+             return out;
+           },
+           py::arg("cams"))
+      .def("set_objects_params",
+           [](Worker& w, int decimate, int threshold, int gap, int open, int grow, int min_area, int max_objects) {
+             const objects::Params p = objects_params_of(decimate, threshold, gap, open, grow, min_area, max_objects);
+             py::gil_scoped_release rel;
+             w.set_objects_params(p);
+           },
+           py::arg("decimate") = 2, py::arg("threshold") = 24, py::arg("gap") = 1, py::arg("open") = 1, py::arg("grow") = 1,
+           py::arg("min_area") = 64, py::arg("max_objects") = 32)
+      .def_property_readonly("objects_params", [](Worker& w) { return objects_params_dict(w.objects_params()); })
       .def("set_privacy_masks",
            [](Worker& w, int i, const std::vector<MaskTuple>& masks) {
              std::shared_ptr<Camera> keep = cam_ref(w, i);

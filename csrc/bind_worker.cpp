@@ -167,6 +167,8 @@ void bind_worker(py::module_& m) {
              d["tamper_frames_tampered"] = c.tamper_frames.load();
              d["flow_evaluations"] = c.flow_evaluations.load();
              d["flow_frames"] = c.flow_frames.load();
+             d["objects_evaluations"] = c.objects_evaluations.load();
+             d["objects_frames"] = c.objects_frames.load();
              d["masked_frames"] = c.masked_frames.load();
              d["mask_dropped"] = c.mask_dropped.load();
              py::list hist;

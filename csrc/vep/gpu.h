@@ -18,6 +18,7 @@
 #include "denoise.h"
 #include "flow.h"
 #include "mask.h"
+#include "objects.h"
 #include "overlay.h"
 #include "scratch.h"
 
@@ -836,6 +837,68 @@ struct FlowSet : DescSet<FlowDesc> {
   void run(int n, int decimate, int range, size_t records, hipStream_t s);
 };
 using FlowPool = ScratchPool<FlowSet>;
+// The first of launch_flow's launches alone (the objects op makes the same planes): false when no
+// picture holds a sample of L and nothing was launched.
+bool launch_flow_luma(const FlowDesc* d_descs, const FlowDesc* h_descs, int n, int decimate, hipStream_t s);
+
+// ---- moving-object boxes (gpu_objects.hip; arithmetic: objects.h) --------------------------------
+// One picture of a batched objects request (device memory). `luma` is the picture's FlowDesc for the
+// luma launch (planes only; no records); the five launches of gpu_objects.hip then make the packed
+// mask, the label plane and the records of plane[0] against plane[1], byte-identical with
+// objects::objects_cpu except that the records come in any order. Pictures of one request may
+// differ in size; the parameters hold for the request. The sources are never written.
+struct ObjectsDesc {
+  const VEP_DEV u8* plane[2];  // ph rows of plane_pitch bytes
+  VEP_DEV u64* mask;           // ph rows of words u64, every word written once
+  VEP_DEV u32* labels;         // pw * ph
+  VEP_DEV u32* area;           // pw * ph, working memory
+  VEP_DEV u32* records;        // capacity records of six u32
+  VEP_DEV u32* count;          // the records written
+  u32 plane_pitch, words;
+  i32 pw, ph;
+  u32 capacity;                // objects::capacity(pw, ph, min_area), at most 2^30
+  i32 threshold, open, grow, min_area;
+  u32 pad_;
+};
+static_assert(sizeof(ObjectsDesc) == 96, "ObjectsDesc layout");
+struct ObjectsJobDescs {
+  FlowDesc luma;
+  ObjectsDesc objects;
+};
+// The descriptors of a job, checked by objects::check_job: every access of the luma kernel and of
+// the five kernels lies inside a source, a plane, the mask, the label or area plane, the records or
+// the count. The launches below do not check.
+ObjectsJobDescs check_objects(const objects::Job& j);
+// Five launches for the n pictures on `s`, after launch_flow_luma: grid = tiles of 64 x 32 samples
+// of the largest plane x pictures, every time. h_descs is the host copy of d_descs.
+void launch_objects(const ObjectsDesc* d_descs, const ObjectsDesc* h_descs, int n, hipStream_t s);
+
+// Objects scratch of one device (pool contract: above): both descriptor arrays, a request's planes
+// (lumas, mask, labels, area: ObjectsSet::scratch_bytes a picture), records and counts, and the
+// counts' and records' copies on the host.
+struct ObjectsSet : DescSet<ObjectsDesc> {
+  DevBuf<FlowDesc> d_luma;
+  PinBuf<FlowDesc> h_luma;
+  DevBuf<u8> scratch;
+  DevBuf<objects::Record> d_records;
+  PinBuf<objects::Record> h_records;
+  DevBuf<u32> d_counts;
+  PinBuf<u32> h_counts;
+  static size_t scratch_bytes(int w, int h, int decimate);
+  static size_t capacity(int w, int h, int decimate, int min_area);
+  void reserve(int ndescs, size_t scratch_bytes, size_t records);
+  // Descriptor k: the two w x h frames against the set's scratch at scratch_at and records at
+  // record_at (both advanced). Checked.
+  void put(int k, const u8* newer, const u8* older, size_t src_bytes, u32 pitch_newer, u32 pitch_older, int w, int h,
+           const objects::Params& p, size_t& scratch_at, size_t& record_at);
+  // Copies the descriptors up, launches the six kernels on `s`, copies the n counts down
+  // (own_counts false: the counts are the caller's own words) and records the event (no wait).
+  void run(int n, int decimate, hipStream_t s, bool own_counts = true);
+  // After the event: copies every picture's count[k] records down behind one another on `s`, waits,
+  // and sorts each picture's by label. The records of picture k start at h_records.p + at[k].
+  void fetch(int n, hipStream_t s, std::vector<size_t>& at);
+};
+using ObjectsPool = ScratchPool<ObjectsSet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

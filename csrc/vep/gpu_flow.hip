@@ -222,21 +222,32 @@ __global__ __launch_bounds__(kThreads) void flow_match_kernel(const FlowDesc* __
 
 }  // namespace
 
+bool launch_flow_luma(const FlowDesc* d_descs, const FlowDesc* h_descs, int n, int decimate, hipStream_t s) {
+  u64 luma = 0;
+  for (int i = 0; i < n; ++i) {
+    const FlowDesc& d = h_descs[i];
+    VEP_CHECK(d.decimate == decimate, "flow: the pictures of a launch share decimate");
+    luma = std::max(luma, u64(luma_tiles(u32(d.pw), u32(d.ph), u32(decimate))));
+  }
+  VEP_CHECK(n <= 65535 && luma < (u64(1) << 31), "flow: launch too large");
+  if (n <= 0 || luma == 0) return false;  // no picture holds a sample of L: nothing to convert
+  hipLaunchKernelGGL(flow_luma_kernel, dim3(u32(luma), u32(n), 2), dim3(kThreads), 0, s, d_descs);
+  VEP_HIP(hipGetLastError());
+  return true;
+}
+
 void launch_flow(const FlowDesc* d_descs, const FlowDesc* h_descs, int n, int decimate, int range, hipStream_t s) {
   if (n <= 0) return;
   VEP_CHECK(n <= 65535, "flow: at most 65535 pictures per launch");
   flow::check_match_params(decimate, range);
-  u64 luma = 0, match = 0;
+  u64 match = 0;
   for (int i = 0; i < n; ++i) {
     const FlowDesc& d = h_descs[i];
     VEP_CHECK(d.decimate == decimate && d.range == range, "flow: the pictures of a launch share decimate and range");
-    luma = std::max(luma, u64(luma_tiles(u32(d.pw), u32(d.ph), u32(decimate))));
     match = std::max(match, u64(match_tiles(u32(d.pw), u32(d.ph))));
   }
-  VEP_CHECK(luma < (u64(1) << 31) && match < (u64(1) << 31), "flow: launch too large");
-  if (luma == 0) return;  // no picture holds a sample of L: nothing to convert, no block to match
-  hipLaunchKernelGGL(flow_luma_kernel, dim3(u32(luma), u32(n), 2), dim3(kThreads), 0, s, d_descs);
-  VEP_HIP(hipGetLastError());
+  VEP_CHECK(match < (u64(1) << 31), "flow: launch too large");
+  if (!launch_flow_luma(d_descs, h_descs, n, decimate, s)) return;  // (then there is no block to match either)
   if (match == 0) return;
   const dim3 grid{u32(match), u32(n), 1};
   switch (slots_of(u32(range))) {

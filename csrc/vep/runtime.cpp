@@ -805,6 +805,12 @@ void Worker::remove_camera(int idx) {
     c->flow.seq = 0;
     c->flow.result = FlowResult{};
   }
+  {
+    std::lock_guard<std::mutex> og(c->objects.mu);
+    c->objects.removed = true;
+    c->objects.seq = 0;
+    c->objects.result = ObjectsResult{};
+  }
   c.reset();
 }
 

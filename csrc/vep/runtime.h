@@ -187,6 +187,26 @@ struct FlowState {
   FlowResult result;           // its answer
 };
 
+// What read_objects answers about one frame pair (objects.h has the arithmetic).
+struct ObjectsResult {
+  i64 seq = 0, prev_seq = 0;   // the newest frame and the one `gap` frames before it (0: none)
+  int width = 0, height = 0;
+  int decimate = 0, gap = 0;
+  bool primed = false;         // false: no earlier frame to compare with; no records
+  objects::Summary summary;
+  std::vector<objects::Record> records;  // sorted by label
+};
+
+// A camera's objects state: the last answer. Nothing lives on the device.
+struct ObjectsState {
+  std::mutex mu;               // one evaluation of the camera at a time
+  bool removed = false;        // the camera left its worker: nothing is evaluated or stored any more
+  u64 gen = 0;                 // Worker::set_objects_params generation the answer was built under
+  std::weak_ptr<FrameRing> ring;  // the ring `seq` counts in
+  i64 seq = 0;                 // the newest frame of the pair last evaluated, 0: none
+  ObjectsResult result;        // its answer
+};
+
 // One picture that left the reorder buffer during a job (frame history, Camera::history): a
 // job of several pictures publishes each of them, not only the newest.
 struct JobOutput {
@@ -409,6 +429,9 @@ class Camera {
   // motion vectors (Worker::read_flow; last again): frame pairs evaluated, and those with motion.
   std::atomic<u64> flow_evaluations{0}, flow_frames{0};
   FlowState flow;
+  // moving-object boxes (Worker::read_objects; last again): frame pairs evaluated, and those with an object.
+  std::atomic<u64> objects_evaluations{0}, objects_frames{0};
+  ObjectsState objects;
 };
 
 struct WorkerOptions {
@@ -636,6 +659,20 @@ class Worker {
   // Parameters are per worker: validates and resets every stored answer.
   void set_flow_params(const flow::Params& p);
   flow::Params flow_params();
+  // Moving-object boxes (objects.h, docs/OBJECTS.md): what moved where between the frame `gap`
+  // frames back and the newest frame with seq > after? The rules are read_flow's: both frames are
+  // read in their ring slots on the serving stream (CPU backend: objects::objects_cpu on the host
+  // ring), only the counts and the records that exist come down, objects::summarize runs on the
+  // host, a pair is evaluated once whoever asks, `after` bounds the newest frame only, primed =
+  // false (no records) when the ring holds fewer than gap + 1 readable frames, and a ring that
+  // keeps no more than `gap` frames throws. False when there is no frame.
+  bool read_objects(int cam, i64 after, ObjectsResult& out);
+  // The newest pair of several cameras, every camera that needs an evaluation in ONE set of
+  // launches a round; ok and the refusal as in read_flow_many.
+  void read_objects_many(const std::vector<int>& cams, std::vector<ObjectsResult>& out, std::vector<char>& ok);
+  // Parameters are per worker: validates and resets every stored answer.
+  void set_objects_params(const objects::Params& p);
+  objects::Params objects_params();
   // Privacy masks (mask.h, docs/PRIVACY.md): the camera's list, applied in its ring slot after the
   // BGR24 conversion and before the commit, so no consumer of the ring sees an unmasked pixel of a
   // masked region. set_privacy_masks throws on an invalid list; an empty list clears. A change
@@ -1037,6 +1074,12 @@ class Worker {
   flow::Params flow_params_;
   u64 flow_gen_ = 1;
   struct FlowOp;  // as MotionOp, over several slots of a ring
+  // moving-object boxes (after the flow's members)
+  gpu::ObjectsPool objects_pool_;  // descriptors and scratch of the objects reads, one set per request in flight
+  std::mutex objects_mu_;          // objects_params_ / objects_gen_
+  objects::Params objects_params_;
+  u64 objects_gen_ = 1;
+  struct ObjectsOp;  // as FlowOp
   void wall_jpeg(const std::vector<int>& cams, int cols, int tw, int th, int quality,
                  const std::vector<ForeignTile>& foreign, const std::vector<std::string>* labels,
                  std::vector<i64>& seqs_out, std::string& out);

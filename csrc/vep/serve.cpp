@@ -1227,6 +1227,193 @@ void Worker::read_flow_many(const std::vector<int>& cams, std::vector<FlowResult
   });
 }
 
+// ---------------------------------------------------------------------- moving-object boxes
+
+void Worker::set_objects_params(const objects::Params& p) {
+  objects::check_params(p);
+  {
+    std::lock_guard<std::mutex> g(objects_mu_);
+    objects_params_ = p;
+    ++objects_gen_;  // an answer of an older generation counts as none
+  }
+  std::vector<std::shared_ptr<Camera>> cams;
+  {
+    std::lock_guard<std::mutex> g(cams_mu_);
+    cams = cams_;
+  }
+  for (auto& c : cams) {
+    if (!c) continue;
+    std::lock_guard<std::mutex> g(c->objects.mu);
+    c->objects.seq = 0;
+    c->objects.result = ObjectsResult{};
+  }
+}
+
+objects::Params Worker::objects_params() {
+  std::lock_guard<std::mutex> g(objects_mu_);
+  return objects_params_;
+}
+
+struct Worker::ObjectsOp {
+  struct Eval : CamEval<ObjectsResult, FramesEntry> {
+    int w = 0, h = 0;
+    bool primed = false;  // the ring held the frame `gap` before the newest, of the same size
+    i64 prev_seq = 0;
+    std::vector<objects::Record> records;
+  };
+  Worker& w;
+  std::vector<Eval>* evs = nullptr;
+  objects::Params prm;
+  u64 gen = 0;
+  static ObjectsState& state(Camera& c) { return c.objects; }
+  static bool live(Camera& c) { return !c.objects.removed; }
+  void snapshot() {
+    std::lock_guard<std::mutex> g(w.objects_mu_);
+    prm = w.objects_params_;
+    gen = w.objects_gen_;
+    for (Eval& e : *evs) e.frames = prm.gap + 1;
+  }
+  bool stored(Eval& e) {
+    ObjectsState& st = e.c->objects;
+    if (st.gen != gen || st.ring.lock() != e.ring) {  // other parameters or a new ring: no stored answer
+      st.seq = 0;
+      st.result = ObjectsResult{};
+      st.gen = gen;
+      st.ring = e.ring;
+    }
+    if (st.seq != e.meta.seq || st.seq == 0) return false;
+    e.result = st.result;  // evaluated already: one evaluation per frame pair
+    return true;
+  }
+  void plan(Eval& e) {
+    VEP_CHECK(e.ring->history() > prm.gap,
+              "objects: the camera's ring keeps too little history: buffer.in_memory must be larger than objects.gap");
+    e.w = e.ring->width();
+    e.h = e.ring->height();
+    const size_t gap = size_t(prm.gap);
+    e.primed = e.have.size() > gap && e.have[gap].first.width == e.meta.width && e.have[gap].first.height == e.meta.height;
+    e.prev_seq = e.primed ? e.have[gap].first.seq : 0;
+    // only the slots that are used have to stay valid: the newest, and the earlier one when primed
+    if (e.primed) e.have[1] = e.have[gap];
+    e.have.resize(e.primed ? 2 : 1);
+    e.records.clear();
+  }
+  void run(std::vector<Eval*>& todo) {
+    size_t records = 0, scratch = 0;
+    int n = 0;
+    for (Eval* e : todo) {
+      if (!e->primed) continue;
+      scratch += gpu::ObjectsSet::scratch_bytes(e->w, e->h, prm.decimate);
+      records += gpu::ObjectsSet::capacity(e->w, e->h, prm.decimate, prm.min_area);
+      ++n;
+    }
+    if (!n) return;
+    if (!w.dev_.gpu()) {
+      std::vector<u8> planes;
+      std::vector<u64> mask;
+      std::vector<u32> labels, area;
+      for (Eval* e : todo) {
+        if (!e->primed) continue;
+        const u32 pw = flow::plane_side(u32(e->w), u32(prm.decimate)), ph = flow::plane_side(u32(e->h), u32(prm.decimate));
+        const size_t half = size_t(flow::plane_pitch(pw)) * ph;  // (a multiple of 16)
+        planes.resize(2 * half + 16);
+        mask.resize(size_t(objects::mask_words(pw)) * ph + 1);
+        labels.resize(size_t(pw) * ph + 1);
+        area.resize(size_t(pw) * ph + 1);
+        u8* base = planes.data() + ((16 - (reinterpret_cast<uintptr_t>(planes.data()) & 15u)) & 15u);
+        e->records.assign(std::max<size_t>(gpu::ObjectsSet::capacity(e->w, e->h, prm.decimate, prm.min_area), 1), objects::Record{});
+        u32 count = 0;
+        objects::Job j;
+        for (int k = 0; k < 2; ++k) {
+          j.src[k] = e->ring->slot_ptr(e->have[size_t(k)].second);
+          j.src_bytes[k] = e->ring->slot_bytes();
+          j.src_pitch[k] = u32(e->w) * 3;
+          j.plane[k] = base + size_t(k) * half;
+          j.plane_bytes[k] = half;
+        }
+        j.mask = mask.data();
+        j.mask_count = mask.size();
+        j.labels = labels.data();
+        j.area = area.data();
+        j.sample_count = size_t(pw) * ph;
+        j.records = e->records.data();
+        j.record_count = e->records.size();
+        j.count = &count;
+        j.w = e->w;
+        j.h = e->h;
+        j.decimate = prm.decimate;
+        j.threshold = prm.threshold;
+        j.open = prm.open;
+        j.grow = prm.grow;
+        j.min_area = prm.min_area;
+        objects::objects_cpu(j);
+        e->records.resize(count);
+      }
+      return;
+    }
+    w.dev_.bind();
+    gpu::ObjectsPool::Lease set = w.objects_pool_.acquire();
+    set->reserve(n, scratch, records);
+    size_t scratch_at = 0, record_at = 0;
+    int k = 0;
+    for (Eval* e : todo) {
+      if (!e->primed) continue;
+      set->put(k++, e->ring->slot_ptr(e->have[0].second), e->ring->slot_ptr(e->have[1].second), e->ring->slot_bytes(),
+               u32(e->w) * 3, u32(e->w) * 3, e->w, e->h, prm, scratch_at, record_at);
+    }
+    set->run(n, prm.decimate, w.serve_stream_);
+    VEP_HIP(hipEventSynchronize(set->ev));
+    std::vector<size_t> at;
+    set->fetch(n, w.serve_stream_, at);
+    k = 0;
+    for (Eval* e : todo) {
+      if (!e->primed) continue;
+      e->records.assign(set->h_records.p + at[size_t(k)], set->h_records.p + at[size_t(k) + 1]);
+      ++k;
+    }
+  }
+  void commit(Eval& e) {
+    ObjectsState& st = e.c->objects;
+    st.seq = e.meta.seq;
+    ObjectsResult& r = st.result;
+    r = ObjectsResult{};
+    r.seq = e.meta.seq;
+    r.prev_seq = e.prev_seq;
+    r.width = e.w;
+    r.height = e.h;
+    r.decimate = prm.decimate;
+    r.gap = prm.gap;
+    r.primed = e.primed;
+    if (e.primed) {
+      r.records = std::move(e.records);
+      e.c->objects_evaluations.fetch_add(1);
+    }
+    r.summary = objects::summarize(r.records.data(), r.records.size(), prm.decimate, prm.max_objects, e.w, e.h);
+    if (r.summary.motion) e.c->objects_frames.fetch_add(1);
+    e.result = r;
+  }
+};
+
+bool Worker::read_objects(int cam, i64 after, ObjectsResult& out) {
+  std::vector<ObjectsResult> res;
+  std::vector<char> ok;
+  ObjectsOp op{*this};
+  read_each_once<ObjectsOp::Eval>({cam}, after, res, ok, [&](std::vector<ObjectsOp::Eval>& evs) {
+    op.evs = &evs;
+    eval_cameras(*this, evs, op);
+  });
+  if (ok[0]) out = std::move(res[0]);
+  return ok[0] != 0;
+}
+
+void Worker::read_objects_many(const std::vector<int>& cams, std::vector<ObjectsResult>& out, std::vector<char>& ok) {
+  ObjectsOp op{*this};
+  read_each_once<ObjectsOp::Eval>(cams, 0, out, ok, [&](std::vector<ObjectsOp::Eval>& evs) {
+    op.evs = &evs;
+    eval_cameras(*this, evs, op);
+  });
+}
+
 // ------------------------------------------------------------------------------------- crops
 
 static u32 pad_word(const crop::Pad& p) { return u32(p.b) | u32(p.g) << 8 | u32(p.r) << 16; }

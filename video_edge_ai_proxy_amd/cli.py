@@ -7,6 +7,7 @@
   list | frame | annotate | storage | proxy   gRPC clients (examples/*.py analogs)
   motion    REST client of the motion detector (--device NAME --rest host:port [--watch])
   flow      REST client of the block motion vectors (--device NAME --rest host:port [--watch])
+  objects   REST client of the moving-object boxes (--device NAME --rest host:port [--watch] [--as-crop-boxes])
   tamper    REST client of the tamper detector (--device NAME --rest host:port [--watch] [--set-reference])
   privacy   REST client of a camera's privacy masks (--device NAME --rest host:port [--set JSON | --clear])
   crop      REST client of crop.jpg: one box of a frame as a JPEG (--device NAME --rest host:port
@@ -310,6 +311,22 @@ def cmd_flow(a):
     cmd_motion(a, "flow", format_flow)
 
 
+def format_objects(m: dict) -> str:
+    """One line per evaluated frame pair of ``vep objects``."""
+    flag = "OBJECTS" if m.get("motion") else ("still" if m.get("primed") else "primed")
+    boxes = " ".join("{},{} {}x{}".format(*o["box"]) for o in m.get("objects") or []) or "-"
+    more = " +" if m.get("truncated") else ""
+    return f"seq {m['seq']} {flag} count {m.get('count', 0)} area {m.get('area', 0)} boxes {boxes}{more}"
+
+
+def cmd_objects(a):
+    """REST client of ``/api/v1/process/{name}/objects``: one line per new evaluated frame pair."""
+    from . import objects
+
+    fmt = (lambda m: f"seq {m['seq']} " + (" ".join(objects.crop_boxes(m)) or "-")) if a.as_crop_boxes else format_objects
+    cmd_motion(a, "objects", fmt)
+
+
 def format_tamper(m: dict) -> str:
     """One line per evaluated frame of ``vep tamper``."""
     flag = "TAMPERED " + ",".join(m.get("causes") or []) if m.get("tampered") else "ok"
@@ -576,6 +593,14 @@ def build_parser():
     fl.add_argument("--watch", action="store_true", help="keep printing, one line per new evaluated frame pair")
     fl.add_argument("--interval", type=float, default=0.1, help="seconds between polls")
     fl.set_defaults(fn=cmd_flow)
+
+    ob = sub.add_parser("objects", help="what moves where: the hub's moving-object boxes of one camera (REST)")
+    ob.add_argument("--device", required=True)
+    ob.add_argument("--rest", default="127.0.0.1:8080", help="host:port of the hub's REST API")
+    ob.add_argument("--watch", action="store_true", help="keep printing, one line per new evaluated frame pair")
+    ob.add_argument("--interval", type=float, default=0.1, help="seconds between polls")
+    ob.add_argument("--as-crop-boxes", action="store_true", help="print the boxes as crop --box takes them (x0,y0,x1,y1 in 1/10000)")
+    ob.set_defaults(fn=cmd_objects)
 
     t = sub.add_parser("tamper", help="does the camera still show what it should: the hub's tamper detection (REST)")
     t.add_argument("--device", required=True)

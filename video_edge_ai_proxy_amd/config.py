@@ -183,6 +183,20 @@ class FlowConfig:
 
 
 @dataclass
+class ObjectsConfig:
+    """Moving-object boxes by frame differencing and connected components (docs/OBJECTS.md;
+    ``Hub.objects``, ``/api/v1/objects``). The parameters hold for every camera of the hub. The
+    defaults are design choices, not measured thresholds. Needs ``buffer.in_memory`` > ``gap``."""
+    decimate: int = 2      # the luma plane's decimation: 1, 2 or 4
+    threshold: int = 24    # a sample differs when its lumas are further apart than this (0..255)
+    gap: int = 1           # the earlier frame lies this many frames before the newest (1..7)
+    open: int = 1          # 1: a 3 x 3 erosion and dilation remove specks; 0: none
+    grow: int = 1          # the radius of the final square dilation (0..3)
+    min_area: int = 64     # samples of the plane a region needs to be reported (4..65535)
+    max_objects: int = 32  # the largest regions listed in an answer (1..1024)
+
+
+@dataclass
 class Config:
     version: str = "0.1.0"
     title: str = "vep MI355X video edge hub"
@@ -203,6 +217,7 @@ class Config:
     enhance: EnhanceConfig = field(default_factory=EnhanceConfig)
     denoise: DenoiseConfig = field(default_factory=DenoiseConfig)
     flow: FlowConfig = field(default_factory=FlowConfig)
+    objects: ObjectsConfig = field(default_factory=ObjectsConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
     bus_tag: str = ""
 
@@ -292,6 +307,8 @@ def validate(cfg: Config) -> None:
         raise ValueError(f"denoise: {e}") from None
     from . import flow
     flow.to_native({k: getattr(cfg.flow, k) for k in flow.DEFAULTS})
+    from . import objects
+    objects.to_native({k: getattr(cfg.objects, k) for k in objects.DEFAULTS})
     for key, (lo, hi) in MOTION_RANGES.items():
         v = getattr(cfg.motion, key)
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:

@@ -22,6 +22,7 @@ from .. import crops, privacy, views
 from .. import denoise as denoise_params
 from .. import enhance as enhance_params
 from .. import flow as flow_params
+from .. import objects as objects_params
 from .. import overlay as osd
 from .._native import gpu_count, native
 from ..config import Config, parse_tile
@@ -112,6 +113,7 @@ class Hub:
             w.set_tamper_params(int(t.cell), int(t.dark_level), int(t.bright_level), int(t.spread_min),
                                 int(t.focus_percent), int(t.shift_level), int(t.shift_percent))
             w.set_flow_params(**flow_params.to_native({k: getattr(cfg.flow, k) for k in flow_params.DEFAULTS}))
+            w.set_objects_params(**objects_params.to_native({k: getattr(cfg.objects, k) for k in objects_params.DEFAULTS}))
             w.start()
             self.workers.append(w)
         # Consumer batch: with letterbox_size > 0 every worker letterboxes each frame it publishes
@@ -750,6 +752,44 @@ class Hub:
                 continue
             for h, r in zip(mine, w.read_flow_many([h.cam for h in mine])):
                 out[h.name] = None if r is None else flow_params.response(r, grid)
+        return {n: out[n] for n in order}
+
+    # ------------------------------------------------------------------ moving-object boxes
+    def objects(self, name: str, after: int = 0, wake: bool = True) -> Optional[dict]:
+        """What moved where between the frame ``objects.gap`` frames back and the newest frame with
+        seq > after? ``None`` when there is no such frame, else a dict of ``seq, prev_seq, primed,
+        width, height, decimate, count, objects, truncated, area, box, motion`` (docs/OBJECTS.md):
+        ``objects`` lists the ``objects.max_objects`` largest separate moving regions, each with
+        ``label``, ``area`` and ``box`` (``[x, y, w, h]`` in picture pixels). Both frames are
+        differenced and labelled on the camera's GPU, in their ring slots, once however many clients
+        ask. ``primed`` false (no objects): the ring holds no earlier frame yet, or a privacy-mask
+        change withdrew it. ``ValueError`` when ``buffer.in_memory`` <= ``objects.gap``. ``wake`` as in
+        :meth:`tamper`."""
+        w, cam = self.worker_of(name)
+        if wake:
+            w.set_last_query(cam, now_ms())
+        r = w.read_objects(cam, int(after))
+        return None if r is None else objects_params.response(r)
+
+    def objects_many(self, names=None, wake: bool = True) -> dict:
+        """``{name: dict | None}`` for the newest frame pair of every listed camera (default: the
+        running cameras, sorted): one set of launches per worker covers all of its cameras that need
+        an evaluation. ``None``: the camera has no frame yet. ``ValueError`` for the whole request
+        when ``buffer.in_memory`` <= ``objects.gap``. ``wake`` as in :meth:`tamper`."""
+        with self._lock:
+            order = sorted(self.cameras) if names is None else list(names)
+            hs = [self.handle(n) for n in order]
+        if wake:
+            now = now_ms()
+            for h in hs:
+                self.workers[h.worker_index].set_last_query(h.cam, now)
+        out = {}
+        for wi, w in enumerate(self.workers):
+            mine = [h for h in hs if h.worker_index == wi]
+            if not mine:
+                continue
+            for h, r in zip(mine, w.read_objects_many([h.cam for h in mine])):
+                out[h.name] = None if r is None else objects_params.response(r)
         return {n: out[n] for n in order}
 
     # ------------------------------------------------------------------ privacy masks

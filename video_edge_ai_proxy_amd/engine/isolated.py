@@ -644,6 +644,17 @@ class ProcessHub:
             self.handle(n)
         return {n: self._call(n, "flow", 0, grid, wake) for n in order}
 
+    def objects(self, name: str, after: int = 0, wake: bool = True):
+        """dict or None: labelled on the worker process's GPU, only the answer crosses the pipe."""
+        return self._call(name, "objects", after, wake)
+
+    def objects_many(self, names=None, wake: bool = True) -> dict:
+        """{name: dict | None}: forwarded per name, as :meth:`flow_many`."""
+        order = sorted(self.cameras) if names is None else list(names)
+        for n in order:
+            self.handle(n)
+        return {n: self._call(n, "objects", 0, wake) for n in order}
+
     def set_privacy_masks(self, name: str, masks) -> None:
         masks = privacy.normalize_list(masks)
         with self._lock:

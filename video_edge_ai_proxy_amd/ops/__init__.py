@@ -42,6 +42,10 @@
   one by exhaustive 8 x 8 block matching on decimated luma (packed 8-bit SADs; two launches for every
   pair of the call: the kernels behind ``/flow``); host tensors run the CPU twin, whose bytes are the
   same.
+* :func:`label_objects` / :func:`label_objects_batch` — the separate moving regions of a BGR24 picture
+  against an earlier one: a thresholded luma difference, a bit-parallel opening and dilation, and
+  8-connected components by union-find in LDS and in the label plane (six launches for every pair of
+  the call: the kernels behind ``/objects``); host tensors run the CPU twin, whose bytes are the same.
 
 The ``*_reference`` functions are the fp32 PyTorch oracles the GPU tests compare against.
 Calling a GPU op on a host with no HIP device raises (no silent CPU fallback).
@@ -1168,6 +1172,74 @@ def block_flow(newer: torch.Tensor, older: torch.Tensor, decimate: int = 2, rang
     size) as a ``[rows, cols, 4]`` int16 tensor of ``vx, vy, best, zero``: see :func:`block_flow_batch`.
     Device tensors run the gfx950 kernels, host tensors the CPU twin."""
     return block_flow_batch([(newer, older)], decimate, range, planes)[0]
+
+
+def label_objects_batch(pairs, decimate: int = 2, threshold: int = 24, open: int = 1, grow: int = 1, min_area: int = 64,
+                        planes: bool = False):
+    """Moving-object boxes (csrc/vep/objects.h, docs/OBJECTS.md) of a list of ``(newer, older)`` pairs
+    of ``[H, W, 3]`` BGR24 tensors of one size: per pair an ``[n, 6]`` int64 tensor of ``label, area,
+    x0, y0, x1, y1``, one row per 8-connected region of at least ``min_area`` samples of the cleaned
+    difference mask, sorted by label (the region's smallest raster index), the box in samples of the
+    luma plane decimated by ``decimate`` with ``x1, y1`` exclusive. Device tensors (all on one device)
+    run the gfx950 kernels, SIX launches for the whole list; host tensors run the CPU twin, whose
+    bytes are the same. Pairs may differ in size; a device picture's rows may start at any byte
+    address and have any pitch. ``planes``: also return the label plane, ``(records, [h', w'] int64)``
+    per pair, 0xFFFFFFFF where nothing moved. No CPU fallback for device tensors."""
+    from .. import objects as params
+
+    decimate, threshold, open, grow, min_area = params.check_label(decimate, threshold, open, grow, min_area)
+    pairs = [tuple(p) for p in pairs]
+    if not pairs or any(len(p) != 2 for p in pairs):
+        raise ValueError("pairs must hold at least one (newer, older) pair")
+    on_device = [isinstance(f, torch.Tensor) and f.is_cuda for p in pairs for f in p]
+    if any(on_device) != all(on_device):
+        raise ValueError("the pictures must all be device tensors or all host tensors")
+    res = []
+    if not on_device[0]:
+        for k, (a, b) in enumerate(pairs):
+            if _check_overlay_picture(a, f"pairs[{k}][0]")[:2] != _check_overlay_picture(b, f"pairs[{k}][1]")[:2]:
+                raise ValueError(f"pairs[{k}]: the pictures of a pair must have one size")
+            rec, lab, _ = native.objects_cpu(a.detach().contiguous().numpy(), b.detach().contiguous().numpy(), decimate,
+                                             threshold, open, grow, min_area)
+            rec = torch.from_numpy(rec)
+            res.append((rec, torch.from_numpy(lab.astype("int64"))) if planes else rec)
+        return res
+    device, work, keep = pairs[0][0].device, [], []
+    for k, (a, b) in enumerate(pairs):
+        w, h, pa = _check_overlay_picture(a, f"pairs[{k}][0]")
+        bw, bh, pb = _check_overlay_picture(b, f"pairs[{k}][1]")
+        if (bw, bh) != (w, h) or a.device != device or b.device != device:
+            raise ValueError(f"pairs[{k}]: the pictures of a pair must have one size and live on one device")
+        pw, ph = w // decimate, h // decimate
+        half = (native.flow_plane_pitch(pw) * ph + 255) & ~255
+        words, cap = (pw + 63) // 64 * ph, pw * ph // min_area
+        plane = torch.empty(max(2 * half, 256), dtype=torch.uint8, device=device)
+        mask = torch.empty(max(words, 1), dtype=torch.int64, device=device)
+        lab = torch.empty((2, max(pw * ph, 1)), dtype=torch.int32, device=device)  # labels, area
+        rec = torch.empty((max(cap, 1), 6), dtype=torch.int32, device=device)
+        count = torch.empty(1, dtype=torch.int32, device=device)
+        sa, sb = _overlay_span(a, w, h, pa), _overlay_span(b, w, h, pb)
+        work.append(((sa[0], sa[1] - sa[0], pa), (sb[0], sb[1] - sb[0], pb), plane.data_ptr(), plane.data_ptr() + half,
+                     half, mask.data_ptr(), mask.numel(), lab[0].data_ptr(), lab[1].data_ptr(), lab.shape[1],
+                     rec.data_ptr(), rec.shape[0], count.data_ptr(), w, h))
+        keep.append((plane, mask, lab, rec, count, pw, ph))
+    require_gpu()
+    with torch.cuda.device(device):
+        native.objects_device_batch(work, decimate, threshold, open, grow, min_area,
+                                    int(torch.cuda.current_stream(device).cuda_stream))
+    for plane, mask, lab, rec, count, pw, ph in keep:
+        r = rec[:int(count.item())].to(torch.int64) & 0xFFFFFFFF
+        r = r[torch.argsort(r[:, 0])]
+        res.append((r, (lab[0, :pw * ph].to(torch.int64) & 0xFFFFFFFF).view(ph, pw)) if planes else r)
+    return res
+
+
+def label_objects(newer: torch.Tensor, older: torch.Tensor, decimate: int = 2, threshold: int = 24, open: int = 1,
+                  grow: int = 1, min_area: int = 64, planes: bool = False):
+    """The separate moving regions between ``older`` and ``newer`` (two ``[H, W, 3]`` BGR24 tensors of
+    one size) as an ``[n, 6]`` int64 tensor of ``label, area, x0, y0, x1, y1``: see
+    :func:`label_objects_batch`. Device tensors run the gfx950 kernels, host tensors the CPU twin."""
+    return label_objects_batch([(newer, older)], decimate, threshold, open, grow, min_area, planes)[0]
 
 
 # ----------------------------------------------------------------------------- references

@@ -38,6 +38,9 @@ class HubCollector:
         fev = CounterMetricFamily("vep_flow_evaluations", "frame pairs block-matched for motion vectors", labels=labels)
         ffr = CounterMetricFamily("vep_flow_frames_with_motion", "matched frame pairs that showed motion",
                                   labels=labels)
+        oev = CounterMetricFamily("vep_objects_evaluations", "frame pairs labelled for moving-object boxes", labels=labels)
+        ofr = CounterMetricFamily("vep_objects_frames_with_objects", "labelled frame pairs that showed an object",
+                                  labels=labels)
         pmf = CounterMetricFamily("vep_privacy_masked_frames", "published frames that had at least one privacy mask",
                                   labels=labels)
         pdr = CounterMetricFamily("vep_privacy_dropped_frames",
@@ -61,6 +64,8 @@ class HubCollector:
             tfr.add_metric(lv, st.get("tamper_frames_tampered", 0))
             fev.add_metric(lv, st.get("flow_evaluations", 0))
             ffr.add_metric(lv, st.get("flow_frames", 0))
+            oev.add_metric(lv, st.get("objects_evaluations", 0))
+            ofr.add_metric(lv, st.get("objects_frames", 0))
             pmf.add_metric(lv, st.get("masked_frames", 0))
             pdr.add_metric(lv, st.get("mask_dropped", 0))
             hist, bounds = st.get("latency_hist"), st.get("latency_bounds_ms")
@@ -70,7 +75,7 @@ class HubCollector:
                     acc += c
                     buckets.append((str(b / 1000.0) if b != float("inf") else "+Inf", acc))
                 lat.add_metric(lv, buckets, st.get("latency_sum_ms", 0) / 1000.0)
-        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr, tev, tfr, fev, ffr, pmf, pdr)
+        yield from (pk, dec, errs, byt, run, rst, lat, mev, mfr, tev, tfr, fev, ffr, oev, ofr, pmf, pdr)
         wb = CounterMetricFamily("vep_worker_batches", "batched decode launches", labels=["device"])
         wf = CounterMetricFamily("vep_worker_frames", "frames decoded by the worker", labels=["device"])
         wg = CounterMetricFamily("vep_worker_gpu_ms", "GPU time of decode batches (ms)", labels=["device"])

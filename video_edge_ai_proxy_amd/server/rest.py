@@ -497,6 +497,21 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return err(404, "no newer frame decoded yet")
         return JSONResponse(content=r, headers={"X-Vep-Seq": str(r["seq"])})
 
+    # ---- moving-object boxes: frame difference and connected components, from the ring slots (docs/OBJECTS.md)
+    @app.get("/api/v1/process/{name}/objects")
+    def objects(name: str, after: int = 0, wake: int = 1):
+        if after < 0 or wake not in (0, 1):
+            return err(400, "after must be >= 0, wake 0 or 1")
+        try:
+            r = pm.hub.objects(name, after, bool(wake))
+        except KeyError:
+            return err(404, f"process {name!r} not found")
+        except ValueError as e:  # (the ring keeps too little history)
+            return err(422, str(e))
+        if r is None:
+            return err(404, "no newer frame decoded yet")
+        return JSONResponse(content=r, headers={"X-Vep-Seq": str(r["seq"])})
+
     # ---- privacy masks: written into the ring slot before a frame is published (docs/PRIVACY.md)
     @app.get("/api/v1/process/{name}/privacy")
     def privacy_get(name: str):
@@ -712,6 +727,28 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             return err(404, "no camera running")
         try:
             res = pm.hub.flow_many(order, bool(grid), bool(wake))
+        except KeyError as e:
+            return err(404, f"process {e.args[0] if e.args else ''!r} not found")
+        except ValueError as e:
+            return err(422, str(e))
+        cams = []
+        for n, r in res.items():
+            cams.append({"name": n, **(r if r is not None else {"seq": 0, "primed": False, "motion": False})})
+        return {"cameras": cams}
+
+    @app.get("/api/v1/objects")
+    def objects_many(names: str | None = None, wake: int = 1):
+        if wake not in (0, 1):
+            return err(400, "wake must be 0 or 1")
+        order = None
+        if names is not None:
+            order = [n for n in names.split(",") if n]
+            if not order:
+                return err(400, "names must list at least one camera")
+        elif not pm.hub.cameras:
+            return err(404, "no camera running")
+        try:
+            res = pm.hub.objects_many(order, bool(wake))
         except KeyError as e:
             return err(404, f"process {e.args[0] if e.args else ''!r} not found")
         except ValueError as e:
