@@ -7,6 +7,7 @@
 
 #include "bind_ext.h"
 #include "vep/clahe.h"
+#include "vep/dehaze.h"
 #include "vep/crop.h"
 #include "vep/denoise.h"
 #include "vep/dewarp.h"
@@ -456,6 +457,25 @@ inline bool denoise_of(const py::object& o, denoise::Params& p) {
   if (o.is_none()) return false;
   const auto t = o.cast<std::tuple<int, int, int>>();
   p = denoise_params_of(std::get<0>(t), std::get<1>(t), std::get<2>(t));
+  return true;
+}
+
+// Dehaze parameters (vep/dehaze.h) cross the boundary as five ints; a bad one is a ValueError.
+inline dehaze::Params dehaze_params_of(int patch, int omega, int t0, int radius, int strength) {
+  const dehaze::Params p{patch, omega, t0, radius, strength};
+  try {
+    dehaze::check_params(p);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return p;
+}
+
+// A serving read's `dehaze` argument: None, or the tuple (patch, omega, t0, radius, strength).
+inline bool dehaze_of(const py::object& o, dehaze::Params& p) {
+  if (o.is_none()) return false;
+  const auto t = o.cast<std::tuple<int, int, int, int, int>>();
+  p = dehaze_params_of(std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t));
   return true;
 }
 

@@ -64,6 +64,45 @@ static void clahe_run(const std::vector<ClahePicture>& pics, uintptr_t stream) {
   });
 }
 
+// dehaze_device_batch: every picture's job (source and destination as address, bytes, pitch, and
+// one buffer of dehaze_plane_words u32 that holds its five planes) checked against the sizes the
+// caller states, then the seven launches on a pooled set.
+using DehazePicture = std::tuple<uintptr_t, size_t, u32, uintptr_t, size_t, u32, int, int, int, int, int, int, int, uintptr_t,
+                                 size_t>;
+static void dehaze_run(const std::vector<DehazePicture>& pics, uintptr_t stream) {
+  const int n = int(pics.size());
+  if (n < 1 || pics.size() > 65535) throw py::value_error("dehaze: 1..65535 pictures expected");
+  std::vector<gpu::DehazeDesc> descs((size_t(n)));
+  for (int k = 0; k < n; ++k) {
+    const auto& [src, src_bytes, src_pitch, dst, dst_bytes, dst_pitch, w, h, patch, omega, t0, radius, strength, planes,
+                 plane_words] = pics[size_t(k)];
+    dehaze::Job j;
+    j.p = dehaze_params_of(patch, omega, t0, radius, strength);
+    if (w < dehaze::kMinSide || h < dehaze::kMinSide || !picture_size_ok(w, h) || uint64_t(w) * uint64_t(h) > dehaze::kMaxPixels)
+      throw py::value_error("dehaze: both sides must be 16..65535 and the picture at most 2^24 pixels");
+    j.src = reinterpret_cast<const u8*>(src);
+    j.src_bytes = src_bytes;
+    j.src_pitch = src_pitch;
+    j.dst = reinterpret_cast<u8*>(dst);
+    j.dst_bytes = dst_bytes;
+    j.dst_pitch = dst_pitch;
+    j.w = w;
+    j.h = h;
+    if (!planes || plane_words < dehaze::plane_words(w, h)) throw py::value_error("dehaze: the planes' buffer is too small");
+    dehaze::carve_planes(j, reinterpret_cast<u32*>(planes));
+    try {
+      descs[size_t(k)] = gpu::check_dehaze(j);
+    } catch (const Error& e) {
+      throw py::value_error(e.what());
+    }
+  }
+  on_pooled_set<gpu::DehazePool>(stream, [&](gpu::DehazePool::Lease& set, hipStream_t s) {
+    set->reserve(n, 0, 0, 0);
+    std::copy(descs.begin(), descs.end(), set->h_descs.p);
+    set->run(n, s);
+  });
+}
+
 // denoise_device_batch: every picture's job (its frames (address, bytes, pitch), newest first, and
 // its destination) checked against the sizes the caller states, then one launch on a pooled set.
 using DenoiseFrame = std::tuple<uintptr_t, size_t, u32>;
@@ -831,6 +870,43 @@ void bind_ops(py::module_& m) {
         py::arg("src"), py::arg("src_bytes"), py::arg("src_pitch"), py::arg("dst"), py::arg("dst_bytes"),
         py::arg("dst_pitch"), py::arg("width"), py::arg("height"), py::arg("tile"), py::arg("clip16"), py::arg("strength"),
         py::arg("hist"), py::arg("hist_words"), py::arg("lut"), py::arg("lut_bytes"), py::arg("stream"));
+  // Dehazing (vep/dehaze.h) on the host: the CPU backend's path, the byte-exact reference of
+  // dehaze_device_batch. -> (out (H, W, 3) uint8, planes (dehaze_plane_words,) uint32: table, air,
+  // ab, mean, cell in this order, as dehaze_device_batch leaves them).
+  m.def("dehaze_cpu",
+        [](py::array_t<uint8_t, py::array::c_style> bgr, int patch, int omega, int t0, int radius, int strength) {
+          if (!is_bgr_picture(bgr)) throw py::value_error("dehaze_cpu: (H, W, 3) uint8 picture expected");
+          dehaze::Job j;
+          j.p = dehaze_params_of(patch, omega, t0, radius, strength);
+          j.h = int(bgr.shape(0));
+          j.w = int(bgr.shape(1));
+          if (j.w < dehaze::kMinSide || j.h < dehaze::kMinSide || uint64_t(j.w) * uint64_t(j.h) > dehaze::kMaxPixels)
+            throw py::value_error("dehaze_cpu: both sides must be at least 16 and the picture at most 2^24 pixels");
+          py::array_t<uint8_t> out({py::ssize_t(j.h), py::ssize_t(j.w), py::ssize_t(3)});
+          // (one word more than needed: the planes start at the buffer's first 8-byte aligned word)
+          py::array_t<uint32_t> buf(py::ssize_t(dehaze::plane_words(j.w, j.h) + 1));
+          u32* words = buf.mutable_data();
+          const py::ssize_t skip = reinterpret_cast<uintptr_t>(words) % 8 ? 1 : 0;
+          j.src = bgr.data();
+          j.dst = out.mutable_data();
+          j.src_pitch = j.dst_pitch = u32(j.w) * 3;
+          j.src_bytes = j.dst_bytes = size_t(j.w) * 3 * size_t(j.h);
+          dehaze::carve_planes(j, words + skip);
+          std::fill(words, words + buf.size(), 0u);
+          {
+            py::gil_scoped_release r;
+            dehaze::run_cpu(j);
+          }
+          return py::make_tuple(out, buf[py::slice(skip, skip + py::ssize_t(dehaze::plane_words(j.w, j.h)), 1)]);
+        },
+        py::arg("bgr").noconvert(), py::arg("patch") = 15, py::arg("omega") = 243, py::arg("t0") = 102, py::arg("radius") = 8,
+        py::arg("strength") = 256);
+  m.def("dehaze_plane_words", [](int w, int h) { return dehaze::plane_words(w, h); }, py::arg("width"), py::arg("height"));
+  // Pictures (src, src_bytes, src_pitch, dst, dst_bytes, dst_pitch, w, h, patch, omega, t0, radius,
+  // strength, planes, plane_words) on caller-owned device buffers: the gfx950 dehaze kernels, each
+  // ONE launch for all of them, on `stream` of the current device. dst == src: in place. The planes
+  // are the caller's too (8-byte aligned), so a test reads every intermediate back.
+  m.def("dehaze_device_batch", &dehaze_run, py::arg("pictures"), py::arg("stream"));
   // Temporal denoising (vep/denoise.h) on the host: the CPU backend's path, the byte-exact
   // reference of denoise_device_batch. frames (K, H, W, 3), frames[0] the newest -> (H, W, 3).
   m.def("denoise_cpu",

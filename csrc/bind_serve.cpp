@@ -16,6 +16,7 @@ static bool serve_released(Read&& read) {
     } catch (const Error& e) {
       const std::string what = e.what();
       if (what.find("overlay:") == std::string::npos && what.find("denoise:") == std::string::npos &&
+          what.find("dehaze:") == std::string::npos &&
           what.find("flow:") == std::string::npos && what.find("objects:") == std::string::npos)
         throw;
       refused = what;
@@ -25,9 +26,11 @@ static bool serve_released(Read&& read) {
   return ok;
 }
 // The meta of a denoised read says how many frames were blended.
-static py::dict denoised_meta(const FrameMeta& m, bool denoised, int frames) {
+// The meta of a dehazed read carries the estimated air light as (b, g, r).
+static py::dict denoised_meta(const FrameMeta& m, bool denoised, int frames, bool dehazed = false, const u32* air = nullptr) {
   py::dict d = meta_dict(m);
   if (denoised) d["denoise_frames"] = frames;
+  if (dehazed) d["dehaze_air"] = py::make_tuple(air[0], air[1], air[2]);
   return d;
 }
 
@@ -58,24 +61,52 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // enhance (None, or (tile, clip16, strength)): contrast-enhanced first (docs/ENHANCE.md).
            // denoise (None, or (frames, level, strength)): blended with the ring's earlier frames before
            // anything else (docs/DENOISE.md); meta then carries denoise_frames, how many were used.
-           [](Worker& w, int i, i64 after, int quality, int width, int height, py::object enhance,
-              py::object denoise) -> py::object {
+           // dehaze (None, or (patch, omega, t0, radius, strength)): dehazed after the denoise and the
+           // scale (docs/DEHAZE.md); meta then carries dehaze_air, the estimated air light (b, g, r).
+           [](Worker& w, int i, i64 after, int quality, int width, int height, py::object enhance, py::object denoise,
+              py::object dehaze) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              clahe::Params p;
              const bool eq = enhance_of(enhance, p);
              denoise::Params dp;
              const bool dn = denoise_of(denoise, dp);
+             dehaze::Params hp;
+             const bool dh = dehaze_of(dehaze, hp);
              FrameMeta m;
              std::string out;
              int used = 0;
+             u32 air[3] = {0, 0, 0};
              const bool ok = serve_released([&] {
-               return w.read_latest_jpeg(i, after, quality, &m, out, width, height, eq ? &p : nullptr, dn ? &dp : nullptr, &used);
+               return w.read_latest_jpeg(i, after, quality, &m, out, width, height, eq ? &p : nullptr, dn ? &dp : nullptr, &used,
+                                         dh ? &hp : nullptr, air);
              });
              if (!ok) return py::none();
-             return py::make_tuple(denoised_meta(m, dn, used), py::bytes(out));
+             return py::make_tuple(denoised_meta(m, dn, used, dh, air), py::bytes(out));
            },
            py::arg("idx"), py::arg("after") = 0, py::arg("quality") = 85, py::arg("width") = 0,
-           py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none())
+           py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none(),
+           py::arg("dehaze") = py::none())
+      .def("read_latest_dehazed",
+           // (meta, ndarray) of the newest frame with seq > after, dehazed (docs/DEHAZE.md); fitted into
+           // width x height first when either is given; None if there is none. meta carries dehaze_air.
+           [](Worker& w, int i, i64 after, int width, int height, int patch, int omega, int t0, int radius,
+              int strength) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const dehaze::Params p = dehaze_params_of(patch, omega, t0, radius, strength);
+             if (after < 0) throw py::value_error("dehaze: after must be >= 0");
+             if (width < 0 || width > 65535 || height < 0 || height > 65535)
+               throw py::value_error("scale: width and height must be 1..65535 (0: not given)");
+             FrameMeta m;
+             std::vector<u8> px;
+             u32 air[3] = {0, 0, 0};
+             if (!serve_released([&] { return w.read_latest_dehazed(i, after, width, height, p, &m, px, air); })) return py::none();
+             py::array_t<uint8_t> a({py::ssize_t(m.height), py::ssize_t(m.width), py::ssize_t(3)});
+             std::memcpy(a.mutable_data(), px.data(), px.size());
+             return py::make_tuple(denoised_meta(m, false, 0, true, air), a);
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("width") = 0, py::arg("height") = 0, py::arg("patch") = 15,
+           py::arg("omega") = 243, py::arg("t0") = 102, py::arg("radius") = 8, py::arg("strength") = 256)
+      .def("dehaze_count", [](Worker& w) { return w.dehaze_count(); })
       .def("read_latest_denoised",
            // (meta, ndarray) of the newest frame with seq > after, blended with up to frames - 1 earlier
            // frames of the ring (docs/DENOISE.md); fitted into width x height afterwards when either is
@@ -198,13 +229,16 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // read_latest_jpeg with the overlay items drawn on the picture (docs/OVERLAY.md): {name},
            // {seq} and {time} come from `name` and the meta of the frame actually encoded.
            [](Worker& w, int i, const std::vector<ItemTuple>& items, const std::string& name, i64 after, int quality,
-              int width, int height, py::object enhance, py::object denoise) -> py::object {
+              int width, int height, py::object enhance, py::object denoise, py::object dehaze) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              const std::vector<overlay::Item> its = items_of(items);
              clahe::Params p;
              const bool eq = enhance_of(enhance, p);
              denoise::Params dp;
              const bool dn = denoise_of(denoise, dp);
+             dehaze::Params hp;
+             const bool dh = dehaze_of(dehaze, hp);
+             u32 air[3] = {0, 0, 0};
              if (after < 0) throw py::value_error("overlay: after must be >= 0");
              if (quality < 1 || quality > 100) throw py::value_error("jpeg: quality must be 1..100");
              if (width < 0 || width > 65535 || height < 0 || height > 65535)
@@ -215,13 +249,14 @@ void bind_worker_serving(py::class_<Worker>& cls) {
              // (of a checked list only the expansion can be refused: too many primitives)
              const bool ok = serve_released([&] {
                return w.read_overlay_jpeg(i, after, quality, its, name, &m, out, width, height, eq ? &p : nullptr,
-                                          dn ? &dp : nullptr, &used);
+                                          dn ? &dp : nullptr, &used, dh ? &hp : nullptr, air);
              });
              if (!ok) return py::none();
-             return py::make_tuple(denoised_meta(m, dn, used), py::bytes(out));
+             return py::make_tuple(denoised_meta(m, dn, used, dh, air), py::bytes(out));
            },
            py::arg("idx"), py::arg("items"), py::arg("name") = "", py::arg("after") = 0, py::arg("quality") = 85,
-           py::arg("width") = 0, py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none())
+           py::arg("width") = 0, py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none(),
+           py::arg("dehaze") = py::none())
       .def("overlay_counts", [](Worker& w) { return w.overlay_counts(); })
       .def_property("wall_max_tiles", &Worker::wall_max_tiles, &Worker::set_wall_max_tiles)
       .def("read_motion",

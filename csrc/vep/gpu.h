@@ -15,6 +15,7 @@
 
 #include "clahe.h"
 #include "common.h"
+#include "dehaze.h"
 #include "denoise.h"
 #include "flow.h"
 #include "mask.h"
@@ -899,6 +900,56 @@ struct ObjectsSet : DescSet<ObjectsDesc> {
   void fetch(int n, hipStream_t s, std::vector<size_t>& at);
 };
 using ObjectsPool = ScratchPool<ObjectsSet>;
+
+// ---- dehazing (gpu_dehaze.hip; arithmetic: dehaze.h) ----------------------------------------------
+// One picture of a batched dehaze request (device memory): the packed BGR24 picture at src
+// dehazed into dst, byte-identical with dehaze::run_cpu, planes included, in seven launches that
+// each cover every picture of the request: clear the table, dark channel and table, air light,
+// dark channel of the normalised picture and cell means, coefficients, their box means, recovery.
+// dst == src (and equal pitches): in place; otherwise the two must not overlap and src is never
+// written. Pictures of one request may differ in size and parameters; their destinations and
+// planes must not overlap.
+struct DehazeDesc {
+  const VEP_DEV u8* src;  // h rows of src_pitch bytes (any alignment)
+  VEP_DEV u8* dst;        // h rows of dst_pitch bytes (any alignment)
+  VEP_DEV u32* table;     // dehaze::kTableWords
+  VEP_DEV u32* air;       // dehaze::kAirWords
+  VEP_DEV u32* cell;      // ch x cw
+  VEP_DEV int2* ab;       // ch x cw
+  VEP_DEV int2* mean;     // ch x cw
+  u32 src_pitch, dst_pitch;  // bytes
+  i32 w, h;
+  i32 patch, omega, t0, radius, strength;  // dehaze::Params
+  u32 pad_;
+};
+static_assert(sizeof(DehazeDesc) == 96, "DehazeDesc layout");
+// The descriptor of a job (dehaze::Job: pictures, planes and their sizes), checked by
+// dehaze::check_job: every access of every kernel lies inside a picture or a plane, and those are
+// apart. The launches below do not check.
+DehazeDesc check_dehaze(const dehaze::Job& j);
+// The seven launches for the n pictures, in order on `s`: grid = (blocks of the largest picture)
+// x pictures each. h_descs is the host copy of d_descs (the grids are sized from it).
+void launch_dehaze(const DehazeDesc* d_descs, const DehazeDesc* h_descs, int n, hipStream_t s);
+
+// Dehaze scratch of one device (pool contract: above): descriptors, the planes of a request's
+// pictures one after the other, a picture for the out-of-place dehazing of a ring slot, and pinned
+// buffers for a result and the air light on their way down.
+struct DehazeSet : DescSet<DehazeDesc> {
+  DevBuf<uint64_t> planes;
+  DevBuf<u8> picture;
+  PinBuf<u8> host;
+  PinBuf<u32> h_air;
+  // 8-byte words of one picture's five planes
+  static size_t plane_words(int w, int h);
+  void reserve(int ndescs, size_t plane_words, size_t picture_bytes, size_t host_bytes);
+  // Descriptor k: the w x h picture at src (src_bytes long) dehazed into dst (dst_bytes long), its
+  // planes at plane_at words into the set's (advanced). Checked. -> the picture's air words (device)
+  const u32* put(int k, const u8* src, size_t src_bytes, u32 src_pitch, u8* dst, size_t dst_bytes, u32 dst_pitch, int w,
+                 int h, const dehaze::Params& p, size_t& plane_at);
+  // Copies the first n host descriptors up, launches them on `s` and records the event (no wait).
+  void run(int n, hipStream_t s);
+};
+using DehazePool = ScratchPool<DehazeSet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

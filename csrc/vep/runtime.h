@@ -548,14 +548,26 @@ class Worker {
   // stood: denoise, scale, enhance, overlay, encoder, all on the serving stream; *denoise_frames
   // is how many frames were used (fewer than asked for while the ring holds fewer; 1: the
   // identity). A ring without history throws. Null: path and bytes as ever.
+  // dehaze (non-null): the picture that is served is dehazed (dehaze.h, docs/DEHAZE.md) after the
+  // denoise and the scale and before the enhancement, the overlay and the encoder: in place on the
+  // denoised or scaled picture, or out of place from the slot into pooled scratch (the slot is
+  // never written), all on the serving stream; air[0..2] (non-null) receives the estimated air
+  // light. The CPU backend runs dehaze::dehaze_cpu. The served picture must have both sides at
+  // least 16 and at most 2^24 pixels. Null: path and bytes as ever.
   bool read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width = 0,
                         int height = 0, const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
-                        int* denoise_frames = nullptr);
+                        int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr);
   // The same scaled picture as packed BGR24 in host memory (dst is resized to ow * oh * 3; only
   // those bytes are copied off the GPU); meta->width / height are the scaled size.
   bool read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst,
                           const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
-                          int* denoise_frames = nullptr);
+                          int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr);
+  // The dehazed picture as packed BGR24 in host memory: scaled as read_latest_scaled, or with
+  // width = height = 0 at native size; air[0..2] (non-null) receives the estimated air light.
+  bool read_latest_dehazed(int cam, i64 after, int width, int height, const dehaze::Params& p, FrameMeta* meta,
+                           std::vector<u8>& dst, u32* air = nullptr);
+  // Dehazed pictures served since the worker started.
+  u64 dehaze_count() const { return dehaze_requests_.load(); }
   // The denoised picture as packed BGR24 in host memory: scaled as read_latest_scaled, or with
   // width = height = 0 at native size.
   bool read_latest_denoised(int cam, i64 after, int width, int height, const denoise::Params& p, FrameMeta* meta,
@@ -592,7 +604,7 @@ class Worker {
   bool read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
                          const std::string& name, FrameMeta* meta, std::string& out, int width = 0, int height = 0,
                          const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
-                         int* denoise_frames = nullptr);
+                         int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr);
   // read_wall_jpeg with labels[t] (non-empty) drawn at the top-left corner of every tile that
   // shows a frame, as a text at auto scale for the tile's height over black at alpha 160, clipped
   // to the tile's cell: one in-place launch on the composed canvas. At most
@@ -1056,11 +1068,16 @@ class Worker {
   // temporal denoise (after the enhancement's members)
   gpu::DenoisePool denoise_pool_;  // descriptors and a picture, one set per request in flight
   std::atomic<u64> denoise_requests_{0};
-  // One denoised read: what is asked of the picture behind the denoise, and where it goes (a JPEG
-  // of `quality`, or raw BGR when jpeg is null).
+  // dehazing (after the denoise's members)
+  gpu::DehazePool dehaze_pool_;  // descriptors, planes, a picture and pinned room, one set per request in flight
+  std::atomic<u64> dehaze_requests_{0};
+  // One denoised or dehazed read (at least one of the two): what is asked of the picture, and
+  // where it goes (a JPEG of `quality`, or raw BGR when jpeg is null).
   struct DenoisedRead {
     const denoise::Params* dn = nullptr;
     int width = 0, height = 0;
+    const dehaze::Params* dehaze = nullptr;
+    u32* air = nullptr;  // with dehaze: the estimated air light, 3 values
     const clahe::Params* enhance = nullptr;
     const std::vector<overlay::Item>* items = nullptr;  // with `name`: the overlay
     const std::string* name = nullptr;

@@ -7,6 +7,7 @@
 
 #include "clahe.h"
 #include "crop.h"
+#include "dehaze.h"
 #include "denoise.h"
 #include "dewarp.h"
 #include "jpeg.h"
@@ -114,12 +115,15 @@ bool Worker::read_scaled(int cam, i64 after, int width, int height, bool downloa
 }
 
 bool Worker::read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst,
-                                const clahe::Params* enhance, const denoise::Params* denoise, int* denoise_frames) {
-  if (denoise) {
+                                const clahe::Params* enhance, const denoise::Params* denoise, int* denoise_frames,
+                                const dehaze::Params* dehaze, u32* air) {
+  if (denoise || dehaze) {
     DenoisedRead rq;
     rq.dn = denoise;
     rq.width = width;
     rq.height = height;
+    rq.dehaze = dehaze;
+    rq.air = air;
     rq.enhance = enhance;
     return read_denoised(cam, after, rq, meta, denoise_frames, nullptr, &dst);
   }
@@ -418,7 +422,8 @@ bool Worker::read_latest_enhanced(int cam, i64 after, int width, int height, con
 // serving stream. The ring's slots are only read. The CPU backend does the same on the host.
 bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta* meta, int* used, std::string* jpeg,
                            std::vector<u8>* raw) {
-  denoise::check_params(*rq.dn);
+  if (rq.dn) denoise::check_params(*rq.dn);
+  if (rq.dehaze) dehaze::check_params(*rq.dehaze);
   if (rq.enhance) clahe::check_params(*rq.enhance);
   VEP_CHECK(rq.width >= 0 && rq.width <= scale::kMaxSide && rq.height >= 0 && rq.height <= scale::kMaxSide,
             "scale: width and height must be 1..65535");
@@ -427,15 +432,18 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
   if (!c) return false;
   std::shared_ptr<FrameRing> ring = c->ring();
   if (!ring) return false;
-  VEP_CHECK(ring->history() >= 2, "denoise: the camera's ring keeps no history: buffer.in_memory must be 2 or more");
+  VEP_CHECK(!rq.dn || ring->history() >= 2, "denoise: the camera's ring keeps no history: buffer.in_memory must be 2 or more");
   const int w = ring->width(), h = ring->height();
   const bool scaled = rq.width || rq.height;
   const scale::Size f = scaled ? scale::fit(w, h, rq.width, rq.height) : scale::Size{w, h};
   const size_t native = ring->slot_bytes(), n = size_t(f.w) * size_t(f.h) * 3, row = size_t(f.w) * 3;
+  VEP_CHECK(!rq.dehaze || (f.w >= dehaze::kMinSide && f.h >= dehaze::kMinSide && u64(f.w) * u64(f.h) <= dehaze::kMaxPixels),
+            "dehaze: both sides of the served picture must be at least 16 and the picture at most 2^24 pixels");
   size_t drawn = 0;
   int count = 0;
+  u32 air[4] = {0, 0, 0, 0};
   const bool ok = read_consistent_frames(
-      *ring, after, std::min(rq.dn->frames, ring->history()), meta, &count,
+      *ring, after, rq.dn ? std::min(rq.dn->frames, ring->history()) : 1, meta, &count,
       [&](const std::vector<std::pair<FrameMeta, int>>& have, const FrameMeta& m) {
         denoise::Job j;
         j.frames = int(have.size());
@@ -448,8 +456,8 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         j.dst_pitch = u32(w) * 3;
         j.w = w;
         j.h = h;
-        j.level = rq.dn->level;
-        j.strength = rq.dn->strength;
+        j.level = rq.dn ? rq.dn->level : 0;
+        j.strength = rq.dn ? rq.dn->strength : 0;
         overlay::Expanded e;  // (the items meet the picture they are drawn on, and the newest frame's meta)
         if (rq.items)
           e = overlay::expand(rq.items->data(), int(rq.items->size()), f.w, f.h, *rq.name, overlay::Meta{m.seq, m.timestamp});
@@ -458,12 +466,14 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         if (!dev_.gpu()) {
           std::vector<u8> pic(native);
           j.dst = pic.data();
-          denoise::denoise_cpu(j);
+          if (rq.dn) denoise::denoise_cpu(j);
+          else std::memcpy(pic.data(), j.src[0], native);
           if (scaled) {
             std::vector<u8> small(n);
             scale::area_cpu(pic.data(), w, h, size_t(w) * 3, small.data(), row, f.w, f.h);
             pic.swap(small);
           }
+          if (rq.dehaze) dehaze::dehaze_cpu(pic.data(), row, pic.data(), row, f.w, f.h, *rq.dehaze, air);
           if (rq.enhance) clahe::enhance_cpu(pic.data(), row, pic.data(), row, f.w, f.h, *rq.enhance);
           if (rq.items)
             overlay::apply_cpu(pic.data(), row, pic.data(), row, f.w, f.h, e.prims.data(), int(e.prims.size()), text,
@@ -473,13 +483,22 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
           return;
         }
         dev_.bind();
-        // (every request takes its sets in one order: denoise, scale, clahe, overlay, encoder)
-        gpu::DenoisePool::Lease dn = denoise_pool_.acquire();
-        dn->reserve(1, native, raw ? n : 0);
+        // (every request takes its sets in one order: denoise, scale, dehaze, clahe, overlay, encoder)
+        gpu::DenoisePool::Lease dn;
+        if (rq.dn) {
+          dn = denoise_pool_.acquire();
+          dn->reserve(1, native, raw && !rq.dehaze ? n : 0);
+        }
         gpu::ScalePool::Lease set;
         if (scaled) {
           set = scale_pool_.acquire();
           set->reserve(n, 1, 0);
+        }
+        gpu::DehazePool::Lease dh;
+        if (rq.dehaze) {
+          dh = dehaze_pool_.acquire();
+          // (a picture of its own only where the one to dehaze is the ring slot, which is never written)
+          dh->reserve(1, gpu::DehazeSet::plane_words(f.w, f.h), rq.dn || scaled ? 0 : n, raw ? n : 0);
         }
         gpu::ClahePool::Lease eq;
         if (rq.enhance) {
@@ -492,13 +511,25 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
           osd->reserve(1, e.prims.size(), e.text.size(), 0);
         }
         // (the same stream: every stage is ordered behind the one before)
-        j.dst = dn->picture.p;
-        dn->put(0, j);
-        dn->run(1, serve_stream_);
-        u8* pic = dn->picture.p;
+        u8* pic = nullptr;  // the picture the stages work on in place; null while it is still the slot
+        if (rq.dn) {
+          j.dst = dn->picture.p;
+          dn->put(0, j);
+          dn->run(1, serve_stream_);
+          pic = dn->picture.p;
+        }
         if (scaled) {
-          scale_picture(*set, pic, w, h, f.w, f.h);
+          scale_picture(*set, pic ? pic : j.src[0], w, h, f.w, f.h);
           pic = set->canvas.p;
+        }
+        if (rq.dehaze) {
+          size_t plane_at = 0;
+          u8* out = pic ? pic : dh->picture.p;
+          const u32* d_air = dh->put(0, pic ? pic : j.src[0], n, u32(row), out, n, u32(row), f.w, f.h, *rq.dehaze, plane_at);
+          dh->run(1, serve_stream_);
+          // (read after the wait for the encoder or for the copy below, which this stream orders behind it)
+          VEP_HIP(hipMemcpyAsync(dh->h_air.p, d_air, 4 * sizeof(u32), hipMemcpyDeviceToHost, serve_stream_));
+          pic = out;
         }
         if (rq.enhance) enhance_device(*eq, pic, n, pic, n, f.w, f.h, *rq.enhance);
         if (rq.items) {
@@ -508,18 +539,25 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         }
         if (jpeg) {
           encode_device(pic, f.w, f.h, rq.quality, *jpeg);
-          return;
+        } else {
+          u8* host = rq.dehaze ? dh->host.p : dn->host.p;
+          hipEvent_t ev = rq.dehaze ? hipEvent_t(dh->ev) : hipEvent_t(dn->ev);
+          VEP_HIP(hipMemcpyAsync(host, pic, n, hipMemcpyDeviceToHost, serve_stream_));
+          VEP_HIP(hipEventRecord(ev, serve_stream_));  // (again: after the copy)
+          VEP_HIP(hipEventSynchronize(ev));
+          raw->assign(host, host + n);
         }
-        VEP_HIP(hipMemcpyAsync(dn->host.p, pic, n, hipMemcpyDeviceToHost, serve_stream_));
-        VEP_HIP(hipEventRecord(dn->ev, serve_stream_));  // (again: after the copy)
-        VEP_HIP(hipEventSynchronize(dn->ev));
-        raw->assign(dn->host.p, dn->host.p + n);
+        if (rq.dehaze) std::copy_n(dh->h_air.p, 3, air);
       });
   if (!ok) return false;
   if (used) *used = count;
   meta->width = f.w;
   meta->height = f.h;
-  denoise_requests_ += 1;
+  if (rq.dn) denoise_requests_ += 1;
+  if (rq.dehaze) {
+    dehaze_requests_ += 1;
+    if (rq.air) std::copy_n(air, 3, rq.air);
+  }
   if (rq.enhance) enhance_requests_ += 1;
   if (rq.items) {
     overlay_requests_ += 1;
@@ -537,15 +575,27 @@ bool Worker::read_latest_denoised(int cam, i64 after, int width, int height, con
   return read_denoised(cam, after, rq, meta, denoise_frames, nullptr, &dst);
 }
 
+bool Worker::read_latest_dehazed(int cam, i64 after, int width, int height, const dehaze::Params& p, FrameMeta* meta,
+                                 std::vector<u8>& dst, u32* air) {
+  DenoisedRead rq;
+  rq.dehaze = &p;
+  rq.air = air;
+  rq.width = width;
+  rq.height = height;
+  return read_denoised(cam, after, rq, meta, nullptr, nullptr, &dst);
+}
+
 bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width,
                               int height, const clahe::Params* enhance, const denoise::Params* denoise,
-                              int* denoise_frames) {
+                              int* denoise_frames, const dehaze::Params* dehaze, u32* air) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-  if (denoise) {
+  if (denoise || dehaze) {
     DenoisedRead rq;
     rq.dn = denoise;
     rq.width = width;
     rq.height = height;
+    rq.dehaze = dehaze;
+    rq.air = air;
     rq.enhance = enhance;
     rq.quality = quality;
     return read_denoised(cam, after, rq, meta, denoise_frames, &out, nullptr);
@@ -597,13 +647,16 @@ bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, 
 
 bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
                                const std::string& name, FrameMeta* meta, std::string& out, int width, int height,
-                               const clahe::Params* enhance, const denoise::Params* denoise, int* denoise_frames) {
+                               const clahe::Params* enhance, const denoise::Params* denoise, int* denoise_frames,
+                               const dehaze::Params* dehaze, u32* air) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-  if (denoise) {
+  if (denoise || dehaze) {
     DenoisedRead rq;
     rq.dn = denoise;
     rq.width = width;
     rq.height = height;
+    rq.dehaze = dehaze;
+    rq.air = air;
     rq.enhance = enhance;
     rq.items = &items;
     rq.name = &name;

@@ -110,6 +110,9 @@ def write_frame(path: str, img) -> None:
         f.write(data)
 
 
+DH_ARGS = ("dh_patch", "dh_omega", "dh_t0", "dh_radius", "dh_strength")
+
+
 def frame_jpg_url(a) -> str:
     """The frame.jpg request of ``vep frame --overlay / --stamp / --enhance / --denoise``."""
     import urllib.parse
@@ -127,6 +130,11 @@ def frame_jpg_url(a) -> str:
     if a.denoise:
         q["denoise"] = "1"
         for k in ("nr_frames", "nr_level", "nr_strength"):
+            if getattr(a, k) is not None:
+                q[k] = str(getattr(a, k))
+    if a.dehaze:
+        q["dehaze"] = "1"
+        for k in DH_ARGS:
             if getattr(a, k) is not None:
                 q[k] = str(getattr(a, k))
     for k in ("width", "height"):
@@ -200,7 +208,9 @@ def cmd_frame(a):
         raise SystemExit("frame: --clip, --tile and --strength go with --enhance")
     if not a.denoise and (a.nr_frames is not None or a.nr_level is not None or a.nr_strength is not None):
         raise SystemExit("frame: --nr-frames, --nr-level and --nr-strength go with --denoise")
-    if a.overlay or a.stamp or a.enhance or a.denoise:
+    if not a.dehaze and any(getattr(a, k) is not None for k in DH_ARGS):
+        raise SystemExit("frame: --dh-patch, --dh-omega, --dh-t0, --dh-radius and --dh-strength go with --dehaze")
+    if a.overlay or a.stamp or a.enhance or a.denoise or a.dehaze:
         return cmd_frame_osd(a)
     import numpy as np
 
@@ -572,8 +582,15 @@ def build_parser():
             p.add_argument("--nr-frames", type=int, default=None, help="--denoise: frames blended, 2..8 (hub default 4)")
             p.add_argument("--nr-level", type=int, default=None, help="--denoise: noise floor 1..64 luma levels (hub default 8)")
             p.add_argument("--nr-strength", type=float, default=None, help="--denoise: 0..1 (hub default 1.0)")
+            p.add_argument("--dehaze", action="store_true",
+                           help="take the veil of fog, haze or smoke off the frame (dark-channel prior, on the hub's GPU), likewise")
+            p.add_argument("--dh-patch", type=int, default=None, help="--dehaze: window of the dark channel, odd, 3..31 (hub default 15)")
+            p.add_argument("--dh-omega", type=float, default=None, help="--dehaze: share of the veil taken off, 0..1 (hub default 0.95)")
+            p.add_argument("--dh-t0", type=float, default=None, help="--dehaze: floor of the transmission, 0.05..1 (hub default 0.1)")
+            p.add_argument("--dh-radius", type=int, default=None, help="--dehaze: refinement radius in cells, 1..16 (hub default 8)")
+            p.add_argument("--dh-strength", type=float, default=None, help="--dehaze: 0..1 (hub default 1.0)")
             p.add_argument("--rest", default="127.0.0.1:8080",
-                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance / --denoise)")
+                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance / --denoise / --dehaze)")
         if name == "annotate":
             p.add_argument("--type", required=True)
         if name in ("storage", "proxy"):

@@ -170,6 +170,17 @@ class DenoiseConfig:
 
 
 @dataclass
+class DehazeConfig:
+    """Hub-wide defaults of the dehazing (``frame.jpg?dehaze=1``, docs/DEHAZE.md); a request
+    overrides any of them."""
+    patch: int = 15        # odd, 3..31 pixels of the served picture
+    omega: float = 0.95    # 0..1
+    t0: float = 0.1        # 0.05..1
+    radius: int = 8        # 1..16 cells of 4 x 4 pixels
+    strength: float = 1.0  # 0..1
+
+
+@dataclass
 class FlowConfig:
     """Motion vectors by block matching (docs/FLOW.md; ``Hub.flow``, ``/api/v1/flow``). The
     parameters hold for every camera of the hub. The defaults are design choices, not measured
@@ -216,6 +227,7 @@ class Config:
     overlay: OverlayConfig = field(default_factory=OverlayConfig)
     enhance: EnhanceConfig = field(default_factory=EnhanceConfig)
     denoise: DenoiseConfig = field(default_factory=DenoiseConfig)
+    dehaze: DehazeConfig = field(default_factory=DehazeConfig)
     flow: FlowConfig = field(default_factory=FlowConfig)
     objects: ObjectsConfig = field(default_factory=ObjectsConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
@@ -305,6 +317,11 @@ def validate(cfg: Config) -> None:
         denoise.to_native(cfg.denoise.frames, cfg.denoise.level, cfg.denoise.strength)
     except ValueError as e:
         raise ValueError(f"denoise: {e}") from None
+    try:
+        from . import dehaze
+        dehaze.to_native(cfg.dehaze.patch, cfg.dehaze.omega, cfg.dehaze.t0, cfg.dehaze.radius, cfg.dehaze.strength)
+    except ValueError as e:
+        raise ValueError(f"dehaze: {e}") from None
     from . import flow
     flow.to_native({k: getattr(cfg.flow, k) for k in flow.DEFAULTS})
     from . import objects

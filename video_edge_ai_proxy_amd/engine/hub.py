@@ -19,6 +19,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 from .. import crops, privacy, views
+from .. import dehaze as dehaze_params
 from .. import denoise as denoise_params
 from .. import enhance as enhance_params
 from .. import flow as flow_params
@@ -365,7 +366,7 @@ class Hub:
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
                     width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False,
-                    enhance=None, denoise=None):
+                    enhance=None, denoise=None, dehaze=None):
         """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
         Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
         ``quality`` 1..100, default ``serving.jpeg_quality``. With ``width`` and / or ``height``
@@ -388,15 +389,26 @@ class Hub:
         ring's earlier frames where the picture stands still, on the camera's GPU: ahead of the
         scale, the enhancement, the overlay and the encoder. ``meta["denoise_frames"]`` says how many
         frames were used. Needs ``buffer.in_memory`` >= 2 (else a ``ValueError``). ``None``: the call
-        and its bytes are what they are without it."""
+        and its bytes are what they are without it.
+
+        ``dehaze``: ``True`` (the hub's ``dehaze:`` defaults) or a dict with any of ``patch``,
+        ``omega``, ``t0``, ``radius`` and ``strength`` (:mod:`..dehaze`, docs/DEHAZE.md) takes the veil
+        of fog, haze or smoke off the picture that is served, by the dark-channel prior on the
+        camera's GPU: after the denoise and the scale, before the enhancement, the overlay and the
+        encoder. ``meta["dehaze_air"]`` is the estimated air light ``(b, g, r)``. The served picture
+        must have both sides at least 16 (else a ``ValueError``). ``None``: the call and its bytes
+        are what they are without it."""
         q = self._quality(quality)
         bw, bh = self._box(width, height)
         if not isinstance(stamp, bool):
             raise ValueError("stamp must be true or false")
         eq = enhance_params.from_request(enhance, self.enhance_defaults())
         dn = denoise_params.from_request(denoise, self.denoise_defaults())
+        dh = dehaze_params.from_request(dehaze, self.dehaze_defaults())
         w, cam = self.worker_of(name)
         if (overlay is None or overlay is False) and not stamp:
+            if dh is not None:
+                return w.read_latest_jpeg(cam, after, q, bw, bh, eq, dn, dh)
             if dn is not None:
                 return w.read_latest_jpeg(cam, after, q, bw, bh, eq, dn)
             if eq is not None:
@@ -412,6 +424,8 @@ class Hub:
             items = osd.normalize_list(overlay)
         if stamp:
             items = items + [osd.STAMP]
+        if dh is not None:
+            return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh, eq, dn, dh)
         if dn is not None:
             return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh, eq, dn)
         if eq is not None:
@@ -460,6 +474,27 @@ class Hub:
     def denoise_count(self) -> int:
         """Denoised pictures served since the hub started (/metrics)."""
         return sum(int(w.denoise_count()) for w in self.workers)
+
+    # ------------------------------------------------------------------ dehazing
+    def dehaze_defaults(self) -> dict:
+        """The hub-wide ``patch``, ``omega``, ``t0``, ``radius`` and ``strength`` (the config's ``dehaze:`` section)."""
+        d = self.cfg.dehaze
+        return {"patch": d.patch, "omega": d.omega, "t0": d.t0, "radius": d.radius, "strength": d.strength}
+
+    def latest_dehazed(self, name: str, after: int = 0, width: int = 0, height: int = 0, **params):
+        """``(seq, ndarray)`` of the newest frame with seq > after, dehazed on the camera's GPU by the
+        dark-channel prior (docs/DEHAZE.md), or None; ``width`` / ``height`` (0: not given) fit and
+        downscale it first. ``params``: any of ``patch``, ``omega``, ``t0``, ``radius``, ``strength``;
+        the rest are the hub's defaults. Only the dehazed picture is copied to the host."""
+        dh = dehaze_params.from_request(params or True, self.dehaze_defaults())
+        bw, bh = self._box(width or None, height or None)
+        w, cam = self.worker_of(name)
+        r = w.read_latest_dehazed(cam, after, bw, bh, *dh)
+        return None if r is None else (int(r[0]["seq"]), r[1])
+
+    def dehaze_count(self) -> int:
+        """Dehazed pictures served since the hub started (/metrics)."""
+        return sum(int(w.dehaze_count()) for w in self.workers)
 
     # ------------------------------------------------------------------ on-screen display
     def set_overlay(self, name: str, items, ttl_ms: int = 0) -> None:

@@ -38,6 +38,10 @@
   luma around a pixel stands still (3 x 3 sums of absolute luma differences, integer weights; one
   launch for every picture of the call: the kernel behind ``frame.jpg?denoise=1``); host tensors run
   the CPU twin, whose bytes are the same.
+* :func:`dehaze` / :func:`dehaze_batch` — BGR24 pictures dehazed by the dark-channel prior (air light
+  from a table over the dark channel, transmission refined by a guided filter on cells of 4 x 4
+  pixels, per-pixel recovery; seven launches for every picture of the call: the kernels behind
+  ``frame.jpg?dehaze=1``); a host tensor runs the CPU twin, whose bytes are the same.
 * :func:`block_flow` / :func:`block_flow_batch` — motion vectors of a BGR24 picture against an earlier
   one by exhaustive 8 x 8 block matching on decimated luma (packed 8-bit SADs; two launches for every
   pair of the call: the kernels behind ``/flow``); host tensors run the CPU twin, whose bytes are the
@@ -1018,6 +1022,88 @@ def clahe(bgr: torch.Tensor, tile: int = 128, clip: float = 2.0, strength: float
     """One ``[H, W, 3]`` BGR24 tensor contrast-enhanced: see :func:`clahe_batch`. A device tensor runs
     the gfx950 kernels, a host tensor the CPU twin; ``out=bgr`` enhances in place."""
     return clahe_batch([bgr], tile, clip, strength, None if out is None else [out], planes)[0]
+
+
+def dehaze_batch(pictures, patch=15, omega=0.95, t0=0.1, radius=8, strength=1.0, outs=None, planes: bool = False):
+    """Dehazing by the dark-channel prior (csrc/vep/dehaze.h, docs/DEHAZE.md) of a list of
+    ``[H, W, 3]`` BGR24 tensors of any sizes (both sides at least 16, at most 2^24 pixels). Device
+    tensors (all on one device) run the gfx950 kernels, each ONE launch for the whole list; host
+    tensors run the CPU twin, whose bytes are the same. The five parameters (:mod:`..dehaze`) are
+    one value or one per picture. A device picture's rows may start at any byte address and have
+    any pitch. ``outs`` None: a new contiguous tensor per picture; else per picture a tensor of its
+    size that receives the result (the picture itself: IN PLACE), which must not overlap the
+    picture otherwise. Returns the results, with ``planes`` a list of ``(result, words)``: the
+    picture's intermediate planes as int32 words of u32 bit patterns, which
+    :func:`..dehaze.split_planes` takes apart (``air`` holds the estimated air light). No CPU
+    fallback for device tensors."""
+    from .. import dehaze as dh
+
+    pictures = list(pictures)
+    n = len(pictures)
+    if not n:
+        raise ValueError("pictures must hold at least one picture")
+    params = [dh.to_native(*v) for v in zip(*(_per_picture(v, n, what) for v, what in (
+        (patch, "patch"), (omega, "omega"), (t0, "t0"), (radius, "radius"), (strength, "strength"))))]
+    outs = [None] * n if outs is None else list(outs)
+    if len(outs) != n:
+        raise ValueError("outs must hold one entry per picture")
+    on_device = [isinstance(p, torch.Tensor) and p.is_cuda for p in pictures]
+    if any(on_device) != all(on_device):
+        raise ValueError("the pictures must all be device tensors or all host tensors")
+    for k, bgr in enumerate(pictures):
+        w, h, _ = _check_overlay_picture(bgr, f"pictures[{k}]")
+        if w < 16 or h < 16 or w * h > 1 << 24:
+            raise ValueError(f"pictures[{k}]: both sides must be at least 16 and the picture at most 2^24 pixels")
+    res = []
+    if not on_device[0]:
+        for k, (bgr, p, out) in enumerate(zip(pictures, params, outs)):
+            o, words = native.dehaze_cpu(bgr.detach().contiguous().numpy(), *p)
+            o = torch.from_numpy(o)
+            if out is not None:
+                if not isinstance(out, torch.Tensor) or out.is_cuda or out.dtype != torch.uint8 or out.shape != bgr.shape:
+                    raise ValueError(f"outs[{k}] must be a host uint8 tensor of the picture's shape")
+                out.copy_(o)
+                o = out
+            res.append((o, torch.from_numpy(words.view("int32").copy())) if planes else o)
+        return res
+    device, work, spans, sources = pictures[0].device, [], [], []
+    for k, (bgr, p, out) in enumerate(zip(pictures, params, outs)):
+        w, h, pitch = _check_overlay_picture(bgr, f"pictures[{k}]")
+        if bgr.device != device:
+            raise ValueError("the pictures must live on one device")
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+        ow, oh, dpitch = _check_overlay_picture(out, f"outs[{k}]")
+        if (ow, oh) != (w, h) or not out.is_cuda or out.device != device:
+            raise ValueError(f"outs[{k}] must be a [{h}, {w}, 3] tensor on the picture's device")
+        a, b = _overlay_span(bgr, w, h, pitch), _overlay_span(out, w, h, dpitch)
+        if (a[0] != b[0] or pitch != dpitch) and a[0] < b[1] and b[0] < a[1]:
+            raise ValueError(f"pictures[{k}] and outs[{k}] overlap")
+        for s in spans:
+            if b[0] < s[1] and s[0] < b[1]:
+                raise ValueError("the destinations of one call must not overlap")
+        spans.append(b)
+        sources.append((k, a, pitch))
+        words = torch.empty(native.dehaze_plane_words(w, h), dtype=torch.int32, device=device)
+        work.append((a[0], a[1] - a[0], pitch, b[0], b[1] - b[0], dpitch, w, h, *p, words.data_ptr(), words.numel()))
+        res.append((out, words) if planes else out)
+    # (one launch reads every source while it writes every destination: a destination may be its
+    # own picture, in place, and no other picture of the call)
+    for k, b in enumerate(spans):
+        for j, a, _ in sources:
+            if j != k and a[0] < b[1] and b[0] < a[1]:
+                raise ValueError(f"outs[{k}] overlaps pictures[{j}]")
+    require_gpu()
+    with torch.cuda.device(device):
+        native.dehaze_device_batch(work, int(torch.cuda.current_stream(device).cuda_stream))
+    return res
+
+
+def dehaze(bgr: torch.Tensor, patch: int = 15, omega: float = 0.95, t0: float = 0.1, radius: int = 8, strength: float = 1.0,
+           out: torch.Tensor | None = None, planes: bool = False):
+    """One ``[H, W, 3]`` BGR24 tensor dehazed: see :func:`dehaze_batch`. A device tensor runs the
+    gfx950 kernels, a host tensor the CPU twin; ``out=bgr`` dehazes in place."""
+    return dehaze_batch([bgr], patch, omega, t0, radius, strength, None if out is None else [out], planes)[0]
 
 
 def _frame_list(frames, what: str) -> list:

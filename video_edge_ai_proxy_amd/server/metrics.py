@@ -115,6 +115,11 @@ class HubCollector:
             dr = CounterMetricFamily("vep_denoise_requests", "pictures served temporally denoised (frame.jpg, stream.mjpg, latest_denoised)")
             dr.add_metric([], count())
             yield dr
+        count = getattr(self.hub, "dehaze_count", None)
+        if count is not None:
+            hr = CounterMetricFamily("vep_dehaze_requests", "pictures served dehazed (frame.jpg, stream.mjpg, latest_dehazed)")
+            hr.add_metric([], count())
+            yield hr
         try:
             from .._native import native
 

@@ -170,8 +170,24 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         dn.from_request(given or True)  # (a bad value is refused before the hub is asked)
         return {"denoise": given or True}
 
+    def dehazed(dehaze, dh_patch, dh_omega, dh_t0, dh_radius, dh_strength) -> dict:
+        """The dehaze argument of latest_jpeg (docs/DEHAZE.md): none when the request names none of
+        the six, so such a request calls the hub exactly as before."""
+        from .. import dehaze as dh
+
+        given = {k: v for k, v in (("patch", dh_patch), ("omega", dh_omega), ("t0", dh_t0), ("radius", dh_radius),
+                                   ("strength", dh_strength)) if v is not None}
+        if dehaze in (None, 0) and not given:
+            return {}
+        if dehaze != 1:
+            raise ValueError("dehaze must be 0 or 1 (the dh_ parameters go with dehaze=1)")
+        dh.from_request(given or True)  # (a bad value is refused before the hub is asked)
+        return {"dehaze": given or True}
+
     def frame_headers(meta) -> dict:
         h = {"X-Vep-Seq": str(meta["seq"])}
+        if "dehaze_air" in meta:
+            h["X-Vep-Dehaze-Air"] = ",".join(str(v) for v in meta["dehaze_air"])
         if "denoise_frames" in meta:
             h["X-Vep-Denoise-Frames"] = str(meta["denoise_frames"])
         return h
@@ -181,7 +197,9 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                   height: int | None = None, overlay: int = 0, stamp: int = 0, enhance: str | None = None,
                   clip: float | None = None, tile: int | None = None, strength: float | None = None,
                   denoise: int | None = None, nr_frames: int | None = None, nr_level: int | None = None,
-                  nr_strength: float | None = None):
+                  nr_strength: float | None = None, dehaze: int | None = None, dh_patch: int | None = None,
+                  dh_omega: float | None = None, dh_t0: float | None = None, dh_radius: int | None = None,
+                  dh_strength: float | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -191,8 +209,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         try:
             size.update(enhanced(enhance, clip, tile, strength))
             size.update(denoised(denoise, nr_frames, nr_level, nr_strength))
+            size.update(dehazed(dehaze, dh_patch, dh_omega, dh_t0, dh_radius, dh_strength))
         except ValueError as e:
             return err(422, str(e))
+        if "dehaze" in size and not hasattr(pm.hub, "dehaze_defaults"):
+            return err(501, "dehazed frames are not served with gpu.isolation: process")
         try:
             pm.hub.touch(name)
             r = pm.hub.latest_jpeg(name, after, q, **size)
@@ -212,7 +233,9 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                     width: int | None = None, height: int | None = None, overlay: int = 0, stamp: int = 0,
                     enhance: str | None = None, clip: float | None = None, tile: int | None = None,
                     strength: float | None = None, denoise: int | None = None, nr_frames: int | None = None,
-                    nr_level: int | None = None, nr_strength: float | None = None):
+                    nr_level: int | None = None, nr_strength: float | None = None, dehaze: int | None = None,
+                    dh_patch: int | None = None, dh_omega: float | None = None, dh_t0: float | None = None,
+                    dh_radius: int | None = None, dh_strength: float | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -226,8 +249,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         try:
             size.update(enhanced(enhance, clip, tile, strength))
             size.update(denoised(denoise, nr_frames, nr_level, nr_strength))
+            size.update(dehazed(dehaze, dh_patch, dh_omega, dh_t0, dh_radius, dh_strength))
         except ValueError as e:
             return err(422, str(e))
+        if "dehaze" in size and not hasattr(pm.hub, "dehaze_defaults"):  # (501 before the stream starts)
+            return err(501, "dehazed frames are not served with gpu.isolation: process")
         try:
             pm.hub.touch(name)
         except KeyError:
@@ -271,6 +297,7 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                 seq, last_new = meta["seq"], now
                 yield (f"--{MJPEG_BOUNDARY}\r\nContent-Type: image/jpeg\r\nContent-Length: {len(jpg)}\r\n"
                        f"X-Vep-Seq: {seq}\r\n" + (f"X-Vep-Denoise-Frames: {meta['denoise_frames']}\r\n" if "denoise_frames" in meta else "")
+                       + (f"X-Vep-Dehaze-Air: {','.join(str(v) for v in meta['dehaze_air'])}\r\n" if "dehaze_air" in meta else "")
                        + "\r\n").encode() + jpg + b"\r\n"
                 sent += 1
                 due = max(due + 1.0 / fps, now)
