@@ -8,6 +8,7 @@
 #include "bind_ext.h"
 #include "vep/clahe.h"
 #include "vep/dehaze.h"
+#include "vep/deinterlace.h"
 #include "vep/crop.h"
 #include "vep/denoise.h"
 #include "vep/dewarp.h"
@@ -476,6 +477,26 @@ inline bool dehaze_of(const py::object& o, dehaze::Params& p) {
   if (o.is_none()) return false;
   const auto t = o.cast<std::tuple<int, int, int, int, int>>();
   p = dehaze_params_of(std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t));
+  return true;
+}
+
+// Deinterlace parameters (vep/deinterlace.h) cross the boundary as two ints (order: 0 tff, 1 bff;
+// temporal: 0 or 1); a bad one is a ValueError.
+inline deinterlace::Params deinterlace_params_of(int order, int temporal) {
+  const deinterlace::Params p{order, temporal};
+  try {
+    deinterlace::check_params(p);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  return p;
+}
+
+// A serving read's `deinterlace` argument: None, or the tuple (order, temporal).
+inline bool deinterlace_of(const py::object& o, deinterlace::Params& p) {
+  if (o.is_none()) return false;
+  const auto t = o.cast<std::tuple<int, int>>();
+  p = deinterlace_params_of(std::get<0>(t), std::get<1>(t));
   return true;
 }
 

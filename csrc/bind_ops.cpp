@@ -141,6 +141,43 @@ static void denoise_run(const std::vector<DenoisePicture>& pics, uintptr_t strea
   });
 }
 
+// deinterlace_device_batch: every picture's job (the newest frame, the one before it (address 0:
+// none) and the destination, each as address, bytes, pitch) checked against the sizes the caller
+// states, then one launch on a pooled set.
+using DeinterlaceFrame = std::tuple<uintptr_t, size_t, u32>;
+using DeinterlacePicture = std::tuple<DeinterlaceFrame, DeinterlaceFrame, DeinterlaceFrame, int, int, int, int>;
+static void deinterlace_run(const std::vector<DeinterlacePicture>& pics, uintptr_t stream) {
+  const int n = int(pics.size());
+  if (n < 1 || pics.size() > 65535) throw py::value_error("deinterlace: 1..65535 pictures expected");
+  std::vector<deinterlace::Job> jobs((size_t(n)));
+  for (int k = 0; k < n; ++k) {
+    const auto& [newer, older, dst, w, h, order, temporal] = pics[size_t(k)];
+    deinterlace::Job& j = jobs[size_t(k)];
+    j.newer = reinterpret_cast<const u8*>(std::get<0>(newer));
+    j.newer_bytes = std::get<1>(newer);
+    j.newer_pitch = std::get<2>(newer);
+    j.older = reinterpret_cast<const u8*>(std::get<0>(older));
+    j.older_bytes = std::get<1>(older);
+    j.older_pitch = std::get<2>(older);
+    j.dst = reinterpret_cast<u8*>(std::get<0>(dst));
+    j.dst_bytes = std::get<1>(dst);
+    j.dst_pitch = std::get<2>(dst);
+    j.w = j.older_w = w;
+    j.h = j.older_h = h;
+    j.p = deinterlace::Params{order, temporal};
+    try {
+      deinterlace::check_job(j);
+    } catch (const Error& e) {
+      throw py::value_error(e.what());
+    }
+  }
+  on_pooled_set<gpu::DeinterlacePool>(stream, [&](gpu::DeinterlacePool::Lease& set, hipStream_t s) {
+    set->reserve(n, 0, 0);
+    for (int k = 0; k < n; ++k) set->put(k, jobs[size_t(k)]);
+    set->run(n, s);
+  });
+}
+
 // flow_device_batch: every picture's job (newer and older frame as (address, bytes, pitch), its two
 // luma planes of plane_bytes each, its records) checked against the sizes the caller states, then
 // the two launches on a pooled set.
@@ -942,6 +979,54 @@ void bind_ops(py::module_& m) {
   // level, strength) on caller-owned device buffers: the gfx950 denoise kernel, ONE launch for all
   // of them, on `stream` of the current device. Out of place only.
   m.def("denoise_device_batch", &denoise_run, py::arg("pictures"), py::arg("stream"));
+  // Deinterlacing (vep/deinterlace.h) on the host: the CPU backend's path, the byte-exact reference
+  // of deinterlace_device_batch. The woven (H, W, 3) frame and the one before it (None: the spatial
+  // prediction alone) -> (H, W, 3). order: "tff" / "bff" (or 0 / 1).
+  m.def("deinterlace_cpu",
+        [](py::array_t<uint8_t, py::array::c_style> newer, py::object older, py::object order, int temporal) {
+          if (!is_bgr_picture(newer)) throw py::value_error("deinterlace_cpu: (H, W, 3) uint8 picture expected");
+          int parity = -1;
+          if (py::isinstance<py::str>(order)) {
+            const std::string o = order.cast<std::string>();
+            parity = o == "tff" ? 0 : (o == "bff" ? 1 : -1);
+          } else if (py::isinstance<py::int_>(order)) {
+            parity = order.cast<int>();
+          }
+          deinterlace::Job j;
+          j.p = deinterlace_params_of(parity, temporal);
+          j.h = int(newer.shape(0));
+          j.w = int(newer.shape(1));
+          const size_t row = size_t(j.w) * 3, bytes = row * size_t(j.h);
+          py::array_t<uint8_t, py::array::c_style> prev;
+          if (!older.is_none()) {
+            if (!py::isinstance<py::array_t<uint8_t, py::array::c_style>>(older))
+              throw py::value_error("deinterlace_cpu: older must be None or a C-contiguous (H, W, 3) uint8 picture");
+            prev = older.cast<py::array_t<uint8_t, py::array::c_style>>();
+            if (!is_bgr_picture(prev)) throw py::value_error("deinterlace_cpu: older must be None or an (H, W, 3) uint8 picture");
+            j.older = prev.data();
+            j.older_h = int(prev.shape(0));
+            j.older_w = int(prev.shape(1));
+            j.older_pitch = u32(size_t(j.older_w) * 3);
+            j.older_bytes = size_t(j.older_pitch) * size_t(j.older_h);
+          }
+          py::array_t<uint8_t> out({py::ssize_t(j.h), py::ssize_t(j.w), py::ssize_t(3)});
+          j.newer = newer.data();
+          j.newer_bytes = j.dst_bytes = bytes;
+          j.newer_pitch = j.dst_pitch = u32(row);
+          j.dst = out.mutable_data();
+          try {
+            py::gil_scoped_release r;
+            deinterlace::deinterlace_cpu(j);
+          } catch (const Error& e) {
+            throw py::value_error(e.what());
+          }
+          return out;
+        },
+        py::arg("newer").noconvert(), py::arg("older") = py::none(), py::arg("order") = "tff", py::arg("temporal") = 1);
+  // Pictures ((newer, bytes, pitch), (older, bytes, pitch) with address 0 for none, (dst, bytes,
+  // pitch), w, h, order, temporal) on caller-owned device buffers: the gfx950 deinterlace kernel,
+  // ONE launch for all of them, on `stream` of the current device. Out of place only.
+  m.def("deinterlace_device_batch", &deinterlace_run, py::arg("pictures"), py::arg("stream"));
   // Motion vectors by block matching (vep/flow.h) on the host: the CPU backend's path, the
   // byte-exact reference of flow_device_batch. Two (H, W, 3) pictures -> (the two luma planes
   // (2, h', w'), the records as a (rows, cols, 4) int16 array of vx, vy, best, zero).

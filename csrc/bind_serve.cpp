@@ -16,7 +16,7 @@ static bool serve_released(Read&& read) {
     } catch (const Error& e) {
       const std::string what = e.what();
       if (what.find("overlay:") == std::string::npos && what.find("denoise:") == std::string::npos &&
-          what.find("dehaze:") == std::string::npos &&
+          what.find("dehaze:") == std::string::npos && what.find("deinterlace:") == std::string::npos &&
           what.find("flow:") == std::string::npos && what.find("objects:") == std::string::npos)
         throw;
       refused = what;
@@ -27,9 +27,12 @@ static bool serve_released(Read&& read) {
 }
 // The meta of a denoised read says how many frames were blended.
 // The meta of a dehazed read carries the estimated air light as (b, g, r).
-static py::dict denoised_meta(const FrameMeta& m, bool denoised, int frames, bool dehazed = false, const u32* air = nullptr) {
+// The meta of a deinterlaced read says how many frames were used, 1 or 2.
+static py::dict denoised_meta(const FrameMeta& m, bool denoised, int frames, bool dehazed = false, const u32* air = nullptr,
+                              bool deinterlaced = false, int woven = 0) {
   py::dict d = meta_dict(m);
   if (denoised) d["denoise_frames"] = frames;
+  if (deinterlaced) d["deinterlace_frames"] = woven;
   if (dehazed) d["dehaze_air"] = py::make_tuple(air[0], air[1], air[2]);
   return d;
 }
@@ -63,8 +66,10 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // anything else (docs/DENOISE.md); meta then carries denoise_frames, how many were used.
            // dehaze (None, or (patch, omega, t0, radius, strength)): dehazed after the denoise and the
            // scale (docs/DEHAZE.md); meta then carries dehaze_air, the estimated air light (b, g, r).
+           // deinterlace (None, or (order, temporal)): deinterlaced before anything else, never with
+           // denoise (docs/DEINTERLACE.md); meta then carries deinterlace_frames, 1 or 2.
            [](Worker& w, int i, i64 after, int quality, int width, int height, py::object enhance, py::object denoise,
-              py::object dehaze) -> py::object {
+              py::object dehaze, py::object deinterlace) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              clahe::Params p;
              const bool eq = enhance_of(enhance, p);
@@ -72,20 +77,44 @@ void bind_worker_serving(py::class_<Worker>& cls) {
              const bool dn = denoise_of(denoise, dp);
              dehaze::Params hp;
              const bool dh = dehaze_of(dehaze, hp);
+             deinterlace::Params ip;
+             const bool di = deinterlace_of(deinterlace, ip);
              FrameMeta m;
              std::string out;
-             int used = 0;
+             int used = 0, woven = 0;
              u32 air[3] = {0, 0, 0};
              const bool ok = serve_released([&] {
                return w.read_latest_jpeg(i, after, quality, &m, out, width, height, eq ? &p : nullptr, dn ? &dp : nullptr, &used,
-                                         dh ? &hp : nullptr, air);
+                                         dh ? &hp : nullptr, air, di ? &ip : nullptr, &woven);
              });
              if (!ok) return py::none();
-             return py::make_tuple(denoised_meta(m, dn, used, dh, air), py::bytes(out));
+             return py::make_tuple(denoised_meta(m, dn, used, dh, air, di, woven), py::bytes(out));
            },
            py::arg("idx"), py::arg("after") = 0, py::arg("quality") = 85, py::arg("width") = 0,
            py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none(),
-           py::arg("dehaze") = py::none())
+           py::arg("dehaze") = py::none(), py::arg("deinterlace") = py::none())
+      .def("read_latest_deinterlaced",
+           // (meta, ndarray) of the newest frame with seq > after, deinterlaced against the frame before
+           // it where the ring has one (docs/DEINTERLACE.md); fitted into width x height afterwards when
+           // either is given; None if there is none. meta carries deinterlace_frames.
+           [](Worker& w, int i, i64 after, int width, int height, int order, int temporal) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const deinterlace::Params p = deinterlace_params_of(order, temporal);
+             if (after < 0) throw py::value_error("deinterlace: after must be >= 0");
+             if (width < 0 || width > 65535 || height < 0 || height > 65535)
+               throw py::value_error("scale: width and height must be 1..65535 (0: not given)");
+             FrameMeta m;
+             std::vector<u8> px;
+             int woven = 0;
+             if (!serve_released([&] { return w.read_latest_deinterlaced(i, after, width, height, p, &m, px, &woven); }))
+               return py::none();
+             py::array_t<uint8_t> a({py::ssize_t(m.height), py::ssize_t(m.width), py::ssize_t(3)});
+             std::memcpy(a.mutable_data(), px.data(), px.size());
+             return py::make_tuple(denoised_meta(m, false, 0, false, nullptr, true, woven), a);
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("width") = 0, py::arg("height") = 0, py::arg("order") = 0,
+           py::arg("temporal") = 1)
+      .def("deinterlace_count", [](Worker& w) { return w.deinterlace_count(); })
       .def("read_latest_dehazed",
            // (meta, ndarray) of the newest frame with seq > after, dehazed (docs/DEHAZE.md); fitted into
            // width x height first when either is given; None if there is none. meta carries dehaze_air.
@@ -229,9 +258,13 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // read_latest_jpeg with the overlay items drawn on the picture (docs/OVERLAY.md): {name},
            // {seq} and {time} come from `name` and the meta of the frame actually encoded.
            [](Worker& w, int i, const std::vector<ItemTuple>& items, const std::string& name, i64 after, int quality,
-              int width, int height, py::object enhance, py::object denoise, py::object dehaze) -> py::object {
+              int width, int height, py::object enhance, py::object denoise, py::object dehaze,
+              py::object deinterlace) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              const std::vector<overlay::Item> its = items_of(items);
+             deinterlace::Params ip;
+             const bool di = deinterlace_of(deinterlace, ip);
+             int woven = 0;
              clahe::Params p;
              const bool eq = enhance_of(enhance, p);
              denoise::Params dp;
@@ -249,14 +282,14 @@ void bind_worker_serving(py::class_<Worker>& cls) {
              // (of a checked list only the expansion can be refused: too many primitives)
              const bool ok = serve_released([&] {
                return w.read_overlay_jpeg(i, after, quality, its, name, &m, out, width, height, eq ? &p : nullptr,
-                                          dn ? &dp : nullptr, &used, dh ? &hp : nullptr, air);
+                                          dn ? &dp : nullptr, &used, dh ? &hp : nullptr, air, di ? &ip : nullptr, &woven);
              });
              if (!ok) return py::none();
-             return py::make_tuple(denoised_meta(m, dn, used, dh, air), py::bytes(out));
+             return py::make_tuple(denoised_meta(m, dn, used, dh, air, di, woven), py::bytes(out));
            },
            py::arg("idx"), py::arg("items"), py::arg("name") = "", py::arg("after") = 0, py::arg("quality") = 85,
            py::arg("width") = 0, py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none(),
-           py::arg("dehaze") = py::none())
+           py::arg("dehaze") = py::none(), py::arg("deinterlace") = py::none())
       .def("overlay_counts", [](Worker& w) { return w.overlay_counts(); })
       .def_property("wall_max_tiles", &Worker::wall_max_tiles, &Worker::set_wall_max_tiles)
       .def("read_motion",

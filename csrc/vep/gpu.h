@@ -16,6 +16,7 @@
 #include "clahe.h"
 #include "common.h"
 #include "dehaze.h"
+#include "deinterlace.h"
 #include "denoise.h"
 #include "flow.h"
 #include "mask.h"
@@ -950,6 +951,45 @@ struct DehazeSet : DescSet<DehazeDesc> {
   void run(int n, hipStream_t s);
 };
 using DehazePool = ScratchPool<DehazeSet>;
+
+// ---- deinterlacing (gpu_deinterlace.hip; arithmetic: deinterlace.h) --------------------------------
+// One picture of a batched deinterlace request (device memory): the woven frame `newer` and the
+// frame before it `older` (null: the spatial prediction alone) of one size, deinterlaced into dst,
+// byte-identical with deinterlace::deinterlace_cpu, in ONE launch for every picture of the request.
+// Out of place only: dst overlaps no source, and a source (a ring slot) is never written. Pictures
+// of one request may differ in size, order and in having an older frame; their destinations must
+// not overlap.
+struct DeinterlaceDesc {
+  const VEP_DEV u8* newer;  // h rows of newer_pitch bytes (any alignment)
+  const VEP_DEV u8* older;  // h rows of older_pitch bytes, or null
+  VEP_DEV u8* dst;          // h rows of dst_pitch bytes (any alignment)
+  u32 newer_pitch, older_pitch, dst_pitch;  // bytes
+  i32 w, h;
+  i32 parity;  // of the earlier field's rows, which are kept (deinterlace::Order)
+};
+static_assert(sizeof(DeinterlaceDesc) == 48, "DeinterlaceDesc layout");
+// The descriptor of a job (deinterlace::Job: sources, destination and their sizes), checked by
+// deinterlace::check_job: every access of the kernel lies inside a source or the destination and
+// the destination overlaps no source. `older` is dropped where Params::temporal is 0. The launch
+// below does not check.
+DeinterlaceDesc check_deinterlace(const deinterlace::Job& j);
+// One launch for the n pictures on `s`: grid = (tiles of the largest picture) x pictures.
+// h_descs is the host copy of d_descs (the grid is sized from it).
+void launch_deinterlace(const DeinterlaceDesc* d_descs, const DeinterlaceDesc* h_descs, int n, hipStream_t s);
+
+// Deinterlace scratch of one device (pool contract: above): descriptors, a picture that receives a
+// frame's deinterlaced copy (where the ring slot stood for the stages behind), and a pinned buffer
+// for results on their way down.
+struct DeinterlaceSet : DescSet<DeinterlaceDesc> {
+  DevBuf<u8> picture;
+  PinBuf<u8> host;
+  void reserve(int ndescs, size_t picture_bytes, size_t host_bytes);
+  // Descriptor k from a checked job.
+  void put(int k, const deinterlace::Job& j);
+  // Copies the first n host descriptors up, launches them on `s` and records the event (no wait).
+  void run(int n, hipStream_t s);
+};
+using DeinterlacePool = ScratchPool<DeinterlaceSet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

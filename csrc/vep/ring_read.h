@@ -62,11 +62,15 @@ bool read_consistent(const FrameRing& ring, i64 after, FrameMeta* meta, Produce&
 // One reused slot spoils the read: it starts again from the then newest frames, kReadAttempts
 // times in all. After invalidate() no earlier frame is readable, so what a privacy-mask change
 // withdrew is never blended into a later picture. *used: how many frames the good read used.
+// any_earlier (the deinterlacer, deinterlace.h): `after` decides only whether the newest frame
+// answers; the earlier frames are picked whatever `after` is, so a client that polls with the last
+// seq it saw still gets the frame before the newest (as FramesEntry below).
 template <class Produce>
-bool read_consistent_frames(const FrameRing& ring, i64 after, int frames, FrameMeta* meta, int* used, Produce&& produce) {
+bool read_consistent_frames(const FrameRing& ring, i64 after, int frames, FrameMeta* meta, int* used, Produce&& produce,
+                            bool any_earlier = false) {
   std::vector<std::pair<FrameMeta, int>> have;
   for (int attempt = 0; attempt < kReadAttempts; ++attempt) {
-    if (ring.range(after, frames, have) < 1) return false;
+    if (ring.range(any_earlier ? 0 : after, frames, have) < 1 || have.back().first.seq <= after) return false;
     std::reverse(have.begin(), have.end());  // newest first
     *meta = have.front().first;
     produce(have, *meta);

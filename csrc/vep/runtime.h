@@ -554,14 +554,28 @@ class Worker {
   // never written), all on the serving stream; air[0..2] (non-null) receives the estimated air
   // light. The CPU backend runs dehaze::dehaze_cpu. The served picture must have both sides at
   // least 16 and at most 2^24 pixels. Null: path and bytes as ever.
+  // deinterlace (non-null): the frame is deinterlaced first (deinterlace.h, docs/DEINTERLACE.md),
+  // from the newest slot and the newest earlier one the ring still holds, into pooled scratch at
+  // native size, which then stands where the ring slot stood: deinterlace, scale, dehaze, enhance,
+  // overlay, encoder, all on the serving stream. *deinterlace_frames is how many frames were used:
+  // 2, or 1 where only the spatial part could run (no history, the first frame, after a privacy-mask
+  // change, a size change between the two, temporal 0). Together with denoise it throws: denoise
+  // blends earlier slots, which are woven. Null: path and bytes as ever.
   bool read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width = 0,
                         int height = 0, const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
-                        int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr);
+                        int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr,
+                        const deinterlace::Params* deinterlace = nullptr, int* deinterlace_frames = nullptr);
   // The same scaled picture as packed BGR24 in host memory (dst is resized to ow * oh * 3; only
   // those bytes are copied off the GPU); meta->width / height are the scaled size.
   bool read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst,
                           const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
                           int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr);
+  // The deinterlaced picture as packed BGR24 in host memory: scaled as read_latest_scaled, or with
+  // width = height = 0 at native size; *frames (non-null): how many frames were used, 1 or 2.
+  bool read_latest_deinterlaced(int cam, i64 after, int width, int height, const deinterlace::Params& p, FrameMeta* meta,
+                                std::vector<u8>& dst, int* frames = nullptr);
+  // Deinterlaced pictures served since the worker started.
+  u64 deinterlace_count() const { return deinterlace_requests_.load(); }
   // The dehazed picture as packed BGR24 in host memory: scaled as read_latest_scaled, or with
   // width = height = 0 at native size; air[0..2] (non-null) receives the estimated air light.
   bool read_latest_dehazed(int cam, i64 after, int width, int height, const dehaze::Params& p, FrameMeta* meta,
@@ -604,7 +618,8 @@ class Worker {
   bool read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
                          const std::string& name, FrameMeta* meta, std::string& out, int width = 0, int height = 0,
                          const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
-                         int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr);
+                         int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr,
+                         const deinterlace::Params* deinterlace = nullptr, int* deinterlace_frames = nullptr);
   // read_wall_jpeg with labels[t] (non-empty) drawn at the top-left corner of every tile that
   // shows a frame, as a text at auto scale for the tile's height over black at alpha 160, clipped
   // to the tile's cell: one in-place launch on the composed canvas. At most
@@ -1071,10 +1086,14 @@ class Worker {
   // dehazing (after the denoise's members)
   gpu::DehazePool dehaze_pool_;  // descriptors, planes, a picture and pinned room, one set per request in flight
   std::atomic<u64> dehaze_requests_{0};
-  // One denoised or dehazed read (at least one of the two): what is asked of the picture, and
+  // deinterlacing (after the dehaze's members)
+  gpu::DeinterlacePool deinterlace_pool_;  // descriptors and a picture, one set per request in flight
+  std::atomic<u64> deinterlace_requests_{0};
+  // One denoised, deinterlaced or dehazed read (at least one of the three): what is asked of the picture, and
   // where it goes (a JPEG of `quality`, or raw BGR when jpeg is null).
   struct DenoisedRead {
     const denoise::Params* dn = nullptr;
+    const deinterlace::Params* di = nullptr;  // not together with dn
     int width = 0, height = 0;
     const dehaze::Params* dehaze = nullptr;
     u32* air = nullptr;  // with dehaze: the estimated air light, 3 values

@@ -8,6 +8,7 @@
 #include "clahe.h"
 #include "crop.h"
 #include "dehaze.h"
+#include "deinterlace.h"
 #include "denoise.h"
 #include "dewarp.h"
 #include "jpeg.h"
@@ -423,6 +424,8 @@ bool Worker::read_latest_enhanced(int cam, i64 after, int width, int height, con
 bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta* meta, int* used, std::string* jpeg,
                            std::vector<u8>* raw) {
   if (rq.dn) denoise::check_params(*rq.dn);
+  if (rq.di) deinterlace::check_params(*rq.di);
+  VEP_CHECK(!(rq.dn && rq.di), "deinterlace: not served together with denoise, which blends the ring's woven frames");
   if (rq.dehaze) dehaze::check_params(*rq.dehaze);
   if (rq.enhance) clahe::check_params(*rq.enhance);
   VEP_CHECK(rq.width >= 0 && rq.width <= scale::kMaxSide && rq.height >= 0 && rq.height <= scale::kMaxSide,
@@ -440,13 +443,30 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
   VEP_CHECK(!rq.dehaze || (f.w >= dehaze::kMinSide && f.h >= dehaze::kMinSide && u64(f.w) * u64(f.h) <= dehaze::kMaxPixels),
             "dehaze: both sides of the served picture must be at least 16 and the picture at most 2^24 pixels");
   size_t drawn = 0;
-  int count = 0;
+  int count = 0, woven = 0;
   u32 air[4] = {0, 0, 0, 0};
+  VEP_CHECK(!rq.di || (w >= deinterlace::kMinSide && h >= deinterlace::kMinSide),
+            "deinterlace: both sides of the picture must be 4..65535");
+  // (the deinterlacer takes the frame before the newest where the ring has it, and does without)
+  const int ask = rq.dn ? std::min(rq.dn->frames, ring->history()) : (rq.di && ring->history() >= 2 ? 2 : 1);
   const bool ok = read_consistent_frames(
-      *ring, after, rq.dn ? std::min(rq.dn->frames, ring->history()) : 1, meta, &count,
+      *ring, after, ask, meta, &count,
       [&](const std::vector<std::pair<FrameMeta, int>>& have, const FrameMeta& m) {
+        deinterlace::Job dj;
+        if (rq.di) {
+          dj.newer = ring->slot_ptr(have[0].second);
+          // the frame before: only one of the newest's size (a stream that changed its size mid-ring)
+          if (have.size() > 1 && have[1].first.width == m.width && have[1].first.height == m.height)
+            dj.older = ring->slot_ptr(have[1].second);
+          dj.newer_bytes = dj.older_bytes = dj.dst_bytes = native;
+          dj.newer_pitch = dj.older_pitch = dj.dst_pitch = u32(w) * 3;
+          dj.w = dj.older_w = w;
+          dj.h = dj.older_h = h;
+          dj.p = *rq.di;
+          woven = deinterlace::temporal_of(dj) ? 2 : 1;
+        }
         denoise::Job j;
-        j.frames = int(have.size());
+        j.frames = rq.di ? 1 : int(have.size());
         for (int k = 0; k < j.frames; ++k) {
           j.src[k] = ring->slot_ptr(have[size_t(k)].second);
           j.src_bytes[k] = native;
@@ -465,8 +485,9 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         drawn = e.prims.size();
         if (!dev_.gpu()) {
           std::vector<u8> pic(native);
-          j.dst = pic.data();
+          j.dst = dj.dst = pic.data();
           if (rq.dn) denoise::denoise_cpu(j);
+          else if (rq.di) deinterlace::deinterlace_cpu(dj);
           else std::memcpy(pic.data(), j.src[0], native);
           if (scaled) {
             std::vector<u8> small(n);
@@ -483,11 +504,16 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
           return;
         }
         dev_.bind();
-        // (every request takes its sets in one order: denoise, scale, dehaze, clahe, overlay, encoder)
+        // (every request takes its sets in one order: denoise, deinterlace, scale, dehaze, clahe, overlay, encoder)
         gpu::DenoisePool::Lease dn;
         if (rq.dn) {
           dn = denoise_pool_.acquire();
           dn->reserve(1, native, raw && !rq.dehaze ? n : 0);
+        }
+        gpu::DeinterlacePool::Lease di;
+        if (rq.di) {
+          di = deinterlace_pool_.acquire();
+          di->reserve(1, native, raw && !rq.dehaze ? n : 0);
         }
         gpu::ScalePool::Lease set;
         if (scaled) {
@@ -498,7 +524,7 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         if (rq.dehaze) {
           dh = dehaze_pool_.acquire();
           // (a picture of its own only where the one to dehaze is the ring slot, which is never written)
-          dh->reserve(1, gpu::DehazeSet::plane_words(f.w, f.h), rq.dn || scaled ? 0 : n, raw ? n : 0);
+          dh->reserve(1, gpu::DehazeSet::plane_words(f.w, f.h), rq.dn || rq.di || scaled ? 0 : n, raw ? n : 0);
         }
         gpu::ClahePool::Lease eq;
         if (rq.enhance) {
@@ -517,6 +543,12 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
           dn->put(0, j);
           dn->run(1, serve_stream_);
           pic = dn->picture.p;
+        }
+        if (rq.di) {
+          dj.dst = di->picture.p;
+          di->put(0, dj);
+          di->run(1, serve_stream_);
+          pic = di->picture.p;
         }
         if (scaled) {
           scale_picture(*set, pic ? pic : j.src[0], w, h, f.w, f.h);
@@ -540,20 +572,22 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         if (jpeg) {
           encode_device(pic, f.w, f.h, rq.quality, *jpeg);
         } else {
-          u8* host = rq.dehaze ? dh->host.p : dn->host.p;
-          hipEvent_t ev = rq.dehaze ? hipEvent_t(dh->ev) : hipEvent_t(dn->ev);
+          u8* host = rq.dehaze ? dh->host.p : (rq.di ? di->host.p : dn->host.p);
+          hipEvent_t ev = rq.dehaze ? hipEvent_t(dh->ev) : (rq.di ? hipEvent_t(di->ev) : hipEvent_t(dn->ev));
           VEP_HIP(hipMemcpyAsync(host, pic, n, hipMemcpyDeviceToHost, serve_stream_));
           VEP_HIP(hipEventRecord(ev, serve_stream_));  // (again: after the copy)
           VEP_HIP(hipEventSynchronize(ev));
           raw->assign(host, host + n);
         }
         if (rq.dehaze) std::copy_n(dh->h_air.p, 3, air);
-      });
+      },
+      rq.di != nullptr);
   if (!ok) return false;
-  if (used) *used = count;
+  if (used) *used = rq.di ? woven : count;
   meta->width = f.w;
   meta->height = f.h;
   if (rq.dn) denoise_requests_ += 1;
+  if (rq.di) deinterlace_requests_ += 1;
   if (rq.dehaze) {
     dehaze_requests_ += 1;
     if (rq.air) std::copy_n(air, 3, rq.air);
@@ -575,6 +609,15 @@ bool Worker::read_latest_denoised(int cam, i64 after, int width, int height, con
   return read_denoised(cam, after, rq, meta, denoise_frames, nullptr, &dst);
 }
 
+bool Worker::read_latest_deinterlaced(int cam, i64 after, int width, int height, const deinterlace::Params& p, FrameMeta* meta,
+                                      std::vector<u8>& dst, int* frames) {
+  DenoisedRead rq;
+  rq.di = &p;
+  rq.width = width;
+  rq.height = height;
+  return read_denoised(cam, after, rq, meta, frames, nullptr, &dst);
+}
+
 bool Worker::read_latest_dehazed(int cam, i64 after, int width, int height, const dehaze::Params& p, FrameMeta* meta,
                                  std::vector<u8>& dst, u32* air) {
   DenoisedRead rq;
@@ -587,18 +630,20 @@ bool Worker::read_latest_dehazed(int cam, i64 after, int width, int height, cons
 
 bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width,
                               int height, const clahe::Params* enhance, const denoise::Params* denoise,
-                              int* denoise_frames, const dehaze::Params* dehaze, u32* air) {
+                              int* denoise_frames, const dehaze::Params* dehaze, u32* air,
+                              const deinterlace::Params* deinterlace, int* deinterlace_frames) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-  if (denoise || dehaze) {
+  if (denoise || dehaze || deinterlace) {
     DenoisedRead rq;
     rq.dn = denoise;
+    rq.di = deinterlace;
     rq.width = width;
     rq.height = height;
     rq.dehaze = dehaze;
     rq.air = air;
     rq.enhance = enhance;
     rq.quality = quality;
-    return read_denoised(cam, after, rq, meta, denoise_frames, &out, nullptr);
+    return read_denoised(cam, after, rq, meta, deinterlace ? deinterlace_frames : denoise_frames, &out, nullptr);
   }
   if (width || height)
     return read_scaled(cam, after, width, height, false, meta, enhance,
@@ -648,11 +693,13 @@ bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, 
 bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vector<overlay::Item>& items,
                                const std::string& name, FrameMeta* meta, std::string& out, int width, int height,
                                const clahe::Params* enhance, const denoise::Params* denoise, int* denoise_frames,
-                               const dehaze::Params* dehaze, u32* air) {
+                               const dehaze::Params* dehaze, u32* air, const deinterlace::Params* deinterlace,
+                               int* deinterlace_frames) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-  if (denoise || dehaze) {
+  if (denoise || dehaze || deinterlace) {
     DenoisedRead rq;
     rq.dn = denoise;
+    rq.di = deinterlace;
     rq.width = width;
     rq.height = height;
     rq.dehaze = dehaze;
@@ -661,7 +708,7 @@ bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vecto
     rq.items = &items;
     rq.name = &name;
     rq.quality = quality;
-    return read_denoised(cam, after, rq, meta, denoise_frames, &out, nullptr);
+    return read_denoised(cam, after, rq, meta, deinterlace ? deinterlace_frames : denoise_frames, &out, nullptr);
   }
   if (enhance) clahe::check_params(*enhance);
   VEP_CHECK(width >= 0 && width <= scale::kMaxSide && height >= 0 && height <= scale::kMaxSide,

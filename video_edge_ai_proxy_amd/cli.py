@@ -137,6 +137,12 @@ def frame_jpg_url(a) -> str:
         for k in DH_ARGS:
             if getattr(a, k) is not None:
                 q[k] = str(getattr(a, k))
+    if a.deinterlace:
+        q["deinterlace"] = "1"
+        if a.di_order is not None:
+            q["di_order"] = a.di_order
+        if a.di_no_temporal:
+            q["di_temporal"] = "0"
     for k in ("width", "height"):
         if getattr(a, k) is not None:
             q[k] = str(getattr(a, k))
@@ -210,7 +216,9 @@ def cmd_frame(a):
         raise SystemExit("frame: --nr-frames, --nr-level and --nr-strength go with --denoise")
     if not a.dehaze and any(getattr(a, k) is not None for k in DH_ARGS):
         raise SystemExit("frame: --dh-patch, --dh-omega, --dh-t0, --dh-radius and --dh-strength go with --dehaze")
-    if a.overlay or a.stamp or a.enhance or a.denoise or a.dehaze:
+    if not a.deinterlace and (a.di_order is not None or a.di_no_temporal):
+        raise SystemExit("frame: --di-order and --di-no-temporal go with --deinterlace")
+    if a.overlay or a.stamp or a.enhance or a.denoise or a.dehaze or a.deinterlace:
         return cmd_frame_osd(a)
     import numpy as np
 
@@ -589,8 +597,12 @@ def build_parser():
             p.add_argument("--dh-t0", type=float, default=None, help="--dehaze: floor of the transmission, 0.05..1 (hub default 0.1)")
             p.add_argument("--dh-radius", type=int, default=None, help="--dehaze: refinement radius in cells, 1..16 (hub default 8)")
             p.add_argument("--dh-strength", type=float, default=None, help="--dehaze: 0..1 (hub default 1.0)")
+            p.add_argument("--deinterlace", action="store_true",
+                           help="deinterlace the woven frame of an interlaced camera (motion-adaptive, on the hub's GPU), likewise")
+            p.add_argument("--di-order", choices=("tff", "bff"), default=None, help="--deinterlace: field order (hub default tff)")
+            p.add_argument("--di-no-temporal", action="store_true", help="--deinterlace: spatial prediction only")
             p.add_argument("--rest", default="127.0.0.1:8080",
-                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance / --denoise / --dehaze)")
+                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance / --denoise / --dehaze / --deinterlace)")
         if name == "annotate":
             p.add_argument("--type", required=True)
         if name in ("storage", "proxy"):

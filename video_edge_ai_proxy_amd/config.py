@@ -181,6 +181,14 @@ class DehazeConfig:
 
 
 @dataclass
+class DeinterlaceConfig:
+    """Hub-wide defaults of the deinterlacing (``frame.jpg?deinterlace=1``, docs/DEINTERLACE.md); a
+    request overrides either of them."""
+    order: str = "tff"     # tff: the even rows are the earlier field; bff: the odd rows
+    temporal: bool = True  # bound the spatial prediction by the frame before
+
+
+@dataclass
 class FlowConfig:
     """Motion vectors by block matching (docs/FLOW.md; ``Hub.flow``, ``/api/v1/flow``). The
     parameters hold for every camera of the hub. The defaults are design choices, not measured
@@ -228,6 +236,7 @@ class Config:
     enhance: EnhanceConfig = field(default_factory=EnhanceConfig)
     denoise: DenoiseConfig = field(default_factory=DenoiseConfig)
     dehaze: DehazeConfig = field(default_factory=DehazeConfig)
+    deinterlace: DeinterlaceConfig = field(default_factory=DeinterlaceConfig)
     flow: FlowConfig = field(default_factory=FlowConfig)
     objects: ObjectsConfig = field(default_factory=ObjectsConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
@@ -322,6 +331,11 @@ def validate(cfg: Config) -> None:
         dehaze.to_native(cfg.dehaze.patch, cfg.dehaze.omega, cfg.dehaze.t0, cfg.dehaze.radius, cfg.dehaze.strength)
     except ValueError as e:
         raise ValueError(f"dehaze: {e}") from None
+    try:
+        from . import deinterlace
+        deinterlace.to_native(cfg.deinterlace.order, cfg.deinterlace.temporal)
+    except ValueError as e:
+        raise ValueError(f"deinterlace: {e}") from None
     from . import flow
     flow.to_native({k: getattr(cfg.flow, k) for k in flow.DEFAULTS})
     from . import objects

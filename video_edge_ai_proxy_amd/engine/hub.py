@@ -20,6 +20,7 @@ from typing import Optional
 
 from .. import crops, privacy, views
 from .. import dehaze as dehaze_params
+from .. import deinterlace as deinterlace_params
 from .. import denoise as denoise_params
 from .. import enhance as enhance_params
 from .. import flow as flow_params
@@ -366,7 +367,7 @@ class Hub:
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
                     width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False,
-                    enhance=None, denoise=None, dehaze=None):
+                    enhance=None, denoise=None, dehaze=None, deinterlace=None):
         """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
         Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
         ``quality`` 1..100, default ``serving.jpeg_quality``. With ``width`` and / or ``height``
@@ -397,7 +398,15 @@ class Hub:
         camera's GPU: after the denoise and the scale, before the enhancement, the overlay and the
         encoder. ``meta["dehaze_air"]`` is the estimated air light ``(b, g, r)``. The served picture
         must have both sides at least 16 (else a ``ValueError``). ``None``: the call and its bytes
-        are what they are without it."""
+        are what they are without it.
+
+        ``deinterlace``: ``True`` (the hub's ``deinterlace:`` defaults) or a dict with ``order`` and /
+        or ``temporal`` (:mod:`..deinterlace`, docs/DEINTERLACE.md) rebuilds the later field's rows of
+        the woven frame of an interlaced camera, motion-adaptively against the frame before, on the
+        camera's GPU: ahead of the scale, the dehazing, the enhancement, the overlay and the encoder.
+        ``meta["deinterlace_frames"]`` says how many frames were used: 2, or 1 where only the spatial
+        part could run (no earlier frame in the ring, or ``temporal`` false). Not together with
+        ``denoise`` (a ``ValueError``). ``None``: the call and its bytes are what they are without it."""
         q = self._quality(quality)
         bw, bh = self._box(width, height)
         if not isinstance(stamp, bool):
@@ -405,8 +414,13 @@ class Hub:
         eq = enhance_params.from_request(enhance, self.enhance_defaults())
         dn = denoise_params.from_request(denoise, self.denoise_defaults())
         dh = dehaze_params.from_request(dehaze, self.dehaze_defaults())
+        di = deinterlace_params.from_request(deinterlace, self.deinterlace_defaults())
+        if di is not None and dn is not None:
+            raise ValueError("deinterlace is not served together with denoise, which blends the ring's woven frames")
         w, cam = self.worker_of(name)
         if (overlay is None or overlay is False) and not stamp:
+            if di is not None:
+                return w.read_latest_jpeg(cam, after, q, bw, bh, eq, dn, dh, di)
             if dh is not None:
                 return w.read_latest_jpeg(cam, after, q, bw, bh, eq, dn, dh)
             if dn is not None:
@@ -424,6 +438,8 @@ class Hub:
             items = osd.normalize_list(overlay)
         if stamp:
             items = items + [osd.STAMP]
+        if di is not None:
+            return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh, eq, dn, dh, di)
         if dh is not None:
             return w.read_overlay_jpeg(cam, osd.to_native(items), name, after, q, bw, bh, eq, dn, dh)
         if dn is not None:
@@ -495,6 +511,27 @@ class Hub:
     def dehaze_count(self) -> int:
         """Dehazed pictures served since the hub started (/metrics)."""
         return sum(int(w.dehaze_count()) for w in self.workers)
+
+    # ------------------------------------------------------------------ deinterlacing
+    def deinterlace_defaults(self) -> dict:
+        """The hub-wide ``order`` and ``temporal`` (the config's ``deinterlace:`` section)."""
+        d = self.cfg.deinterlace
+        return {"order": d.order, "temporal": d.temporal}
+
+    def latest_deinterlaced(self, name: str, after: int = 0, width: int = 0, height: int = 0, **params):
+        """``(seq, ndarray)`` of the newest frame with seq > after, deinterlaced on the camera's GPU
+        against the frame before it where the ring has one (docs/DEINTERLACE.md), or None; ``width`` /
+        ``height`` (0: not given) fit and downscale it afterwards. ``params``: ``order``, ``temporal``;
+        the rest are the hub's defaults. Only the deinterlaced picture is copied to the host."""
+        di = deinterlace_params.from_request(params or True, self.deinterlace_defaults())
+        bw, bh = self._box(width or None, height or None)
+        w, cam = self.worker_of(name)
+        r = w.read_latest_deinterlaced(cam, after, bw, bh, *di)
+        return None if r is None else (int(r[0]["seq"]), r[1])
+
+    def deinterlace_count(self) -> int:
+        """Deinterlaced pictures served since the hub started (/metrics)."""
+        return sum(int(w.deinterlace_count()) for w in self.workers)
 
     # ------------------------------------------------------------------ on-screen display
     def set_overlay(self, name: str, items, ttl_ms: int = 0) -> None:

@@ -42,6 +42,10 @@
   from a table over the dark channel, transmission refined by a guided filter on cells of 4 x 4
   pixels, per-pixel recovery; seven launches for every picture of the call: the kernels behind
   ``frame.jpg?dehaze=1``); a host tensor runs the CPU twin, whose bytes are the same.
+* :func:`deinterlace` / :func:`deinterlace_batch` — woven BGR24 frames of interlaced cameras
+  deinterlaced motion-adaptively (edge-directed prediction by packed 8-bit SADs on a luma plane in
+  LDS, bounded by the fields before and after; one launch for every picture of the call: the kernel
+  behind ``frame.jpg?deinterlace=1``); host tensors run the CPU twin, whose bytes are the same.
 * :func:`block_flow` / :func:`block_flow_batch` — motion vectors of a BGR24 picture against an earlier
   one by exhaustive 8 x 8 block matching on decimated luma (packed 8-bit SADs; two launches for every
   pair of the call: the kernels behind ``/flow``); host tensors run the CPU twin, whose bytes are the
@@ -1189,6 +1193,92 @@ def denoise(frames, level: int = 8, strength: float = 1.0, out: torch.Tensor | N
     ``[H, W, 3]`` tensors), temporally denoised into one ``[H, W, 3]`` tensor: see
     :func:`denoise_batch`. Device tensors run the gfx950 kernel, host tensors the CPU twin."""
     return denoise_batch([frames], level, strength, None if out is None else [out])[0]
+
+
+def deinterlace_batch(pairs, order="tff", temporal=True, outs=None):
+    """Motion-adaptive deinterlacing (csrc/vep/deinterlace.h, docs/DEINTERLACE.md) of a list of woven
+    frames, each given as ``(newer, older)``: two ``[H, W, 3]`` BGR24 tensors of one size, the frame
+    and the one before it, or ``(newer, None)`` (or the tensor alone) for the spatial prediction
+    only. The rows of the earlier field are kept, the others rebuilt along the edge direction and,
+    with ``older``, bounded by the fields before and after. Device tensors (all on one device) run
+    the gfx950 kernel, ONE launch for the whole list, which may mix pairs and single frames; host
+    tensors run the CPU twin, whose bytes are the same. ``order`` (``"tff"`` / ``"bff"``) and
+    ``temporal`` are one value or one per picture; pictures may differ in size (both sides at least
+    4). A device frame's rows may start at any byte address and have any pitch. ``outs`` None: a new
+    contiguous tensor per picture; else per picture a tensor of its size that receives the result
+    and overlaps neither frame (out of place only). No CPU fallback for device tensors."""
+    from .. import deinterlace as params
+
+    pairs = [tuple(p) if isinstance(p, (list, tuple)) else (p, None) for p in pairs]
+    n = len(pairs)
+    if not n:
+        raise ValueError("pairs must hold at least one picture")
+    if any(len(p) != 2 for p in pairs):
+        raise ValueError("every entry of pairs must be (newer, older), (newer, None) or a tensor")
+    native_params = [params.to_native(o, t) for o, t in
+                     zip(_per_picture(order, n, "order"), _per_picture(temporal, n, "temporal"))]
+    outs = [None] * n if outs is None else list(outs)
+    if len(outs) != n:
+        raise ValueError("outs must hold one entry per picture")
+    on_device = [isinstance(f, torch.Tensor) and f.is_cuda for p in pairs for f in p if f is not None]
+    if any(on_device) != all(on_device):
+        raise ValueError("the frames must all be device tensors or all host tensors")
+    res, sizes = [], []
+    for k, (newer, older) in enumerate(pairs):
+        w, h, _ = _check_overlay_picture(newer, f"pairs[{k}][0]")
+        if w < 4 or h < 4:
+            raise ValueError(f"pairs[{k}]: both sides must be at least 4")
+        if older is not None and _check_overlay_picture(older, f"pairs[{k}][1]")[:2] != (w, h):
+            raise ValueError(f"pairs[{k}]: the two frames must have one size")
+        sizes.append((w, h))
+    if not on_device[0]:
+        for k, ((newer, older), (o, t), out) in enumerate(zip(pairs, native_params, outs)):
+            r = torch.from_numpy(native.deinterlace_cpu(newer.detach().contiguous().numpy(),
+                                                        None if older is None else older.detach().contiguous().numpy(), o, t))
+            if out is not None:
+                if not isinstance(out, torch.Tensor) or out.is_cuda or out.dtype != torch.uint8 or out.shape != r.shape:
+                    raise ValueError(f"outs[{k}] must be a host uint8 tensor of the picture's shape")
+                out.copy_(r)
+                r = out
+            res.append(r)
+        return res
+    device, work, spans = pairs[0][0].device, [], []
+    for k, ((newer, older), (o, t), out, (w, h)) in enumerate(zip(pairs, native_params, outs, sizes)):
+        srcs = []
+        for f in (newer, older):
+            if f is None:
+                srcs.append((0, 0, 0))
+                continue
+            if f.device != device:
+                raise ValueError("the frames must live on one device")
+            pitch = _check_overlay_picture(f, f"pairs[{k}]")[2]
+            srcs.append(_overlay_span(f, w, h, pitch) + (pitch,))
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+        ow, oh, dpitch = _check_overlay_picture(out, f"outs[{k}]")
+        if (ow, oh) != (w, h) or not out.is_cuda or out.device != device:
+            raise ValueError(f"outs[{k}] must be a [{h}, {w}, 3] tensor on the frames' device")
+        b = _overlay_span(out, w, h, dpitch)
+        if any(a[0] < b[1] and b[0] < a[1] for a in srcs):
+            raise ValueError(f"outs[{k}] overlaps a frame of its picture")
+        if any(b[0] < s[1] and s[0] < b[1] for s in spans):
+            raise ValueError("the destinations of one call must not overlap")
+        spans.append(b)
+        work.append(((srcs[0][0], srcs[0][1] - srcs[0][0], srcs[0][2]), (srcs[1][0], srcs[1][1] - srcs[1][0], srcs[1][2]),
+                     (b[0], b[1] - b[0], dpitch), w, h, o, t))
+        res.append(out)
+    require_gpu()
+    with torch.cuda.device(device):
+        native.deinterlace_device_batch(work, int(torch.cuda.current_stream(device).cuda_stream))
+    return res
+
+
+def deinterlace(newer: torch.Tensor, older: torch.Tensor | None = None, order: str = "tff", temporal: bool = True,
+                out: torch.Tensor | None = None):
+    """One woven ``[H, W, 3]`` BGR24 frame deinterlaced, against the frame before it where ``older``
+    is given: see :func:`deinterlace_batch`. Device tensors run the gfx950 kernel, host tensors the
+    CPU twin."""
+    return deinterlace_batch([(newer, older)], order, temporal, None if out is None else [out])[0]
 
 
 def block_flow_batch(pairs, decimate: int = 2, range: int = 7, planes: bool = False):

@@ -120,6 +120,11 @@ class HubCollector:
             hr = CounterMetricFamily("vep_dehaze_requests", "pictures served dehazed (frame.jpg, stream.mjpg, latest_dehazed)")
             hr.add_metric([], count())
             yield hr
+        count = getattr(self.hub, "deinterlace_count", None)
+        if count is not None:
+            ir = CounterMetricFamily("vep_deinterlace_requests", "pictures served deinterlaced (frame.jpg, stream.mjpg, latest_deinterlaced)")
+            ir.add_metric([], count())
+            yield ir
         try:
             from .._native import native
 

@@ -184,8 +184,29 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
         dh.from_request(given or True)  # (a bad value is refused before the hub is asked)
         return {"dehaze": given or True}
 
+    def deinterlaced(deinterlace, di_order, di_temporal, size) -> dict:
+        """The deinterlace argument of latest_jpeg (docs/DEINTERLACE.md): none when the request names
+        none of the three, so such a request calls the hub exactly as before."""
+        from .. import deinterlace as di
+
+        given = {k: v for k, v in (("order", di_order), ("temporal", di_temporal)) if v is not None}
+        if deinterlace in (None, 0) and not given:
+            return {}
+        if deinterlace != 1:
+            raise ValueError("deinterlace must be 0 or 1 (di_order and di_temporal go with deinterlace=1)")
+        if "temporal" in given:
+            if given["temporal"] not in (0, 1):
+                raise ValueError("di_temporal must be 0 or 1")
+            given["temporal"] = bool(given["temporal"])
+        di.from_request(given or True)  # (a bad value is refused before the hub is asked)
+        if "denoise" in size:
+            raise ValueError("deinterlace is not served together with denoise, which blends the ring's woven frames")
+        return {"deinterlace": given or True}
+
     def frame_headers(meta) -> dict:
         h = {"X-Vep-Seq": str(meta["seq"])}
+        if "deinterlace_frames" in meta:
+            h["X-Vep-Deinterlace-Frames"] = str(meta["deinterlace_frames"])
         if "dehaze_air" in meta:
             h["X-Vep-Dehaze-Air"] = ",".join(str(v) for v in meta["dehaze_air"])
         if "denoise_frames" in meta:
@@ -199,7 +220,8 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                   denoise: int | None = None, nr_frames: int | None = None, nr_level: int | None = None,
                   nr_strength: float | None = None, dehaze: int | None = None, dh_patch: int | None = None,
                   dh_omega: float | None = None, dh_t0: float | None = None, dh_radius: int | None = None,
-                  dh_strength: float | None = None):
+                  dh_strength: float | None = None, deinterlace: int | None = None, di_order: str | None = None,
+                  di_temporal: int | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -210,8 +232,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             size.update(enhanced(enhance, clip, tile, strength))
             size.update(denoised(denoise, nr_frames, nr_level, nr_strength))
             size.update(dehazed(dehaze, dh_patch, dh_omega, dh_t0, dh_radius, dh_strength))
+            size.update(deinterlaced(deinterlace, di_order, di_temporal, size))
         except ValueError as e:
             return err(422, str(e))
+        if "deinterlace" in size and not hasattr(pm.hub, "deinterlace_defaults"):  # (501 before a stream starts)
+            return err(501, "deinterlaced frames are not served with gpu.isolation: process")
         if "dehaze" in size and not hasattr(pm.hub, "dehaze_defaults"):
             return err(501, "dehazed frames are not served with gpu.isolation: process")
         try:
@@ -235,7 +260,8 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                     strength: float | None = None, denoise: int | None = None, nr_frames: int | None = None,
                     nr_level: int | None = None, nr_strength: float | None = None, dehaze: int | None = None,
                     dh_patch: int | None = None, dh_omega: float | None = None, dh_t0: float | None = None,
-                    dh_radius: int | None = None, dh_strength: float | None = None):
+                    dh_radius: int | None = None, dh_strength: float | None = None, deinterlace: int | None = None,
+                    di_order: str | None = None, di_temporal: int | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -250,8 +276,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             size.update(enhanced(enhance, clip, tile, strength))
             size.update(denoised(denoise, nr_frames, nr_level, nr_strength))
             size.update(dehazed(dehaze, dh_patch, dh_omega, dh_t0, dh_radius, dh_strength))
+            size.update(deinterlaced(deinterlace, di_order, di_temporal, size))
         except ValueError as e:
             return err(422, str(e))
+        if "deinterlace" in size and not hasattr(pm.hub, "deinterlace_defaults"):  # (501 before a stream starts)
+            return err(501, "deinterlaced frames are not served with gpu.isolation: process")
         if "dehaze" in size and not hasattr(pm.hub, "dehaze_defaults"):  # (501 before the stream starts)
             return err(501, "dehazed frames are not served with gpu.isolation: process")
         try:
@@ -298,6 +327,7 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                 yield (f"--{MJPEG_BOUNDARY}\r\nContent-Type: image/jpeg\r\nContent-Length: {len(jpg)}\r\n"
                        f"X-Vep-Seq: {seq}\r\n" + (f"X-Vep-Denoise-Frames: {meta['denoise_frames']}\r\n" if "denoise_frames" in meta else "")
                        + (f"X-Vep-Dehaze-Air: {','.join(str(v) for v in meta['dehaze_air'])}\r\n" if "dehaze_air" in meta else "")
+                       + (f"X-Vep-Deinterlace-Frames: {meta['deinterlace_frames']}\r\n" if "deinterlace_frames" in meta else "")
                        + "\r\n").encode() + jpg + b"\r\n"
                 sent += 1
                 due = max(due + 1.0 / fps, now)
