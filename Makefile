@@ -7,7 +7,7 @@ HIP_SRCS = $(wildcard csrc/vep/*.hip)
 TSAN_DIR = build/tsan
 ASAN_DIR = build/asan
 
-.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask asan-crop asan-overlay asan-dewarp asan-clahe asan-denoise asan-dehaze asan-deinterlace tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve flow-selftest asan-flow objects-selftest asan-objects tsan-rpc asan-rpc link-check parse-prof clean
+.PHONY: build test test-gpu bench bench-full bench-h265 smoke tsan asan asan-jpeg asan-scale asan-motion asan-tamper asan-mask asan-crop asan-overlay asan-dewarp asan-clahe asan-denoise asan-dehaze asan-deinterlace asan-orient tsan-scratch asan-scratch scratch-selftest plan-selftest asan-plan serve-selftest asan-serve flow-selftest asan-flow objects-selftest asan-objects tsan-rpc asan-rpc link-check parse-prof clean
 
 build:                     ## compile the extension in-tree (video_edge_ai_proxy_amd/_vep*.so)
 	$(PY) csrc/build.py
@@ -67,7 +67,7 @@ asan: $(ASAN_DIR)/native_stress
 # The CPU implementation of one op alone on its extreme inputs, edge shapes and closed forms
 # (csrc/vep/<op>.cpp driven by csrc/tests/<op>_selftest.cpp), under AddressSanitizer +
 # UndefinedBehaviorSanitizer: a stand-alone host program, no GPU. One rule for every op.
-ASAN_OPS = jpeg scale motion tamper mask crop overlay dewarp clahe denoise dehaze deinterlace
+ASAN_OPS = jpeg scale motion tamper mask crop overlay dewarp clahe denoise dehaze deinterlace orient
 
 $(ASAN_DIR)/%_selftest: csrc/vep/%.cpp csrc/tests/%_selftest.cpp $(wildcard csrc/vep/*.h)
 	mkdir -p $(ASAN_DIR)

@@ -12,6 +12,7 @@
 #include "vep/crop.h"
 #include "vep/denoise.h"
 #include "vep/dewarp.h"
+#include "vep/orient.h"
 #include "vep/overlay.h"
 #include "vep/runtime.h"
 
@@ -498,6 +499,23 @@ inline bool deinterlace_of(const py::object& o, deinterlace::Params& p) {
   const auto t = o.cast<std::tuple<int, int>>();
   p = deinterlace_params_of(std::get<0>(t), std::get<1>(t));
   return true;
+}
+
+// An orientation (vep/orient.h) crosses the boundary as two ints (rotate: 0, 90, 180 or 270; flip:
+// 0 none, 1 h, 2 v); a bad one is a ValueError. -> orient::Bits.
+inline int orient_op_of(int rotate, int flip) {
+  const int op = orient::of(rotate, flip);
+  if (op < 0) throw py::value_error("orient: rotate must be 0, 90, 180 or 270 and flip none, h or v");
+  return op;
+}
+
+// A serving read's `orient` argument: None, or the tuple (rotate, flip). -> whether a step runs
+// (the identity skips it).
+inline bool orient_of(const py::object& o, int& op) {
+  if (o.is_none()) return false;
+  const auto t = o.cast<std::tuple<int, int>>();
+  op = orient_op_of(std::get<0>(t), std::get<1>(t));
+  return op != 0;
 }
 
 // Overlay items (vep/overlay.h) cross the boundary as tuples (kind, x0, y0, x1, y1, b, g, r, alpha,

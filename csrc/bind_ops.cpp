@@ -178,6 +178,40 @@ static void deinterlace_run(const std::vector<DeinterlacePicture>& pics, uintptr
   });
 }
 
+// orient_device_batch: every picture's job (the source and the destination, each as address, bytes,
+// pitch; the source's size; rotate and flip) checked against the sizes the caller states, then one
+// launch on a pooled set.
+using OrientFrame = std::tuple<uintptr_t, size_t, u32>;
+using OrientPicture = std::tuple<OrientFrame, OrientFrame, int, int, int, int>;
+static void orient_run(const std::vector<OrientPicture>& pics, uintptr_t stream) {
+  const int n = int(pics.size());
+  if (n < 1 || pics.size() > 65535) throw py::value_error("orient: 1..65535 pictures expected");
+  std::vector<orient::Job> jobs((size_t(n)));
+  for (int k = 0; k < n; ++k) {
+    const auto& [src, dst, w, h, rotate, flip] = pics[size_t(k)];
+    orient::Job& j = jobs[size_t(k)];
+    j.src = reinterpret_cast<const u8*>(std::get<0>(src));
+    j.src_bytes = std::get<1>(src);
+    j.src_pitch = std::get<2>(src);
+    j.dst = reinterpret_cast<u8*>(std::get<0>(dst));
+    j.dst_bytes = std::get<1>(dst);
+    j.dst_pitch = std::get<2>(dst);
+    j.w = w;
+    j.h = h;
+    j.op = orient_op_of(rotate, flip);
+    try {
+      orient::check_job(j);
+    } catch (const Error& e) {
+      throw py::value_error(e.what());
+    }
+  }
+  on_pooled_set<gpu::OrientPool>(stream, [&](gpu::OrientPool::Lease& set, hipStream_t s) {
+    set->reserve(n, 0, 0);
+    for (int k = 0; k < n; ++k) set->put(k, jobs[size_t(k)]);
+    set->run(n, s);
+  });
+}
+
 // flow_device_batch: every picture's job (newer and older frame as (address, bytes, pitch), its two
 // luma planes of plane_bytes each, its records) checked against the sizes the caller states, then
 // the two launches on a pooled set.
@@ -1027,6 +1061,44 @@ void bind_ops(py::module_& m) {
   // pitch), w, h, order, temporal) on caller-owned device buffers: the gfx950 deinterlace kernel,
   // ONE launch for all of them, on `stream` of the current device. Out of place only.
   m.def("deinterlace_device_batch", &deinterlace_run, py::arg("pictures"), py::arg("stream"));
+  // Quarter turns and mirrors (vep/orient.h) on the host: the CPU backend's path, the byte-exact
+  // reference of orient_device_batch. (H, W, 3) -> (H, W, 3), or (W, H, 3) for rotate 90 and 270.
+  // rotate: 0, 90, 180 or 270 degrees clockwise; then flip: "none" / "h" / "v" (or 0 / 1 / 2).
+  m.def("orient_cpu",
+        [](py::array_t<uint8_t, py::array::c_style> bgr, int rotate, py::object flip) {
+          if (!is_bgr_picture(bgr)) throw py::value_error("orient_cpu: (H, W, 3) uint8 picture expected");
+          int f = -1;
+          if (py::isinstance<py::str>(flip)) {
+            const std::string s = flip.cast<std::string>();
+            f = s == "none" ? orient::kNone : (s == "h" ? orient::kH : (s == "v" ? orient::kV : -1));
+          } else if (py::isinstance<py::int_>(flip)) {
+            f = flip.cast<int>();
+          }
+          orient::Job j;
+          j.op = orient_op_of(rotate, f);
+          j.h = int(bgr.shape(0));
+          j.w = int(bgr.shape(1));
+          const int ow = orient::out_w(j.op, j.w, j.h), oh = orient::out_h(j.op, j.w, j.h);
+          py::array_t<uint8_t> out({py::ssize_t(oh), py::ssize_t(ow), py::ssize_t(3)});
+          j.src = bgr.data();
+          j.src_pitch = u32(size_t(j.w) * 3);
+          j.src_bytes = size_t(j.src_pitch) * size_t(j.h);
+          j.dst = out.mutable_data();
+          j.dst_pitch = u32(size_t(ow) * 3);
+          j.dst_bytes = size_t(j.dst_pitch) * size_t(oh);
+          try {
+            py::gil_scoped_release r;
+            orient::apply_cpu(j);
+          } catch (const Error& e) {
+            throw py::value_error(e.what());
+          }
+          return out;
+        },
+        py::arg("bgr").noconvert(), py::arg("rotate") = 0, py::arg("flip") = "none");
+  // Pictures ((src, bytes, pitch), (dst, bytes, pitch), w, h of the source, rotate, flip as 0 / 1 /
+  // 2) on caller-owned device buffers: the gfx950 orient kernel, ONE launch for all of them, on
+  // `stream` of the current device. Out of place only.
+  m.def("orient_device_batch", &orient_run, py::arg("pictures"), py::arg("stream"));
   // Motion vectors by block matching (vep/flow.h) on the host: the CPU backend's path, the
   // byte-exact reference of flow_device_batch. Two (H, W, 3) pictures -> (the two luma planes
   // (2, h', w'), the records as a (rows, cols, 4) int16 array of vx, vy, best, zero).

@@ -17,6 +17,7 @@ static bool serve_released(Read&& read) {
       const std::string what = e.what();
       if (what.find("overlay:") == std::string::npos && what.find("denoise:") == std::string::npos &&
           what.find("dehaze:") == std::string::npos && what.find("deinterlace:") == std::string::npos &&
+          what.find("orient:") == std::string::npos &&
           what.find("flow:") == std::string::npos && what.find("objects:") == std::string::npos)
         throw;
       refused = what;
@@ -68,8 +69,10 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // scale (docs/DEHAZE.md); meta then carries dehaze_air, the estimated air light (b, g, r).
            // deinterlace (None, or (order, temporal)): deinterlaced before anything else, never with
            // denoise (docs/DEINTERLACE.md); meta then carries deinterlace_frames, 1 or 2.
+           // orient (None, or (rotate, flip)): turned and mirrored behind the denoise or the deinterlacing
+           // and in front of everything else (docs/ORIENT.md); width / height refer to the upright picture.
            [](Worker& w, int i, i64 after, int quality, int width, int height, py::object enhance, py::object denoise,
-              py::object dehaze, py::object deinterlace) -> py::object {
+              py::object dehaze, py::object deinterlace, py::object orient) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              clahe::Params p;
              const bool eq = enhance_of(enhance, p);
@@ -79,20 +82,43 @@ void bind_worker_serving(py::class_<Worker>& cls) {
              const bool dh = dehaze_of(dehaze, hp);
              deinterlace::Params ip;
              const bool di = deinterlace_of(deinterlace, ip);
+             int op = 0;
+             orient_of(orient, op);
              FrameMeta m;
              std::string out;
              int used = 0, woven = 0;
              u32 air[3] = {0, 0, 0};
              const bool ok = serve_released([&] {
                return w.read_latest_jpeg(i, after, quality, &m, out, width, height, eq ? &p : nullptr, dn ? &dp : nullptr, &used,
-                                         dh ? &hp : nullptr, air, di ? &ip : nullptr, &woven);
+                                         dh ? &hp : nullptr, air, di ? &ip : nullptr, &woven, op);
              });
              if (!ok) return py::none();
              return py::make_tuple(denoised_meta(m, dn, used, dh, air, di, woven), py::bytes(out));
            },
            py::arg("idx"), py::arg("after") = 0, py::arg("quality") = 85, py::arg("width") = 0,
            py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none(),
-           py::arg("dehaze") = py::none(), py::arg("deinterlace") = py::none())
+           py::arg("dehaze") = py::none(), py::arg("deinterlace") = py::none(), py::arg("orient") = py::none())
+      .def("read_latest_oriented",
+           // (meta, ndarray) of the newest frame with seq > after, turned and mirrored (docs/ORIENT.md;
+           // not the identity); fitted into width x height afterwards when either is given; None if
+           // there is none.
+           [](Worker& w, int i, i64 after, int width, int height, int rotate, int flip) -> py::object {
+             std::shared_ptr<Camera> keep = cam_ref(w, i);
+             const int op = orient_op_of(rotate, flip);
+             if (op == 0) throw py::value_error("orient: the identity is not an oriented read");
+             if (after < 0) throw py::value_error("orient: after must be >= 0");
+             if (width < 0 || width > 65535 || height < 0 || height > 65535)
+               throw py::value_error("scale: width and height must be 1..65535 (0: not given)");
+             FrameMeta m;
+             std::vector<u8> px;
+             if (!serve_released([&] { return w.read_latest_oriented(i, after, width, height, op, &m, px); })) return py::none();
+             py::array_t<uint8_t> a({py::ssize_t(m.height), py::ssize_t(m.width), py::ssize_t(3)});
+             std::memcpy(a.mutable_data(), px.data(), px.size());
+             return py::make_tuple(meta_dict(m), a);
+           },
+           py::arg("idx"), py::arg("after") = 0, py::arg("width") = 0, py::arg("height") = 0, py::arg("rotate") = 0,
+           py::arg("flip") = 0)
+      .def("orient_count", [](Worker& w) { return w.orient_count(); })
       .def("read_latest_deinterlaced",
            // (meta, ndarray) of the newest frame with seq > after, deinterlaced against the frame before
            // it where the ring has one (docs/DEINTERLACE.md); fitted into width x height afterwards when
@@ -259,9 +285,11 @@ void bind_worker_serving(py::class_<Worker>& cls) {
            // {seq} and {time} come from `name` and the meta of the frame actually encoded.
            [](Worker& w, int i, const std::vector<ItemTuple>& items, const std::string& name, i64 after, int quality,
               int width, int height, py::object enhance, py::object denoise, py::object dehaze,
-              py::object deinterlace) -> py::object {
+              py::object deinterlace, py::object orient) -> py::object {
              std::shared_ptr<Camera> keep = cam_ref(w, i);
              const std::vector<overlay::Item> its = items_of(items);
+             int op = 0;
+             orient_of(orient, op);
              deinterlace::Params ip;
              const bool di = deinterlace_of(deinterlace, ip);
              int woven = 0;
@@ -282,14 +310,14 @@ void bind_worker_serving(py::class_<Worker>& cls) {
              // (of a checked list only the expansion can be refused: too many primitives)
              const bool ok = serve_released([&] {
                return w.read_overlay_jpeg(i, after, quality, its, name, &m, out, width, height, eq ? &p : nullptr,
-                                          dn ? &dp : nullptr, &used, dh ? &hp : nullptr, air, di ? &ip : nullptr, &woven);
+                                          dn ? &dp : nullptr, &used, dh ? &hp : nullptr, air, di ? &ip : nullptr, &woven, op);
              });
              if (!ok) return py::none();
              return py::make_tuple(denoised_meta(m, dn, used, dh, air, di, woven), py::bytes(out));
            },
            py::arg("idx"), py::arg("items"), py::arg("name") = "", py::arg("after") = 0, py::arg("quality") = 85,
            py::arg("width") = 0, py::arg("height") = 0, py::arg("enhance") = py::none(), py::arg("denoise") = py::none(),
-           py::arg("dehaze") = py::none(), py::arg("deinterlace") = py::none())
+           py::arg("dehaze") = py::none(), py::arg("deinterlace") = py::none(), py::arg("orient") = py::none())
       .def("overlay_counts", [](Worker& w) { return w.overlay_counts(); })
       .def_property("wall_max_tiles", &Worker::wall_max_tiles, &Worker::set_wall_max_tiles)
       .def("read_motion",

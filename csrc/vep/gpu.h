@@ -21,6 +21,7 @@
 #include "flow.h"
 #include "mask.h"
 #include "objects.h"
+#include "orient.h"
 #include "overlay.h"
 #include "scratch.h"
 
@@ -990,6 +991,42 @@ struct DeinterlaceSet : DescSet<DeinterlaceDesc> {
   void run(int n, hipStream_t s);
 };
 using DeinterlacePool = ScratchPool<DeinterlaceSet>;
+
+// ---- orientation (gpu_orient.hip; index arithmetic: orient.h) ---------------------------------------
+// One picture of a batched orient request (device memory): the source of w x h turned and mirrored
+// into dst of orient::out_w x orient::out_h, byte-identical with orient::apply_cpu, in ONE launch
+// for every picture of the request. Out of place only: dst does not overlap src, and src (a ring
+// slot) is never written. Pictures of one request may differ in size and op; their destinations
+// must not overlap.
+struct OrientDesc {
+  const VEP_DEV u8* src;  // h rows of src_pitch bytes (any alignment)
+  VEP_DEV u8* dst;        // out_h rows of dst_pitch bytes (any alignment)
+  u32 src_pitch, dst_pitch;  // bytes
+  i32 w, h;               // of the source
+  i32 op;                 // orient::Bits
+  i32 pad;
+};
+static_assert(sizeof(OrientDesc) == 40, "OrientDesc layout");
+// The descriptor of a job, checked by orient::check_job: every access of the kernel lies inside
+// the source or the destination and the two do not overlap. The launch below does not check.
+OrientDesc check_orient(const orient::Job& j);
+// One launch for the n pictures on `s`: grid = (64 x 64 tiles of the largest output) x pictures.
+// h_descs is the host copy of d_descs (the grid is sized from it).
+void launch_orient(const OrientDesc* d_descs, const OrientDesc* h_descs, int n, hipStream_t s);
+
+// Orient scratch of one device (pool contract: above): descriptors, a picture that receives a
+// frame's oriented copy (where the ring slot stood for the stages behind), and a pinned buffer for
+// results on their way down.
+struct OrientSet : DescSet<OrientDesc> {
+  DevBuf<u8> picture;
+  PinBuf<u8> host;
+  void reserve(int ndescs, size_t picture_bytes, size_t host_bytes);
+  // Descriptor k from a checked job.
+  void put(int k, const orient::Job& j);
+  // Copies the first n host descriptors up, launches them on `s` and records the event (no wait).
+  void run(int n, hipStream_t s);
+};
+using OrientPool = ScratchPool<OrientSet>;
 
 enum ChwDtype : int { kChwNone = 0, kChwF16 = 1, kChwBF16 = 2, kChwF32 = 3 };
 

@@ -561,10 +561,21 @@ class Worker {
   // 2, or 1 where only the spatial part could run (no history, the first frame, after a privacy-mask
   // change, a size change between the two, temporal 0). Together with denoise it throws: denoise
   // blends earlier slots, which are woven. Null: path and bytes as ever.
+  // orient (orient::Bits, not 0): the picture is turned and mirrored (orient.h, docs/ORIENT.md)
+  // behind the deinterlace or denoise step, which are sensor-domain steps, and in front of
+  // everything else, into pooled scratch at native size, which then stands where the ring slot
+  // stood: width / height, the enhancement's tiles and the overlay's coordinates refer to the
+  // oriented picture. The CPU backend runs orient::apply_cpu. 0: path and bytes as ever.
   bool read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width = 0,
                         int height = 0, const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
                         int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr,
-                        const deinterlace::Params* deinterlace = nullptr, int* deinterlace_frames = nullptr);
+                        const deinterlace::Params* deinterlace = nullptr, int* deinterlace_frames = nullptr, int orient = 0);
+  // The oriented picture as packed BGR24 in host memory: scaled as read_latest_scaled (the box
+  // refers to the oriented picture), or with width = height = 0 at native size. op: orient::Bits,
+  // not 0 (the identity is read_latest or read_latest_scaled).
+  bool read_latest_oriented(int cam, i64 after, int width, int height, int op, FrameMeta* meta, std::vector<u8>& dst);
+  // Oriented pictures served since the worker started (the identity is not counted).
+  u64 orient_count() const { return orient_requests_.load(); }
   // The same scaled picture as packed BGR24 in host memory (dst is resized to ow * oh * 3; only
   // those bytes are copied off the GPU); meta->width / height are the scaled size.
   bool read_latest_scaled(int cam, i64 after, int width, int height, FrameMeta* meta, std::vector<u8>& dst,
@@ -619,7 +630,7 @@ class Worker {
                          const std::string& name, FrameMeta* meta, std::string& out, int width = 0, int height = 0,
                          const clahe::Params* enhance = nullptr, const denoise::Params* denoise = nullptr,
                          int* denoise_frames = nullptr, const dehaze::Params* dehaze = nullptr, u32* air = nullptr,
-                         const deinterlace::Params* deinterlace = nullptr, int* deinterlace_frames = nullptr);
+                         const deinterlace::Params* deinterlace = nullptr, int* deinterlace_frames = nullptr, int orient = 0);
   // read_wall_jpeg with labels[t] (non-empty) drawn at the top-left corner of every tile that
   // shows a frame, as a text at auto scale for the tile's height over black at alpha 160, clipped
   // to the tile's cell: one in-place launch on the composed canvas. At most
@@ -1089,11 +1100,15 @@ class Worker {
   // deinterlacing (after the dehaze's members)
   gpu::DeinterlacePool deinterlace_pool_;  // descriptors and a picture, one set per request in flight
   std::atomic<u64> deinterlace_requests_{0};
-  // One denoised, deinterlaced or dehazed read (at least one of the three): what is asked of the picture, and
-  // where it goes (a JPEG of `quality`, or raw BGR when jpeg is null).
+  // orientation (after the deinterlace's members)
+  gpu::OrientPool orient_pool_;  // descriptors and a picture, one set per request in flight
+  std::atomic<u64> orient_requests_{0};
+  // One denoised, deinterlaced, oriented or dehazed read (at least one of the four): what is asked of
+  // the picture, and where it goes (a JPEG of `quality`, or raw BGR when jpeg is null).
   struct DenoisedRead {
     const denoise::Params* dn = nullptr;
     const deinterlace::Params* di = nullptr;  // not together with dn
+    int orient = 0;  // orient::Bits; behind dn / di, in front of the scale
     int width = 0, height = 0;
     const dehaze::Params* dehaze = nullptr;
     u32* air = nullptr;  // with dehaze: the estimated air light, 3 values

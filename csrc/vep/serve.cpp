@@ -12,6 +12,7 @@
 #include "denoise.h"
 #include "dewarp.h"
 #include "jpeg.h"
+#include "orient.h"
 #include "ring_read.h"
 #include "runtime.h"
 #include "scale.h"
@@ -426,6 +427,8 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
   if (rq.dn) denoise::check_params(*rq.dn);
   if (rq.di) deinterlace::check_params(*rq.di);
   VEP_CHECK(!(rq.dn && rq.di), "deinterlace: not served together with denoise, which blends the ring's woven frames");
+  VEP_CHECK(rq.orient >= 0 && rq.orient <= (orient::kT | orient::kMX | orient::kMY),
+            "orient: rotate must be 0, 90, 180 or 270 and flip none, h or v");
   if (rq.dehaze) dehaze::check_params(*rq.dehaze);
   if (rq.enhance) clahe::check_params(*rq.enhance);
   VEP_CHECK(rq.width >= 0 && rq.width <= scale::kMaxSide && rq.height >= 0 && rq.height <= scale::kMaxSide,
@@ -437,8 +440,10 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
   if (!ring) return false;
   VEP_CHECK(!rq.dn || ring->history() >= 2, "denoise: the camera's ring keeps no history: buffer.in_memory must be 2 or more");
   const int w = ring->width(), h = ring->height();
+  // the upright picture: what the scale and every step behind it see (w x h without an orientation)
+  const int uw = orient::out_w(rq.orient, w, h), uh = orient::out_h(rq.orient, w, h);
   const bool scaled = rq.width || rq.height;
-  const scale::Size f = scaled ? scale::fit(w, h, rq.width, rq.height) : scale::Size{w, h};
+  const scale::Size f = scaled ? scale::fit(uw, uh, rq.width, rq.height) : scale::Size{uw, uh};
   const size_t native = ring->slot_bytes(), n = size_t(f.w) * size_t(f.h) * 3, row = size_t(f.w) * 3;
   VEP_CHECK(!rq.dehaze || (f.w >= dehaze::kMinSide && f.h >= dehaze::kMinSide && u64(f.w) * u64(f.h) <= dehaze::kMaxPixels),
             "dehaze: both sides of the served picture must be at least 16 and the picture at most 2^24 pixels");
@@ -478,6 +483,13 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         j.h = h;
         j.level = rq.dn ? rq.dn->level : 0;
         j.strength = rq.dn ? rq.dn->strength : 0;
+        orient::Job oj;  // (source and destination: below, where the step before it has its picture)
+        oj.src_bytes = oj.dst_bytes = native;
+        oj.src_pitch = u32(w) * 3;
+        oj.dst_pitch = u32(uw) * 3;
+        oj.w = w;
+        oj.h = h;
+        oj.op = rq.orient;
         overlay::Expanded e;  // (the items meet the picture they are drawn on, and the newest frame's meta)
         if (rq.items)
           e = overlay::expand(rq.items->data(), int(rq.items->size()), f.w, f.h, *rq.name, overlay::Meta{m.seq, m.timestamp});
@@ -488,10 +500,17 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
           j.dst = dj.dst = pic.data();
           if (rq.dn) denoise::denoise_cpu(j);
           else if (rq.di) deinterlace::deinterlace_cpu(dj);
-          else std::memcpy(pic.data(), j.src[0], native);
+          else if (!rq.orient) std::memcpy(pic.data(), j.src[0], native);
+          if (rq.orient) {
+            std::vector<u8> upright(native);
+            oj.src = rq.dn || rq.di ? pic.data() : j.src[0];
+            oj.dst = upright.data();
+            orient::apply_cpu(oj);
+            pic.swap(upright);
+          }
           if (scaled) {
             std::vector<u8> small(n);
-            scale::area_cpu(pic.data(), w, h, size_t(w) * 3, small.data(), row, f.w, f.h);
+            scale::area_cpu(pic.data(), uw, uh, size_t(uw) * 3, small.data(), row, f.w, f.h);
             pic.swap(small);
           }
           if (rq.dehaze) dehaze::dehaze_cpu(pic.data(), row, pic.data(), row, f.w, f.h, *rq.dehaze, air);
@@ -504,7 +523,7 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
           return;
         }
         dev_.bind();
-        // (every request takes its sets in one order: denoise, deinterlace, scale, dehaze, clahe, overlay, encoder)
+        // (every request takes its sets in one order: denoise, deinterlace, orient, scale, dehaze, clahe, overlay, encoder)
         gpu::DenoisePool::Lease dn;
         if (rq.dn) {
           dn = denoise_pool_.acquire();
@@ -515,6 +534,11 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
           di = deinterlace_pool_.acquire();
           di->reserve(1, native, raw && !rq.dehaze ? n : 0);
         }
+        gpu::OrientPool::Lease up;
+        if (rq.orient) {
+          up = orient_pool_.acquire();
+          up->reserve(1, native, raw && !rq.dehaze ? n : 0);
+        }
         gpu::ScalePool::Lease set;
         if (scaled) {
           set = scale_pool_.acquire();
@@ -524,7 +548,7 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         if (rq.dehaze) {
           dh = dehaze_pool_.acquire();
           // (a picture of its own only where the one to dehaze is the ring slot, which is never written)
-          dh->reserve(1, gpu::DehazeSet::plane_words(f.w, f.h), rq.dn || rq.di || scaled ? 0 : n, raw ? n : 0);
+          dh->reserve(1, gpu::DehazeSet::plane_words(f.w, f.h), rq.dn || rq.di || rq.orient || scaled ? 0 : n, raw ? n : 0);
         }
         gpu::ClahePool::Lease eq;
         if (rq.enhance) {
@@ -550,8 +574,15 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
           di->run(1, serve_stream_);
           pic = di->picture.p;
         }
+        if (rq.orient) {
+          oj.src = pic ? pic : j.src[0];
+          oj.dst = up->picture.p;
+          up->put(0, oj);
+          up->run(1, serve_stream_);
+          pic = up->picture.p;
+        }
         if (scaled) {
-          scale_picture(*set, pic ? pic : j.src[0], w, h, f.w, f.h);
+          scale_picture(*set, pic ? pic : j.src[0], uw, uh, f.w, f.h);
           pic = set->canvas.p;
         }
         if (rq.dehaze) {
@@ -572,8 +603,9 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
         if (jpeg) {
           encode_device(pic, f.w, f.h, rq.quality, *jpeg);
         } else {
-          u8* host = rq.dehaze ? dh->host.p : (rq.di ? di->host.p : dn->host.p);
-          hipEvent_t ev = rq.dehaze ? hipEvent_t(dh->ev) : (rq.di ? hipEvent_t(di->ev) : hipEvent_t(dn->ev));
+          u8* host = rq.dehaze ? dh->host.p : (rq.orient ? up->host.p : (rq.di ? di->host.p : dn->host.p));
+          hipEvent_t ev = rq.dehaze ? hipEvent_t(dh->ev)
+                                    : (rq.orient ? hipEvent_t(up->ev) : (rq.di ? hipEvent_t(di->ev) : hipEvent_t(dn->ev)));
           VEP_HIP(hipMemcpyAsync(host, pic, n, hipMemcpyDeviceToHost, serve_stream_));
           VEP_HIP(hipEventRecord(ev, serve_stream_));  // (again: after the copy)
           VEP_HIP(hipEventSynchronize(ev));
@@ -588,6 +620,7 @@ bool Worker::read_denoised(int cam, i64 after, const DenoisedRead& rq, FrameMeta
   meta->height = f.h;
   if (rq.dn) denoise_requests_ += 1;
   if (rq.di) deinterlace_requests_ += 1;
+  if (rq.orient) orient_requests_ += 1;
   if (rq.dehaze) {
     dehaze_requests_ += 1;
     if (rq.air) std::copy_n(air, 3, rq.air);
@@ -618,6 +651,15 @@ bool Worker::read_latest_deinterlaced(int cam, i64 after, int width, int height,
   return read_denoised(cam, after, rq, meta, frames, nullptr, &dst);
 }
 
+bool Worker::read_latest_oriented(int cam, i64 after, int width, int height, int op, FrameMeta* meta, std::vector<u8>& dst) {
+  VEP_CHECK(op != 0, "orient: the identity is not an oriented read");
+  DenoisedRead rq;
+  rq.orient = op;
+  rq.width = width;
+  rq.height = height;
+  return read_denoised(cam, after, rq, meta, nullptr, nullptr, &dst);
+}
+
 bool Worker::read_latest_dehazed(int cam, i64 after, int width, int height, const dehaze::Params& p, FrameMeta* meta,
                                  std::vector<u8>& dst, u32* air) {
   DenoisedRead rq;
@@ -631,12 +673,13 @@ bool Worker::read_latest_dehazed(int cam, i64 after, int width, int height, cons
 bool Worker::read_latest_jpeg(int cam, i64 after, int quality, FrameMeta* meta, std::string& out, int width,
                               int height, const clahe::Params* enhance, const denoise::Params* denoise,
                               int* denoise_frames, const dehaze::Params* dehaze, u32* air,
-                              const deinterlace::Params* deinterlace, int* deinterlace_frames) {
+                              const deinterlace::Params* deinterlace, int* deinterlace_frames, int orient) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-  if (denoise || dehaze || deinterlace) {
+  if (denoise || dehaze || deinterlace || orient) {
     DenoisedRead rq;
     rq.dn = denoise;
     rq.di = deinterlace;
+    rq.orient = orient;
     rq.width = width;
     rq.height = height;
     rq.dehaze = dehaze;
@@ -694,12 +737,13 @@ bool Worker::read_overlay_jpeg(int cam, i64 after, int quality, const std::vecto
                                const std::string& name, FrameMeta* meta, std::string& out, int width, int height,
                                const clahe::Params* enhance, const denoise::Params* denoise, int* denoise_frames,
                                const dehaze::Params* dehaze, u32* air, const deinterlace::Params* deinterlace,
-                               int* deinterlace_frames) {
+                               int* deinterlace_frames, int orient) {
   VEP_CHECK(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-  if (denoise || dehaze || deinterlace) {
+  if (denoise || dehaze || deinterlace || orient) {
     DenoisedRead rq;
     rq.dn = denoise;
     rq.di = deinterlace;
+    rq.orient = orient;
     rq.width = width;
     rq.height = height;
     rq.dehaze = dehaze;

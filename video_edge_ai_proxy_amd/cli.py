@@ -143,6 +143,10 @@ def frame_jpg_url(a) -> str:
             q["di_order"] = a.di_order
         if a.di_no_temporal:
             q["di_temporal"] = "0"
+    if a.rotate is not None:
+        q["rotate"] = str(a.rotate)
+    if a.flip is not None:
+        q["flip"] = a.flip
     for k in ("width", "height"):
         if getattr(a, k) is not None:
             q[k] = str(getattr(a, k))
@@ -218,7 +222,7 @@ def cmd_frame(a):
         raise SystemExit("frame: --dh-patch, --dh-omega, --dh-t0, --dh-radius and --dh-strength go with --dehaze")
     if not a.deinterlace and (a.di_order is not None or a.di_no_temporal):
         raise SystemExit("frame: --di-order and --di-no-temporal go with --deinterlace")
-    if a.overlay or a.stamp or a.enhance or a.denoise or a.dehaze or a.deinterlace:
+    if a.overlay or a.stamp or a.enhance or a.denoise or a.dehaze or a.deinterlace or a.rotate is not None or a.flip is not None:
         return cmd_frame_osd(a)
     import numpy as np
 
@@ -601,8 +605,12 @@ def build_parser():
                            help="deinterlace the woven frame of an interlaced camera (motion-adaptive, on the hub's GPU), likewise")
             p.add_argument("--di-order", choices=("tff", "bff"), default=None, help="--deinterlace: field order (hub default tff)")
             p.add_argument("--di-no-temporal", action="store_true", help="--deinterlace: spatial prediction only")
+            p.add_argument("--rotate", type=int, choices=(0, 90, 180, 270), default=None,
+                           help="turn the picture clockwise on the hub's GPU (a camera mounted sideways or upside down), likewise")
+            p.add_argument("--flip", choices=("none", "h", "v"), default=None,
+                           help="mirror the (rotated) picture left-right (h) or top-bottom (v), likewise")
             p.add_argument("--rest", default="127.0.0.1:8080",
-                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance / --denoise / --dehaze / --deinterlace)")
+                           help="host:port of the hub's REST API (--overlay / --stamp / --enhance / --denoise / --dehaze / --deinterlace / --rotate / --flip)")
         if name == "annotate":
             p.add_argument("--type", required=True)
         if name in ("storage", "proxy"):

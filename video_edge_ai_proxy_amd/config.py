@@ -189,6 +189,14 @@ class DeinterlaceConfig:
 
 
 @dataclass
+class OrientConfig:
+    """How the cameras are mounted (docs/ORIENT.md): ``cameras: {name: {rotate: 90, flip: h}}``. A
+    camera's entry is the orientation of ``frame.jpg``, ``stream.mjpg`` and ``Hub.latest_jpeg`` where
+    the request names none; every other endpoint stays in sensor orientation."""
+    cameras: dict = field(default_factory=dict)
+
+
+@dataclass
 class FlowConfig:
     """Motion vectors by block matching (docs/FLOW.md; ``Hub.flow``, ``/api/v1/flow``). The
     parameters hold for every camera of the hub. The defaults are design choices, not measured
@@ -237,6 +245,7 @@ class Config:
     denoise: DenoiseConfig = field(default_factory=DenoiseConfig)
     dehaze: DehazeConfig = field(default_factory=DehazeConfig)
     deinterlace: DeinterlaceConfig = field(default_factory=DeinterlaceConfig)
+    orient: OrientConfig = field(default_factory=OrientConfig)
     flow: FlowConfig = field(default_factory=FlowConfig)
     objects: ObjectsConfig = field(default_factory=ObjectsConfig)
     # frame-bus tag of this hub instance (set at start-up when the bus is in use; not a YAML key)
@@ -336,6 +345,11 @@ def validate(cfg: Config) -> None:
         deinterlace.to_native(cfg.deinterlace.order, cfg.deinterlace.temporal)
     except ValueError as e:
         raise ValueError(f"deinterlace: {e}") from None
+    try:
+        from . import orient
+        orient.check_mountings(cfg.orient.cameras)
+    except ValueError as e:
+        raise ValueError(f"orient: {e}") from None
     from . import flow
     flow.to_native({k: getattr(cfg.flow, k) for k in flow.DEFAULTS})
     from . import objects

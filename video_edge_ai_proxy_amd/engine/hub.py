@@ -25,6 +25,7 @@ from .. import denoise as denoise_params
 from .. import enhance as enhance_params
 from .. import flow as flow_params
 from .. import objects as objects_params
+from .. import orient as orient_params
 from .. import overlay as osd
 from .._native import gpu_count, native
 from ..config import Config, parse_tile
@@ -367,7 +368,7 @@ class Hub:
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
                     width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False,
-                    enhance=None, denoise=None, dehaze=None, deinterlace=None):
+                    enhance=None, denoise=None, dehaze=None, deinterlace=None, orient=None):
         """``(meta, bytes)`` of the newest frame with seq > after as a baseline JPEG, or None.
         Encoded on the camera's GPU straight from its ring slot (CPU backend: on the host);
         ``quality`` 1..100, default ``serving.jpeg_quality``. With ``width`` and / or ``height``
@@ -406,7 +407,15 @@ class Hub:
         camera's GPU: ahead of the scale, the dehazing, the enhancement, the overlay and the encoder.
         ``meta["deinterlace_frames"]`` says how many frames were used: 2, or 1 where only the spatial
         part could run (no earlier frame in the ring, or ``temporal`` false). Not together with
-        ``denoise`` (a ``ValueError``). ``None``: the call and its bytes are what they are without it."""
+        ``denoise`` (a ``ValueError``). ``None``: the call and its bytes are what they are without it.
+
+        ``orient``: a dict with ``rotate`` (0, 90, 180, 270 degrees clockwise) and / or ``flip``
+        (``"none"``, ``"h"``, ``"v"``, applied to the rotated picture; :mod:`..orient`, docs/ORIENT.md)
+        turns and mirrors the picture on the camera's GPU, behind the denoise or the deinterlacing and
+        ahead of everything else: ``width`` / ``height``, the enhancement's tiles and the overlay's
+        coordinates refer to the upright picture. ``meta["orient"]`` is ``"<rotate>[,<flip>]"``.
+        ``None``: the camera's entry in the config's ``orient:`` section, where it has one; else the
+        call and its bytes are what they are without it. The identity serves the sensor picture."""
         q = self._quality(quality)
         bw, bh = self._box(width, height)
         if not isinstance(stamp, bool):
@@ -417,7 +426,17 @@ class Hub:
         di = deinterlace_params.from_request(deinterlace, self.deinterlace_defaults())
         if di is not None and dn is not None:
             raise ValueError("deinterlace is not served together with denoise, which blends the ring's woven frames")
+        up = orient_params.from_request(orient, self.orient_mounting(name))
         w, cam = self.worker_of(name)
+        if up is not None:
+            if (overlay is None or overlay is False) and not stamp:
+                r = w.read_latest_jpeg(cam, after, q, bw, bh, eq, dn, dh, di, up)
+            else:
+                items = self.overlay(name) if overlay is True else osd.normalize_list(overlay or [])
+                r = w.read_overlay_jpeg(cam, osd.to_native(items + [osd.STAMP] * stamp), name, after, q, bw, bh, eq, dn, dh, di, up)
+            if r is not None:
+                r[0]["orient"] = orient_params.header(up)
+            return r
         if (overlay is None or overlay is False) and not stamp:
             if di is not None:
                 return w.read_latest_jpeg(cam, after, q, bw, bh, eq, dn, dh, di)
@@ -532,6 +551,31 @@ class Hub:
     def deinterlace_count(self) -> int:
         """Deinterlaced pictures served since the hub started (/metrics)."""
         return sum(int(w.deinterlace_count()) for w in self.workers)
+
+    # ------------------------------------------------------------------ orientation
+    def orient_mounting(self, name: str):
+        """How the camera is mounted: its ``{rotate, flip}`` entry in the config's ``orient:`` section,
+        or None. ``latest_jpeg`` serves it where the call names no orientation."""
+        return self.cfg.orient.cameras.get(name)
+
+    def latest_oriented(self, name: str, after: int = 0, width: int = 0, height: int = 0, rotate: int = 0,
+                        flip: str = "none"):
+        """``(seq, ndarray)`` of the newest frame with seq > after, turned by ``rotate`` degrees
+        clockwise and then mirrored by ``flip`` on the camera's GPU (docs/ORIENT.md), or None;
+        ``width`` / ``height`` (0: not given) fit and downscale the upright picture afterwards. Only
+        that picture is copied to the host. The identity is the frame itself and is not counted."""
+        up = orient_params.from_request({"rotate": rotate, "flip": flip})
+        bw, bh = self._box(width or None, height or None)
+        w, cam = self.worker_of(name)
+        if up is None:
+            r = w.read_latest_scaled(cam, after, bw, bh) if bw or bh else w.read_latest(cam, after)
+        else:
+            r = w.read_latest_oriented(cam, after, bw, bh, *up)
+        return None if r is None else (int(r[0]["seq"]), r[1])
+
+    def orient_count(self) -> int:
+        """Oriented pictures served since the hub started (/metrics)."""
+        return sum(int(w.orient_count()) for w in self.workers)
 
     # ------------------------------------------------------------------ on-screen display
     def set_overlay(self, name: str, items, ttl_ms: int = 0) -> None:

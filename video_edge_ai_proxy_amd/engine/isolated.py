@@ -570,7 +570,7 @@ class ProcessHub:
 
     def latest_jpeg(self, name: str, after: int = 0, quality: Optional[int] = None,
                     width: Optional[int] = None, height: Optional[int] = None, overlay=None, stamp: bool = False,
-                    enhance=None, denoise=None, dehaze=None, deinterlace=None):
+                    enhance=None, denoise=None, dehaze=None, deinterlace=None, orient=None):
         """(meta, JPEG bytes) or None: the worker process scales (width / height given) and encodes
         on its GPU, only the compressed bytes cross the pipe."""
         if overlay is not None or stamp:
@@ -583,6 +583,8 @@ class ProcessHub:
             raise NotImplementedError("dehazed frames are not served with gpu.isolation: process")
         if deinterlace is not None and deinterlace is not False:
             raise NotImplementedError("deinterlaced frames are not served with gpu.isolation: process")
+        if orient is not None:
+            raise NotImplementedError("oriented frames are not served with gpu.isolation: process")
         if width is None and height is None:
             return self._call(name, "latest_jpeg", after, quality)
         return self._call(name, "latest_jpeg", after, quality, width, height)
@@ -609,6 +611,13 @@ class ProcessHub:
         raise NotImplementedError("deinterlaced frames are not served with gpu.isolation: process")
 
     def deinterlace_count(self) -> int:
+        return 0
+
+    def latest_oriented(self, name: str, after: int = 0, width: int = 0, height: int = 0, rotate: int = 0,
+                        flip: str = "none"):
+        raise NotImplementedError("oriented frames are not served with gpu.isolation: process")
+
+    def orient_count(self) -> int:
         return 0
 
     def latest_scaled(self, name: str, after: int = 0, width: Optional[int] = None,

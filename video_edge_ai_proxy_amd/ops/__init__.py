@@ -46,6 +46,10 @@
   deinterlaced motion-adaptively (edge-directed prediction by packed 8-bit SADs on a luma plane in
   LDS, bounded by the fields before and after; one launch for every picture of the call: the kernel
   behind ``frame.jpg?deinterlace=1``); host tensors run the CPU twin, whose bytes are the same.
+* :func:`orient` / :func:`orient_batch` — BGR24 pictures turned by quarter turns and mirrored (64 x 64
+  tiles transposed in LDS, whole dwords assembled with ``v_alignbyte`` / ``v_perm``, 16-byte vectors
+  along rows on both global sides; one launch for every picture of the call: the kernel behind
+  ``frame.jpg?rotate=90``); host tensors run the CPU twin, whose bytes are the same.
 * :func:`block_flow` / :func:`block_flow_batch` — motion vectors of a BGR24 picture against an earlier
   one by exhaustive 8 x 8 block matching on decimated luma (packed 8-bit SADs; two launches for every
   pair of the call: the kernels behind ``/flow``); host tensors run the CPU twin, whose bytes are the
@@ -1279,6 +1283,72 @@ def deinterlace(newer: torch.Tensor, older: torch.Tensor | None = None, order: s
     is given: see :func:`deinterlace_batch`. Device tensors run the gfx950 kernel, host tensors the
     CPU twin."""
     return deinterlace_batch([(newer, older)], order, temporal, None if out is None else [out])[0]
+
+
+def orient_batch(pictures, rotates=0, flips="none", outs=None):
+    """Quarter turns and mirrors (csrc/vep/orient.h, docs/ORIENT.md) of a list of ``[H, W, 3]`` BGR24
+    tensors of any sizes: each turned by ``rotate`` degrees clockwise (0, 90, 180, 270), then mirrored
+    by ``flip`` (``"none"``, ``"h"`` left-right, ``"v"`` top-bottom); the result is ``[W, H, 3]`` for
+    90 and 270. Device tensors (all on one device) run the gfx950 kernel, ONE launch for the whole
+    list, which may mix sizes and orientations; host tensors run the CPU twin, whose bytes are the
+    same. ``rotates`` and ``flips`` are one value or one per picture. A device picture's rows may
+    start at any byte address and have any pitch. ``outs`` None: a new contiguous tensor per picture;
+    else per picture a tensor of the result's size that receives it and does not overlap the picture
+    (out of place only). The identity is a copy. No CPU fallback for device tensors."""
+    from .. import orient as params
+
+    pictures = list(pictures)
+    n = len(pictures)
+    if not n:
+        raise ValueError("pictures must hold at least one picture")
+    native_params = [params.to_native(r, f) for r, f in
+                     zip(_per_picture(rotates, n, "rotates"), _per_picture(flips, n, "flips"))]
+    outs = [None] * n if outs is None else list(outs)
+    if len(outs) != n:
+        raise ValueError("outs must hold one entry per picture")
+    sizes = [_check_overlay_picture(p, f"pictures[{k}]") for k, p in enumerate(pictures)]
+    on_device = [p.is_cuda for p in pictures]
+    if any(on_device) != all(on_device):
+        raise ValueError("the pictures must all be device tensors or all host tensors")
+    res = []
+    if not on_device[0]:
+        for k, (p, (r, f), out) in enumerate(zip(pictures, native_params, outs)):
+            got = torch.from_numpy(native.orient_cpu(p.detach().contiguous().numpy(), r, f))
+            if out is not None:
+                if not isinstance(out, torch.Tensor) or out.is_cuda or out.dtype != torch.uint8 or out.shape != got.shape:
+                    raise ValueError(f"outs[{k}] must be a host uint8 tensor of the result's shape")
+                out.copy_(got)
+                got = out
+            res.append(got)
+        return res
+    device, work, spans = pictures[0].device, [], []
+    for k, (p, (r, f), out, (w, h, pitch)) in enumerate(zip(pictures, native_params, outs, sizes)):
+        if p.device != device:
+            raise ValueError("the pictures must live on one device")
+        ow, oh = (h, w) if r in (90, 270) else (w, h)
+        if out is None:
+            out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=device)
+        dw, dh, dpitch = _check_overlay_picture(out, f"outs[{k}]")
+        if (dw, dh) != (ow, oh) or not out.is_cuda or out.device != device:
+            raise ValueError(f"outs[{k}] must be a [{oh}, {ow}, 3] tensor on the pictures' device")
+        a, b = _overlay_span(p, w, h, pitch), _overlay_span(out, ow, oh, dpitch)
+        if a[0] < b[1] and b[0] < a[1]:
+            raise ValueError(f"outs[{k}] overlaps its picture")
+        if any(b[0] < s[1] and s[0] < b[1] for s in spans):
+            raise ValueError("the destinations of one call must not overlap")
+        spans.append(b)
+        work.append(((a[0], a[1] - a[0], pitch), (b[0], b[1] - b[0], dpitch), w, h, r, f))
+        res.append(out)
+    require_gpu()
+    with torch.cuda.device(device):
+        native.orient_device_batch(work, int(torch.cuda.current_stream(device).cuda_stream))
+    return res
+
+
+def orient(bgr: torch.Tensor, rotate: int = 0, flip: str = "none", out: torch.Tensor | None = None):
+    """One ``[H, W, 3]`` BGR24 picture turned and mirrored: see :func:`orient_batch`. A device tensor
+    runs the gfx950 kernel, a host tensor the CPU twin."""
+    return orient_batch([bgr], rotate, flip, None if out is None else [out])[0]
 
 
 def block_flow_batch(pairs, decimate: int = 2, range: int = 7, planes: bool = False):

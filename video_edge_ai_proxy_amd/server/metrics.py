@@ -125,6 +125,11 @@ class HubCollector:
             ir = CounterMetricFamily("vep_deinterlace_requests", "pictures served deinterlaced (frame.jpg, stream.mjpg, latest_deinterlaced)")
             ir.add_metric([], count())
             yield ir
+        count = getattr(self.hub, "orient_count", None)
+        if count is not None:
+            orr = CounterMetricFamily("vep_orient_requests", "pictures served turned or mirrored (frame.jpg, stream.mjpg, latest_oriented)")
+            orr.add_metric([], count())
+            yield orr
         try:
             from .._native import native
 

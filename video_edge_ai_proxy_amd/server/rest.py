@@ -203,8 +203,22 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             raise ValueError("deinterlace is not served together with denoise, which blends the ring's woven frames")
         return {"deinterlace": given or True}
 
+    def oriented(rotate, flip) -> dict:
+        """The orient argument of latest_jpeg (docs/ORIENT.md): none when the request names neither
+        parameter, so such a request calls the hub exactly as before (the hub then applies the
+        camera's mounting, where the config has one)."""
+        from .. import orient as ori
+
+        given = {k: v for k, v in (("rotate", rotate), ("flip", flip)) if v is not None}
+        if not given:
+            return {}
+        ori.from_request(given)  # (a bad value is refused before the hub is asked)
+        return {"orient": given}
+
     def frame_headers(meta) -> dict:
         h = {"X-Vep-Seq": str(meta["seq"])}
+        if "orient" in meta:
+            h["X-Vep-Orient"] = meta["orient"]
         if "deinterlace_frames" in meta:
             h["X-Vep-Deinterlace-Frames"] = str(meta["deinterlace_frames"])
         if "dehaze_air" in meta:
@@ -221,7 +235,7 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                   nr_strength: float | None = None, dehaze: int | None = None, dh_patch: int | None = None,
                   dh_omega: float | None = None, dh_t0: float | None = None, dh_radius: int | None = None,
                   dh_strength: float | None = None, deinterlace: int | None = None, di_order: str | None = None,
-                  di_temporal: int | None = None):
+                  di_temporal: int | None = None, rotate: int | None = None, flip: str | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -233,8 +247,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             size.update(denoised(denoise, nr_frames, nr_level, nr_strength))
             size.update(dehazed(dehaze, dh_patch, dh_omega, dh_t0, dh_radius, dh_strength))
             size.update(deinterlaced(deinterlace, di_order, di_temporal, size))
+            size.update(oriented(rotate, flip))
         except ValueError as e:
             return err(422, str(e))
+        if "orient" in size and not hasattr(pm.hub, "orient_mounting"):  # (501 before a stream starts)
+            return err(501, "oriented frames are not served with gpu.isolation: process")
         if "deinterlace" in size and not hasattr(pm.hub, "deinterlace_defaults"):  # (501 before a stream starts)
             return err(501, "deinterlaced frames are not served with gpu.isolation: process")
         if "dehaze" in size and not hasattr(pm.hub, "dehaze_defaults"):
@@ -261,7 +278,8 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                     nr_level: int | None = None, nr_strength: float | None = None, dehaze: int | None = None,
                     dh_patch: int | None = None, dh_omega: float | None = None, dh_t0: float | None = None,
                     dh_radius: int | None = None, dh_strength: float | None = None, deinterlace: int | None = None,
-                    di_order: str | None = None, di_temporal: int | None = None):
+                    di_order: str | None = None, di_temporal: int | None = None, rotate: int | None = None,
+                    flip: str | None = None):
         try:
             q = jpeg_quality(quality)
             size = box(width, height)
@@ -277,8 +295,11 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
             size.update(denoised(denoise, nr_frames, nr_level, nr_strength))
             size.update(dehazed(dehaze, dh_patch, dh_omega, dh_t0, dh_radius, dh_strength))
             size.update(deinterlaced(deinterlace, di_order, di_temporal, size))
+            size.update(oriented(rotate, flip))
         except ValueError as e:
             return err(422, str(e))
+        if "orient" in size and not hasattr(pm.hub, "orient_mounting"):  # (501 before a stream starts)
+            return err(501, "oriented frames are not served with gpu.isolation: process")
         if "deinterlace" in size and not hasattr(pm.hub, "deinterlace_defaults"):  # (501 before a stream starts)
             return err(501, "deinterlaced frames are not served with gpu.isolation: process")
         if "dehaze" in size and not hasattr(pm.hub, "dehaze_defaults"):  # (501 before the stream starts)
@@ -328,6 +349,7 @@ def create_app(pm: ProcessManager, sm: SettingsManager, metrics=None) -> FastAPI
                        f"X-Vep-Seq: {seq}\r\n" + (f"X-Vep-Denoise-Frames: {meta['denoise_frames']}\r\n" if "denoise_frames" in meta else "")
                        + (f"X-Vep-Dehaze-Air: {','.join(str(v) for v in meta['dehaze_air'])}\r\n" if "dehaze_air" in meta else "")
                        + (f"X-Vep-Deinterlace-Frames: {meta['deinterlace_frames']}\r\n" if "deinterlace_frames" in meta else "")
+                       + (f"X-Vep-Orient: {meta['orient']}\r\n" if "orient" in meta else "")
                        + "\r\n").encode() + jpg + b"\r\n"
                 sent += 1
                 due = max(due + 1.0 / fps, now)
